@@ -18,7 +18,7 @@ Two ways through the C ABI, bit-identical results (tests/test_gpu_parity.py::tes
 --pipeline one-pass (default) calls fnx_gaussian_blur_ssim_fast_batch, whose blur kernel also
 accumulates SSIMFast's boxDownsample sums, so neither full-size image is read a second time;
 --pipeline two-call calls fnx_gaussian_blur_batch then fnx_ssim_fast_batch, as the reference does.
-The default line carries both beside `value`: `two_call`, and `two_call_keep` -- the same two calls with
+The --full line carries both beside `value`: `two_call`, and `two_call_keep` -- the same two calls with
 FNX_BLUR_KEEP_BOX_SUMS on the blur, whose kernel then leaves the box sums of both sides for the scoring call.
 
 --depth 1 (default): one step at a time -- the blur kernel has the GPU to itself, which is what `roofline`
@@ -27,11 +27,21 @@ second set of destination images -- before step s's B scores are fetched, the wa
 keeps the queue full (batch.go:84-123).  Every step still blurs and scores all B images and fetches its
 results inside the timed region; two blur kernels then share the GPU (each launch takes twice as long, the
 pair finishes 7 % sooner than back to back: their phases decorrelate and a step's small tail kernels run
-underneath).  The default line reports that rate too (`pipelined`), measured after the timed region.
+underneath).  The --full line reports that rate too (`pipelined`), measured after the timed region.
 
 Rank 0 prints ONE JSON line with `roofline` (dominant kernel, HIP events on the stream the
-kernel runs on) and, at N == 1, `cpu_baseline` (the oracle -- a C restatement of the Go
-reference with its threading model -- on a bounded sample of the same workload).
+kernel runs on, taken from the timed steps themselves).  A plain run does only that: set-up,
+pre-warm and warm-up, the K timed steps, the line.  --full adds every measurement made after the
+timed region: `pipelined` / `serial`, `exact_mode`, `long_run`, `two_call`, `two_call_keep`,
+`pcie_inclusive`, `batch` (BASELINE config 5), `other_configs` and, at N == 1, `cpu_baseline`
+(the oracle -- a C restatement of the Go reference with its threading model -- on a bounded
+sample of the same workload); --no-extras, --no-batch and --no-cpu-baseline drop parts of it.
+
+--dump-outputs DIR writes what the last timed step returned to its caller, as .npy files (rank 0):
+ssim.npy (float64, the B scores), blurred_row_sums.npy (float64 [n, H, 4]: every row's per-channel
+sum of the first n = min(B, 64) blurred images) and blurred_sample.npy (float32: 2^22 bytes of the
+B blurred images at positions drawn by a fixed seed).  The inputs depend only on the arguments, so
+two builds can be compared file for file.
 """
 from __future__ import annotations
 
@@ -98,6 +108,28 @@ def dist_identity(torch, dist, dev: int, rank: int, world: int) -> dict:
             "collectives": "barrier + MAX(elapsed) + SUM(Summarize partials): 3 small all-reduces per run, none on the data path"}
 
 
+DUMP_SAMPLE = 1 << 22     # --dump-outputs: blurred bytes sampled (float32: 16 MB)
+DUMP_ROW_IMAGES = 64      # --dump-outputs: images whose row sums are written (float64: 66 KB per 4K image)
+
+
+def dump_outputs(path: str, torch, scores: np.ndarray, blurred: list) -> None:
+    """The last timed step's results as a caller receives them: the B scores whole, the B blurred images as per-row channel
+    sums (every byte of the first DUMP_ROW_IMAGES images counts) and a sample of DUMP_SAMPLE bytes at seeded positions."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "ssim.npy"), np.asarray(scores, dtype=np.float64))
+    rows = [d.sum(dim=1, dtype=torch.int64).cpu().numpy() for d in blurred[:DUMP_ROW_IMAGES]]    # [H, 4] each, exact
+    np.save(os.path.join(path, "blurred_row_sums.npy"), np.stack(rows).astype(np.float64))
+    per = blurred[0].numel()
+    idx = np.sort(np.random.default_rng(20261016).integers(0, per * len(blurred), size=DUMP_SAMPLE))
+    img = idx // per
+    sample = np.empty(DUMP_SAMPLE, dtype=np.float32)
+    for i in np.unique(img):
+        sel = img == i
+        off = torch.from_numpy(idx[sel] - i * per).to(blurred[i].device)
+        sample[sel] = blurred[i].view(-1)[off].cpu().numpy()
+    np.save(os.path.join(path, "blurred_sample.npy"), sample)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -115,7 +147,7 @@ def main() -> int:
     ap.add_argument("--depth", type=int, default=1,
                     help="one-pass pipeline: steps in flight.  1 (default): one step at a time, so the blur kernel runs "
                          "alone and `roofline` describes it; 2: step s+1 is enqueued (on a second context = stream, into "
-                         "a second set of destinations) before step s's results are fetched (+7 %%; the default line "
+                         "a second set of destinations) before step s's results are fetched (+7 %%; the --full line "
                          "reports that rate as `pipelined`)")
     ap.add_argument("--config3-chunk", type=int, default=4,
                     help="config 3: images per batched call (fnx_lanczos_resize_batch + fennec_MSSSIM_batch_enqueue: one set of resize "
@@ -130,12 +162,12 @@ def main() -> int:
     ap.add_argument("--prewarm", type=float, default=None,
                     help="seconds of untimed steps before the warm-up steps (GPU clock ramp; setup, not measurement)")
     ap.add_argument("--workers", type=int, default=0, help="config5: host worker threads per GPU (0 = min(8, cores))")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip `cpu_baseline` (config2 measures it under --full only)")
     ap.add_argument("--no-queue-ahead", action="store_true",
                     help="one-pass, depth 1: fetch step s before enqueueing step s+1 (the stream drains for ~15 us per step)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the measurements made after the timed region (pipelined, exact_mode, pcie_inclusive): "
-                         "profiler runs use it so that kernel statistics cover the timed configuration only")
+                    help="skip the measurements made after the timed region (config2, under --full: pipelined, exact_mode, pcie_inclusive, "
+                         "other_configs ...): profiler runs use it so that kernel statistics cover the timed configuration only")
     ap.add_argument("--threads", type=int, default=None,
                     help="configs 3/4: host threads driving the worker contexts (default: 2 for config3's four contexts -- python "
                          "threads contend for the interpreter lock; every call only enqueues, so one thread feeds several streams)")
@@ -149,13 +181,21 @@ def main() -> int:
     ap.add_argument("--device-search", action="store_true",
                     help="config5: the quality search round-trips every candidate on the device (fnx_jpeg_quality_search); the host "
                          "codec decodes the source and encodes the winner only")
-    ap.add_argument("--no-batch", action="store_true", help="skip the `batch` object (CompressBatch images/s over --batch-items 4K JPEGs)")
+    ap.add_argument("--no-batch", action="store_true", help="skip the `batch` object of --full (CompressBatch images/s over --batch-items 4K JPEGs)")
     ap.add_argument("--batch-items", type=int, default=4096, help="items of the `batch` job (BASELINE config 5: 4096)")
     ap.add_argument("--batch-files", type=int, default=512,
                     help="distinct synthetic 4K JPEG files the items cycle through (256 distinct images x 2 qualities; 3.2 GB of host memory)")
     ap.add_argument("--workload", default="config2", choices=["config2", "config3", "config4", "config5", "analyze", "palette", "scale-search"],
                     help="BASELINE.json config to run; config2 (default) is the headline metric")
+    ap.add_argument("--full", action="store_true",
+                    help="config2: after the timed region also measure the side figures (pipelined / serial, exact_mode, long_run, "
+                         "two_call, two_call_keep, pcie_inclusive, batch, other_configs, cpu_baseline); a plain run prints the "
+                         "headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="config2: write the last timed step's results to DIR/*.npy (float32 / float64, < 64 MB in all)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "config2":
+        ap.error("--dump-outputs covers the default workload (config2) only")
     if args.prewarm is None:                # configs 3 and 4: the governor needs > 1 s of these lighter loads (see other_configs)
         args.prewarm = 1.5 if args.workload in ("config3", "config4") else PREWARM_S
     if args.contexts is None:
@@ -322,6 +362,10 @@ def main() -> int:
         n_items, ssim_sum = int(red[0].item()), float(red[1].item())
     else:
         n_items, ssim_sum = len(vals), float(np.sum(vals))
+    if args.dump_outputs and rank == 0:
+        # the last timed step wrote the destination set of step K - 1 (pipe_dsts alternate at depth > 1)
+        dump_outputs(args.dump_outputs, torch, vals, pipe_dsts[(args.steps - 1) % depth])
+    full = args.full and not args.no_extras
 
     total_mp = mp_per_image * B * world * args.steps
     value = total_mp / elapsed
@@ -479,7 +523,7 @@ def main() -> int:
                               "ms_per_step": round(step_kernel_ms, 4)}
         if one_pass and nctx == 1 and not args.no_queue_ahead:
             out["kernel_only"]["note"] = "with the next step queued ahead the stream never drains: GPU time per step = wall time per step"
-        if rank == 0 and world == 1 and one_pass and nctx == 1 and not args.no_extras:
+        if rank == 0 and world == 1 and one_pass and nctx == 1 and full:
             # the same steps two in flight (--depth 2), after the timed region; never `value`
             ctx.profile(False)
             c2 = fennec_amd.Context(local_rank)
@@ -505,7 +549,7 @@ def main() -> int:
             ctx.profile(True)
             del pl, d2
             c2.close()
-    elif rank == 0 and world == 1 and not args.no_extras:
+    elif rank == 0 and world == 1 and full:
         # the same step one at a time (depth 1), after the timed region: the blur kernel alone on the GPU
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t_s = time.perf_counter()
@@ -530,7 +574,7 @@ def main() -> int:
                          "note": "--depth 1: one step at a time, 10 steps after the timed region"}
         out["kernel_only"] = {"value": round(mp_per_image * B / (l_ms * 1e-3), 1), "unit": "MP/s", "ms_per_step": round(l_ms, 4),
                               "note": "HIP-event time of one serial step's kernels"}
-    if rank == 0 and world == 1 and one_pass and not exact and nctx == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and one_pass and not exact and nctx == 1 and full:
         # the same step with bit-exact blurred images (FNX_BLUR_EXACT), after the timed region; never `value`
         ctx.profile(False)
         xplan = ctx.plan_blur_ssim_fast_batch(srcs, SIGMA, outs=dsts, exact=True)
@@ -556,7 +600,7 @@ def main() -> int:
                                      "bit-identical to the reference's, scores from exactly those images; same protocol as the "
                                      "timed region (warm-up, synchronize on both sides), run right after it; "
                                      "`python bench.py --blur-mode exact` makes it the headline line"}
-    if rank == 0 and world == 1 and one_pass and nctx == 1 and depth == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and one_pass and nctx == 1 and depth == 1 and full:
         # (a) the timed loop again over 500 steps: the driver's 20 steps last 14 ms, inside the clock governor's settling time
         ctx.profile(False)
         torch.cuda.synchronize()
@@ -610,8 +654,9 @@ def main() -> int:
                                         "both sides as it passes, fnx_ssim_fast_batch reads neither image again (2*S of traffic, priced "
                                         "against the path's 4*S like `value`); the caller promises the scoring call comes next"}
         ctx.profile(True)
-    host0 = srcs[0].cpu().numpy() if rank == 0 else None
-    if rank == 0 and not args.no_extras:
+    want_cpu = args.full and not args.no_cpu_baseline and rank == 0 and world == 1
+    host0 = srcs[0].cpu().numpy() if rank == 0 and (full or want_cpu) else None
+    if rank == 0 and full:
         host = host0
         S_mb = host.nbytes / 1e6
         hb = np.empty_like(host)
@@ -673,13 +718,13 @@ def main() -> int:
         di = dist_identity(torch, dist, local_rank, rank, world)       # a collective: every rank calls it
         di["queue"] = "config 2 (`value`): images sharded statically, no queue; `batch`: one dynamic queue for the job (store counter, chunks of 4 indices)"
         out["dist"] = di
-    if not args.no_batch:
+    if args.full and not args.no_batch:
         # BASELINE.json's second metric: CompressBatch images/s, at every N (all ranks take part: ONE queue for the job)
         ctx.profile(False)
         bm = batch_metric(args, rank, world, local_rank, red_dev, ctx)
         if rank == 0:
             out["batch"] = bm
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and full:
         def heavy_burst(seconds=0.5):
             # configs 3 and 4 are light loads; from a cold box their own 1.5 s of pre-warm leaves the clocks where a minute of
             # them would not (first process on a fresh box: 67 k MP/s for config 3, every later one 79-81 k).  Half a second
@@ -690,7 +735,7 @@ def main() -> int:
                 run_steps(8)
             torch.cuda.synchronize()
         out["other_configs"] = other_configs(args, heavy_burst)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if want_cpu:
         out["cpu_baseline"] = cpu_baseline(host0)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -66,7 +66,7 @@ def test_bench_line_with_the_process_group_up():
         env.pop(k)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", env["MASTER_PORT"], os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4",
-           "--no-extras", "--no-cpu-baseline", "--batch-items", "24", "--batch-files", "4", "--prewarm", "0.05"]
+           "--full", "--no-extras", "--no-cpu-baseline", "--batch-items", "24", "--batch-files", "4", "--prewarm", "0.05"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
