@@ -74,6 +74,19 @@ class NativeBatchResult(C.Structure):
 FNX_ERR_INVALID = -1
 FNX_ERR_UNSUPPORTED = -5
 
+# fnx_jpeg_target_size's strategies (include/fennec_hip.h): strategy 1, 3, 4 of hitTargetSize and its JPEG fallback
+FNX_TS_QUALITY, FNX_TS_QUALITY_SCALE, FNX_TS_SCALE, FNX_TS_FALLBACK = 1, 2, 4, 8
+FNX_TS_ALL = FNX_TS_QUALITY | FNX_TS_QUALITY_SCALE | FNX_TS_SCALE | FNX_TS_FALLBACK
+
+
+class SizeCandidate(C.Structure):
+    """fnx_size_candidate (include/fennec_hip.h): one strategy's sizeResult."""
+    _fields_ = [("strategy", C.c_int32), ("quality", C.c_int32), ("final_w", C.c_int32), ("final_h", C.c_int32),
+                ("steps", C.c_int32), ("reserved", C.c_int32), ("nbytes", C.c_int64), ("ssim", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
 
 class FileOptions(C.Structure):
     """fennec_FileOptions (include/fennec_hip.h): the Options fields CompressFile's JPEG path reads."""
@@ -196,6 +209,9 @@ def load_library() -> C.CDLL:
         _sig(L, "fnx_jpeg_recompress", i, [ctx, _u8p, C.c_size_t, d, _f64p, _u8p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i), _f64p,
                                             C.POINTER(i), C.POINTER(i), C.POINTER(i)])
         _sig(L, "fnx_jpeg_quality_search", i, [ctx, i] + img + [i, i, d, _f64p, C.POINTER(i), _f64p, C.POINTER(i)])
+        _sig(L, "fnx_jpeg_encode_scaled", i, [ctx, i] + img + [i, i, i, i, i, _u8p, C.c_size_t, C.POINTER(C.c_size_t)])
+        _sig(L, "fnx_jpeg_target_size", i, [ctx, i] + img + [i, i, C.c_longlong, i, _f64p, C.POINTER(C.c_int), C.POINTER(SizeCandidate),
+                                             C.POINTER(i), _u8p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, i])
         _sig(L, "fnx_gaussian_blur_ssim_fast", i, [ctx, i] + img + [i, i, _f64p, i, i] + img + [_f64p, _f64p])
         _sig(L, "fnx_ssim_batch_enqueue", i, [ctx, i, C.POINTER(C.c_void_p), i, C.POINTER(C.c_void_p), i, i, i, _f64p])
         _sig(L, "fnx_sharpen_batch", i, [ctx, i, C.POINTER(C.c_void_p), i, i, i, C.c_double, C.POINTER(C.c_void_p), i])
@@ -708,6 +724,73 @@ class Context:
                     break
                 cap = n.value
         self._chk(rc, "fnx_jpeg_compress")
+
+    def jpeg_encode_scaled(self, img, dw: int, dh: int, quality: int, size_only: bool = False):
+        """jpeg.Encode(boxDownsample(img, dw, dh), quality) (fnx_jpeg_encode_scaled) without the scaled image -> the file's
+        bytes, or with size_only=True its length only."""
+        s = _Img(img)
+        dw, dh = int(dw), int(dh)
+        if dw <= 0 or dh <= 0 or dw > 65535 or dh > 65535:
+            raise FennecError(f"jpeg_encode_scaled: {dw} x {dh} is not a JPEG size (1..65535 each way)")
+        n = C.c_size_t(0)
+        with self._ordered(img):
+            if size_only:
+                self._chk(self._lib.fnx_jpeg_encode_scaled(self._h, s.space, s.ptr, s.stride, s.w, s.h, dw, dh, int(quality), None, 0,
+                                                           C.byref(n)), "fnx_jpeg_encode_scaled")
+                return int(n.value)
+            cap = 4096 + (dw * dh * 3) // 2
+            for _ in range(2):
+                buf = np.empty(cap, dtype=np.uint8)
+                rc = self._lib.fnx_jpeg_encode_scaled(self._h, s.space, s.ptr, s.stride, s.w, s.h, dw, dh, int(quality),
+                                                      buf.ctypes.data_as(_u8p), cap, C.byref(n))
+                if rc == FNX_OK:
+                    return buf[:n.value].tobytes()
+                if n.value <= cap:
+                    break
+                cap = n.value
+        self._chk(rc, "fnx_jpeg_encode_scaled")
+
+    def jpeg_target_size(self, img, target_bytes: int, strategies: int = FNX_TS_ALL, cancel=None, window=None):
+        """hitTargetSize's JPEG strategies (targetsize.go:26-357) on the device (fnx_jpeg_target_size) -> a dict: `candidates`
+        (four dicts in FNX_TS_* bit order; strategy 0 = none), `winner` (index, or None), `data` (the winner's file, or None),
+        `image` (the winner's final image: the source itself for strategy 1 and the fallback, else the Lanczos-scaled image --
+        numpy for a host source, a device tensor for a device one) and `status` (FNX_OK / FNX_NOOP).  `cancel`: a
+        ctypes.c_int whose non-zero value stops the search where the reference checks ctx.Err()."""
+        s = _Img(img)
+        target_bytes, strategies = int(target_bytes), int(strategies)
+        if s.w <= 0 or s.h <= 0 or s.w > 65535 or s.h > 65535:
+            raise FennecError(f"jpeg_target_size: a {s.w} x {s.h} source is not a JPEG size (1..65535 each way)")
+        if target_bytes <= 0:
+            raise FennecError("jpeg_target_size: target_bytes must be > 0")
+        if strategies <= 0 or strategies & ~FNX_TS_ALL:
+            raise FennecError("jpeg_target_size: strategies must be a non-empty set of FNX_TS_* bits")
+        if cancel is not None and not isinstance(cancel, C.c_int):
+            raise FennecError("jpeg_target_size: cancel must be a ctypes.c_int (or None)")
+        k, pk = _f64(self.gaussianKernel() if window is None else window)
+        cand = (SizeCandidate * 4)()
+        win, n = C.c_int(-1), C.c_size_t(0)
+        scaled = s.like(s.w, s.h)                  # the winner's final image fits the source's footprint
+        sv = _Img(scaled)
+        cap = max(4096, target_bytes + 4096)
+        buf = np.empty(cap, dtype=np.uint8)
+        with self._ordered(img, scaled):
+            rc = self._lib.fnx_jpeg_target_size(self._h, s.space, s.ptr, s.stride, s.w, s.h, target_bytes, strategies, pk,
+                                                C.byref(cancel) if cancel is not None else None, cand, C.byref(win),
+                                                buf.ctypes.data_as(_u8p), cap, C.byref(n), sv.ptr, sv.stride)
+            too_small = rc == FNX_ERR_INVALID and n.value > cap and win.value >= 0
+            if not too_small:
+                self._chk(rc, "fnx_jpeg_target_size")
+            if s.space == FNX_DEVICE:
+                self.sync()
+        cands = [c.as_dict() for c in cand]
+        if rc == FNX_NOOP:
+            return {"candidates": cands, "winner": None, "data": None, "image": None, "status": rc}
+        c = cands[win.value]
+        image = scaled[:c["final_h"], :c["final_w"]] if c["strategy"] in (FNX_TS_QUALITY_SCALE, FNX_TS_SCALE) else img
+        # a winner over the target (the fallback, strategy 4's encode at bestQ) did not fit `buf`: its file from the image the
+        # call left, at its quality -- no second search
+        data = self.jpeg_encode(image, c["quality"]) if too_small else buf[:n.value].tobytes()
+        return {"candidates": cands, "winner": win.value, "data": data, "image": image, "status": FNX_OK}
 
     @staticmethod
     def jpeg_progressive_coefficients(data: bytes):

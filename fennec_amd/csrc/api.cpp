@@ -1554,6 +1554,326 @@ int fnx_jpeg_compress(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, 
     return jpeg_file_from_planes(ctx, orig, w, h, *quality, out, cap, nbytes);
 }
 
+int fnx_jpeg_encode_scaled(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int dw, int dh, int quality,
+                           uint8_t *out, size_t cap, size_t *nbytes)
+{
+    FNX_ENTER(ctx);
+    FNX_TRY(check_space(space));
+    FNX_REQUIRE(nbytes != nullptr && w > 0 && h > 0 && dw > 0 && dh > 0 && dw <= 65535 && dh <= 65535,
+                "encode_scaled arguments (JPEG dims are 16-bit)");
+    FNX_TRY(check_img(src, sstride, w, h, "src"));
+    *nbytes = 0;
+    DevImg s;
+    FNX_TRY(stage_in(ctx, space, src, sstride, w, h, SLOT_IN_A, &s));
+    JpegPlanes pl;
+    FNX_TRY(jpeg_planes(ctx, SLOT_JPEG1, dw, dh, &pl));
+    FNX_TRY(launch_jpeg_box_ycc(ctx, s.p, s.stride, w, h, dw, dh, pl.p[0], pl.p[1], pl.p[2]));
+    return jpeg_file_from_planes(ctx, pl, dw, dh, quality, out, cap, nbytes);
+}
+
+// ---- hitTargetSize's JPEG strategies (targetsize.go:26-357) in one call ---------------------------------------
+// The source is staged once; every scale step's planes come from jpeg_box_ycc_kernel and only its file sizes (8 bytes
+// a query) come back.  Slots: the source SLOT_IN_A, its planes SLOT_JPEG0, a scale step's planes SLOT_JPEG1, strategy 1's
+// decoded winner SLOT_JPEG2, the prepared SSIMFast side of the source SLOT_JPEG3, the Lanczos-scaled image SLOT_TS_SCALED
+// and its upscale for computeSSIMNRGBA SLOT_TS_UP.  At most one scaled candidate exists per call (strategy 4 runs only
+// when strategy 3 found none), so SLOT_TS_SCALED still holds the winner's image at the end.
+namespace {
+
+constexpr int TS_MIN_QUALITY = 20;     // minJPEGQuality (targetsize.go:14)
+
+struct TsRun {
+    fnx_ctx *ctx;
+    DevImg s;
+    int w, h;
+    long long target;
+    const double *window;
+    const volatile int *cancel;
+    JpegPlanes orig{};
+    bool have_orig = false;
+    fnx_prepared ref;
+    bool have_ref = false;
+
+    bool cancelled() const { return cancel && *cancel != 0; }
+
+    int orig_planes()
+    {
+        if (have_orig) return FNX_OK;
+        FNX_TRY(jpeg_planes(ctx, SLOT_JPEG0, w, h, &orig));
+        FNX_TRY(launch_jpeg_ycc(ctx, s.p, s.stride, w, h, orig.p[0], orig.p[1], orig.p[2]));
+        have_orig = true;
+        return FNX_OK;
+    }
+
+    // SSIMFast's side of the source (ssim.go:52-58), once per call
+    int prepared()
+    {
+        if (have_ref) return FNX_OK;
+        ref.w = w; ref.h = h;
+        const bool ds = ssim_fast_dims(w, h, &ref.pw, &ref.ph);
+        void *rp = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_JPEG3, static_cast<size_t>(ref.pw) * ref.ph * 4 + 16, &rp));
+        ref.pix = static_cast<uint8_t *>(rp);
+        if (ds) FNX_TRY(launch_box_downsample(ctx, 1, s.p, nullptr, s.stride, w, h, ref.pix, ref.pw * 4, 0, ref.pw, ref.ph));
+        else FNX_HIP(hipMemcpy2DAsync(ref.pix, size_t(w) * 4, s.p, s.stride, size_t(w) * 4, h, hipMemcpyDeviceToDevice, ctx->stream));
+        have_ref = true;
+        return FNX_OK;
+    }
+
+    // computeSSIMNRGBA(src, b) (targetsize.go:534-539): b (device, bw x bh) Lanczos-resized to the source's size when the
+    // dims differ, then SSIMFast against the prepared source
+    int ssim_against(const uint8_t *b, int bstride, int bw, int bh, double *out)
+    {
+        FNX_TRY(prepared());
+        if (bw != w || bh != h) {
+            void *up = nullptr;
+            FNX_TRY(scratch(ctx, SLOT_TS_UP, static_cast<size_t>(w) * h * 4 + 16, &up));
+            FNX_TRY(fennec_lanczosResize(ctx, FNX_DEVICE, b, bstride, bw, bh, static_cast<uint8_t *>(up), w * 4, w, h));
+            b = static_cast<const uint8_t *>(up);
+            bstride = w * 4;
+        }
+        return against_device(ctx, &ref, b, bstride, window, out);
+    }
+
+    // jpegQualitySearchOpt's bisection (targetsize.go:129-165) over the planes of a pw x ph image, file sizes only:
+    // *q = the highest fitting quality (0: none), *sz its file's size; *n += the encodes it ran
+    int bisect(const JpegPlanes &pl, int pw, int ph, int *q, size_t *sz, int *n)
+    {
+        const double pixels = static_cast<double>(static_cast<long long>(pw) * ph);
+        const double bpp = static_cast<double>(target * 8) / pixels;
+        int lo = 1, hi = 100;
+        if (bpp < 0.5) hi = 40;
+        else if (bpp < 1.0) { lo = 10; hi = 70; }
+        else if (bpp < 2.0) { lo = 30; hi = 90; }
+        else if (bpp > 4.0) lo = 60;
+        *q = 0; *sz = 0;
+        while (lo <= hi) {
+            const int mid = (lo + hi) / 2;
+            size_t len = 0;
+            FNX_TRY(jpeg_file_from_planes(ctx, pl, pw, ph, mid, nullptr, 0, &len));
+            ++*n;
+            if (static_cast<long long>(len) <= target) {
+                *q = mid; *sz = len;
+                lo = mid + 1;
+            } else {
+                hi = mid - 1;
+            }
+        }
+        return FNX_OK;
+    }
+
+    // jpegQualitySearchFast(boxDownsample(src, dw, dh)) (targetsize.go:236, 260, 306): the scaled image never exists
+    int scaled_query(int dw, int dh, int *q, size_t *sz, int *n)
+    {
+        JpegPlanes pl;
+        FNX_TRY(jpeg_planes(ctx, SLOT_JPEG1, dw, dh, &pl));
+        FNX_TRY(launch_jpeg_box_ycc(ctx, s.p, s.stride, w, h, dw, dh, pl.p[0], pl.p[1], pl.p[2]));
+        return bisect(pl, dw, dh, q, sz, n);
+    }
+
+    // lanczosResize(src, fw, fh) into SLOT_TS_SCALED and its planes into SLOT_JPEG1
+    int lanczos_scaled(int fw, int fh, uint8_t **img, JpegPlanes *pl)
+    {
+        void *d = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_TS_SCALED, static_cast<size_t>(fw) * fh * 4 + 16, &d));
+        *img = static_cast<uint8_t *>(d);
+        FNX_TRY(fennec_lanczosResize(ctx, FNX_DEVICE, s.p, s.stride, w, h, *img, fw * 4, fw, fh));
+        FNX_TRY(jpeg_planes(ctx, SLOT_JPEG1, fw, fh, pl));
+        return launch_jpeg_ycc(ctx, *img, fw * 4, fw, fh, pl->p[0], pl->p[1], pl->p[2]);
+    }
+
+    // ---- strategy 1: jpegQualitySearch(src) (targetsize.go:33-37, 125-176) ----
+    int quality(fnx_size_candidate *c)
+    {
+        FNX_TRY(orig_planes());
+        int q = 0, n = 0;
+        size_t sz = 0;
+        FNX_TRY(bisect(orig, w, h, &q, &sz, &n));
+        c->steps = n;
+        if (q < TS_MIN_QUALITY) return FNX_OK;           // nil, or below minJPEGQuality: not a candidate
+        // computeSSIMNRGBA(src, decoded winner): the SSIM of every earlier fitting quality is overwritten by the reference
+        void *dec = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_JPEG2, static_cast<size_t>(w) * h * 4 + 16, &dec));
+        FNX_TRY(jpeg_decode_at(ctx, orig, w, h, q, static_cast<uint8_t *>(dec), w * 4));
+        FNX_TRY(prepared());
+        FNX_TRY(against_device(ctx, &ref, static_cast<const uint8_t *>(dec), w * 4, window, &c->ssim));
+        c->strategy = FNX_TS_QUALITY; c->quality = q; c->final_w = w; c->final_h = h; c->nbytes = static_cast<int64_t>(sz);
+        return FNX_OK;
+    }
+
+    // ---- strategy 3: jpegQualityScaleSearch (targetsize.go:210-283) ----
+    int quality_scale(fnx_size_candidate *c)
+    {
+        int n = 0;
+        bool have = false;
+        double best = 0;
+        double lo = 0.05, hi = 1.0;                      // findBestScaleBinary
+        for (int i = 0; i < 10; i++) {
+            if (cancelled()) break;
+            const double mid = (lo + hi) / 2;
+            const int nw = static_cast<int>(static_cast<double>(w) * mid), nh = static_cast<int>(static_cast<double>(h) * mid);
+            if (nw < 8 || nh < 8) {
+                lo = mid;
+                continue;
+            }
+            int q = 0;
+            size_t sz = 0;
+            FNX_TRY(scaled_query(nw, nh, &q, &sz, &n));
+            if (q != 0 && static_cast<long long>(sz) <= target && q >= TS_MIN_QUALITY) {
+                have = true; best = mid;
+                lo = mid;
+            } else {
+                hi = mid;
+            }
+        }
+        static const double fixed[4] = {0.75, 0.50, 0.375, 0.25};   // findBestScaleFixed
+        for (double scale : fixed) {
+            if (cancelled()) break;
+            const int nw = static_cast<int>(static_cast<double>(w) * scale), nh = static_cast<int>(static_cast<double>(h) * scale);
+            if (nw < 8 || nh < 8) continue;
+            int q = 0;
+            size_t sz = 0;
+            FNX_TRY(scaled_query(nw, nh, &q, &sz, &n));
+            if (q != 0 && static_cast<long long>(sz) <= target && q >= TS_MIN_QUALITY && (!have || scale > best)) {
+                have = true; best = scale;
+            }
+        }
+        c->steps = n;
+        if (!have) return FNX_OK;
+        const int fw = static_cast<int>(static_cast<double>(w) * best), fh = static_cast<int>(static_cast<double>(h) * best);
+        uint8_t *img = nullptr;
+        JpegPlanes pl;
+        FNX_TRY(lanczos_scaled(fw, fh, &img, &pl));
+        int q = 0;
+        size_t sz = 0;
+        FNX_TRY(bisect(pl, fw, fh, &q, &sz, &n));        // jpegQualitySearch(finalScaled): its SSIM is overwritten below
+        c->steps = n;
+        if (q < TS_MIN_QUALITY) return FNX_OK;
+        FNX_TRY(ssim_against(img, fw * 4, fw, fh, &c->ssim));
+        c->strategy = FNX_TS_QUALITY_SCALE; c->quality = q; c->final_w = fw; c->final_h = fh; c->nbytes = static_cast<int64_t>(sz);
+        return FNX_OK;
+    }
+
+    // ---- strategy 4: scaleSearch(src, target, JPEG) (targetsize.go:285-357) ----
+    int scale(fnx_size_candidate *c)
+    {
+        int n = 0, best_q = 0;
+        double lo = 0.05, hi = 1.0, best = 0.0;
+        for (int i = 0; i < 12; i++) {
+            if (cancelled()) break;
+            const double mid = (lo + hi) / 2;
+            const int nw = static_cast<int>(static_cast<double>(w) * mid), nh = static_cast<int>(static_cast<double>(h) * mid);
+            if (nw < 1 || nh < 1) {
+                lo = mid;
+                continue;
+            }
+            int q = 0;
+            size_t sz = 0;
+            FNX_TRY(scaled_query(nw, nh, &q, &sz, &n));
+            if (q != 0 && static_cast<long long>(sz) <= target && q >= TS_MIN_QUALITY) {   // testScaleFits
+                best = mid; best_q = q;
+                lo = mid;
+            } else {
+                hi = mid;
+            }
+        }
+        c->steps = n;
+        if (best == 0.0) return FNX_OK;
+        // executeFinalScaleEncode: jpegQualitySearchFast of the Lanczos image, else the file at bestQ (which may not fit)
+        const int fw = static_cast<int>(static_cast<double>(w) * best), fh = static_cast<int>(static_cast<double>(h) * best);
+        uint8_t *img = nullptr;
+        JpegPlanes pl;
+        FNX_TRY(lanczos_scaled(fw, fh, &img, &pl));
+        int q = 0;
+        size_t sz = 0;
+        FNX_TRY(bisect(pl, fw, fh, &q, &sz, &n));
+        if (q == 0) {
+            q = best_q;
+            FNX_TRY(jpeg_file_from_planes(ctx, pl, fw, fh, q, nullptr, 0, &sz));
+            n++;
+        }
+        c->steps = n;
+        FNX_TRY(ssim_against(img, fw * 4, fw, fh, &c->ssim));
+        c->strategy = FNX_TS_SCALE; c->quality = q; c->final_w = fw; c->final_h = fh; c->nbytes = static_cast<int64_t>(sz);
+        return FNX_OK;
+    }
+
+    // ---- fallbackTargetSizeEncode's JPEG branch (targetsize.go:77-90) ----
+    int fallback(fnx_size_candidate *c)
+    {
+        FNX_TRY(orig_planes());
+        size_t sz = 0;
+        FNX_TRY(jpeg_file_from_planes(ctx, orig, w, h, 1, nullptr, 0, &sz));
+        FNX_TRY(ssim_against(s.p, s.stride, w, h, &c->ssim));     // computeSSIMNRGBA(original, original)
+        c->strategy = FNX_TS_FALLBACK; c->quality = 1; c->final_w = w; c->final_h = h; c->steps = 1;
+        c->nbytes = static_cast<int64_t>(sz);
+        return FNX_OK;
+    }
+};
+
+// betterFit (targetsize.go:92-115)
+bool better_fit(const fnx_size_candidate &c, const fnx_size_candidate &b, long long t)
+{
+    const bool cu = c.nbytes <= t, bu = b.nbytes <= t;
+    if (cu && !bu) return true;
+    if (!cu && bu) return false;
+    if (cu && bu) {
+        if (c.ssim != b.ssim) return c.ssim > b.ssim;
+        return c.quality > b.quality;
+    }
+    return c.nbytes < b.nbytes;
+}
+
+}  // namespace
+
+int fnx_jpeg_target_size(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, long long target_bytes, int strategies,
+                         const double *window, const volatile int *cancel, fnx_size_candidate cand[4], int *winner, uint8_t *out,
+                         size_t cap, size_t *nbytes, uint8_t *img, int istride)
+{
+    FNX_ENTER(ctx);
+    FNX_TRY(check_space(space));
+    FNX_REQUIRE(cand && winner && nbytes, "target_size: cand, winner and nbytes are required");
+    FNX_REQUIRE(window, "target_size: window is required");
+    FNX_REQUIRE(w > 0 && h > 0 && w <= 65535 && h <= 65535, "target_size: dimensions must be 1..65535 (JPEG dims are 16-bit)");
+    FNX_REQUIRE(target_bytes > 0, "target_size: target_bytes must be > 0");
+    FNX_REQUIRE(strategies > 0 && (strategies & ~(FNX_TS_QUALITY | FNX_TS_QUALITY_SCALE | FNX_TS_SCALE | FNX_TS_FALLBACK)) == 0,
+                "target_size: strategies must be a non-empty subset of bits 1, 2, 4, 8");
+    FNX_REQUIRE(img == nullptr || istride >= 4 * w, "target_size: img needs a stride of at least 4 * w (the source's width)");
+    FNX_TRY(check_img(src, sstride, w, h, "src"));
+    std::memset(cand, 0, sizeof(fnx_size_candidate) * 4);
+    *winner = -1;
+    *nbytes = 0;
+    TsRun run{ctx, {}, w, h, target_bytes, window, cancel};
+    FNX_TRY(stage_in(ctx, space, src, sstride, w, h, SLOT_IN_A, &run.s));
+    // hitTargetSize (targetsize.go:26-75): the JPEG legs in the reference's order, ctx.Err() before each
+    if ((strategies & FNX_TS_QUALITY) && !run.cancelled()) FNX_TRY(run.quality(&cand[0]));
+    if ((strategies & FNX_TS_QUALITY_SCALE) && !run.cancelled()) FNX_TRY(run.quality_scale(&cand[1]));
+    auto none = [&] { return !cand[0].strategy && !cand[1].strategy && !cand[2].strategy; };
+    if ((strategies & FNX_TS_SCALE) && none() && !run.cancelled()) FNX_TRY(run.scale(&cand[2]));
+    if ((strategies & FNX_TS_FALLBACK) && none()) FNX_TRY(run.fallback(&cand[3]));       // also after a cancellation
+    int best = -1;
+    for (int i = 0; i < 4; i++)
+        if (cand[i].strategy && (best < 0 || better_fit(cand[i], cand[best], target_bytes))) best = i;
+    if (best < 0) return FNX_NOOP;
+    *winner = best;
+    const fnx_size_candidate &c = cand[best];
+    JpegPlanes pl;
+    if (best == 1 || best == 2) {
+        // the winner's image (SLOT_TS_SCALED) and its planes once more: a later query may have used SLOT_JPEG1
+        const uint8_t *scaled = static_cast<const uint8_t *>(ctx->slot[SLOT_TS_SCALED].p);
+        FNX_TRY(jpeg_planes(ctx, SLOT_JPEG1, c.final_w, c.final_h, &pl));
+        FNX_TRY(launch_jpeg_ycc(ctx, scaled, c.final_w * 4, c.final_w, c.final_h, pl.p[0], pl.p[1], pl.p[2]));
+        if (img)
+            FNX_HIP(hipMemcpy2DAsync(img, istride, scaled, size_t(c.final_w) * 4, size_t(c.final_w) * 4, c.final_h,
+                                     space == FNX_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+    } else {
+        FNX_TRY(run.orig_planes());
+        pl = run.orig;
+    }
+    FNX_TRY(jpeg_file_from_planes(ctx, pl, c.final_w, c.final_h, c.quality, out, cap, nbytes));
+    if (space == FNX_HOST) FNX_HIP(hipStreamSynchronize(ctx->stream));
+    return FNX_OK;
+}
+
 // ---- image.Decode of a baseline JPEG on the device (third slice: jpeg_dec.hip) ----------------
 // toNRGBARef(jpeg.Decode(data)) into SLOT_JPEG_DEC_IMG (tight rows); *f describes the file
 int fnx_jpeg_decode(fnx_ctx *ctx, const uint8_t *data, size_t n, int space, uint8_t *dst, int dstride, int *w, int *h)

@@ -102,6 +102,7 @@ enum Slot {
     SLOT_FILE0, SLOT_FILE1, SLOT_FILE_SAMPLES,                     // host_api.cpp: fennec_CompressFileJPEG's images between its stages
     SLOT_JPEG_DEC, SLOT_JPEG_DEC_PLANES, SLOT_JPEG_DEC_IMG,        // jpeg_dec.hip: the decoder's work arrays, its planes, toNRGBARef's image
     SLOT_AN_HASH0, SLOT_AN_HASH1,   // analyze.hip: the colour-set tables of this call and the next (the launch that uses one zeroes the other)
+    SLOT_TS_SCALED, SLOT_TS_UP,    // api.cpp: fnx_jpeg_target_size's Lanczos-scaled image and its upscale back to the source's size
     SLOT_DONE,       // workgroup counters of the kernels that finish their own reduction (ssim.hip), zero between launches
     SLOT_COUNT
 };
@@ -475,6 +476,9 @@ void jpeg_plane_dims(int w, int h, int *ys, int *yh, int *cs, int *ch);
 int launch_jpeg_ycc(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, uint8_t *yp, uint8_t *cbp, uint8_t *crp);
 int launch_jpeg_ycc_planes(fnx_ctx *ctx, const uint8_t *dy, int dys, const uint8_t *dcb, const uint8_t *dcr, int dcs, int ratio, int w, int h,
                            uint8_t *yp, uint8_t *cbp, uint8_t *crp);
+// the planes of boxDownsample(src, dw, dh) straight from the w x h source, the downsampled image never written
+int launch_jpeg_box_ycc(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, int dw, int dh, uint8_t *yp, uint8_t *cbp,
+                        uint8_t *crp);
 void jpeg_header(int w, int h, int quality, std::vector<uint8_t> &out);
 int jpeg_entropy_code(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *const planes[3], unsigned long long *totals);
 size_t jpeg_ecs_capacity(unsigned long long total_bits);

@@ -90,6 +90,149 @@ __global__ __launch_bounds__(256) void jpeg_ycc_kernel(YccArgs a)
     *reinterpret_cast<uint16_t *>(a.crp + static_cast<size_t>(py / 2) * a.cs + px / 2) = static_cast<uint16_t>(cr2);
 }
 
+// ------------------------------------------------------------------------------------
+// jpeg_ycc_kernel's planes of boxDownsample(src, dw, dh) (ssim.go:244-309) without the downsampled image: the target-size
+// searches (targetsize.go:210-357) ask for the file size of up to 26 scaled copies of one source, and every copy would
+// otherwise be written as NRGBA only to be read back by the colour conversion.  Workgroup = one chroma row (two padded
+// output rows) x a segment of padded output columns.  Per output row: box_tiled_body's column sums (16-byte loads, packed
+// 2 x 16-bit per source column, <= 257 box rows) into LDS, then one lane per output column adds its box's columns and
+// finishes with the one fp64 multiply by 1 / count -- the same integers and the same clampF as box_tiled_kernel /
+// box_generic_kernel.  Shapes the column sums do not cover (an upscale, boxes over 256 px) take box_generic_kernel's
+// per-pixel sums (GENERIC).  The two rows' pixels then go through rgb_to_ycc and writer.go's chroma averaging exactly as
+// in jpeg_ycc_kernel; padded positions take the box pixel at min(x, dw - 1) / min(y, dh - 1).
+// ------------------------------------------------------------------------------------
+constexpr int JB_CHUNKS = 256;            // 16-byte chunks (4 px) of the source a workgroup row covers
+constexpr int JB_MAXROWS = 257;           // 257 * 255 < 65536: the packed column sums cannot overflow
+constexpr int JB_SEG = 240;               // most box columns per workgroup: + 15 padding columns <= 256 lanes
+
+struct BoxYccJob {
+    const uint8_t *src;
+    int sstride, srcW, srcH;
+    int dw, dh;
+    double xRatio, yRatio;
+    int seg, vec_in;
+    uint8_t *yp, *cbp, *crp;
+    int ys, cs;
+};
+
+template <bool GENERIC>
+__global__ __launch_bounds__(256) void jpeg_box_ycc_kernel(BoxYccJob a)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t s_col[JB_CHUNKS * 4 * 2];
+    __shared__ uint32_t s_px[2][256];
+    const int tid = threadIdx.x;
+    const int py = 2 * blockIdx.y;                                  // first padded output row of the chroma row
+    const int dx_lo = blockIdx.x * a.seg;
+    const int dx_hi = min(dx_lo + a.seg, a.dw);                     // box columns of this segment
+    const int dx_end = dx_hi == a.dw ? a.ys : dx_hi;                // ... plus the MCU padding in the last one
+    const int ncol = dx_end - dx_lo;
+    const int bxc = min(dx_lo + tid, a.dw - 1);                     // this lane's box column (padding: the last one)
+    int sx0, sx1;
+    box_edge(bxc, a.xRatio, a.srcW, sx0, sx1);
+    int c0 = 0, nchunk = 0;
+    if (!GENERIC) {
+        int sxa, t1, t0, sxb;
+        box_edge(dx_lo, a.xRatio, a.srcW, sxa, t1);
+        box_edge(dx_hi - 1, a.xRatio, a.srcW, t0, sxb);
+        c0 = sxa >> 2;
+        nchunk = ((sxb + 3) >> 2) - c0;                             // <= JB_CHUNKS by the choice of seg
+    }
+    const int nrow = min(py + 1, a.dh - 1) == min(py, a.dh - 1) ? 1 : 2;   // padding rows repeat row dh - 1
+    for (int j = 0; j < nrow; j++) {
+        const int ry = min(py + j, a.dh - 1);
+        int sy0, sy1;
+        box_edge(ry, a.yRatio, a.srcH, sy0, sy1);
+        uint32_t px = 0;
+        if (GENERIC) {
+            if (tid < ncol) {
+                unsigned long long r = 0, g = 0, b = 0, al = 0;
+                for (int sy = sy0; sy < sy1; sy++) {
+                    const uint8_t *row = a.src + static_cast<size_t>(sy) * a.sstride;
+                    for (int sx = sx0; sx < sx1; sx++) {
+                        const uint32_t p = ld_px(row, sx);
+                        r += p & 0xffu; g += (p >> 8) & 0xffu; b += (p >> 16) & 0xffu; al += p >> 24;
+                    }
+                }
+                const long long count = static_cast<long long>(sy1 - sy0) * (sx1 - sx0);
+                if (count > 0) {                                    // count == 0 (an upscale's sx1 == 0): the zero pixel
+                    const double inv = 1.0 / static_cast<double>(count);
+                    px = clampF_dev(static_cast<double>(r) * inv) | (clampF_dev(static_cast<double>(g) * inv) << 8) |
+                         (clampF_dev(static_cast<double>(b) * inv) << 16) | (clampF_dev(static_cast<double>(al) * inv) << 24);
+                }
+            }
+        } else {
+            if (tid < nchunk) {
+                const int x = 4 * (c0 + tid);
+                uint32_t lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0};
+                const uint8_t *p = a.src + static_cast<size_t>(sy0) * a.sstride;
+                if (a.vec_in && x + 3 < a.srcW) {
+                    // four rows of 16-byte loads in flight per trip; a short last trip re-reads the box's last row and adds
+                    // nothing for it
+                    const uint8_t *q = p + 4 * static_cast<size_t>(x);
+                    for (int sy = sy0; sy < sy1; sy += 4) {
+                        u32x4 v[4];
+#pragma unroll
+                        for (int u = 0; u < 4; u++) v[u] = ld16_stream(q + static_cast<size_t>(min(sy + u, sy1 - 1) - sy0) * a.sstride);
+#pragma unroll
+                        for (int u = 0; u < 4; u++) {
+                            if (sy + u < sy1) {                     // uniform across the workgroup: one box row
+#pragma unroll
+                                for (int e = 0; e < 4; e++) {
+                                    lo[e] += v[u][e] & 0x00ff00ffu;
+                                    hi[e] += (v[u][e] >> 8) & 0x00ff00ffu;
+                                }
+                            }
+                        }
+                    }
+                } else {
+                    // an unaligned source, or the chunk that sticks out of the row: pixel by pixel, clamped (the surplus
+                    // columns belong to no box)
+                    for (int sy = sy0; sy < sy1; sy++, p += a.sstride) {
+#pragma unroll
+                        for (int e = 0; e < 4; e++) {
+                            const uint32_t q = ld_px(p, min(x + e, a.srcW - 1));
+                            lo[e] += q & 0x00ff00ffu;
+                            hi[e] += (q >> 8) & 0x00ff00ffu;
+                        }
+                    }
+                }
+                uint4 *sp = reinterpret_cast<uint4 *>(s_col + tid * 8);
+                sp[0] = make_uint4(lo[0], hi[0], lo[1], hi[1]);
+                sp[1] = make_uint4(lo[2], hi[2], lo[3], hi[3]);
+            }
+            __syncthreads();
+            if (tid < ncol) {
+                uint32_t r = 0, g = 0, b = 0, al = 0;
+                for (int sx = sx0; sx < sx1; sx++) {
+                    const uint2 c = *reinterpret_cast<const uint2 *>(s_col + (sx - 4 * c0) * 2);
+                    r += c.x & 0xffffu; b += c.x >> 16;
+                    g += c.y & 0xffffu; al += c.y >> 16;
+                }
+                px = box_finish(r, g, b, al, (sy1 - sy0) * (sx1 - sx0));   // a downscale: every box is non-empty
+            }
+        }
+        if (tid < ncol) s_px[j][tid] = px;
+        __syncthreads();                                            // s_col is refilled by the next row
+    }
+    // lane = a pair of padded columns: 2 x 2 pixels -> 4 luma samples and one (Cb, Cr) pair, as jpeg_ycc_kernel
+    if (2 * tid < ncol) {
+        uint32_t ycc[2][2];
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int i = 0; i < 2; i++) ycc[j][i] = rgb_to_ycc(s_px[j < nrow ? j : 0][2 * tid + i]);
+        const int dx = dx_lo + 2 * tid;
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+            *reinterpret_cast<uint16_t *>(a.yp + static_cast<size_t>(py + j) * a.ys + dx) =
+                static_cast<uint16_t>((ycc[j][0] & 0xffu) | ((ycc[j][1] & 0xffu) << 8));
+        const uint32_t sb = ((ycc[0][0] >> 8) & 0xffu) + ((ycc[0][1] >> 8) & 0xffu) + ((ycc[1][0] >> 8) & 0xffu) + ((ycc[1][1] >> 8) & 0xffu);
+        const uint32_t sr = ((ycc[0][0] >> 16) & 0xffu) + ((ycc[0][1] >> 16) & 0xffu) + ((ycc[1][0] >> 16) & 0xffu) + ((ycc[1][1] >> 16) & 0xffu);
+        a.cbp[static_cast<size_t>(py / 2) * a.cs + dx / 2] = static_cast<uint8_t>((sb + 2) >> 2);
+        a.crp[static_cast<size_t>(py / 2) * a.cs + dx / 2] = static_cast<uint8_t>((sr + 2) >> 2);
+    }
+}
+
 // ---- fdct.go (jfdctint.c's algorithm, 13-bit constants) and idct.go (Chen-Wang) on 8 values in registers ----
 template <int PASS>
 __device__ __forceinline__ void fdct8(int32_t &x0, int32_t &x1, int32_t &x2, int32_t &x3, int32_t &x4, int32_t &x5, int32_t &x6, int32_t &x7)
@@ -214,6 +357,36 @@ int launch_jpeg_ycc_planes(fnx_ctx *ctx, const uint8_t *dy, int dys, const uint8
     a.w = w; a.h = h; a.yp = yp; a.cbp = cbp; a.crp = crp; a.my = yh / 16;
     a.dy = dy; a.dcb = dcb; a.dcr = dcr; a.dys = dys; a.dcs = dcs; a.dxs = xs[ratio]; a.dysh = ysh[ratio];
     hipLaunchKernelGGL(jpeg_ycc_kernel, dim3((a.ys / 4 + 63) / 64, (yh / 2 + 3) / 4), dim3(256), 0, ctx->stream, a);
+    FNX_HIP(hipGetLastError());
+    return FNX_OK;
+}
+
+// src (device NRGBA, w x h) -> the unquantised planes of boxDownsample(src, dw, dh) (jpeg_box_ycc_kernel)
+int launch_jpeg_box_ycc(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, int dw, int dh, uint8_t *yp, uint8_t *cbp,
+                        uint8_t *crp)
+{
+    if (w <= 0 || h <= 0 || dw <= 0 || dh <= 0) {
+        set_error("invalid argument: box-downsampled planes of a %d x %d image at %d x %d", w, h, dw, dh);
+        return FNX_ERR_INVALID;
+    }
+    BoxYccJob a{};
+    int yh, chh;
+    jpeg_plane_dims(dw, dh, &a.ys, &yh, &a.cs, &chh);
+    a.src = src; a.sstride = sstride; a.srcW = w; a.srcH = h; a.dw = dw; a.dh = dh;
+    a.xRatio = static_cast<double>(w) / static_cast<double>(dw);   // ssim.go:251-252
+    a.yRatio = static_cast<double>(h) / static_cast<double>(dh);
+    a.yp = yp; a.cbp = cbp; a.crp = crp;
+    a.vec_in = aligned16(src, sstride);
+    // launch_box_downsample_pair's test for the column sums: boxes tile the source, fit 16-bit sums and one LDS row
+    const bool tiled = w >= dw && h >= dh && a.yRatio + 1.0 < JB_MAXROWS && a.xRatio + 1.0 < JB_MAXROWS &&
+                       a.xRatio * 2 + 8 < 4 * JB_CHUNKS;
+    int seg = tiled ? static_cast<int>((4 * JB_CHUNKS - 8) / a.xRatio) : JB_SEG;
+    seg = seg > JB_SEG ? JB_SEG : seg;
+    seg &= ~1;                                                     // chroma pairs never straddle two workgroups
+    a.seg = seg < 2 ? 2 : seg;
+    const dim3 grid((dw + a.seg - 1) / a.seg, yh / 2);
+    if (tiled) hipLaunchKernelGGL(jpeg_box_ycc_kernel<false>, grid, dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(jpeg_box_ycc_kernel<true>, grid, dim3(256), 0, ctx->stream, a);
     FNX_HIP(hipGetLastError());
     return FNX_OK;
 }

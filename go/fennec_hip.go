@@ -11,7 +11,8 @@
 // after renaming each shadowed function in the reference to its `...Go` twin (one-line edits,
 // listed in INTEGRATION.md) and giving the originals a `//go:build !fennec_hip` twin file.
 // Everything above these functions -- CompressFile/CompressBytes/CompressBatch, the JPEG
-// quality search, target-size mode, the CLI -- is untouched.
+// quality search, the CLI -- is untouched; target-size mode's JPEG strategies are replaced
+// behind the useDeviceSearch opt-in (hitTargetSize, INTEGRATION.md 8).
 //
 // NOTE: there is no Go toolchain in the image this repository is developed in, so this file
 // has never been compiled.  It is the binding a maintainer would add; the C ABI it calls is
@@ -29,11 +30,13 @@ package fennec
 
 /*
 #include <stdint.h>
+#include <stdlib.h>
 #include "fennec_hip.h"
 */
 import "C"
 
 import (
+	"context"
 	"image"
 	"image/color"
 	"log"
@@ -41,6 +44,7 @@ import (
 	"os"
 	"runtime"
 	"sync"
+	"sync/atomic"
 	"unsafe"
 )
 
@@ -898,4 +902,135 @@ func jpegQualitySearchOptHIP(src *image.NRGBA, targetBytes int, skipSSIM bool) (
 		return nil, 0, 0, true
 	}
 	return nil, 0, 0, false
+}
+
+// ---- targetsize.go: hitTargetSize's JPEG strategies on the device (opt-in) ---------------------
+
+// hitTargetSize replaces targetsize.go:26 (the reference's body renamed hitTargetSizeGo).  Behind the same opt-in as
+// jpegQualitySearchOptHIP: the files come from the device's encoder, whose byte parity with image/jpeg is unpinned.
+//   - PNG wanted, or no JPEG leg would run (Auto with a translucent source): the Go path;
+//   - JPEG wanted: ONE fnx_jpeg_target_size call with all four strategies;
+//   - Auto with an opaque source: the source goes up once, then strategy 1 on the device, quantizeStrategy on the host,
+//     strategy 3 on the device and -- only when nothing came back, the PNG candidate included -- strategy 4 and the JPEG
+//     fallback on the device.  The reference's strategy order, ctx.Err() checks and betterFit tie rule are kept across
+//     the PNG candidate.
+func hitTargetSize(ctx context.Context, original *image.NRGBA, targetBytes int, opts Options) (*sizeResult, error) {
+	w, h := original.Bounds().Dx(), original.Bounds().Dy()
+	wantJPEG := opts.Format == JPEG
+	if !useDeviceSearch || opts.Format == PNG || w <= 0 || h <= 0 || w > 65535 || h > 65535 || targetBytes <= 0 {
+		return hitTargetSizeGo(ctx, original, targetBytes, opts)
+	}
+	canUseJPEG := isOpaque(original)
+	if !wantJPEG && !canUseJPEG {
+		return hitTargetSizeGo(ctx, original, targetBytes, opts)
+	}
+	rs := uploadSrc(original)
+	defer rs.close()
+	var dimg unsafe.Pointer // the winner's scaled image on the device (w x h is enough: scales are below 1)
+	if rs.c == nil || C.fnx_malloc(rs.c, C.size_t(4*w*h), &dimg) != C.FNX_OK {
+		fellBack("hitTargetSize")
+		return hitTargetSizeGo(ctx, original, targetBytes, opts)
+	}
+	defer C.fnx_free(rs.c, dimg)
+	// the cancel word: set before the first call when ctx is already done, else by the watcher when it becomes done
+	cancel := (*C.int)(C.malloc(C.size_t(unsafe.Sizeof(C.int(0)))))
+	defer C.free(unsafe.Pointer(cancel))
+	*cancel = 0
+	if ctx.Err() != nil {
+		*cancel = 1
+	}
+	stop := make(chan struct{})
+	defer close(stop)
+	go func() {
+		select {
+		case <-ctx.Done():
+			atomic.StoreInt32((*int32)(unsafe.Pointer(cancel)), 1)
+		case <-stop:
+		}
+	}()
+	// one call -> its winner (nil: no candidate); ok == false: the device failed and the Go path takes the item
+	run := func(strategies C.int) (*sizeResult, bool) {
+		var cand [4]C.fnx_size_candidate
+		var win C.int
+		var n C.size_t
+		buf := make([]byte, targetBytes+4096)
+		st := C.fnx_jpeg_target_size(rs.c, C.FNX_DEVICE, (*C.uint8_t)(rs.d), C.int(rs.stride), C.int(w), C.int(h),
+			C.longlong(targetBytes), strategies, (*C.double)(unsafe.Pointer(&ssimWindow[0])), cancel, &cand[0], &win,
+			(*C.uint8_t)(unsafe.Pointer(&buf[0])), C.size_t(len(buf)), &n, (*C.uint8_t)(dimg), C.int(4*w))
+		if st == C.FNX_NOOP {
+			return nil, true
+		}
+		tooSmall := st == C.FNX_ERR_INVALID && int(n) > len(buf) && win >= 0
+		if st != C.FNX_OK && !tooSmall {
+			return nil, false
+		}
+		c := cand[int(win)]
+		scaled := c.strategy == C.FNX_TS_QUALITY_SCALE || c.strategy == C.FNX_TS_SCALE
+		if tooSmall {
+			// a winner over the target (the fallback, strategy 4's encode at bestQ): its file from the image the call
+			// left on the device, at its quality -- no second search
+			img, stride := rs.d, rs.stride
+			if scaled {
+				img, stride = dimg, 4*w
+			}
+			buf = make([]byte, int(n))
+			if C.fnx_jpeg_encode(rs.c, C.FNX_DEVICE, (*C.uint8_t)(img), C.int(stride), c.final_w, c.final_h, c.quality,
+				(*C.uint8_t)(unsafe.Pointer(&buf[0])), C.size_t(len(buf)), &n) != C.FNX_OK {
+				return nil, false
+			}
+		}
+		r := &sizeResult{data: buf[:int(n)], format: JPEG, quality: int(c.quality), ssim: float64(c.ssim),
+			finalW: int(c.final_w), finalH: int(c.final_h), img: original}
+		if scaled {
+			r.img = image.NewNRGBA(image.Rect(0, 0, r.finalW, r.finalH))
+			if C.fnx_download(rs.c, unsafe.Pointer(pix(r.img)), C.int(r.img.Stride), dimg, C.int(4*w), C.int(r.finalW),
+				C.int(r.finalH)) != C.FNX_OK {
+				return nil, false
+			}
+		}
+		return r, true
+	}
+	goPath := func() (*sizeResult, error) {
+		fellBack("hitTargetSize")
+		return hitTargetSizeGo(ctx, original, targetBytes, opts)
+	}
+	if wantJPEG {
+		r, ok := run(C.FNX_TS_QUALITY | C.FNX_TS_QUALITY_SCALE | C.FNX_TS_SCALE | C.FNX_TS_FALLBACK)
+		if !ok || r == nil {
+			return goPath()
+		}
+		return r, nil
+	}
+	r, ok := run(C.FNX_TS_QUALITY)
+	if !ok {
+		return goPath()
+	}
+	candidates := make([]*sizeResult, 0, 3)
+	if r != nil {
+		candidates = append(candidates, r)
+	}
+	if ctx.Err() == nil {
+		if q, err := quantizeStrategy(original, targetBytes); err == nil && q != nil {
+			candidates = append(candidates, q)
+		}
+	}
+	if r, ok = run(C.FNX_TS_QUALITY_SCALE); !ok {
+		return goPath()
+	}
+	if r != nil {
+		candidates = append(candidates, r)
+	}
+	if len(candidates) == 0 {
+		if r, ok = run(C.FNX_TS_SCALE | C.FNX_TS_FALLBACK); !ok || r == nil {
+			return goPath()
+		}
+		candidates = append(candidates, r)
+	}
+	best := candidates[0]
+	for _, c := range candidates[1:] {
+		if betterFit(c, best, targetBytes) {
+			best = c
+		}
+	}
+	return best, nil
 }

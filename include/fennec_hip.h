@@ -323,6 +323,41 @@ int fnx_jpeg_compress(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, 
                       int *steps /* may be NULL */);
 int fnx_jpeg_quality_search(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, double target_ssim,
                             const double *window /* 64 */, int *quality, double *ssim, int *steps);
+/* jpeg.Encode(boxDownsample(src, dw, dh), quality) (ssim.go:244, io.go:157): the scaled image is never materialised --
+ * the box sums go straight into the encoder's YCbCr planes (jpeg.hip: jpeg_box_ycc_kernel).  src is w x h in `space`,
+ * dw x dh anything from 1 x 1 up to 65535 (also above w x h, as boxDownsample allows).  out / cap / *nbytes as
+ * fnx_jpeg_encode: out == NULL with cap == 0: the size only (testScaleFits / findBestScale*'s question). */
+int fnx_jpeg_encode_scaled(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int dw, int dh,
+                           int quality, uint8_t *out, size_t cap, size_t *nbytes);
+/* hitTargetSize's JPEG strategies (targetsize.go:26-357) in one call, the source staged once and every scale step's
+ * file size taken on the device (fnx_jpeg_encode_scaled's planes; 8 bytes come back per size query).  `strategies`: */
+#define FNX_TS_QUALITY 1       /* strategy 1: jpegQualitySearch(src)                        targetsize.go:33-37, 117-176 */
+#define FNX_TS_QUALITY_SCALE 2 /* strategy 3: jpegQualityScaleSearch                        targetsize.go:45-49, 210-283 */
+#define FNX_TS_SCALE 4         /* strategy 4: scaleSearch(src, target, JPEG); runs only when no
+                                  strategy of this call produced a candidate                targetsize.go:51-62, 285-357 */
+#define FNX_TS_FALLBACK 8      /* fallbackTargetSizeEncode's JPEG branch: quality 1 at full size,
+                                  ssim = computeSSIMNRGBA(src, src); only when nothing else  targetsize.go:64-90 */
+typedef struct fnx_size_candidate {
+    int32_t strategy;        /* the FNX_TS_* bit; 0: not run or no candidate */
+    int32_t quality, final_w, final_h;
+    int32_t steps;           /* encodes this strategy ran (size queries, plus strategy 4's encode at bestQ when its final
+                                search finds nothing; the fallback's one) -- also when it produced no candidate */
+    int32_t reserved;
+    int64_t nbytes;          /* len(data) */
+    double ssim;             /* sizeResult.ssim exactly as the reference sets it */
+} fnx_size_candidate;
+/* cand[i]: strategy bit i's result (cand[0] FNX_TS_QUALITY ... cand[3] FNX_TS_FALLBACK); *winner: the index betterFit
+ * (targetsize.go:92-115) picks over them in the reference's order, a tie keeping the earlier one.  `out` gets the
+ * winner's file (out == NULL with cap == 0: *nbytes only); `img` (may be NULL; in `space`, stride istride >= 4 w) the
+ * winner's final_w x final_h Lanczos image when it is strategy 3's or 4's -- left untouched otherwise (the image is then
+ * the source).  *cancel != 0 (may be NULL) is looked at where the reference checks ctx.Err(): before each strategy and
+ * each scale step; the fallback runs also after a cancellation, as the reference's does.  FNX_OK: there is a winner;
+ * FNX_NOOP: no candidate; FNX_ERR_INVALID: bad arguments, or cap too small -- then *nbytes, cand, *winner and img are
+ * filled and fnx_jpeg_encode(img or src, cand[*winner].quality) gives the file without searching again. */
+int fnx_jpeg_target_size(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, long long target_bytes,
+                         int strategies, const double *window /* 64 */, const volatile int *cancel /* may be NULL */,
+                         fnx_size_candidate cand[4], int *winner, uint8_t *out, size_t cap, size_t *nbytes, uint8_t *img,
+                         int istride);
 /* SURVEY 8(f)2, third slice -- image.Decode of a JPEG source (batch.go:88-101 via io.go:60-95) on the device:
  * dst = toNRGBARef(jpeg.Decode(data)), *w x *h.  `data` is HOST memory (the file); dst is in `space`.  dst == NULL:
  * only the dimensions (jpeg.DecodeConfig) -- and whether the device decoder takes the file at all (host work: ctx may be
@@ -593,7 +628,8 @@ int fennec_CompressBatchNRGBADevices(const int *devices, int ndev, int workers, 
  * smartResize when max_w or max_h > 0 (Options.MaxWidth / MaxHeight), analyzeFormat when auto_format (Format: Auto),
  * compressJPEGOptimal at target_ssim.  dims = {OriginalDimensions (after orientation), FinalDimensions}.
  * FNX_NOOP: analyzeFormat chose PNG (fewer than 256 sampled colours) -- the caller's compressPNG takes the item, dims are
- * set.  FNX_ERR_UNSUPPORTED as fnx_jpeg_decode.  Target-size mode stays the caller's (fnx_jpeg_size_search is its JPEG leg). */
+ * set.  FNX_ERR_UNSUPPORTED as fnx_jpeg_decode.  Target-size mode is a call of its own: hitTargetSize's JPEG
+ * strategies run on the device in fnx_jpeg_target_size (the PNG strategy stays the caller's). */
 typedef struct fennec_FileOptions {
     int32_t orient;      /* EXIF orientation 1..8; <= 1: none */
     int32_t max_w, max_h;
