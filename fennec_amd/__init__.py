@@ -202,6 +202,9 @@ def load_library() -> C.CDLL:
                                              _f64p, C.POINTER(i)])
         _sig(L, "fnx_jpeg_compress", i, [ctx, i] + img + [i, i, d, _f64p, _u8p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i), _f64p,
                                           C.POINTER(i)])
+        _sig(L, "fnx_jpeg_compress_batch", i, [ctx, i, C.POINTER(C.c_void_p), i, i, i, _f64p, _f64p, C.POINTER(C.c_void_p),
+                                                C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(i), _f64p, C.POINTER(i),
+                                                C.POINTER(i)])
         _sig(L, "fnx_jpeg_roundtrip", i, [ctx, i] + img + [i, i, i] + img)
         _sig(L, "fnx_jpeg_decode", i, [ctx, _u8p, C.c_size_t, i, C.c_void_p, i, C.POINTER(i), C.POINTER(i)])
         _sig(L, "fnx_jpeg_progressive_coefficients", i, [_u8p, C.c_size_t, C.POINTER(C.c_int16), C.c_size_t, C.POINTER(C.c_size_t),
@@ -724,6 +727,44 @@ class Context:
                     break
                 cap = n.value
         self._chk(rc, "fnx_jpeg_compress")
+
+    def jpeg_compress_batch(self, imgs, target_ssim, window=None):
+        """compressJPEGOptimal of n device images of one geometry in one call (fnx_jpeg_compress_batch) -> a list of
+        (bytes, quality, ssim, steps): item i's is what jpeg_compress(imgs[i], target_ssim[i]) returns.  target_ssim: one
+        float for every item, or a sequence of n."""
+        views = [_Img(t) for t in imgs]
+        if not views or any(v.space != FNX_DEVICE for v in views):
+            raise FennecError("jpeg_compress_batch takes a non-empty list of device tensors")
+        v0 = views[0]
+        if any((v.w, v.h, v.stride) != (v0.w, v0.h, v0.stride) for v in views):
+            raise FennecError("every image of a batch must share width, height and stride")
+        n = len(views)
+        if isinstance(target_ssim, (int, float)):
+            targets = [float(target_ssim)] * n
+        else:
+            targets = [float(t) for t in target_ssim]
+            if len(targets) != n:
+                raise FennecError(f"jpeg_compress_batch: {len(targets)} targets for {n} images")
+        k, pk = _f64(self.gaussianKernel() if window is None else window)
+        tg, ptg = _f64(targets)
+        cap = 4096 + (v0.w * v0.h * 3) // 2          # as jpeg_compress
+        buf = np.empty((n, cap), dtype=np.uint8)
+        srcs = (C.c_void_p * n)(*[v.ptr for v in views])
+        outs = (C.c_void_p * n)(*[buf.ctypes.data + i * cap for i in range(n)])
+        caps = (C.c_size_t * n)(*([cap] * n))
+        nb, q, st, status = (C.c_size_t * n)(), (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        v = (C.c_double * n)()
+        with self._ordered(*imgs):
+            self._chk(self._lib.fnx_jpeg_compress_batch(self._h, n, srcs, v0.stride, v0.w, v0.h, ptg, pk, outs, caps, nb, q, v, st,
+                                                        status), "fnx_jpeg_compress_batch")
+            res = []
+            for i in range(n):
+                if status[i] == FNX_OK:
+                    data = buf[i, :nb[i]].tobytes()
+                else:                                       # the buffer was small: the file at the quality found, no new search
+                    data = self.jpeg_encode(imgs[i], q[i])
+                res.append((data, q[i], v[i], st[i]))
+        return res
 
     def jpeg_encode_scaled(self, img, dw: int, dh: int, quality: int, size_only: bool = False):
         """jpeg.Encode(boxDownsample(img, dw, dh), quality) (fnx_jpeg_encode_scaled) without the scaled image -> the file's

@@ -1554,6 +1554,232 @@ int fnx_jpeg_compress(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, 
     return jpeg_file_from_planes(ctx, orig, w, h, *quality, out, cap, nbytes);
 }
 
+// ---- compressJPEGOptimal of n device images of one geometry in lockstep (fnx_jpeg_compress_batch) -------------------------
+// Per item, jpeg_search_device's search and jpeg_file_from_planes' file.  The items still searching take ONE set of launches
+// per step (each at its own mid) and ONE read-back of their scores; the winners are entropy-coded together with one read-back
+// per phase.  Every kernel runs the single call's arithmetic on each item, and SSIMFast picks its kernel, tiling and
+// reduction order as for one image: per item, the results are fnx_jpeg_compress's bit for bit.
+namespace {
+
+// device scratch a chunk of the batch may hold (orig + candidate planes, reference / candidate SSIMFast planes, decoded
+// candidates where the route needs them, the entropy coder's per-block arrays); the entropy coder's bit strings and file
+// bytes come on top (about 3 x the files' size)
+constexpr size_t JPEG_BATCH_SCRATCH = size_t(1) << 30;
+
+size_t al256(size_t v) { return (v + 255) & ~size_t(255); }
+
+const uint32_t *jpeg_qtab_host()
+{
+    static const std::vector<uint32_t> t = [] {
+        std::vector<uint32_t> v(JPEG_QTAB_WORDS);
+        jpeg_qtab(v.data());
+        return v;
+    }();
+    return t.data();
+}
+
+struct BatchSearch {
+    double target;
+    int lo, hi, best_q, n;
+    double best_ssim;
+    bool found;
+};
+
+}  // namespace
+
+int fnx_jpeg_compress_batch(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstride, int w, int h, const double *target_ssim,
+                            const double *window, uint8_t *const *outs, const size_t *caps, size_t *nbytes, int *quality, double *ssim,
+                            int *steps, int *status)
+{
+    FNX_ENTER(ctx);
+    FNX_REQUIRE(n >= 1 && n <= FNX_BATCH_MAX, "compress batch: n must be 1..FNX_BATCH_MAX (65535)");
+    FNX_REQUIRE(srcs && target_ssim && outs && caps && nbytes && quality && ssim && status, "compress batch: NULL array");
+    FNX_REQUIRE(window != nullptr, "compress batch: NULL window");
+    FNX_REQUIRE(w >= 1 && w <= 65535 && h >= 1 && h <= 65535, "compress batch: w and h must be 1..65535 (JPEG dims are 16-bit)");
+    FNX_REQUIRE(sstride >= 4 * w && (sstride & 3) == 0, "compress batch: sstride must be a multiple of 4 and >= 4 * w");
+    for (int i = 0; i < n; i++) {
+        if (!srcs[i] || !outs[i]) {
+            set_error("invalid argument: compress batch: srcs[%d] or outs[%d] is NULL", i, i);
+            return FNX_ERR_INVALID;
+        }
+    }
+    FNX_REQUIRE(ctx->res_count == 0, "enqueued batches are waiting for fnx_results_fetch: fetch them before a blocking batch call");
+
+    // the route is the single call's for this geometry: tested once, taken for every item
+    int pw, ph, ys, yh, cs, chh;
+    const bool ds = ssim_fast_dims(w, h, &pw, &ph);
+    const bool fused = ds && box_downsample_ycc_fused(w, h, pw, ph);     // candidate plane straight from its planes
+    const bool pixel = pw < 8 || ph < 8;                                 // pixelSSIM instead of the windowed form
+    jpeg_plane_dims(w, h, &ys, &yh, &cs, &chh);
+    size_t cb_off = 0, cr_off = 0;
+    const size_t PB = jpeg_batch_plane_bytes(w, h, &cb_off, &cr_off);
+    const size_t RB = al256(static_cast<size_t>(pw) * ph * 4 + 16);     // a tight SSIMFast plane
+    const size_t DB = al256(static_cast<size_t>(w) * h * 4 + 16);       // a decoded candidate (routes without the fused sums)
+    const size_t per_item = 2 * PB + RB + (ds ? RB : 0) + (fused ? 0 : DB) + jpeg_entropy_batch_bytes(w, h);
+    const size_t chunk_cap = JPEG_BATCH_SCRATCH / per_item;
+    const int chunk = static_cast<int>(chunk_cap < 1 ? 1 : (chunk_cap > static_cast<size_t>(n) ? n : chunk_cap));
+
+    void *dwin = nullptr, *dq = nullptr;
+    FNX_TRY(upload_table(ctx, SLOT_TABLE0, window, sizeof(double) * 64, &dwin));
+    FNX_TRY(upload_table(ctx, SLOT_JPEG_QTAB, jpeg_qtab_host(), sizeof(uint32_t) * JPEG_QTAB_WORDS, &dq));
+    const uint32_t *d_qtab = static_cast<const uint32_t *>(dq);
+
+    std::vector<BatchSearch> st(chunk);
+    std::vector<int2> jobs(chunk);
+    std::vector<const uint8_t *> pa(chunk), pb(chunk), pd(chunk);
+    std::vector<int> qv(chunk), act(chunk);
+    std::vector<double> vals(chunk);
+    std::vector<unsigned long long> tbits(chunk);
+    std::vector<size_t> ecs_off(chunk), ecs_len(chunk), host_off(chunk);
+    std::vector<std::vector<uint8_t>> hdr(101);
+    for (int c0 = 0; c0 < n; c0 += chunk) {
+        const int m = n - c0 < chunk ? n - c0 : chunk;
+        void *t = nullptr;
+        FNX_TRY(upload_table(ctx, SLOT_PTRS, srcs + c0, sizeof(void *) * m, &t));
+        const uint8_t *const *d_srcs = static_cast<const uint8_t *const *>(t);
+        // the unquantised planes and the prepared reference planes of the chunk's sources, one launch each
+        FNX_TRY(scratch(ctx, SLOT_JPEG0, PB * m, &t));
+        uint8_t *orig = static_cast<uint8_t *>(t);
+        FNX_TRY(launch_jpeg_ycc_batch(ctx, m, d_srcs, sstride, w, h, orig));
+        FNX_TRY(scratch(ctx, SLOT_JPEG3, RB * m, &t));
+        uint8_t *refs = static_cast<uint8_t *>(t);
+        if (ds) {
+            bool al = true;                                  // the single call's box kernel form depends on the source's alignment
+            for (int i = 0; i < m; i++) al = al && aligned16(srcs[c0 + i], sstride);
+            if (al) {
+                FNX_TRY(launch_box_downsample(ctx, m, nullptr, d_srcs, sstride, w, h, refs, pw * 4, RB, pw, ph));
+            } else {
+                for (int i = 0; i < m; i++)
+                    FNX_TRY(launch_box_downsample(ctx, 1, srcs[c0 + i], nullptr, sstride, w, h, refs + RB * i, pw * 4, 0, pw, ph));
+            }
+        } else {
+            FNX_TRY(launch_copy_tight_batch(ctx, m, d_srcs, sstride, w, h, refs, RB));
+        }
+        uint8_t *work = nullptr, *cand = nullptr, *dec = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_JPEG1, PB * m, &t));
+        work = static_cast<uint8_t *>(t);
+        if (ds) {
+            FNX_TRY(scratch(ctx, SLOT_TMP2, RB * m, &t));
+            cand = static_cast<uint8_t *>(t);
+        }
+        if (!fused) {
+            FNX_TRY(scratch(ctx, SLOT_JPEG2, DB * m, &t));
+            dec = static_cast<uint8_t *>(t);
+        }
+        // compress.go:24-74, per item
+        for (int i = 0; i < m; i++) {
+            BatchSearch &b = st[i];
+            b.target = target_ssim[c0 + i] >= 1.0 ? 0.999 : target_ssim[c0 + i];
+            b.lo = 1; b.hi = 100; b.best_q = 100; b.n = 0; b.best_ssim = 1.0; b.found = false;
+            if (b.target >= 0.99) b.lo = 75;
+            else if (b.target >= 0.97) b.lo = 50;
+            else if (b.target >= 0.94) b.lo = 30;
+            else if (b.target >= 0.90) b.lo = 15;
+        }
+        for (;;) {
+            int nj = 0;
+            for (int i = 0; i < m; i++) {
+                const BatchSearch &b = st[i];
+                if (b.lo > b.hi) continue;
+                act[nj] = i;
+                jobs[nj] = make_int2(i, (b.lo + b.hi) / 2);
+                pa[nj] = refs + RB * i;
+                pb[nj] = ds ? cand + RB * nj : dec + DB * nj;
+                pd[nj] = fused ? nullptr : dec + DB * nj;
+                nj++;
+            }
+            if (nj == 0) break;
+            const void *hosts[4] = {jobs.data(), pa.data(), pb.data(), pd.data()};
+            const size_t sizes[4] = {sizeof(int2) * nj, sizeof(void *) * nj, sizeof(void *) * nj, sizeof(void *) * nj};
+            void *dp[4];
+            FNX_TRY(upload_tables(ctx, SLOT_JPEG_JOBS, hosts, sizes, 4, dp));
+            const uint8_t *const *d_as = static_cast<const uint8_t *const *>(dp[1]);
+            const uint8_t *const *d_bs = static_cast<const uint8_t *const *>(dp[2]);
+            FNX_TRY(launch_jpeg_blocks_batch(ctx, nj, w, h, orig, work, static_cast<const int2 *>(dp[0]), d_qtab));
+            if (fused) {
+                FNX_TRY(launch_box_downsample_ycc_batch(ctx, nj, work, PB, cb_off, cr_off, ys, cs, w, h, cand, RB, pw, ph));
+            } else {
+                FNX_TRY(launch_ycbcr_to_nrgba_batch(ctx, nj, work, PB, cb_off, cr_off, ys, cs, w, h, dec, DB));
+                if (ds) FNX_TRY(launch_box_downsample(ctx, nj, nullptr, static_cast<const uint8_t *const *>(dp[3]), w * 4, w, h, cand,
+                                                      pw * 4, RB, pw, ph));
+            }
+            double *dres;
+            FNX_TRY(result_slot(ctx, nj, &dres));
+            if (pixel) FNX_TRY(launch_pixel_ssim_batch(ctx, nj, d_as, d_bs, pw, ph, static_cast<size_t>(pw) * ph * 4, dres));
+            else FNX_TRY(launch_windowed_ssim(ctx, nj, nullptr, pw * 4, 0, nullptr, pw * 4, 0, pw, ph, window,
+                                              static_cast<const double *>(dwin), dres, nullptr, 0, d_as, d_bs, true));
+            FNX_TRY(result_wait(ctx, dres, vals.data(), nj));
+            for (int j = 0; j < nj; j++) {
+                BatchSearch &b = st[act[j]];
+                const int mid = jobs[j].y;
+                b.n++;
+                if (vals[j] >= b.target) {
+                    b.best_q = mid; b.best_ssim = vals[j]; b.found = true;
+                    b.hi = mid - 1;
+                } else {
+                    b.lo = mid + 1;
+                }
+            }
+        }
+        // compress.go:76-86: every item's file at its best quality (100 when nothing reached the target), entropy-coded together
+        for (int i = 0; i < m; i++) qv[i] = st[i].best_q;
+        FNX_TRY(upload_table(ctx, SLOT_JPEG_JOBS, qv.data(), sizeof(int) * m, &t));
+        void *pin = nullptr;
+        FNX_TRY(pinned_alloc(ctx, sizeof(unsigned long long) * 2 * m, &pin));
+        unsigned long long *tot = static_cast<unsigned long long *>(pin);
+        for (int i = 0; i < 2 * m; i++) tot[i] = ~0ull;
+        FNX_TRY(jpeg_entropy_code_batch(ctx, m, w, h, orig, static_cast<const int *>(t), d_qtab, tot));
+        FNX_HIP(hipStreamSynchronize(ctx->stream));
+        for (int i = 0; i < m; i++) tbits[i] = tot[i];
+        uint8_t *ecs = nullptr;
+        FNX_TRY(jpeg_entropy_pack_batch(ctx, m, w, h, tbits.data(), &ecs, ecs_off.data(), tot + m));
+        FNX_HIP(hipStreamSynchronize(ctx->stream));
+        size_t end = 0, exact = 0;
+        for (int i = 0; i < m; i++) {
+            ecs_len[i] = static_cast<size_t>((tbits[i] + 7) / 8) + static_cast<size_t>(tbits[i] ? tot[m + i] : 0);
+            end = ecs_off[i] + ecs_len[i] > end ? ecs_off[i] + ecs_len[i] : end;
+            exact += ecs_len[i];
+        }
+        // the segments come down into pinned memory: each on its own (exact bytes) for a few items, the whole buffer with the
+        // gaps its worst-case sizing leaves (~2x) for many small ones; one wait either way (tot is not read after this)
+        const bool each = m <= 256;
+        void *stage = nullptr;
+        FNX_TRY(pinned_alloc(ctx, (each ? exact : end) + 64, &stage));
+        uint8_t *hs = static_cast<uint8_t *>(stage);
+        size_t o = 0;
+        for (int i = 0; i < m; i++) {
+            if (!each) {
+                host_off[i] = ecs_off[i];
+                continue;
+            }
+            host_off[i] = o;
+            if (ecs_len[i]) FNX_HIP(hipMemcpyAsync(hs + o, ecs + ecs_off[i], ecs_len[i], hipMemcpyDeviceToHost, ctx->stream));
+            o += ecs_len[i];
+        }
+        if (!each && end) FNX_HIP(hipMemcpyAsync(hs, ecs, end, hipMemcpyDeviceToHost, ctx->stream));
+        FNX_HIP(hipStreamSynchronize(ctx->stream));
+        for (int i = 0; i < m; i++) {
+            const int k = c0 + i, q = st[i].best_q;
+            if (hdr[q].empty()) jpeg_header(w, h, q, hdr[q]);
+            const size_t eb = ecs_len[i], total = hdr[q].size() + eb + 2;
+            nbytes[k] = total;
+            quality[k] = q;
+            ssim[k] = st[i].best_ssim;
+            if (steps) steps[k] = st[i].n;
+            if (caps[k] < total) {
+                status[k] = FNX_ERR_INVALID;
+                continue;
+            }
+            std::memcpy(outs[k], hdr[q].data(), hdr[q].size());
+            if (eb) std::memcpy(outs[k] + hdr[q].size(), hs + host_off[i], eb);
+            outs[k][total - 2] = 0xff;
+            outs[k][total - 1] = 0xd9;          // EOI
+            status[k] = FNX_OK;
+        }
+    }
+    return FNX_OK;
+}
+
 int fnx_jpeg_encode_scaled(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int dw, int dh, int quality,
                            uint8_t *out, size_t cap, size_t *nbytes)
 {

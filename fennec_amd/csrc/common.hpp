@@ -103,6 +103,7 @@ enum Slot {
     SLOT_JPEG_DEC, SLOT_JPEG_DEC_PLANES, SLOT_JPEG_DEC_IMG,        // jpeg_dec.hip: the decoder's work arrays, its planes, toNRGBARef's image
     SLOT_AN_HASH0, SLOT_AN_HASH1,   // analyze.hip: the colour-set tables of this call and the next (the launch that uses one zeroes the other)
     SLOT_TS_SCALED, SLOT_TS_UP,    // api.cpp: fnx_jpeg_target_size's Lanczos-scaled image and its upscale back to the source's size
+    SLOT_JPEG_QTAB, SLOT_JPEG_JOBS,  // fnx_jpeg_compress_batch: the quantiser tables of qualities 1..100, a search step's job list
     SLOT_DONE,       // workgroup counters of the kernels that finish their own reduction (ssim.hip), zero between launches
     SLOT_COUNT
 };
@@ -430,7 +431,8 @@ int launch_windowed_ssim(fnx_ctx *ctx, int n, const uint8_t *a, int astride, siz
                          const uint8_t *b, int bstride, size_t b_image_bytes, int w, int h,
                          const double *h_window, const double *d_window, double *d_out,
                          SsimDeferred *defer = nullptr, int defer_out_index = 0,
-                         const uint8_t *const *d_as = nullptr, const uint8_t *const *d_bs = nullptr);   // device pointer arrays: image z = d_as[z] / d_bs[z]
+                         const uint8_t *const *d_as = nullptr, const uint8_t *const *d_bs = nullptr,    // device pointer arrays: image z = d_as[z] / d_bs[z]
+                         bool select_as_one = false);   // kernel, tiling and reduction order of a call with n == 1
 int launch_ssim_finish_deferred(fnx_ctx *ctx, const SsimDeferred &d, double *d_out, int nimg = 1, size_t part_img = 0, int out_img = 0);
 // MSSSIM's levels in five launches (ssim.hip); FNX_NOOP (nothing launched) for shapes it does not cover.
 // d_out[i] = SSIMFast of level i; *nlev = levels the reference's loop visits.
@@ -439,6 +441,8 @@ int launch_msssim_fused(fnx_ctx *ctx, const uint8_t *a, int astride, const uint8
                         int nimg = 1, const uint8_t *const *d_as = nullptr, const uint8_t *const *d_bs = nullptr);
 int launch_pixel_ssim(fnx_ctx *ctx, const uint8_t *a, const uint8_t *b, int w, int h,
                       size_t pix_len, double *d_out);
+int launch_pixel_ssim_batch(fnx_ctx *ctx, int n, const uint8_t *const *d_as, const uint8_t *const *d_bs, int w, int h, size_t pix_len,
+                            double *d_out);
 // Analyze's device side (analyze.hip): n images -> d_res[n]; aligned16_ok: every base pointer is 16-byte aligned
 int launch_analyze(fnx_ctx *ctx, int n, const uint8_t *src, const uint8_t *const *srcs, int sstride, int w, int h,
                    bool aligned16_ok, fnx_analysis *d_res);
@@ -484,6 +488,27 @@ int jpeg_entropy_code(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *co
 size_t jpeg_ecs_capacity(unsigned long long total_bits);
 int jpeg_entropy_pack(fnx_ctx *ctx, int w, int h, unsigned long long total_bits, uint8_t *ecs, unsigned long long *totals);
 int launch_jpeg_blocks(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *const in[3], uint8_t *const out[3]);
+// ---- batched forms (fnx_jpeg_compress_batch): n images of one geometry, the image index in grid x ----
+constexpr int JPEG_QTAB_WORDS = 101 * 2 * 2 * 64;   // [quality 0..100][luma, chroma][step, magic][64]: the per-ctx quality table
+void jpeg_qtab(uint32_t *tab);
+// bytes per image of the unquantised / candidate planes (Y | Cb at *cb_off | Cr at *cr_off; 256-byte multiple)
+size_t jpeg_batch_plane_bytes(int w, int h, size_t *cb_off, size_t *cr_off);
+int launch_jpeg_ycc_batch(fnx_ctx *ctx, int n, const uint8_t *const *d_srcs, int sstride, int w, int h, uint8_t *planes);
+// d_jobs: (image, quality) per job: image's planes at orig + image * plane bytes -> job j's at work + j * plane bytes
+int launch_jpeg_blocks_batch(fnx_ctx *ctx, int njobs, int w, int h, const uint8_t *orig, uint8_t *work, const int2 *d_jobs,
+                             const uint32_t *d_qtab);
+int launch_copy_tight_batch(fnx_ctx *ctx, int n, const uint8_t *const *d_srcs, int sstride, int w, int h, uint8_t *dst, size_t dst_bytes);
+int launch_ycbcr_to_nrgba_batch(fnx_ctx *ctx, int njobs, const uint8_t *planes, size_t plane_bytes, size_t cb_off, size_t cr_off,
+                                int ystride, int cstride, int w, int h, uint8_t *dst, size_t dst_bytes);
+// does launch_box_downsample_ycc take a w x h 4:2:0 candidate (jpeg_planes' aligned layout) to dstW x dstH?  (ssim.hip)
+bool box_downsample_ycc_fused(int srcW, int srcH, int dstW, int dstH);
+int launch_box_downsample_ycc_batch(fnx_ctx *ctx, int njobs, const uint8_t *planes, size_t plane_bytes, size_t cb_off, size_t cr_off,
+                                    int ystride, int cstride, int srcW, int srcH, uint8_t *dst, size_t dst_bytes, int dstW, int dstH);
+size_t jpeg_entropy_batch_bytes(int w, int h);
+int jpeg_entropy_code_batch(fnx_ctx *ctx, int n, int w, int h, const uint8_t *planes, const int *d_quality, const uint32_t *d_qtab,
+                            unsigned long long *tot);
+int jpeg_entropy_pack_batch(fnx_ctx *ctx, int n, int w, int h, const unsigned long long *tbits, uint8_t **ecs, size_t *ecs_off,
+                            unsigned long long *fftot);
 
 // jpeg_dec.hip: Huffman decoding tables of one file (tables 0, 1: DC th 0, 1; 2, 3: AC th 0, 1) and what its segments say
 constexpr int DEC_FAST_BITS = 11;                    // DecTables::fast is indexed by this many bits of the string

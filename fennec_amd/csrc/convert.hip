@@ -17,10 +17,10 @@ struct YccArgs {
 };
 
 // (the per-pixel arithmetic is devutil.hpp's ycc_nrgba_px)
-__global__ __launch_bounds__(256) void ycbcr_to_nrgba_kernel(YccArgs a)
+__device__ __forceinline__ void ycbcr_to_nrgba_body(const YccArgs &a, int bx, int by)
 {
-    const int x0 = 4 * (blockIdx.x * 64 + (threadIdx.x & 63));
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int x0 = 4 * (bx * 64 + (threadIdx.x & 63));
+    const int y = by * 4 + (threadIdx.x >> 6);
     if (x0 >= a.w || y >= a.h) return;
     const uint8_t *yrow = a.y + static_cast<size_t>(y) * a.ystride;
     const int cnt = min(4, a.w - x0);
@@ -43,6 +43,47 @@ __global__ __launch_bounds__(256) void ycbcr_to_nrgba_kernel(YccArgs a)
     } else {
         for (int e = 0; e < cnt; e++) *reinterpret_cast<uint32_t *>(dp + 4 * e) = out[e];
     }
+}
+
+__global__ __launch_bounds__(256) void ycbcr_to_nrgba_kernel(YccArgs a)
+{
+    ycbcr_to_nrgba_body(a, blockIdx.x, blockIdx.y);
+}
+
+// fnx_jpeg_compress_batch: job j's 4:2:0 planes at planes + j * plane_bytes (Cb at cb_off, Cr at cr_off) -> its tight image at
+// dst + j * dst_bytes.  Job = blockIdx.x / gx.
+struct YccConvBatchArgs {
+    YccArgs one;
+    const uint8_t *planes;
+    size_t plane_bytes, cb_off, cr_off, dst_bytes;
+    uint8_t *dst;
+    int gx;
+};
+
+__global__ __launch_bounds__(256) void ycbcr_to_nrgba_batch_kernel(YccConvBatchArgs b)
+{
+    const int job = blockIdx.x / b.gx;
+    YccArgs a = b.one;
+    a.y = b.planes + static_cast<size_t>(job) * b.plane_bytes;
+    a.cb = a.y + b.cb_off;
+    a.cr = a.y + b.cr_off;
+    a.dst = b.dst + static_cast<size_t>(job) * b.dst_bytes;
+    ycbcr_to_nrgba_body(a, blockIdx.x - job * b.gx, blockIdx.y);
+}
+
+int launch_ycbcr_to_nrgba_batch(fnx_ctx *ctx, int njobs, const uint8_t *planes, size_t plane_bytes, size_t cb_off, size_t cr_off,
+                                int ystride, int cstride, int w, int h, uint8_t *dst, size_t dst_bytes)
+{
+    if (w <= 0 || h <= 0 || njobs <= 0) return FNX_OK;
+    YccConvBatchArgs b{};
+    b.one.ystride = ystride; b.one.cstride = cstride; b.one.dstride = w * 4; b.one.w = w; b.one.h = h;
+    b.one.xshift = 1; b.one.yshift = 1;               // 4:2:0
+    b.planes = planes; b.plane_bytes = plane_bytes; b.cb_off = cb_off; b.cr_off = cr_off;
+    b.dst = dst; b.dst_bytes = dst_bytes;
+    b.gx = (w + 255) / 256;
+    hipLaunchKernelGGL(ycbcr_to_nrgba_batch_kernel, dim3(b.gx * njobs, (h + 3) / 4), dim3(256), 0, ctx->stream, b);
+    FNX_HIP(hipGetLastError());
+    return FNX_OK;
 }
 
 // ratio: image.YCbCrSubsampleRatio (0 4:4:4, 1 4:2:2, 2 4:2:0, 3 4:4:0, 4 4:1:1, 5 4:1:0); device pointers

@@ -50,10 +50,11 @@ __device__ __forceinline__ uint32_t rgb_to_ycc(uint32_t p)
 }
 
 // a lane converts a 4 x 2 pixel patch of the MCU-padded image: 8 luma samples, 2 chroma pairs
-__global__ __launch_bounds__(256) void jpeg_ycc_kernel(YccArgs a)
+// (workgroup (bx, by) of one image: jpeg_ycc_kernel's and jpeg_ycc_batch_kernel's)
+__device__ __forceinline__ void jpeg_ycc_body(const YccArgs &a, int bx, int by)
 {
-    const int px = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;
-    const int py = (blockIdx.y * 4 + (threadIdx.x >> 6)) * 2;
+    const int px = (bx * 64 + (threadIdx.x & 63)) * 4;
+    const int py = (by * 4 + (threadIdx.x >> 6)) * 2;
     if (px >= a.ys || py >= 16 * a.my) return;
     uint32_t ycc[2][4];
 #pragma unroll
@@ -88,6 +89,32 @@ __global__ __launch_bounds__(256) void jpeg_ycc_kernel(YccArgs a)
     }
     *reinterpret_cast<uint16_t *>(a.cbp + static_cast<size_t>(py / 2) * a.cs + px / 2) = static_cast<uint16_t>(cb2);
     *reinterpret_cast<uint16_t *>(a.crp + static_cast<size_t>(py / 2) * a.cs + px / 2) = static_cast<uint16_t>(cr2);
+}
+
+__global__ __launch_bounds__(256) void jpeg_ycc_kernel(YccArgs a)
+{
+    jpeg_ycc_body(a, blockIdx.x, blockIdx.y);
+}
+
+// fnx_jpeg_compress_batch: the unquantised planes of n sources of one geometry.  Image = blockIdx.x / gx (images in x: the
+// grid's y stays the one image's row count); image i's planes at planes + i * plane_bytes (Y | Cb | Cr, jpeg_planes' layout)
+struct YccBatchArgs {
+    YccArgs one;                  // geometry (src and plane pointers unused)
+    const uint8_t *const *srcs;   // [n] device
+    uint8_t *planes;
+    size_t plane_bytes, cb_off, cr_off;
+    int gx;
+};
+
+__global__ __launch_bounds__(256) void jpeg_ycc_batch_kernel(YccBatchArgs b)
+{
+    const int img = blockIdx.x / b.gx;
+    YccArgs a = b.one;
+    a.src = b.srcs[img];
+    a.yp = b.planes + static_cast<size_t>(img) * b.plane_bytes;
+    a.cbp = a.yp + b.cb_off;
+    a.crp = a.yp + b.cr_off;
+    jpeg_ycc_body(a, blockIdx.x - img * b.gx, blockIdx.y);
 }
 
 // ------------------------------------------------------------------------------------
@@ -273,16 +300,11 @@ struct BlockArgs {
     uint32_t magic[2][64];    // floor(2^32 / 8q) + 1: (|c| + 4q) / 8q by one v_mul_hi_u32 (|c| + 4q < 2^18, 8q <= 2040)
 };
 
-// one lane = one 8 x 8 block, all 64 samples in registers: no LDS, no transposes, no barriers
-__global__ __launch_bounds__(256) void jpeg_block_kernel(BlockArgs a)
+// one 8 x 8 block's round trip, all 64 samples in registers: no LDS, no transposes, no barriers.  q / magic: the plane's
+// table (kernel arguments in jpeg_block_kernel, the per-ctx quality table in jpeg_block_batch_kernel)
+template <typename QT>
+__device__ __forceinline__ void jpeg_block_body(const uint8_t *ip, uint8_t *op, int stride, const QT *q_tab, const QT *magic_tab)
 {
-    const int plane = blockIdx.y;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= a.nblocks[plane]) return;
-    const int t = plane ? 1 : 0;
-    const int by = i / a.nbx[plane], bx = i - by * a.nbx[plane];
-    const int stride = a.stride[plane];
-    const uint8_t *ip = a.in[plane] + static_cast<size_t>(8 * by) * stride + 8 * bx;
     int32_t b[64];
 #pragma unroll
     for (int r = 0; r < 8; r++) {
@@ -297,16 +319,15 @@ __global__ __launch_bounds__(256) void jpeg_block_kernel(BlockArgs a)
     // writer.go div(b, 8 * q) -- nearest, halves away from zero -- then reader.go's multiplication by q
 #pragma unroll
     for (int k = 0; k < 64; k++) {
-        const int32_t q = static_cast<int32_t>(a.q[t][k]);
+        const int32_t q = static_cast<int32_t>(q_tab[k]);
         const uint32_t mag = static_cast<uint32_t>(b[k] < 0 ? -b[k] : b[k]) + 4u * static_cast<uint32_t>(q);
-        const int32_t quot = static_cast<int32_t>(__umulhi(mag, a.magic[t][k]));
+        const int32_t quot = static_cast<int32_t>(__umulhi(mag, magic_tab[k]));
         b[k] = (b[k] < 0 ? -quot : quot) * q;
     }
 #pragma unroll
     for (int r = 0; r < 8; r++) idct8_row(b[8 * r], b[8 * r + 1], b[8 * r + 2], b[8 * r + 3], b[8 * r + 4], b[8 * r + 5], b[8 * r + 6], b[8 * r + 7]);
 #pragma unroll
     for (int c = 0; c < 8; c++) idct8_col(b[c], b[8 + c], b[16 + c], b[24 + c], b[32 + c], b[40 + c], b[48 + c], b[56 + c]);
-    uint8_t *op = a.out[plane] + static_cast<size_t>(8 * by) * stride + 8 * bx;
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         u32x2 v = {0, 0};
@@ -318,6 +339,52 @@ __global__ __launch_bounds__(256) void jpeg_block_kernel(BlockArgs a)
         }
         *reinterpret_cast<u32x2 *>(op + static_cast<size_t>(r) * stride) = v;
     }
+}
+
+// one lane = one 8 x 8 block
+__global__ __launch_bounds__(256) void jpeg_block_kernel(BlockArgs a)
+{
+    const int plane = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.nblocks[plane]) return;
+    const int t = plane ? 1 : 0;
+    const int by = i / a.nbx[plane], bx = i - by * a.nbx[plane];
+    const int stride = a.stride[plane];
+    const size_t o = static_cast<size_t>(8 * by) * stride + 8 * bx;
+    jpeg_block_body(a.in[plane] + o, a.out[plane] + o, stride, a.q[t], a.magic[t]);
+}
+
+// The per-ctx quality table of the batched forms: for quality 1..100, [q][t][0][k] = the quantiser step, [q][t][1][k] = its
+// magic -- exactly what launch_jpeg_blocks / quant_tables compute for one quality (JPEG_QTAB_WORDS, common.hpp)
+
+// fnx_jpeg_compress_batch's search step: the candidate planes of every item still searching, each at its own quality.
+// Job j = (image, quality): reads image's unquantised planes (orig + image * plane_bytes), writes job j's planes
+// (work + j * plane_bytes).  Job = blockIdx.x / gx (jobs in x), plane = blockIdx.y.
+struct BlockBatchArgs {
+    const uint8_t *orig;
+    uint8_t *work;
+    size_t plane_bytes;
+    size_t off[3];
+    int stride[3], nbx[3], nblocks[3];
+    const int2 *jobs;                 // [njobs] (image, quality)
+    const uint32_t *qtab;             // JPEG_QTAB_WORDS
+    int gx;
+};
+
+__global__ __launch_bounds__(256) void jpeg_block_batch_kernel(BlockBatchArgs a)
+{
+    const int plane = blockIdx.y;
+    const int job = blockIdx.x / a.gx;
+    const int i = (blockIdx.x - job * a.gx) * 256 + threadIdx.x;
+    if (i >= a.nblocks[plane]) return;
+    const int t = plane ? 1 : 0;
+    const int2 jb = a.jobs[job];
+    const int by = i / a.nbx[plane], bx = i - by * a.nbx[plane];
+    const int stride = a.stride[plane];
+    const size_t o = a.off[plane] + static_cast<size_t>(8 * by) * stride + 8 * bx;
+    const uint32_t *qt = a.qtab + (static_cast<size_t>(jb.y) * 2 + t) * 128;
+    jpeg_block_body(a.orig + static_cast<size_t>(jb.x) * a.plane_bytes + o, a.work + static_cast<size_t>(job) * a.plane_bytes + o, stride,
+                    qt, qt + 64);
 }
 
 // writer.go, Encode: quality in [1, 100], scale = 5000 / q below 50, 200 - 2 q from 50, x = (x * scale + 50) / 100 in [1, 255]
@@ -454,16 +521,14 @@ struct CoefArgs {
 };
 
 // lane = block (plane-major, so that loads coalesce); stores go to the block's place in SCAN order:
-// MCU-major, Y0 Y1 Y2 Y3 Cb Cr inside an MCU (writer.go writeSOS)
-__global__ __launch_bounds__(256) void jpeg_coef_kernel(CoefArgs a)
+// MCU-major, Y0 Y1 Y2 Y3 Cb Cr inside an MCU (writer.go writeSOS).  in: the image's planes; base: its first block in the
+// coefficient array (0 for one image)
+__device__ __forceinline__ void jpeg_coef_body(const CoefArgs &a, const uint8_t *const in[3], int plane, int i, const uint32_t *q_tab,
+                                               const uint32_t *magic_tab, int base)
 {
-    const int plane = blockIdx.y;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= a.nblocks[plane]) return;
-    const int t = plane ? 1 : 0;
     const int by = i / a.nbx[plane], bx = i - by * a.nbx[plane];
     const int stride = a.stride[plane];
-    const uint8_t *ip = a.in[plane] + static_cast<size_t>(8 * by) * stride + 8 * bx;
+    const uint8_t *ip = in[plane] + static_cast<size_t>(8 * by) * stride + 8 * bx;
     int32_t b[64];
 #pragma unroll
     for (int r = 0; r < 8; r++) {
@@ -475,14 +540,47 @@ __global__ __launch_bounds__(256) void jpeg_coef_kernel(CoefArgs a)
     for (int r = 0; r < 8; r++) fdct8<1>(b[8 * r], b[8 * r + 1], b[8 * r + 2], b[8 * r + 3], b[8 * r + 4], b[8 * r + 5], b[8 * r + 6], b[8 * r + 7]);
 #pragma unroll
     for (int c = 0; c < 8; c++) fdct8<2>(b[c], b[8 + c], b[16 + c], b[24 + c], b[32 + c], b[40 + c], b[48 + c], b[56 + c]);
-    const int sb = plane == 0 ? ((by >> 1) * a.mx + (bx >> 1)) * 6 + (by & 1) * 2 + (bx & 1) : (by * a.mx + bx) * 6 + 3 + plane;
+    const int sb = base + (plane == 0 ? ((by >> 1) * a.mx + (bx >> 1)) * 6 + (by & 1) * 2 + (bx & 1) : (by * a.mx + bx) * 6 + 3 + plane);
 #pragma unroll
     for (int k = 0; k < 64; k++) {
-        const int32_t q = static_cast<int32_t>(a.q[t][k]);
+        const int32_t q = static_cast<int32_t>(q_tab[k]);
         const uint32_t mag = static_cast<uint32_t>(b[k] < 0 ? -b[k] : b[k]) + 4u * static_cast<uint32_t>(q);
-        const int32_t quot = static_cast<int32_t>(__umulhi(mag, a.magic[t][k]));     // writer.go div(b, 8 * q)
+        const int32_t quot = static_cast<int32_t>(__umulhi(mag, magic_tab[k]));     // writer.go div(b, 8 * q)
         a.coef[static_cast<size_t>(c_zigpos[k]) * a.nblk + sb] = static_cast<int16_t>(b[k] < 0 ? -quot : quot);
     }
+}
+
+__global__ __launch_bounds__(256) void jpeg_coef_kernel(CoefArgs a)
+{
+    const int plane = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.nblocks[plane]) return;
+    const int t = plane ? 1 : 0;
+    jpeg_coef_body(a, a.in, plane, i, a.q[t], a.magic[t], 0);
+}
+
+// the winners of fnx_jpeg_compress_batch: image = blockIdx.x / gx, its planes at planes + image * plane_bytes, its blocks at
+// image * seg of ONE coefficient array (a.nblk = n * seg), its quality quality[image] (the per-ctx table)
+struct CoefBatchArgs {
+    CoefArgs one;                 // geometry, coef, nblk = all images' blocks (in / q / magic unused)
+    const uint8_t *planes;
+    size_t plane_bytes, off[3];
+    const int *quality;           // [n]
+    const uint32_t *qtab;         // JPEG_QTAB_WORDS
+    int seg, gx;
+};
+
+__global__ __launch_bounds__(256) void jpeg_coef_batch_kernel(CoefBatchArgs b)
+{
+    const int plane = blockIdx.y;
+    const int img = blockIdx.x / b.gx;
+    const int i = (blockIdx.x - img * b.gx) * 256 + threadIdx.x;
+    if (i >= b.one.nblocks[plane]) return;
+    const int t = plane ? 1 : 0;
+    const uint8_t *base = b.planes + static_cast<size_t>(img) * b.plane_bytes;
+    const uint8_t *const in[3] = {base + b.off[0], base + b.off[1], base + b.off[2]};
+    const uint32_t *qt = b.qtab + (static_cast<size_t>(b.quality[img]) * 2 + t) * 128;
+    jpeg_coef_body(b.one, in, plane, i, qt, qt + 64, img * b.seg);
 }
 
 constexpr int JPEG_STRIP = 52;            // words per block's staging strip: 20 + 63 * 26 bits at most
@@ -493,6 +591,7 @@ struct CodeArgs {
     uint32_t *strip;          // [JPEG_STRIP][nblk]
     uint32_t *nbits;          // [nblk]
     int nblk;
+    int seg;                  // blocks per image: the batched form's images lie back to back (one image: seg = nblk)
 };
 
 __global__ __launch_bounds__(256) void jpeg_code_kernel(CodeArgs a)
@@ -506,8 +605,9 @@ __global__ __launch_bounds__(256) void jpeg_code_kernel(CodeArgs a)
     const uint32_t *dc_lut = s_lut + (j < 4 ? 0 : 512), *ac_lut = dc_lut + 256;
     // the component's previous block in scan order
     const int prev = j == 0 ? blk - 3 : (j < 4 ? blk - 1 : blk - 6);
+    const int first = blk - blk % a.seg;                   // the image's first block (seg is a multiple of 6)
     const int32_t dc = a.coef[blk];
-    const int32_t pd = prev >= 0 ? static_cast<int32_t>(a.coef[prev]) : 0;
+    const int32_t pd = prev >= first ? static_cast<int32_t>(a.coef[prev]) : 0;
     unsigned long long acc = 0;      // MSB-first bit accumulator: the low `nacc` bits are pending
     int nacc = 0, nw = 0;
     auto emit = [&](uint32_t bits, int n) {                // n <= 27
@@ -811,7 +911,7 @@ int jpeg_entropy_code(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *co
     hipLaunchKernelGGL(jpeg_coef_kernel, dim3((ca.nblocks[0] + 255) / 256, 3), dim3(256), 0, ctx->stream, ca);
     FNX_HIP(hipGetLastError());
     FNX_TRY(prof_end(ctx));
-    CodeArgs co{coef, static_cast<const uint32_t *>(dlut), strip, nbits, nblk};
+    CodeArgs co{coef, static_cast<const uint32_t *>(dlut), strip, nbits, nblk, nblk};
     hipLaunchKernelGGL(jpeg_code_kernel, dim3((nblk + 255) / 256), dim3(256), 0, ctx->stream, co);
     FNX_HIP(hipGetLastError());
     return launch_scan(ctx, nbits, pos, wgt, nblk, totals);
@@ -860,6 +960,321 @@ int jpeg_entropy_pack(fnx_ctx *ctx, int w, int h, unsigned long long total_bits,
         FNX_TRY(launch_scan(ctx, ffc, ffb, wgt, nwords, totals + 1));
         hipLaunchKernelGGL(jpeg_stuff_kernel, dim3((nwords + 255) / 256), dim3(256), 0, ctx->stream, sa);
     }
+    FNX_HIP(hipGetLastError());
+    return FNX_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// Batched forms of the above (fnx_jpeg_compress_batch): n images of ONE geometry.  Every kernel puts the image index in
+// x (blockIdx.x = image * gx + workgroup), so no grid dimension is the image count times anything but x; each image's
+// arithmetic is the single-image kernel's body.
+// ------------------------------------------------------------------------------------
+void jpeg_qtab(uint32_t *tab)                     // JPEG_QTAB_WORDS: see jpeg_block_batch_kernel
+{
+    for (int q = 0; q <= 100; q++) {
+        uint32_t qq[2][64], mm[2][64];
+        quant_tables(q, qq, mm);
+        for (int t = 0; t < 2; t++)
+            for (int k = 0; k < 64; k++) {
+                tab[(q * 2 + t) * 128 + k] = qq[t][k];
+                tab[(q * 2 + t) * 128 + 64 + k] = mm[t][k];
+            }
+    }
+}
+
+// item i's Y | Cb | Cr planes at base + i * jpeg_batch_plane_bytes(): jpeg_planes' layout, 256-byte aligned per item
+size_t jpeg_batch_plane_bytes(int w, int h, size_t *cb_off, size_t *cr_off)
+{
+    int ys, yh, cs, chh;
+    jpeg_plane_dims(w, h, &ys, &yh, &cs, &chh);
+    const size_t yb = static_cast<size_t>(ys) * yh, cb = static_cast<size_t>(cs) * chh;
+    if (cb_off) *cb_off = yb;
+    if (cr_off) *cr_off = yb + cb;
+    return (yb + 2 * cb + 16 + 255) & ~size_t(255);
+}
+
+int launch_jpeg_ycc_batch(fnx_ctx *ctx, int n, const uint8_t *const *d_srcs, int sstride, int w, int h, uint8_t *planes)
+{
+    YccBatchArgs b{};
+    int yh, chh;
+    jpeg_plane_dims(w, h, &b.one.ys, &yh, &b.one.cs, &chh);
+    b.one.sstride = sstride; b.one.w = w; b.one.h = h; b.one.my = yh / 16;
+    b.srcs = d_srcs; b.planes = planes;
+    b.plane_bytes = jpeg_batch_plane_bytes(w, h, &b.cb_off, &b.cr_off);
+    b.gx = (b.one.ys / 4 + 63) / 64;
+    hipLaunchKernelGGL(jpeg_ycc_batch_kernel, dim3(b.gx * n, (yh / 2 + 3) / 4), dim3(256), 0, ctx->stream, b);
+    FNX_HIP(hipGetLastError());
+    return FNX_OK;
+}
+
+// d_jobs: [njobs] (image, quality) device; job j's planes at work + j * plane bytes
+int launch_jpeg_blocks_batch(fnx_ctx *ctx, int njobs, int w, int h, const uint8_t *orig, uint8_t *work, const int2 *d_jobs,
+                             const uint32_t *d_qtab)
+{
+    BlockBatchArgs a{};
+    int ys, yh, cs, chh;
+    jpeg_plane_dims(w, h, &ys, &yh, &cs, &chh);
+    a.orig = orig; a.work = work; a.jobs = d_jobs; a.qtab = d_qtab;
+    a.plane_bytes = jpeg_batch_plane_bytes(w, h, &a.off[1], &a.off[2]);
+    a.off[0] = 0;
+    for (int p = 0; p < 3; p++) {
+        a.stride[p] = p ? cs : ys;
+        a.nbx[p] = (p ? cs : ys) / 8;
+        a.nblocks[p] = a.nbx[p] * ((p ? chh : yh) / 8);
+    }
+    a.gx = (a.nblocks[0] + 255) / 256;
+    FNX_TRY(prof_begin(ctx, FNX_PROF_JPEG));
+    hipLaunchKernelGGL(jpeg_block_batch_kernel, dim3(a.gx * njobs, 3), dim3(256), 0, ctx->stream, a);
+    FNX_HIP(hipGetLastError());
+    return prof_end(ctx);
+}
+
+// n images' w x h sources -> tight w x h copies at dst + i * dst_bytes (the prepared reference of a search that does not
+// downsample: against_device's side `a` is tight).  Workgroup = one row of one image.
+__global__ __launch_bounds__(256) void copy_tight_batch_kernel(const uint8_t *const *srcs, int sstride, int w, int h, uint8_t *dst,
+                                                               size_t dst_bytes)
+{
+    const int img = blockIdx.x / h, y = blockIdx.x - img * h;
+    const uint8_t *s = srcs[img] + static_cast<size_t>(y) * sstride;
+    uint8_t *d = dst + static_cast<size_t>(img) * dst_bytes + static_cast<size_t>(y) * w * 4;
+    for (int x = threadIdx.x; x < w; x += 256) *reinterpret_cast<uint32_t *>(d + 4 * static_cast<size_t>(x)) = ld_px(s, x);
+}
+
+int launch_copy_tight_batch(fnx_ctx *ctx, int n, const uint8_t *const *d_srcs, int sstride, int w, int h, uint8_t *dst, size_t dst_bytes)
+{
+    hipLaunchKernelGGL(copy_tight_batch_kernel, dim3(n * h), dim3(256), 0, ctx->stream, d_srcs, sstride, w, h, dst, dst_bytes);
+    FNX_HIP(hipGetLastError());
+    return FNX_OK;
+}
+
+// ---- entropy coding of n winners: the blocks of all images in one array (image i's at i * seg, seg = its block count), ONE
+// prefix sum over all of them, each image's positions relative to its first block (a segmented sum by subtraction: integer,
+// any order).  The bit strings are per image (word base wbase[i]), stuffed into per-image ranges of one ECS buffer.
+struct PackItem {
+    unsigned long long wbase;     // first word of the image's bit string (nw + 2 words: the pack kernel's overhang, a zero count)
+    unsigned long long ecs;       // first byte of its entropy-coded segment
+    unsigned long long tbits;     // bits of its string
+    int nw, pad;
+};
+
+// out[i] = the bits of image i's string (pos is exclusive: the last block's position + its count - the first block's position)
+__global__ __launch_bounds__(256) void seg_bits_kernel(const unsigned long long *pos, const uint32_t *nbits, int seg, int n,
+                                                       unsigned long long *out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const size_t last = static_cast<size_t>(i + 1) * seg - 1;
+    out[i] = pos[last] + nbits[last] - pos[static_cast<size_t>(i) * seg];
+}
+
+struct PackBatchArgs {
+    const uint32_t *strip, *nbits;
+    const unsigned long long *pos;
+    uint32_t *bits;
+    const PackItem *item;
+    int nblk, seg;
+};
+
+__global__ __launch_bounds__(256) void jpeg_pack_batch_kernel(PackBatchArgs a)
+{
+    const int blk = blockIdx.x * 256 + threadIdx.x;
+    if (blk >= a.nblk) return;
+    const int img = blk / a.seg;
+    const unsigned long long p0 = a.pos[blk] - a.pos[static_cast<size_t>(img) * a.seg];
+    const int nw = static_cast<int>((a.nbits[blk] + 31u) >> 5);
+    const int s = static_cast<int>(p0 & 31u);
+    uint32_t *bits = a.bits + a.item[img].wbase;
+    size_t d = static_cast<size_t>(p0 >> 5);
+    for (int k = 0; k < nw; k++, d++) {
+        const uint32_t w = a.strip[static_cast<size_t>(k) * a.nblk + blk];
+        atomicOr(&bits[d], w >> s);
+        if (s) atomicOr(&bits[d + 1], w << (32 - s));
+    }
+}
+
+struct StuffBatchArgs {
+    uint32_t *bits;
+    const PackItem *item;
+    uint32_t *ffcount;                    // one array over every image's words (+ 2 zero words each)
+    const unsigned long long *ffbefore;   // its exclusive prefix sum
+    uint8_t *ecs;
+    unsigned long long *fftot;            // [n] 0xff bytes of image i's string
+    int gx;
+};
+
+__global__ __launch_bounds__(256) void jpeg_ffcount_batch_kernel(StuffBatchArgs b)
+{
+    const int img = blockIdx.x / b.gx;
+    const int k = (blockIdx.x - img * b.gx) * 256 + threadIdx.x;
+    const PackItem it = b.item[img];
+    if (k >= it.nw + 2) return;
+    uint32_t c = 0;
+    if (k < it.nw) {
+        StuffArgs a{};
+        a.bits = b.bits + it.wbase;
+        int nb;
+        const uint32_t w = padded_word(a, k, it.tbits, &nb);
+        for (int e = 0; e < nb; e++) c += ((w >> (24 - 8 * e)) & 0xffu) == 0xffu ? 1u : 0u;
+    }
+    b.ffcount[it.wbase + k] = c;
+}
+
+__global__ __launch_bounds__(256) void jpeg_stuff_batch_kernel(StuffBatchArgs b)
+{
+    const int img = blockIdx.x / b.gx;
+    const int k = (blockIdx.x - img * b.gx) * 256 + threadIdx.x;
+    const PackItem it = b.item[img];
+    if (k == 0) b.fftot[img] = b.ffbefore[it.wbase + it.nw] - b.ffbefore[it.wbase];
+    if (k >= it.nw) return;
+    StuffArgs a{};
+    a.bits = b.bits + it.wbase;
+    int nb;
+    const uint32_t w = padded_word(a, k, it.tbits, &nb);
+    uint8_t *o = b.ecs + it.ecs + static_cast<size_t>(k) * 4 + (b.ffbefore[it.wbase + k] - b.ffbefore[it.wbase]);
+    for (int e = 0; e < nb; e++) {
+        const uint8_t v = static_cast<uint8_t>(w >> (24 - 8 * e));
+        *o++ = v;
+        if (v == 0xffu) *o++ = 0x00;
+    }
+}
+
+static void entropy_batch_layout(int n, int w, int h, int *seg, size_t *sizes)
+{
+    int ys, yh, cs, chh;
+    jpeg_plane_dims(w, h, &ys, &yh, &cs, &chh);
+    *seg = (ys / 16) * (yh / 16) * 6;
+    const size_t nblk = static_cast<size_t>(n) * *seg;
+    auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
+    sizes[0] = al(sizeof(int16_t) * 64 * nblk);
+    sizes[1] = al(4 * nblk * JPEG_STRIP);
+    sizes[2] = al(4 * nblk);
+    sizes[3] = al(8 * nblk);
+    sizes[4] = al(8 * (nblk / SCAN_PER_WG + 2));
+}
+
+// device bytes per image of phase 1 (fnx_jpeg_compress_batch's chunking)
+size_t jpeg_entropy_batch_bytes(int w, int h)
+{
+    int seg;
+    size_t sz[5];
+    entropy_batch_layout(1, w, h, &seg, sz);
+    return static_cast<size_t>(seg) * (2 * 64 + 4 * JPEG_STRIP + 4 + 8) + 256;
+}
+
+// phase 1 of n images: coefficients at quality[i] (device [n]), codes, positions; tot[i] (host-mapped, n) = bits of image i
+int jpeg_entropy_code_batch(fnx_ctx *ctx, int n, int w, int h, const uint8_t *planes, const int *d_quality, const uint32_t *d_qtab,
+                            unsigned long long *tot)
+{
+    int seg;
+    size_t sz[5];
+    entropy_batch_layout(n, w, h, &seg, sz);
+    const long long nblk_ll = static_cast<long long>(n) * seg;
+    if (nblk_ll >= (1LL << 31) / JPEG_STRIP) {
+        set_error("jpeg batch: %lld blocks in one entropy pass", nblk_ll);
+        return FNX_ERR_INVALID;
+    }
+    const int nblk = static_cast<int>(nblk_ll);
+    void *sc = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_JPEG_ENC, sz[0] + sz[1] + sz[2] + sz[3] + sz[4], &sc));
+    unsigned char *p = static_cast<unsigned char *>(sc);
+    int16_t *coef = reinterpret_cast<int16_t *>(p); p += sz[0];
+    uint32_t *strip = reinterpret_cast<uint32_t *>(p); p += sz[1];
+    uint32_t *nbits = reinterpret_cast<uint32_t *>(p); p += sz[2];
+    unsigned long long *pos = reinterpret_cast<unsigned long long *>(p); p += sz[3];
+    unsigned long long *wgt = reinterpret_cast<unsigned long long *>(p);
+    uint32_t hlut[4 * 256];
+    huffman_luts(hlut);
+    void *dlut = nullptr;
+    FNX_TRY(upload_table(ctx, SLOT_JPEG_LUT, hlut, sizeof(hlut), &dlut));
+
+    CoefBatchArgs cb{};
+    int ys, yh, cs, chh;
+    jpeg_plane_dims(w, h, &ys, &yh, &cs, &chh);
+    for (int pl = 0; pl < 3; pl++) {
+        cb.one.stride[pl] = pl ? cs : ys;
+        cb.one.nbx[pl] = (pl ? cs : ys) / 8;
+        cb.one.nblocks[pl] = cb.one.nbx[pl] * ((pl ? chh : yh) / 8);
+    }
+    cb.one.coef = coef; cb.one.mx = ys / 16; cb.one.nblk = nblk;
+    cb.planes = planes;
+    cb.plane_bytes = jpeg_batch_plane_bytes(w, h, &cb.off[1], &cb.off[2]);
+    cb.off[0] = 0;
+    cb.quality = d_quality; cb.qtab = d_qtab; cb.seg = seg;
+    cb.gx = (cb.one.nblocks[0] + 255) / 256;
+    FNX_TRY(prof_begin(ctx, FNX_PROF_JPEG));
+    hipLaunchKernelGGL(jpeg_coef_batch_kernel, dim3(cb.gx * n, 3), dim3(256), 0, ctx->stream, cb);
+    FNX_HIP(hipGetLastError());
+    FNX_TRY(prof_end(ctx));
+    CodeArgs co{coef, static_cast<const uint32_t *>(dlut), strip, nbits, nblk, seg};
+    hipLaunchKernelGGL(jpeg_code_kernel, dim3((nblk + 255) / 256), dim3(256), 0, ctx->stream, co);
+    FNX_HIP(hipGetLastError());
+    FNX_TRY(launch_scan(ctx, nbits, pos, wgt, nblk, nullptr));
+    hipLaunchKernelGGL(seg_bits_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, pos, nbits, seg, n, tot);
+    FNX_HIP(hipGetLastError());
+    return FNX_OK;
+}
+
+// phase 2: tbits[i] (host) known; image i's entropy-coded segment goes to *ecs + ecs_off[i] (ecs_off: host, filled here);
+// fftot[i] (host-mapped) = its 0xff bytes
+int jpeg_entropy_pack_batch(fnx_ctx *ctx, int n, int w, int h, const unsigned long long *tbits, uint8_t **ecs, size_t *ecs_off,
+                            unsigned long long *fftot)
+{
+    int seg;
+    size_t sz[5];
+    entropy_batch_layout(n, w, h, &seg, sz);
+    const int nblk = n * seg;
+    void *sc = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_JPEG_ENC, sz[0] + sz[1] + sz[2] + sz[3] + sz[4], &sc));   // phase 1's layout: nothing moves
+    unsigned char *p = static_cast<unsigned char *>(sc) + sz[0];
+    const uint32_t *strip = reinterpret_cast<const uint32_t *>(p); p += sz[1];
+    const uint32_t *nbits = reinterpret_cast<const uint32_t *>(p); p += sz[2];
+    const unsigned long long *pos = reinterpret_cast<const unsigned long long *>(p);
+    std::vector<PackItem> items(n);
+    size_t words = 0, bytes = 0;
+    int maxw = 0;
+    for (int i = 0; i < n; i++) {
+        const size_t nw = static_cast<size_t>((tbits[i] + 31) / 32);
+        if (nw > static_cast<size_t>(seg) * JPEG_STRIP) {
+            set_error("jpeg: bit string of %llu bits does not fit its blocks' strips", tbits[i]);
+            return FNX_ERR_INVALID;
+        }
+        items[i].wbase = words;
+        items[i].ecs = bytes;
+        items[i].tbits = tbits[i];
+        items[i].nw = static_cast<int>(nw);
+        words += nw + 2;
+        bytes += (jpeg_ecs_capacity(tbits[i]) + 15) & ~size_t(15);
+        maxw = static_cast<int>(nw) + 2 > maxw ? static_cast<int>(nw) + 2 : maxw;
+        ecs_off[i] = items[i].ecs;
+    }
+    if (words >= (size_t(1) << 31)) {
+        set_error("jpeg batch: %zu words of bit strings in one pass", words);
+        return FNX_ERR_INVALID;
+    }
+    void *ditems = nullptr;
+    FNX_TRY(upload_table(ctx, SLOT_PTRS, items.data(), sizeof(PackItem) * n, &ditems));
+    auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
+    const size_t b_bits = al(4 * words), b_ffc = al(4 * words), b_ffb = al(8 * words), b_tot = al(8 * (words / SCAN_PER_WG + 2));
+    void *s2 = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_JPEG_ENC2, b_bits + b_ffc + b_ffb + b_tot, &s2));
+    p = static_cast<unsigned char *>(s2);
+    uint32_t *bits = reinterpret_cast<uint32_t *>(p); p += b_bits;
+    uint32_t *ffc = reinterpret_cast<uint32_t *>(p); p += b_ffc;
+    unsigned long long *ffb = reinterpret_cast<unsigned long long *>(p); p += b_ffb;
+    unsigned long long *wgt = reinterpret_cast<unsigned long long *>(p);
+    void *dec = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_JPEG_ECS, bytes + 64, &dec));
+    *ecs = static_cast<uint8_t *>(dec);
+    FNX_HIP(hipMemsetAsync(bits, 0, 4 * words, ctx->stream));
+    const PackItem *it = static_cast<const PackItem *>(ditems);
+    PackBatchArgs pa{strip, nbits, pos, bits, it, nblk, seg};
+    hipLaunchKernelGGL(jpeg_pack_batch_kernel, dim3((nblk + 255) / 256), dim3(256), 0, ctx->stream, pa);
+    FNX_HIP(hipGetLastError());
+    StuffBatchArgs sb{bits, it, ffc, ffb, *ecs, fftot, (maxw + 255) / 256};
+    hipLaunchKernelGGL(jpeg_ffcount_batch_kernel, dim3(sb.gx * n), dim3(256), 0, ctx->stream, sb);
+    FNX_HIP(hipGetLastError());
+    FNX_TRY(launch_scan(ctx, ffc, ffb, wgt, static_cast<int>(words), nullptr));
+    hipLaunchKernelGGL(jpeg_stuff_batch_kernel, dim3(sb.gx * n), dim3(256), 0, ctx->stream, sb);
     FNX_HIP(hipGetLastError());
     return FNX_OK;
 }

@@ -204,11 +204,10 @@ struct BoxYccArgs {
 };
 
 template <int XS>
-__global__ __launch_bounds__(256) void box_tiled_ycc_kernel(BoxYccArgs ya)
+__device__ __forceinline__ void box_tiled_ycc_body(const BoxYccArgs &ya, const int bx, const int dy)
 {
     __shared__ __attribute__((aligned(16))) uint32_t s_col[BOX_CHUNKS * 4 * 2];
     const BoxArgs &a = ya.box;
-    const int bx = blockIdx.x, dy = blockIdx.y;
     const int dx_lo = bx * a.seg;
     const int dx_hi = min(dx_lo + a.seg, a.dstW);
     int sy0, sy1, sxa, sxb, t0, t1;
@@ -317,21 +316,93 @@ __global__ __launch_bounds__(256) void box_tiled_ycc_kernel(BoxYccArgs ya)
     }
 }
 
+template <int XS>
+__global__ __launch_bounds__(256) void box_tiled_ycc_kernel(BoxYccArgs ya)
+{
+    box_tiled_ycc_body<XS>(ya, blockIdx.x, blockIdx.y);
+}
+
+// the shapes box_tiled_ycc_kernel covers (besides its planes' alignment): a downscale by boxes of < 257 rows / columns
+static bool box_ycc_tiled(int srcW, int srcH, int dstW, int dstH, double xRatio, double yRatio)
+{
+    return srcW >= dstW && srcH >= dstH && yRatio + 1.0 < BOX_MAXROWS && xRatio + 1.0 < BOX_MAXROWS && xRatio * 2 + 8 < 4 * BOX_CHUNKS;
+}
+
+static bool box_ycc_off()
+{
+    static const bool off = [] { const char *e = dev_env("FNX_BOX_YCC"); return e && e[0] == '0'; }();   // A/B and tests
+    return off;
+}
+
+// fnx_jpeg_compress_batch's route test: does launch_box_downsample_ycc take a 4:2:0 candidate of srcW x srcH (planes as
+// jpeg_planes lays them out: aligned) to dstW x dstH?  The same test the launcher makes.
+bool box_downsample_ycc_fused(int srcW, int srcH, int dstW, int dstH)
+{
+    if (box_ycc_off() || srcW <= 0 || srcH <= 0 || dstW <= 0 || dstH <= 0) return false;
+    return box_ycc_tiled(srcW, srcH, dstW, dstH, static_cast<double>(srcW) / static_cast<double>(dstW),
+                         static_cast<double>(srcH) / static_cast<double>(dstH));
+}
+
+// the candidates of a batched search step at 4:2:0: job j's planes at planes + j * plane_bytes (Y, then Cb at cb_off, Cr at
+// cr_off), its plane at dst + j * dst_bytes.  Job = blockIdx.x / gx: the grid's y stays the plane's rows.
+struct BoxYccBatchArgs {
+    BoxYccArgs one;
+    const uint8_t *planes;
+    size_t plane_bytes, cb_off, cr_off, dst_bytes;
+    uint8_t *dst;
+    int gx;
+};
+
+__global__ __launch_bounds__(256) void box_tiled_ycc_batch_kernel(BoxYccBatchArgs b)
+{
+    const int job = blockIdx.x / b.gx;
+    BoxYccArgs ya = b.one;
+    ya.y = b.planes + static_cast<size_t>(job) * b.plane_bytes;
+    ya.cb = ya.y + b.cb_off;
+    ya.cr = ya.y + b.cr_off;
+    ya.box.dst = b.dst + static_cast<size_t>(job) * b.dst_bytes;
+    box_tiled_ycc_body<1>(ya, blockIdx.x - job * b.gx, blockIdx.y);
+}
+
+int launch_box_downsample_ycc_batch(fnx_ctx *ctx, int njobs, const uint8_t *planes, size_t plane_bytes, size_t cb_off, size_t cr_off,
+                                    int ystride, int cstride, int srcW, int srcH, uint8_t *dst, size_t dst_bytes, int dstW, int dstH)
+{
+    if (!box_downsample_ycc_fused(srcW, srcH, dstW, dstH) || ((plane_bytes | cb_off | cr_off | ystride | cstride) & 3u) ||
+        (reinterpret_cast<uintptr_t>(planes) & 3u)) {
+        set_error("batched box downsample of JPEG planes: %d x %d -> %d x %d is not the fused kernel's case", srcW, srcH, dstW, dstH);
+        return FNX_ERR_INVALID;
+    }
+    BoxYccBatchArgs b{};
+    BoxArgs &a = b.one.box;
+    a.srcW = srcW; a.srcH = srcH; a.dstride = dstW * 4; a.dstW = dstW; a.dstH = dstH;
+    a.xRatio = static_cast<double>(srcW) / static_cast<double>(dstW);   // ssim.go:251-252
+    a.yRatio = static_cast<double>(srcH) / static_cast<double>(dstH);
+    int seg = static_cast<int>((4 * BOX_CHUNKS - 8) / a.xRatio);
+    if (seg > 256) seg = 256;
+    if (seg < 1) seg = 1;
+    a.seg = seg;
+    b.one.ystride = ystride; b.one.cstride = cstride; b.one.yshift = 1;
+    b.planes = planes; b.plane_bytes = plane_bytes; b.cb_off = cb_off; b.cr_off = cr_off;
+    b.dst = dst; b.dst_bytes = dst_bytes;
+    b.gx = (dstW + seg - 1) / seg;
+    hipLaunchKernelGGL(box_tiled_ycc_batch_kernel, dim3(b.gx * njobs, dstH), dim3(256), 0, ctx->stream, b);
+    FNX_HIP(hipGetLastError());
+    return FNX_OK;
+}
+
 // *done = false: not this kernel's case (grey, an upscale, huge boxes, unaligned planes) -- the caller converts and downsamples
 int launch_box_downsample_ycc(fnx_ctx *ctx, const uint8_t *y, int ystride, const uint8_t *cb, const uint8_t *cr, int cstride,
                               int ratio, int srcW, int srcH, uint8_t *dst, int dstride, int dstW, int dstH, bool *done)
 {
     *done = false;
-    static const bool off = [] { const char *e = dev_env("FNX_BOX_YCC"); return e && e[0] == '0'; }();   // A/B and tests
-    if (off || !cb || !cr || ratio < 0 || ratio > 5 || srcW <= 0 || srcH <= 0 || dstW <= 0 || dstH <= 0) return FNX_OK;
+    if (box_ycc_off() || !cb || !cr || ratio < 0 || ratio > 5 || srcW <= 0 || srcH <= 0 || dstW <= 0 || dstH <= 0) return FNX_OK;
     static const int xs[6] = {0, 1, 1, 0, 2, 2}, ys[6] = {0, 0, 1, 1, 0, 1};
     BoxYccArgs ya{};
     BoxArgs &a = ya.box;
     a.dst = dst; a.srcW = srcW; a.srcH = srcH; a.dstride = dstride; a.dstW = dstW; a.dstH = dstH;
     a.xRatio = static_cast<double>(srcW) / static_cast<double>(dstW);   // ssim.go:251-252
     a.yRatio = static_cast<double>(srcH) / static_cast<double>(dstH);
-    const bool tiled = srcW >= dstW && srcH >= dstH && a.yRatio + 1.0 < BOX_MAXROWS &&
-                       a.xRatio + 1.0 < BOX_MAXROWS && a.xRatio * 2 + 8 < 4 * BOX_CHUNKS;
+    const bool tiled = box_ycc_tiled(srcW, srcH, dstW, dstH, a.xRatio, a.yRatio);
     const int cal = 4 >> xs[ratio];                               // bytes of a chunk's chroma
     const bool aligned = (reinterpret_cast<uintptr_t>(y) & 3u) == 0 && (ystride & 3) == 0 &&
                          (reinterpret_cast<uintptr_t>(cb) % cal) == 0 && (reinterpret_cast<uintptr_t>(cr) % cal) == 0 && (cstride % cal) == 0;
@@ -1616,9 +1687,13 @@ static bool ssim_use_tiled()
 int launch_windowed_ssim(fnx_ctx *ctx, int n, const uint8_t *a, int astride, size_t a_image_bytes,
                          const uint8_t *b, int bstride, size_t b_image_bytes, int w, int h,
                          const double *h_window, const double *d_window, double *d_out,
-                         SsimDeferred *defer, int defer_out_index, const uint8_t *const *d_as, const uint8_t *const *d_bs)
+                         SsimDeferred *defer, int defer_out_index, const uint8_t *const *d_as, const uint8_t *const *d_bs,
+                         bool select_as_one)
 {
     const int ww = w - 8, wh = h - 8;     // window grid
+    // select_as_one: the kernel, its tiling and its reduction order are those of a call with n == 1 (every image's score is
+    // then bit for bit the single call's: fnx_jpeg_compress_batch); n only widens the grid
+    const long nsel = select_as_one ? 1L : static_cast<long>(n);
     const bool have = ww > 0 && wh > 0;
     WinSepArgs sa{};
     const bool sep = have && window_rank1(h_window, sa.col, sa.row);
@@ -1626,9 +1701,9 @@ int launch_windowed_ssim(fnx_ctx *ctx, int n, const uint8_t *a, int astride, siz
     // wave): single small planes (one SSIMFast, the MSSSIM levels) keep the tile kernels, 2-5 us a launch
     // against ~19.  FNX_SSIM_MARCH_MIN overrides the window count from which it takes over (experiments).
     static const long march_min = [] { const char *e = dev_env("FNX_SSIM_MARCH_MIN"); return e ? atol(e) : 1500000L; }();
-    const bool march = sep && !ssim_use_tiled() && static_cast<long>(ww) * wh * n >= march_min;
+    const bool march = sep && !ssim_use_tiled() && static_cast<long>(ww) * wh * nsel >= march_min;
     // tile kernels (FNX_SSIM_TILED=1, and the 64-tap kernel for tables that are not rank-1)
-    const bool big = sep && static_cast<long>(ww) * wh * n >= 4L * 1024 * ctx->num_cus;
+    const bool big = sep && static_cast<long>(ww) * wh * nsel >= 4L * 1024 * ctx->num_cus;
     const int TX = sep ? WSS_TX : WS_TX, TY = sep ? (big ? W24_TY : WSS_TY) : WS_TY;
     int tiles_x = 0, tiles = 0;
     MarchArgs ma{};
@@ -1646,7 +1721,7 @@ int launch_windowed_ssim(fnx_ctx *ctx, int n, const uint8_t *a, int astride, siz
         static const long m2_env = [] { const char *e = dev_env("FNX_SSIM_M2_WAVES"); return e ? atol(e) : 0L; }();   // experiments
         const long m2_per_cu = m2_env ? m2_env : 8L;                // (both two-column kernels run two waves per SIMD)
         const long target = (march2 ? m2_per_cu : 16L) * ctx->num_cus;
-        long segs = target / (static_cast<long>(n) * ma.strips);
+        long segs = target / (nsel * ma.strips);
         const long max_segs = wh / 32 > 0 ? wh / 32 : 1;
         if (segs > max_segs) segs = max_segs;
         if (segs < 1) segs = 1;
@@ -2226,11 +2301,10 @@ int launch_ssim_finish_deferred(fnx_ctx *ctx, const SsimDeferred &d, double *d_o
 // pixelSSIM (ssim.go:169-204): images with a dimension < 8.  One lane, the reference's
 // exact running-sum order over the flat Pix slices.
 // ------------------------------------------------------------------------------------
-__global__ void pixel_ssim_kernel(const uint8_t *a, const uint8_t *b, int w, int h, size_t pix_len, double *out)
+__device__ __forceinline__ double pixel_ssim_body(const uint8_t *a, const uint8_t *b, int w, int h, size_t pix_len)
 {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const double n = static_cast<double>(w * h);
-    if (n == 0) { *out = 1.0; return; }
+    if (n == 0) return 1.0;
     double muA = 0, muB = 0;
     for (size_t i = 0; i < pix_len; i += 4) {
         muA += lum601(*reinterpret_cast<const uint32_t *>(a + i));
@@ -2246,7 +2320,28 @@ __global__ void pixel_ssim_kernel(const uint8_t *a, const uint8_t *b, int w, int
     sAA /= n; sBB /= n; sAB /= n;
     const double num = (2 * muA * muB + 6.5025) * (2 * sAB + 58.5225);
     const double den = (muA * muA + muB * muB + 6.5025) * (sAA + sBB + 58.5225);
-    *out = num / den;
+    return num / den;
+}
+
+__global__ void pixel_ssim_kernel(const uint8_t *a, const uint8_t *b, int w, int h, size_t pix_len, double *out)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    *out = pixel_ssim_body(a, b, w, h, pix_len);
+}
+
+// n pairs, one workgroup each (image = blockIdx.x): d_as[i] / d_bs[i] tight w x h
+__global__ void pixel_ssim_batch_kernel(const uint8_t *const *as, const uint8_t *const *bs, int w, int h, size_t pix_len, double *out)
+{
+    if (threadIdx.x != 0) return;
+    out[blockIdx.x] = pixel_ssim_body(as[blockIdx.x], bs[blockIdx.x], w, h, pix_len);
+}
+
+int launch_pixel_ssim_batch(fnx_ctx *ctx, int n, const uint8_t *const *d_as, const uint8_t *const *d_bs, int w, int h, size_t pix_len,
+                            double *d_out)
+{
+    hipLaunchKernelGGL(pixel_ssim_batch_kernel, dim3(n), dim3(64), 0, ctx->stream, d_as, d_bs, w, h, pix_len, d_out);
+    FNX_HIP(hipGetLastError());
+    return FNX_OK;
 }
 
 int launch_pixel_ssim(fnx_ctx *ctx, const uint8_t *a, const uint8_t *b, int w, int h,

@@ -441,6 +441,16 @@ int fnx_msssim_enqueue(fnx_ctx *ctx, const uint8_t *a, int astride, const uint8_
  * slot, one result event, and -- through fennec_MSSSIM_batch_enqueue -- ONE batched resize for the pairs whose dims differ. */
 int fnx_msssim_batch_enqueue(fnx_ctx *ctx, int n, const uint8_t *const *as, int astride, const uint8_t *const *bs, int bstride,
                              int w, int h, const double *window /* 64 */);
+/* compressJPEGOptimal (compress.go:21-87) of n device images of ONE geometry: item i is searched against target_ssim[i]
+ * and its file goes to outs[i] (capacity caps[i], host memory).  Per item, (file bytes, *quality, *ssim, *steps) are
+ * those fnx_jpeg_compress returns for the same image and target, byte for byte and bit for bit.  status[i]: FNX_OK, or
+ * FNX_ERR_INVALID when caps[i] is too small -- nbytes[i] and quality[i] are then set, and fnx_jpeg_encode at quality[i]
+ * gives the file without searching again.  Returns FNX_OK when the batch ran (per-item outcomes in status), an error
+ * for bad arguments before anything is launched.  Blocking; like the other blocking forms, it needs an empty result FIFO. */
+int fnx_jpeg_compress_batch(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstride, int w, int h,
+                            const double *target_ssim /* n */, const double *window /* 64 */,
+                            uint8_t *const *outs, const size_t *caps, size_t *nbytes /* n */, int *quality /* n */,
+                            double *ssim /* n */, int *steps /* n, may be NULL */, int *status /* n */);
 
 /* dsts[i] = GaussianBlur(srcs[i]) AND out[i] = SSIMFast(srcs[i], dsts[i]) -- the pair of calls
  * the reference makes whenever it scores a processed image against its source (effects.go:146
