@@ -318,6 +318,18 @@ def _i32(a):
     return a, a.ctypes.data_as(_i32p)
 
 
+def _into_buffer(call, cap: int, n):
+    """call(buf, cap) -> rc: an entry point that writes a file into `buf` and its size into the c_size_t `n`.  When it fails
+    with a size over `cap`, it runs once more into a buffer of that size.  -> (rc, buf)"""
+    buf = np.empty(cap, dtype=np.uint8)
+    rc = call(buf, cap)
+    if rc < 0 and n.value > cap:
+        cap = n.value
+        buf = np.empty(cap, dtype=np.uint8)
+        rc = call(buf, cap)
+    return rc, buf
+
+
 class Context:
     """One GPU, one stream, its scratch (fnx_ctx).  Not re-entrant: one per worker thread."""
 
@@ -674,15 +686,10 @@ class Context:
         cap = 4096 + (s.w * s.h * 3) // 2
         n = C.c_size_t(0)
         with self._ordered(img):
-            for _ in range(2):
-                buf = np.empty(cap, dtype=np.uint8)
-                rc = self._lib.fnx_jpeg_encode(self._h, s.space, s.ptr, s.stride, s.w, s.h, int(quality), buf.ctypes.data_as(_u8p),
-                                               cap, C.byref(n))
-                if rc == FNX_OK:
-                    return buf[:n.value].tobytes()
-                if n.value <= cap:
-                    self._chk(rc, "fnx_jpeg_encode")
-                cap = n.value
+            rc, buf = _into_buffer(lambda b, c: self._lib.fnx_jpeg_encode(self._h, s.space, s.ptr, s.stride, s.w, s.h, int(quality),
+                                                                          b.ctypes.data_as(_u8p), c, C.byref(n)), cap, n)
+            if rc == FNX_OK:
+                return buf[:n.value].tobytes()
         self._chk(rc, "fnx_jpeg_encode")
 
     def jpeg_encoded_size(self, img, quality: int) -> int:
@@ -717,15 +724,11 @@ class Context:
         cap = 4096 + (s.w * s.h * 3) // 2
         n, q, st, v = C.c_size_t(0), C.c_int(), C.c_int(), C.c_double()
         with self._ordered(img):
-            for _ in range(2):
-                buf = np.empty(cap, dtype=np.uint8)
-                rc = self._lib.fnx_jpeg_compress(self._h, s.space, s.ptr, s.stride, s.w, s.h, float(target_ssim), pk,
-                                                 buf.ctypes.data_as(_u8p), cap, C.byref(n), C.byref(q), C.byref(v), C.byref(st))
-                if rc == FNX_OK:
-                    return buf[:n.value].tobytes(), q.value, v.value, st.value
-                if n.value <= cap:
-                    break
-                cap = n.value
+            rc, buf = _into_buffer(lambda b, c: self._lib.fnx_jpeg_compress(self._h, s.space, s.ptr, s.stride, s.w, s.h, float(target_ssim), pk,
+                                                                            b.ctypes.data_as(_u8p), c, C.byref(n), C.byref(q), C.byref(v),
+                                                                            C.byref(st)), cap, n)
+            if rc == FNX_OK:
+                return buf[:n.value].tobytes(), q.value, v.value, st.value
         self._chk(rc, "fnx_jpeg_compress")
 
     def jpeg_compress_batch(self, imgs, target_ssim, window=None):
@@ -780,15 +783,10 @@ class Context:
                                                            C.byref(n)), "fnx_jpeg_encode_scaled")
                 return int(n.value)
             cap = 4096 + (dw * dh * 3) // 2
-            for _ in range(2):
-                buf = np.empty(cap, dtype=np.uint8)
-                rc = self._lib.fnx_jpeg_encode_scaled(self._h, s.space, s.ptr, s.stride, s.w, s.h, dw, dh, int(quality),
-                                                      buf.ctypes.data_as(_u8p), cap, C.byref(n))
-                if rc == FNX_OK:
-                    return buf[:n.value].tobytes()
-                if n.value <= cap:
-                    break
-                cap = n.value
+            rc, buf = _into_buffer(lambda b, c: self._lib.fnx_jpeg_encode_scaled(self._h, s.space, s.ptr, s.stride, s.w, s.h, dw, dh, int(quality),
+                                                                                 b.ctypes.data_as(_u8p), c, C.byref(n)), cap, n)
+            if rc == FNX_OK:
+                return buf[:n.value].tobytes()
         self._chk(rc, "fnx_jpeg_encode_scaled")
 
     def jpeg_target_size(self, img, target_bytes: int, strategies: int = FNX_TS_ALL, cancel=None, window=None):
@@ -896,15 +894,11 @@ class Context:
         k, pk = _f64(self.gaussianKernel() if window is None else window)
         cap = len(data) + 4096       # a search ends below the quality a camera wrote; a larger file asks again with its size
         n, q, st, v, w, h = C.c_size_t(0), C.c_int(), C.c_int(), C.c_double(), C.c_int(), C.c_int()
-        for _ in range(2):
-            buf = np.empty(cap, dtype=np.uint8)
-            rc = self._lib.fnx_jpeg_recompress(self._h, src.ctypes.data_as(_u8p), len(data), float(target_ssim), pk, buf.ctypes.data_as(_u8p),
-                                               cap, C.byref(n), C.byref(q), C.byref(v), C.byref(st), C.byref(w), C.byref(h))
-            if rc == FNX_OK:
-                return buf[:n.value].tobytes(), q.value, v.value, st.value, (w.value, h.value)
-            if n.value <= cap:
-                break
-            cap = n.value
+        rc, buf = _into_buffer(lambda b, c: self._lib.fnx_jpeg_recompress(self._h, src.ctypes.data_as(_u8p), len(data), float(target_ssim), pk,
+                                                                          b.ctypes.data_as(_u8p), c, C.byref(n), C.byref(q), C.byref(v),
+                                                                          C.byref(st), C.byref(w), C.byref(h)), cap, n)
+        if rc == FNX_OK:
+            return buf[:n.value].tobytes(), q.value, v.value, st.value, (w.value, h.value)
         self._chk(rc, "fnx_jpeg_recompress")
 
     def compress_file_jpeg(self, data: bytes, target_ssim: float, orient: int = 1, max_w: int = 0, max_h: int = 0, auto_format: bool = False):
@@ -916,17 +910,13 @@ class Context:
         cap = max(4096, len(data) + 4096)
         n, q, st, v = C.c_size_t(0), C.c_int(), C.c_int(), C.c_double()
         dims = (C.c_int * 4)()
-        for _ in range(2):
-            buf = np.empty(cap, dtype=np.uint8)
-            rc = self._lib.fennec_CompressFileJPEG(self._h, src.ctypes.data_as(_u8p), len(data), C.byref(o), buf.ctypes.data_as(_u8p), cap,
-                                                   C.byref(n), C.byref(q), C.byref(v), C.byref(st), dims)
-            if rc == FNX_OK:
-                return buf[:n.value].tobytes(), q.value, v.value, st.value, (dims[0], dims[1]), (dims[2], dims[3])
-            if rc == FNX_NOOP:
-                return None, 0, 1.0, 0, (dims[0], dims[1]), (dims[2], dims[3])
-            if n.value <= cap:
-                break
-            cap = n.value
+        rc, buf = _into_buffer(lambda b, c: self._lib.fennec_CompressFileJPEG(self._h, src.ctypes.data_as(_u8p), len(data), C.byref(o),
+                                                                              b.ctypes.data_as(_u8p), c, C.byref(n), C.byref(q), C.byref(v),
+                                                                              C.byref(st), dims), cap, n)
+        if rc == FNX_OK:
+            return buf[:n.value].tobytes(), q.value, v.value, st.value, (dims[0], dims[1]), (dims[2], dims[3])
+        if rc == FNX_NOOP:
+            return None, 0, 1.0, 0, (dims[0], dims[1]), (dims[2], dims[3])
         self._chk(rc, "fennec_CompressFileJPEG")
 
     def jpeg_quality_search(self, img, target_ssim: float, window=None):

@@ -102,7 +102,7 @@ enum Slot {
     SLOT_FILE0, SLOT_FILE1, SLOT_FILE_SAMPLES,                     // host_api.cpp: fennec_CompressFileJPEG's images between its stages
     SLOT_JPEG_DEC, SLOT_JPEG_DEC_PLANES, SLOT_JPEG_DEC_IMG,        // jpeg_dec.hip: the decoder's work arrays, its planes, toNRGBARef's image
     SLOT_AN_HASH0, SLOT_AN_HASH1,   // analyze.hip: the colour-set tables of this call and the next (the launch that uses one zeroes the other)
-    SLOT_TS_SCALED, SLOT_TS_UP,    // api.cpp: fnx_jpeg_target_size's Lanczos-scaled image and its upscale back to the source's size
+    SLOT_TS_SCALED, SLOT_TS_UP,    // jpeg_api.cpp: fnx_jpeg_target_size's Lanczos-scaled image and its upscale back to the source's size
     SLOT_JPEG_QTAB, SLOT_JPEG_JOBS,  // fnx_jpeg_compress_batch: the quantiser tables of qualities 1..100, a search step's job list
     SLOT_DONE,       // workgroup counters of the kernels that finish their own reduction (ssim.hip), zero between launches
     SLOT_COUNT
@@ -320,6 +320,23 @@ inline bool aligned16(const void *p, int stride)
 {
     return ((reinterpret_cast<uintptr_t>(p) | static_cast<uintptr_t>(stride)) & 15u) == 0;
 }
+
+// ---- api.cpp: what its entry points and jpeg_api.cpp's share ----
+// argument checks: an image's pointer and stride (nothing to check when w or h <= 0); the space of an op with a scalar
+// result (FNX_HOST, FNX_DEVICE) and of an image -> image op (those or FNX_DEVICE_SRC: device source, host destination)
+int check_img(const void *p, int stride, int w, int h, const char *what);
+int check_space(int space);
+int check_space_io(int space);
+// SSIMFast's dims (ssim.go:52-56): true when the w x h image is compared box-downsampled, at *nw x *nh (<= 512 px)
+bool ssim_fast_dims(int w, int h, int *nw, int *nh);
+// n result doubles in pinned memory that the result kernels write (NaN until then), and the wait for them (-> out)
+int result_slot(fnx_ctx *ctx, int n, double **d);
+int result_wait(fnx_ctx *ctx, const double *pinned, double *out, int n);
+// SSIMFast(prepared reference, device image b) -> *out; b_is_plane: b is already the candidate's tight pw x ph plane
+int against_device(fnx_ctx *ctx, const fnx_prepared *ref, const uint8_t *b, int bstride, const double *window, double *out,
+                   bool b_is_plane = false);
+// the reference's own plane from the device image src into ref.pix (ref.w, ref.h, ref.pw, ref.ph as ssim_fast_dims set them)
+int prepared_plane(fnx_ctx *ctx, const uint8_t *src, int sstride, const fnx_prepared &ref);
 
 // ---- kernel launchers (each enqueues on ctx->stream; device pointers only) ----
 int launch_blur(fnx_ctx *ctx, int n, const uint8_t *src, const uint8_t *const *srcs, int sstride,

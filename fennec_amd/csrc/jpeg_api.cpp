@@ -1,0 +1,869 @@
+// fnx_jpeg_* entry points: the JPEG encoder's host flow (compress.go, targetsize.go) around jpeg.hip's kernels, and the
+// decoder's around jpeg_dec.hip and jpeg_prog.cpp.
+#include "common.hpp"
+
+using namespace fnx;
+
+// ---- the JPEG quantisation round trip (compress.go:45-74; SURVEY 8(f)2, first slice: jpeg.hip) -------------
+namespace {
+
+// a JPEG file's dimensions are 16-bit
+bool jpeg_dims(int w, int h) { return w >= 1 && w <= 65535 && h >= 1 && h <= 65535; }
+
+struct JpegPlanes {
+    uint8_t *p[3];
+    int ys, yh, cs, ch;
+};
+
+int jpeg_planes(fnx_ctx *ctx, Slot slot, int w, int h, JpegPlanes *jp)
+{
+    jpeg_plane_dims(w, h, &jp->ys, &jp->yh, &jp->cs, &jp->ch);
+    const size_t yb = static_cast<size_t>(jp->ys) * jp->yh, cb = static_cast<size_t>(jp->cs) * jp->ch;
+    void *t = nullptr;
+    FNX_TRY(scratch(ctx, slot, yb + 2 * cb + 16, &t));
+    jp->p[0] = static_cast<uint8_t *>(t);
+    jp->p[1] = jp->p[0] + yb;
+    jp->p[2] = jp->p[1] + cb;
+    return FNX_OK;
+}
+
+// the unquantised planes of the device image img in `slot`: what every encode of it starts from
+int jpeg_ycc_planes(fnx_ctx *ctx, Slot slot, const uint8_t *img, int stride, int w, int h, JpegPlanes *pl)
+{
+    FNX_TRY(jpeg_planes(ctx, slot, w, h, pl));
+    return launch_jpeg_ycc(ctx, img, stride, w, h, pl->p[0], pl->p[1], pl->p[2]);
+}
+
+// planes at `quality` from the unquantised planes in SLOT_JPEG0, then the NRGBA image toNRGBARef makes of them
+int jpeg_decode_at(fnx_ctx *ctx, const JpegPlanes &orig, int w, int h, int quality, uint8_t *dst, int dstride)
+{
+    JpegPlanes work;
+    FNX_TRY(jpeg_planes(ctx, SLOT_JPEG1, w, h, &work));
+    const uint8_t *in[3] = {orig.p[0], orig.p[1], orig.p[2]};
+    FNX_TRY(launch_jpeg_blocks(ctx, w, h, quality, in, work.p));
+    return launch_ycbcr_to_nrgba(ctx, work.p[0], work.ys, work.p[1], work.p[2], work.cs, 2, w, h, dst, dstride);
+}
+
+// the source side of every SSIMFast of a call (ssim.go:52-58), prepared once: its dims and its plane's buffer in SLOT_JPEG3
+// (the plane: prepared_plane, or launch_box_downsample_ycc from a decoded file's planes)
+int jpeg_prepared(fnx_ctx *ctx, int w, int h, fnx_prepared *ref)
+{
+    ref->w = w; ref->h = h;
+    ssim_fast_dims(w, h, &ref->pw, &ref->ph);
+    void *rp = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_JPEG3, static_cast<size_t>(ref->pw) * ref->ph * 4 + 16, &rp));
+    ref->pix = static_cast<uint8_t *>(rp);
+    return FNX_OK;
+}
+
+// compressJPEGOptimal's bisection (compress.go:24-74): a target >= 1 is 0.999, the lower bound comes from the target, and
+// quality 100 (SSIM 1) stands when no quality reaches it
+struct QualitySearch {
+    double target;
+    int lo = 1, hi = 100, best_q = 100, steps = 0;
+    double best_ssim = 1.0;
+    bool found = false;
+
+    explicit QualitySearch(double t) : target(t >= 1.0 ? 0.999 : t)
+    {
+        if (target >= 0.99) lo = 75;
+        else if (target >= 0.97) lo = 50;
+        else if (target >= 0.94) lo = 30;
+        else if (target >= 0.90) lo = 15;
+    }
+    bool done() const { return lo > hi; }
+    int mid() const { return (lo + hi) / 2; }
+    void record(int q, double ssim)
+    {
+        steps++;
+        if (ssim >= target) {
+            best_q = q; best_ssim = ssim; found = true;
+            hi = q - 1;
+        } else {
+            lo = q + 1;
+        }
+    }
+};
+
+// compressJPEGOptimal's search over the unquantised planes `orig` of a w x h source whose prepared side is `ref`;
+// FNX_NOOP: no quality reached the target
+int jpeg_search_device(fnx_ctx *ctx, const fnx_prepared &ref, const JpegPlanes &orig, int w, int h, double target_ssim,
+                       const double *window, int *quality, double *ssim, int *steps)
+{
+    void *dec = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_JPEG2, static_cast<size_t>(w) * h * 4 + 16, &dec));
+    const bool ds = ref.pw != w || ref.ph != h;
+    void *cand = nullptr;                                         // the candidate's SSIMFast plane
+    if (ds) FNX_TRY(scratch(ctx, SLOT_TMP2, static_cast<size_t>(ref.pw) * ref.ph * 4 + 16, &cand));
+    QualitySearch qs(target_ssim);
+    while (!qs.done()) {
+        const int mid = qs.mid();
+        double v = 0;
+        // the candidate: planes at quality `mid`; its <= 256 px plane straight from them where the image would only be
+        // written to be box-summed (r3), else toNRGBARef's image
+        JpegPlanes work;
+        FNX_TRY(jpeg_planes(ctx, SLOT_JPEG1, w, h, &work));
+        const uint8_t *in[3] = {orig.p[0], orig.p[1], orig.p[2]};
+        FNX_TRY(launch_jpeg_blocks(ctx, w, h, mid, in, work.p));
+        bool fused = false;
+        if (ds) FNX_TRY(launch_box_downsample_ycc(ctx, work.p[0], work.ys, work.p[1], work.p[2], work.cs, 2, w, h, static_cast<uint8_t *>(cand),
+                                                  ref.pw * 4, ref.pw, ref.ph, &fused));
+        if (fused) {
+            FNX_TRY(against_device(ctx, &ref, static_cast<const uint8_t *>(cand), ref.pw * 4, window, &v, true));
+        } else {
+            FNX_TRY(launch_ycbcr_to_nrgba(ctx, work.p[0], work.ys, work.p[1], work.p[2], work.cs, 2, w, h, static_cast<uint8_t *>(dec), w * 4));
+            FNX_TRY(against_device(ctx, &ref, static_cast<const uint8_t *>(dec), w * 4, window, &v));
+        }
+        qs.record(mid, v);
+    }
+    *quality = qs.best_q;
+    *ssim = qs.best_ssim;
+    if (steps) *steps = qs.steps;
+    return qs.found ? FNX_OK : FNX_NOOP;
+}
+
+// compressJPEGOptimal up to its file: src staged, its planes (-> *orig), the search
+int jpeg_search_src(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, double target_ssim, const double *window,
+                    JpegPlanes *orig, int *quality, double *ssim, int *steps)
+{
+    DevImg s;
+    FNX_TRY(stage_in(ctx, space, src, sstride, w, h, SLOT_IN_A, &s));
+    FNX_TRY(jpeg_ycc_planes(ctx, SLOT_JPEG0, s.p, s.stride, w, h, orig));
+    fnx_prepared ref;
+    FNX_TRY(jpeg_prepared(ctx, w, h, &ref));
+    FNX_TRY(prepared_plane(ctx, s.p, s.stride, ref));
+    return jpeg_search_device(ctx, ref, *orig, w, h, target_ssim, window, quality, ssim, steps);
+}
+
+// The file: header | entropy-coded segment | EOI.  The segment of a scan of `bits` bits with `ff` 0xff bytes in it is the bits
+// padded to whole bytes plus the zero stuffed behind each 0xff.
+size_t jpeg_ecs_bytes(unsigned long long bits, unsigned long long ff)
+{
+    return static_cast<size_t>((bits + 7) / 8) + static_cast<size_t>(bits ? ff : 0);
+}
+
+// -> the size of the file around a segment of `ecs` bytes; when it fits `cap`, its header and EOI go into out (the caller puts
+// the segment at out + hdr.size())
+size_t jpeg_file_frame(const std::vector<uint8_t> &hdr, size_t ecs, uint8_t *out, size_t cap)
+{
+    const size_t total = hdr.size() + ecs + 2;
+    if (out == nullptr || cap < total) return total;
+    std::memcpy(out, hdr.data(), hdr.size());
+    out[total - 2] = 0xff;
+    out[total - 1] = 0xd9;          // EOI
+    return total;
+}
+
+// the file of `orig`'s image at `quality` into host memory (see fnx_jpeg_encode)
+int jpeg_file_from_planes(fnx_ctx *ctx, const JpegPlanes &orig, int w, int h, int quality, uint8_t *out, size_t cap, size_t *nbytes)
+{
+    // two u64 the kernels write and the host reads: bits of the scan's string, 0xff bytes in it
+    double *slot;
+    FNX_TRY(result_slot(ctx, 2, &slot));
+    unsigned long long *totals = reinterpret_cast<unsigned long long *>(slot);
+    totals[0] = totals[1] = ~0ull;
+    const uint8_t *planes[3] = {orig.p[0], orig.p[1], orig.p[2]};
+    FNX_TRY(jpeg_entropy_code(ctx, w, h, quality, planes, totals));
+    FNX_HIP(hipStreamSynchronize(ctx->stream));
+    const unsigned long long tbits = totals[0];
+    void *ecs = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_JPEG_ECS, jpeg_ecs_capacity(tbits), &ecs));
+    FNX_TRY(jpeg_entropy_pack(ctx, w, h, tbits, static_cast<uint8_t *>(ecs), totals));
+    FNX_HIP(hipStreamSynchronize(ctx->stream));
+    const size_t ecs_bytes = jpeg_ecs_bytes(tbits, totals[1]);
+    std::vector<uint8_t> hdr;
+    jpeg_header(w, h, quality, hdr);
+    const size_t total = jpeg_file_frame(hdr, ecs_bytes, out, cap);
+    *nbytes = total;
+    if (out == nullptr && cap == 0) return FNX_OK;       // size query: targetsize.go's searches need len(encoded) only
+    if (out == nullptr || cap < total) {
+        set_error("invalid argument: the file needs %zu bytes, the buffer holds %zu", total, cap);
+        return FNX_ERR_INVALID;
+    }
+    if (ecs_bytes) FNX_HIP(hipMemcpy(out + hdr.size(), ecs, ecs_bytes, hipMemcpyDeviceToHost));
+    return FNX_OK;
+}
+
+// jpegQualitySearchOpt's bisection (targetsize.go:129-165) over the planes of a w x h image, file sizes only: *q = the highest
+// quality whose file fits `target` bytes (0: none), *sz its file's size; *n += the encodes it ran
+int jpeg_size_bisect(fnx_ctx *ctx, const JpegPlanes &pl, int w, int h, long long target, int *q, size_t *sz, int *n)
+{
+    const double pixels = static_cast<double>(static_cast<long long>(w) * h);
+    const double bpp = static_cast<double>(target * 8) / pixels;
+    int lo = 1, hi = 100;
+    if (bpp < 0.5) hi = 40;
+    else if (bpp < 1.0) { lo = 10; hi = 70; }
+    else if (bpp < 2.0) { lo = 30; hi = 90; }
+    else if (bpp > 4.0) lo = 60;
+    *q = 0; *sz = 0;
+    while (lo <= hi) {
+        const int mid = (lo + hi) / 2;
+        size_t len = 0;
+        FNX_TRY(jpeg_file_from_planes(ctx, pl, w, h, mid, nullptr, 0, &len));       // len(encoded) only
+        ++*n;
+        if (static_cast<long long>(len) <= target) {
+            *q = mid; *sz = len;
+            lo = mid + 1;
+        } else {
+            hi = mid - 1;
+        }
+    }
+    return FNX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fnx_jpeg_roundtrip(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int quality,
+                       uint8_t *dst, int dstride)
+{
+    FNX_ENTER(ctx);
+    FNX_TRY(check_space_io(space));
+    FNX_TRY(check_img(src, sstride, w, h, "src"));
+    FNX_TRY(check_img(dst, dstride, w, h, "dst"));
+    if (w <= 0 || h <= 0) return FNX_OK;
+    DevImg s;
+    DevOut d;
+    FNX_TRY(stage_in(ctx, space, src, sstride, w, h, SLOT_IN_A, &s));
+    FNX_TRY(stage_out(ctx, space, dst, dstride, w, h, SLOT_OUT, &d));
+    JpegPlanes orig;
+    FNX_TRY(jpeg_ycc_planes(ctx, SLOT_JPEG0, s.p, s.stride, w, h, &orig));
+    FNX_TRY(jpeg_decode_at(ctx, orig, w, h, quality, d.p, d.stride));
+    return finish(ctx, space, &d);
+}
+
+int fnx_jpeg_quality_search(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, double target_ssim,
+                            const double *window, int *quality, double *ssim, int *steps)
+{
+    FNX_ENTER(ctx);
+    FNX_TRY(check_space(space));
+    FNX_REQUIRE(window && quality && ssim && w > 0 && h > 0, "search arguments");
+    FNX_TRY(check_img(src, sstride, w, h, "src"));
+    JpegPlanes orig;
+    // FNX_NOOP: no quality reached the target (compress.go:82-86: encode at 100)
+    return jpeg_search_src(ctx, space, src, sstride, w, h, target_ssim, window, &orig, quality, ssim, steps);
+}
+
+int fnx_jpeg_encode(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int quality, uint8_t *out, size_t cap,
+                    size_t *nbytes)
+{
+    FNX_ENTER(ctx);
+    FNX_TRY(check_space(space));
+    FNX_REQUIRE(nbytes != nullptr && jpeg_dims(w, h), "encode arguments (JPEG dims are 16-bit)");
+    FNX_TRY(check_img(src, sstride, w, h, "src"));
+    *nbytes = 0;
+    DevImg s;
+    JpegPlanes orig;
+    FNX_TRY(stage_in(ctx, space, src, sstride, w, h, SLOT_IN_A, &s));
+    FNX_TRY(jpeg_ycc_planes(ctx, SLOT_JPEG0, s.p, s.stride, w, h, &orig));
+    return jpeg_file_from_planes(ctx, orig, w, h, quality, out, cap, nbytes);
+}
+
+int fnx_jpeg_size_search(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, long long target_bytes, int skip_ssim,
+                         const double *window, uint8_t *out, size_t cap, size_t *nbytes, int *quality, double *ssim, int *steps)
+{
+    FNX_ENTER(ctx);
+    FNX_TRY(check_space(space));
+    FNX_REQUIRE(nbytes && quality && ssim && (skip_ssim || window) && jpeg_dims(w, h), "size search arguments");
+    FNX_TRY(check_img(src, sstride, w, h, "src"));
+    *nbytes = 0; *quality = 0; *ssim = 0.0;
+    DevImg s;
+    JpegPlanes orig;
+    FNX_TRY(stage_in(ctx, space, src, sstride, w, h, SLOT_IN_A, &s));
+    FNX_TRY(jpeg_ycc_planes(ctx, SLOT_JPEG0, s.p, s.stride, w, h, &orig));
+    // targetsize.go:125-176
+    int best_q = 0, n = 0;
+    size_t sz = 0;
+    FNX_TRY(jpeg_size_bisect(ctx, orig, w, h, target_bytes, &best_q, &sz, &n));
+    if (steps) *steps = n;
+    if (best_q == 0) return FNX_NOOP;                        // bestBuf == nil: nothing fits (the caller tries its next strategy)
+    *quality = best_q;
+    if (!skip_ssim) {
+        // the SSIMFast the reference takes of every fitting candidate; the one that survives is the best quality's
+        fnx_prepared ref;
+        FNX_TRY(jpeg_prepared(ctx, w, h, &ref));
+        FNX_TRY(prepared_plane(ctx, s.p, s.stride, ref));
+        void *dec = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_JPEG2, static_cast<size_t>(w) * h * 4 + 16, &dec));
+        FNX_TRY(jpeg_decode_at(ctx, orig, w, h, best_q, static_cast<uint8_t *>(dec), w * 4));
+        FNX_TRY(against_device(ctx, &ref, static_cast<const uint8_t *>(dec), w * 4, window, ssim));
+    }
+    return jpeg_file_from_planes(ctx, orig, w, h, best_q, out, cap, nbytes);
+}
+
+int fnx_jpeg_compress(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, double target_ssim, const double *window,
+                      uint8_t *out, size_t cap, size_t *nbytes, int *quality, double *ssim, int *steps)
+{
+    FNX_ENTER(ctx);
+    FNX_TRY(check_space(space));
+    FNX_REQUIRE(window && nbytes && quality && ssim && jpeg_dims(w, h), "compress arguments");
+    FNX_TRY(check_img(src, sstride, w, h, "src"));
+    *nbytes = 0;
+    JpegPlanes orig;
+    FNX_TRY(jpeg_search_src(ctx, space, src, sstride, w, h, target_ssim, window, &orig, quality, ssim, steps));
+    // compress.go:76-86: the best candidate's bytes, or -- nothing reached the target -- an encode at bestQuality (100)
+    return jpeg_file_from_planes(ctx, orig, w, h, *quality, out, cap, nbytes);
+}
+
+// ---- compressJPEGOptimal of n device images of one geometry in lockstep (fnx_jpeg_compress_batch) -------------------------
+// Per item, jpeg_search_device's search and jpeg_file_from_planes' file.  The items still searching take ONE set of launches
+// per step (each at its own mid) and ONE read-back of their scores; the winners are entropy-coded together with one read-back
+// per phase.  Every kernel runs the single call's arithmetic on each item, and SSIMFast picks its kernel, tiling and
+// reduction order as for one image: per item, the results are fnx_jpeg_compress's bit for bit.
+namespace {
+
+// device scratch a chunk of the batch may hold (orig + candidate planes, reference / candidate SSIMFast planes, decoded
+// candidates where the route needs them, the entropy coder's per-block arrays); the entropy coder's bit strings and file
+// bytes come on top (about 3 x the files' size)
+constexpr size_t JPEG_BATCH_SCRATCH = size_t(1) << 30;
+
+size_t al256(size_t v) { return (v + 255) & ~size_t(255); }
+
+const uint32_t *jpeg_qtab_host()
+{
+    static const std::vector<uint32_t> t = [] {
+        std::vector<uint32_t> v(JPEG_QTAB_WORDS);
+        jpeg_qtab(v.data());
+        return v;
+    }();
+    return t.data();
+}
+
+}  // namespace
+
+int fnx_jpeg_compress_batch(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstride, int w, int h, const double *target_ssim,
+                            const double *window, uint8_t *const *outs, const size_t *caps, size_t *nbytes, int *quality, double *ssim,
+                            int *steps, int *status)
+{
+    FNX_ENTER(ctx);
+    FNX_REQUIRE(n >= 1 && n <= FNX_BATCH_MAX, "compress batch: n must be 1..FNX_BATCH_MAX (65535)");
+    FNX_REQUIRE(srcs && target_ssim && outs && caps && nbytes && quality && ssim && status, "compress batch: NULL array");
+    FNX_REQUIRE(window != nullptr, "compress batch: NULL window");
+    FNX_REQUIRE(jpeg_dims(w, h), "compress batch: w and h must be 1..65535 (JPEG dims are 16-bit)");
+    FNX_REQUIRE(sstride >= 4 * w && (sstride & 3) == 0, "compress batch: sstride must be a multiple of 4 and >= 4 * w");
+    for (int i = 0; i < n; i++) {
+        if (!srcs[i] || !outs[i]) {
+            set_error("invalid argument: compress batch: srcs[%d] or outs[%d] is NULL", i, i);
+            return FNX_ERR_INVALID;
+        }
+    }
+    FNX_REQUIRE(ctx->res_count == 0, "enqueued batches are waiting for fnx_results_fetch: fetch them before a blocking batch call");
+
+    // the route is the single call's for this geometry: tested once, taken for every item
+    int pw, ph, ys, yh, cs, chh;
+    const bool ds = ssim_fast_dims(w, h, &pw, &ph);
+    const bool fused = ds && box_downsample_ycc_fused(w, h, pw, ph);     // candidate plane straight from its planes
+    const bool pixel = pw < 8 || ph < 8;                                 // pixelSSIM instead of the windowed form
+    jpeg_plane_dims(w, h, &ys, &yh, &cs, &chh);
+    size_t cb_off = 0, cr_off = 0;
+    const size_t PB = jpeg_batch_plane_bytes(w, h, &cb_off, &cr_off);
+    const size_t RB = al256(static_cast<size_t>(pw) * ph * 4 + 16);     // a tight SSIMFast plane
+    const size_t DB = al256(static_cast<size_t>(w) * h * 4 + 16);       // a decoded candidate (routes without the fused sums)
+    const size_t per_item = 2 * PB + RB + (ds ? RB : 0) + (fused ? 0 : DB) + jpeg_entropy_batch_bytes(w, h);
+    const size_t chunk_cap = JPEG_BATCH_SCRATCH / per_item;
+    const int chunk = static_cast<int>(chunk_cap < 1 ? 1 : (chunk_cap > static_cast<size_t>(n) ? n : chunk_cap));
+
+    void *dwin = nullptr, *dq = nullptr;
+    FNX_TRY(upload_table(ctx, SLOT_TABLE0, window, sizeof(double) * 64, &dwin));
+    FNX_TRY(upload_table(ctx, SLOT_JPEG_QTAB, jpeg_qtab_host(), sizeof(uint32_t) * JPEG_QTAB_WORDS, &dq));
+    const uint32_t *d_qtab = static_cast<const uint32_t *>(dq);
+
+    std::vector<QualitySearch> st;
+    st.reserve(chunk);
+    std::vector<int2> jobs(chunk);
+    std::vector<const uint8_t *> pa(chunk), pb(chunk), pd(chunk);
+    std::vector<int> qv(chunk), act(chunk);
+    std::vector<double> vals(chunk);
+    std::vector<unsigned long long> tbits(chunk);
+    std::vector<size_t> ecs_off(chunk), ecs_len(chunk), host_off(chunk);
+    std::vector<std::vector<uint8_t>> hdr(101);
+    for (int c0 = 0; c0 < n; c0 += chunk) {
+        const int m = n - c0 < chunk ? n - c0 : chunk;
+        void *t = nullptr;
+        FNX_TRY(upload_table(ctx, SLOT_PTRS, srcs + c0, sizeof(void *) * m, &t));
+        const uint8_t *const *d_srcs = static_cast<const uint8_t *const *>(t);
+        // the unquantised planes and the prepared reference planes of the chunk's sources, one launch each
+        FNX_TRY(scratch(ctx, SLOT_JPEG0, PB * m, &t));
+        uint8_t *orig = static_cast<uint8_t *>(t);
+        FNX_TRY(launch_jpeg_ycc_batch(ctx, m, d_srcs, sstride, w, h, orig));
+        FNX_TRY(scratch(ctx, SLOT_JPEG3, RB * m, &t));
+        uint8_t *refs = static_cast<uint8_t *>(t);
+        if (ds) {
+            bool al = true;                                  // the single call's box kernel form depends on the source's alignment
+            for (int i = 0; i < m; i++) al = al && aligned16(srcs[c0 + i], sstride);
+            if (al) {
+                FNX_TRY(launch_box_downsample(ctx, m, nullptr, d_srcs, sstride, w, h, refs, pw * 4, RB, pw, ph));
+            } else {
+                for (int i = 0; i < m; i++)
+                    FNX_TRY(launch_box_downsample(ctx, 1, srcs[c0 + i], nullptr, sstride, w, h, refs + RB * i, pw * 4, 0, pw, ph));
+            }
+        } else {
+            FNX_TRY(launch_copy_tight_batch(ctx, m, d_srcs, sstride, w, h, refs, RB));
+        }
+        uint8_t *work = nullptr, *cand = nullptr, *dec = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_JPEG1, PB * m, &t));
+        work = static_cast<uint8_t *>(t);
+        if (ds) {
+            FNX_TRY(scratch(ctx, SLOT_TMP2, RB * m, &t));
+            cand = static_cast<uint8_t *>(t);
+        }
+        if (!fused) {
+            FNX_TRY(scratch(ctx, SLOT_JPEG2, DB * m, &t));
+            dec = static_cast<uint8_t *>(t);
+        }
+        st.clear();
+        for (int i = 0; i < m; i++) st.emplace_back(target_ssim[c0 + i]);
+        for (;;) {
+            int nj = 0;
+            for (int i = 0; i < m; i++) {
+                if (st[i].done()) continue;
+                act[nj] = i;
+                jobs[nj] = make_int2(i, st[i].mid());
+                pa[nj] = refs + RB * i;
+                pb[nj] = ds ? cand + RB * nj : dec + DB * nj;
+                pd[nj] = fused ? nullptr : dec + DB * nj;
+                nj++;
+            }
+            if (nj == 0) break;
+            const void *hosts[4] = {jobs.data(), pa.data(), pb.data(), pd.data()};
+            const size_t sizes[4] = {sizeof(int2) * nj, sizeof(void *) * nj, sizeof(void *) * nj, sizeof(void *) * nj};
+            void *dp[4];
+            FNX_TRY(upload_tables(ctx, SLOT_JPEG_JOBS, hosts, sizes, 4, dp));
+            const uint8_t *const *d_as = static_cast<const uint8_t *const *>(dp[1]);
+            const uint8_t *const *d_bs = static_cast<const uint8_t *const *>(dp[2]);
+            FNX_TRY(launch_jpeg_blocks_batch(ctx, nj, w, h, orig, work, static_cast<const int2 *>(dp[0]), d_qtab));
+            if (fused) {
+                FNX_TRY(launch_box_downsample_ycc_batch(ctx, nj, work, PB, cb_off, cr_off, ys, cs, w, h, cand, RB, pw, ph));
+            } else {
+                FNX_TRY(launch_ycbcr_to_nrgba_batch(ctx, nj, work, PB, cb_off, cr_off, ys, cs, w, h, dec, DB));
+                if (ds) FNX_TRY(launch_box_downsample(ctx, nj, nullptr, static_cast<const uint8_t *const *>(dp[3]), w * 4, w, h, cand,
+                                                      pw * 4, RB, pw, ph));
+            }
+            double *dres;
+            FNX_TRY(result_slot(ctx, nj, &dres));
+            if (pixel) FNX_TRY(launch_pixel_ssim_batch(ctx, nj, d_as, d_bs, pw, ph, static_cast<size_t>(pw) * ph * 4, dres));
+            else FNX_TRY(launch_windowed_ssim(ctx, nj, nullptr, pw * 4, 0, nullptr, pw * 4, 0, pw, ph, window,
+                                              static_cast<const double *>(dwin), dres, nullptr, 0, d_as, d_bs, true));
+            FNX_TRY(result_wait(ctx, dres, vals.data(), nj));
+            for (int j = 0; j < nj; j++) st[act[j]].record(jobs[j].y, vals[j]);
+        }
+        // compress.go:76-86: every item's file at its best quality (100 when nothing reached the target), entropy-coded together
+        for (int i = 0; i < m; i++) qv[i] = st[i].best_q;
+        FNX_TRY(upload_table(ctx, SLOT_JPEG_JOBS, qv.data(), sizeof(int) * m, &t));
+        void *pin = nullptr;
+        FNX_TRY(pinned_alloc(ctx, sizeof(unsigned long long) * 2 * m, &pin));
+        unsigned long long *tot = static_cast<unsigned long long *>(pin);
+        for (int i = 0; i < 2 * m; i++) tot[i] = ~0ull;
+        FNX_TRY(jpeg_entropy_code_batch(ctx, m, w, h, orig, static_cast<const int *>(t), d_qtab, tot));
+        FNX_HIP(hipStreamSynchronize(ctx->stream));
+        for (int i = 0; i < m; i++) tbits[i] = tot[i];
+        uint8_t *ecs = nullptr;
+        FNX_TRY(jpeg_entropy_pack_batch(ctx, m, w, h, tbits.data(), &ecs, ecs_off.data(), tot + m));
+        FNX_HIP(hipStreamSynchronize(ctx->stream));
+        size_t end = 0, exact = 0;
+        for (int i = 0; i < m; i++) {
+            ecs_len[i] = jpeg_ecs_bytes(tbits[i], tot[m + i]);
+            end = ecs_off[i] + ecs_len[i] > end ? ecs_off[i] + ecs_len[i] : end;
+            exact += ecs_len[i];
+        }
+        // the segments come down into pinned memory: each on its own (exact bytes) for a few items, the whole buffer with the
+        // gaps its worst-case sizing leaves (~2x) for many small ones; one wait either way (tot is not read after this)
+        const bool each = m <= 256;
+        void *stage = nullptr;
+        FNX_TRY(pinned_alloc(ctx, (each ? exact : end) + 64, &stage));
+        uint8_t *hs = static_cast<uint8_t *>(stage);
+        size_t o = 0;
+        for (int i = 0; i < m; i++) {
+            if (!each) {
+                host_off[i] = ecs_off[i];
+                continue;
+            }
+            host_off[i] = o;
+            if (ecs_len[i]) FNX_HIP(hipMemcpyAsync(hs + o, ecs + ecs_off[i], ecs_len[i], hipMemcpyDeviceToHost, ctx->stream));
+            o += ecs_len[i];
+        }
+        if (!each && end) FNX_HIP(hipMemcpyAsync(hs, ecs, end, hipMemcpyDeviceToHost, ctx->stream));
+        FNX_HIP(hipStreamSynchronize(ctx->stream));
+        for (int i = 0; i < m; i++) {
+            const int k = c0 + i, q = st[i].best_q;
+            if (hdr[q].empty()) jpeg_header(w, h, q, hdr[q]);
+            const size_t eb = ecs_len[i], total = jpeg_file_frame(hdr[q], eb, outs[k], caps[k]);
+            nbytes[k] = total;
+            quality[k] = q;
+            ssim[k] = st[i].best_ssim;
+            if (steps) steps[k] = st[i].steps;
+            if (caps[k] < total) {
+                status[k] = FNX_ERR_INVALID;
+                continue;
+            }
+            if (eb) std::memcpy(outs[k] + hdr[q].size(), hs + host_off[i], eb);
+            status[k] = FNX_OK;
+        }
+    }
+    return FNX_OK;
+}
+
+int fnx_jpeg_encode_scaled(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int dw, int dh, int quality,
+                           uint8_t *out, size_t cap, size_t *nbytes)
+{
+    FNX_ENTER(ctx);
+    FNX_TRY(check_space(space));
+    FNX_REQUIRE(nbytes != nullptr && w > 0 && h > 0 && jpeg_dims(dw, dh), "encode_scaled arguments (JPEG dims are 16-bit)");
+    FNX_TRY(check_img(src, sstride, w, h, "src"));
+    *nbytes = 0;
+    DevImg s;
+    FNX_TRY(stage_in(ctx, space, src, sstride, w, h, SLOT_IN_A, &s));
+    JpegPlanes pl;
+    FNX_TRY(jpeg_planes(ctx, SLOT_JPEG1, dw, dh, &pl));
+    FNX_TRY(launch_jpeg_box_ycc(ctx, s.p, s.stride, w, h, dw, dh, pl.p[0], pl.p[1], pl.p[2]));
+    return jpeg_file_from_planes(ctx, pl, dw, dh, quality, out, cap, nbytes);
+}
+
+// ---- hitTargetSize's JPEG strategies (targetsize.go:26-357) in one call ---------------------------------------
+// The source is staged once; every scale step's planes come from jpeg_box_ycc_kernel and only its file sizes (8 bytes
+// a query) come back.  Slots: the source SLOT_IN_A, its planes SLOT_JPEG0, a scale step's planes SLOT_JPEG1, strategy 1's
+// decoded winner SLOT_JPEG2, the prepared SSIMFast side of the source SLOT_JPEG3, the Lanczos-scaled image SLOT_TS_SCALED
+// and its upscale for computeSSIMNRGBA SLOT_TS_UP.  At most one scaled candidate exists per call (strategy 4 runs only
+// when strategy 3 found none), so SLOT_TS_SCALED still holds the winner's image at the end.
+namespace {
+
+constexpr int TS_MIN_QUALITY = 20;     // minJPEGQuality (targetsize.go:14)
+
+struct TsRun {
+    fnx_ctx *ctx;
+    DevImg s;
+    int w, h;
+    long long target;
+    const double *window;
+    const volatile int *cancel;
+    JpegPlanes orig{};      // SLOT_JPEG0 once orig_planes() has run
+    fnx_prepared ref;       // SLOT_JPEG3 once prepared() has run
+
+    bool cancelled() const { return cancel && *cancel != 0; }
+
+    int orig_planes()
+    {
+        return orig.p[0] ? FNX_OK : jpeg_ycc_planes(ctx, SLOT_JPEG0, s.p, s.stride, w, h, &orig);
+    }
+
+    // SSIMFast's side of the source (ssim.go:52-58), once per call
+    int prepared()
+    {
+        if (ref.pix) return FNX_OK;
+        FNX_TRY(jpeg_prepared(ctx, w, h, &ref));
+        return prepared_plane(ctx, s.p, s.stride, ref);
+    }
+
+    // computeSSIMNRGBA(src, b) (targetsize.go:534-539): b (device, bw x bh) Lanczos-resized to the source's size when the
+    // dims differ, then SSIMFast against the prepared source
+    int ssim_against(const uint8_t *b, int bstride, int bw, int bh, double *out)
+    {
+        FNX_TRY(prepared());
+        if (bw != w || bh != h) {
+            void *up = nullptr;
+            FNX_TRY(scratch(ctx, SLOT_TS_UP, static_cast<size_t>(w) * h * 4 + 16, &up));
+            FNX_TRY(fennec_lanczosResize(ctx, FNX_DEVICE, b, bstride, bw, bh, static_cast<uint8_t *>(up), w * 4, w, h));
+            b = static_cast<const uint8_t *>(up);
+            bstride = w * 4;
+        }
+        return against_device(ctx, &ref, b, bstride, window, out);
+    }
+
+    // jpegQualitySearchFast(boxDownsample(src, dw, dh)) (targetsize.go:236, 260, 306): the scaled image never exists
+    int scaled_query(int dw, int dh, int *q, size_t *sz, int *n)
+    {
+        JpegPlanes pl;
+        FNX_TRY(jpeg_planes(ctx, SLOT_JPEG1, dw, dh, &pl));
+        FNX_TRY(launch_jpeg_box_ycc(ctx, s.p, s.stride, w, h, dw, dh, pl.p[0], pl.p[1], pl.p[2]));
+        return jpeg_size_bisect(ctx, pl, dw, dh, target, q, sz, n);
+    }
+
+    // lanczosResize(src, fw, fh) into SLOT_TS_SCALED and its planes into SLOT_JPEG1
+    int lanczos_scaled(int fw, int fh, uint8_t **img, JpegPlanes *pl)
+    {
+        void *d = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_TS_SCALED, static_cast<size_t>(fw) * fh * 4 + 16, &d));
+        *img = static_cast<uint8_t *>(d);
+        FNX_TRY(fennec_lanczosResize(ctx, FNX_DEVICE, s.p, s.stride, w, h, *img, fw * 4, fw, fh));
+        return jpeg_ycc_planes(ctx, SLOT_JPEG1, *img, fw * 4, fw, fh, pl);
+    }
+
+    // ---- strategy 1: jpegQualitySearch(src) (targetsize.go:33-37, 125-176) ----
+    int quality(fnx_size_candidate *c)
+    {
+        FNX_TRY(orig_planes());
+        int q = 0, n = 0;
+        size_t sz = 0;
+        FNX_TRY(jpeg_size_bisect(ctx, orig, w, h, target, &q, &sz, &n));
+        c->steps = n;
+        if (q < TS_MIN_QUALITY) return FNX_OK;           // nil, or below minJPEGQuality: not a candidate
+        // computeSSIMNRGBA(src, decoded winner): the SSIM of every earlier fitting quality is overwritten by the reference
+        void *dec = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_JPEG2, static_cast<size_t>(w) * h * 4 + 16, &dec));
+        FNX_TRY(jpeg_decode_at(ctx, orig, w, h, q, static_cast<uint8_t *>(dec), w * 4));
+        FNX_TRY(prepared());
+        FNX_TRY(against_device(ctx, &ref, static_cast<const uint8_t *>(dec), w * 4, window, &c->ssim));
+        c->strategy = FNX_TS_QUALITY; c->quality = q; c->final_w = w; c->final_h = h; c->nbytes = static_cast<int64_t>(sz);
+        return FNX_OK;
+    }
+
+    // ---- strategy 3: jpegQualityScaleSearch (targetsize.go:210-283) ----
+    int quality_scale(fnx_size_candidate *c)
+    {
+        int n = 0;
+        bool have = false;
+        double best = 0;
+        double lo = 0.05, hi = 1.0;                      // findBestScaleBinary
+        for (int i = 0; i < 10; i++) {
+            if (cancelled()) break;
+            const double mid = (lo + hi) / 2;
+            const int nw = static_cast<int>(static_cast<double>(w) * mid), nh = static_cast<int>(static_cast<double>(h) * mid);
+            if (nw < 8 || nh < 8) {
+                lo = mid;
+                continue;
+            }
+            int q = 0;
+            size_t sz = 0;
+            FNX_TRY(scaled_query(nw, nh, &q, &sz, &n));
+            if (q != 0 && static_cast<long long>(sz) <= target && q >= TS_MIN_QUALITY) {
+                have = true; best = mid;
+                lo = mid;
+            } else {
+                hi = mid;
+            }
+        }
+        static const double fixed[4] = {0.75, 0.50, 0.375, 0.25};   // findBestScaleFixed
+        for (double scale : fixed) {
+            if (cancelled()) break;
+            const int nw = static_cast<int>(static_cast<double>(w) * scale), nh = static_cast<int>(static_cast<double>(h) * scale);
+            if (nw < 8 || nh < 8) continue;
+            int q = 0;
+            size_t sz = 0;
+            FNX_TRY(scaled_query(nw, nh, &q, &sz, &n));
+            if (q != 0 && static_cast<long long>(sz) <= target && q >= TS_MIN_QUALITY && (!have || scale > best)) {
+                have = true; best = scale;
+            }
+        }
+        c->steps = n;
+        if (!have) return FNX_OK;
+        const int fw = static_cast<int>(static_cast<double>(w) * best), fh = static_cast<int>(static_cast<double>(h) * best);
+        uint8_t *img = nullptr;
+        JpegPlanes pl;
+        FNX_TRY(lanczos_scaled(fw, fh, &img, &pl));
+        int q = 0;
+        size_t sz = 0;
+        FNX_TRY(jpeg_size_bisect(ctx, pl, fw, fh, target, &q, &sz, &n));        // jpegQualitySearch(finalScaled): its SSIM is overwritten below
+        c->steps = n;
+        if (q < TS_MIN_QUALITY) return FNX_OK;
+        FNX_TRY(ssim_against(img, fw * 4, fw, fh, &c->ssim));
+        c->strategy = FNX_TS_QUALITY_SCALE; c->quality = q; c->final_w = fw; c->final_h = fh; c->nbytes = static_cast<int64_t>(sz);
+        return FNX_OK;
+    }
+
+    // ---- strategy 4: scaleSearch(src, target, JPEG) (targetsize.go:285-357) ----
+    int scale(fnx_size_candidate *c)
+    {
+        int n = 0, best_q = 0;
+        double lo = 0.05, hi = 1.0, best = 0.0;
+        for (int i = 0; i < 12; i++) {
+            if (cancelled()) break;
+            const double mid = (lo + hi) / 2;
+            const int nw = static_cast<int>(static_cast<double>(w) * mid), nh = static_cast<int>(static_cast<double>(h) * mid);
+            if (nw < 1 || nh < 1) {
+                lo = mid;
+                continue;
+            }
+            int q = 0;
+            size_t sz = 0;
+            FNX_TRY(scaled_query(nw, nh, &q, &sz, &n));
+            if (q != 0 && static_cast<long long>(sz) <= target && q >= TS_MIN_QUALITY) {   // testScaleFits
+                best = mid; best_q = q;
+                lo = mid;
+            } else {
+                hi = mid;
+            }
+        }
+        c->steps = n;
+        if (best == 0.0) return FNX_OK;
+        // executeFinalScaleEncode: jpegQualitySearchFast of the Lanczos image, else the file at bestQ (which may not fit)
+        const int fw = static_cast<int>(static_cast<double>(w) * best), fh = static_cast<int>(static_cast<double>(h) * best);
+        uint8_t *img = nullptr;
+        JpegPlanes pl;
+        FNX_TRY(lanczos_scaled(fw, fh, &img, &pl));
+        int q = 0;
+        size_t sz = 0;
+        FNX_TRY(jpeg_size_bisect(ctx, pl, fw, fh, target, &q, &sz, &n));
+        if (q == 0) {
+            q = best_q;
+            FNX_TRY(jpeg_file_from_planes(ctx, pl, fw, fh, q, nullptr, 0, &sz));
+            n++;
+        }
+        c->steps = n;
+        FNX_TRY(ssim_against(img, fw * 4, fw, fh, &c->ssim));
+        c->strategy = FNX_TS_SCALE; c->quality = q; c->final_w = fw; c->final_h = fh; c->nbytes = static_cast<int64_t>(sz);
+        return FNX_OK;
+    }
+
+    // ---- fallbackTargetSizeEncode's JPEG branch (targetsize.go:77-90) ----
+    int fallback(fnx_size_candidate *c)
+    {
+        FNX_TRY(orig_planes());
+        size_t sz = 0;
+        FNX_TRY(jpeg_file_from_planes(ctx, orig, w, h, 1, nullptr, 0, &sz));
+        FNX_TRY(ssim_against(s.p, s.stride, w, h, &c->ssim));     // computeSSIMNRGBA(original, original)
+        c->strategy = FNX_TS_FALLBACK; c->quality = 1; c->final_w = w; c->final_h = h; c->steps = 1;
+        c->nbytes = static_cast<int64_t>(sz);
+        return FNX_OK;
+    }
+};
+
+// betterFit (targetsize.go:92-115)
+bool better_fit(const fnx_size_candidate &c, const fnx_size_candidate &b, long long t)
+{
+    const bool cu = c.nbytes <= t, bu = b.nbytes <= t;
+    if (cu && !bu) return true;
+    if (!cu && bu) return false;
+    if (cu && bu) {
+        if (c.ssim != b.ssim) return c.ssim > b.ssim;
+        return c.quality > b.quality;
+    }
+    return c.nbytes < b.nbytes;
+}
+
+}  // namespace
+
+int fnx_jpeg_target_size(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, long long target_bytes, int strategies,
+                         const double *window, const volatile int *cancel, fnx_size_candidate cand[4], int *winner, uint8_t *out,
+                         size_t cap, size_t *nbytes, uint8_t *img, int istride)
+{
+    FNX_ENTER(ctx);
+    FNX_TRY(check_space(space));
+    FNX_REQUIRE(cand && winner && nbytes, "target_size: cand, winner and nbytes are required");
+    FNX_REQUIRE(window, "target_size: window is required");
+    FNX_REQUIRE(jpeg_dims(w, h), "target_size: dimensions must be 1..65535 (JPEG dims are 16-bit)");
+    FNX_REQUIRE(target_bytes > 0, "target_size: target_bytes must be > 0");
+    FNX_REQUIRE(strategies > 0 && (strategies & ~(FNX_TS_QUALITY | FNX_TS_QUALITY_SCALE | FNX_TS_SCALE | FNX_TS_FALLBACK)) == 0,
+                "target_size: strategies must be a non-empty subset of bits 1, 2, 4, 8");
+    FNX_REQUIRE(img == nullptr || istride >= 4 * w, "target_size: img needs a stride of at least 4 * w (the source's width)");
+    FNX_TRY(check_img(src, sstride, w, h, "src"));
+    std::memset(cand, 0, sizeof(fnx_size_candidate) * 4);
+    *winner = -1;
+    *nbytes = 0;
+    TsRun run{ctx, {}, w, h, target_bytes, window, cancel};
+    FNX_TRY(stage_in(ctx, space, src, sstride, w, h, SLOT_IN_A, &run.s));
+    // hitTargetSize (targetsize.go:26-75): the JPEG legs in the reference's order, ctx.Err() before each
+    if ((strategies & FNX_TS_QUALITY) && !run.cancelled()) FNX_TRY(run.quality(&cand[0]));
+    if ((strategies & FNX_TS_QUALITY_SCALE) && !run.cancelled()) FNX_TRY(run.quality_scale(&cand[1]));
+    auto none = [&] { return !cand[0].strategy && !cand[1].strategy && !cand[2].strategy; };
+    if ((strategies & FNX_TS_SCALE) && none() && !run.cancelled()) FNX_TRY(run.scale(&cand[2]));
+    if ((strategies & FNX_TS_FALLBACK) && none()) FNX_TRY(run.fallback(&cand[3]));       // also after a cancellation
+    int best = -1;
+    for (int i = 0; i < 4; i++)
+        if (cand[i].strategy && (best < 0 || better_fit(cand[i], cand[best], target_bytes))) best = i;
+    if (best < 0) return FNX_NOOP;
+    *winner = best;
+    const fnx_size_candidate &c = cand[best];
+    JpegPlanes pl;
+    if (best == 1 || best == 2) {
+        // the winner's image (SLOT_TS_SCALED) and its planes once more: a later query may have used SLOT_JPEG1
+        const uint8_t *scaled = static_cast<const uint8_t *>(ctx->slot[SLOT_TS_SCALED].p);
+        FNX_TRY(jpeg_ycc_planes(ctx, SLOT_JPEG1, scaled, c.final_w * 4, c.final_w, c.final_h, &pl));
+        if (img)
+            FNX_HIP(hipMemcpy2DAsync(img, istride, scaled, size_t(c.final_w) * 4, size_t(c.final_w) * 4, c.final_h,
+                                     space == FNX_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+    } else {
+        FNX_TRY(run.orig_planes());
+        pl = run.orig;
+    }
+    FNX_TRY(jpeg_file_from_planes(ctx, pl, c.final_w, c.final_h, c.quality, out, cap, nbytes));
+    if (space == FNX_HOST) FNX_HIP(hipStreamSynchronize(ctx->stream));
+    return FNX_OK;
+}
+
+// ---- image.Decode of a baseline JPEG on the device (third slice: jpeg_dec.hip) ----------------
+// toNRGBARef(jpeg.Decode(data)) into SLOT_JPEG_DEC_IMG (tight rows); *f describes the file
+int fnx_jpeg_decode(fnx_ctx *ctx, const uint8_t *data, size_t n, int space, uint8_t *dst, int dstride, int *w, int *h)
+{
+    FNX_REQUIRE(data != nullptr && w != nullptr && h != nullptr, "decode arguments");
+    JpegFile f;
+    if (dst == nullptr) {                        // jpeg.DecodeConfig: the dimensions only (and whether the device handles the file);
+        FNX_TRY(jpeg_parse(data, n, &f));        // host work, no ctx needed
+        *w = f.w; *h = f.h;
+        return FNX_OK;
+    }
+    FNX_ENTER(ctx);
+    FNX_TRY(check_space_io(space));
+    FNX_TRY(jpeg_parse(data, n, &f));
+    *w = f.w; *h = f.h;
+    FNX_TRY(check_img(dst, dstride, f.w, f.h, "dst"));
+    DevOut d;
+    FNX_TRY(stage_out(ctx, space, dst, dstride, f.w, f.h, SLOT_OUT, &d));
+    uint8_t *pl[4] = {nullptr, nullptr, nullptr, nullptr};
+    int ys = 0, cs = 0;
+    FNX_TRY(jpeg_decode_planes(ctx, data, n, &f, pl, &ys, &cs));
+    const bool grey = f.ncomp == 1;
+    if (f.ncomp == 4) FNX_TRY(launch_cmyk_to_nrgba(ctx, pl, ys, f.adobe, f.w, f.h, d.p, d.stride));
+    else FNX_TRY(launch_ycbcr_to_nrgba(ctx, pl[0], ys, grey ? nullptr : pl[1], grey ? nullptr : pl[2], cs, grey ? 0 : f.ratio, f.w, f.h, d.p, d.stride));
+    return finish(ctx, space, &d);
+}
+
+// host only: jpeg_prog.cpp's output as the tests and the sanitizer runs read it
+int fnx_jpeg_progressive_coefficients(const uint8_t *data, size_t n, int16_t *coef, size_t cap_blocks, size_t *blocks, int *w, int *h, int *ratio)
+{
+    FNX_REQUIRE(data != nullptr && blocks != nullptr && w != nullptr && h != nullptr && ratio != nullptr, "coefficient arguments");
+    JpegFile f;
+    FNX_TRY(jpeg_parse(data, n, &f));
+    if (!f.progressive) return jpeg_unsupported("a baseline file here (its scan is decoded on the device)");
+    const unsigned long long nblk = static_cast<unsigned long long>(f.mx) * f.my * f.nslots;
+    *blocks = static_cast<size_t>(nblk);
+    *w = f.w; *h = f.h; *ratio = f.ratio;
+    if (nblk > static_cast<unsigned long long>(JPEG_HOST_MAX_BLOCKS)) return jpeg_unsupported("a host-decoded file of more than 4 M blocks (FNX_JPEG_HOST_MAX_BLOCKS)");
+    if (coef == nullptr) return FNX_OK;
+    FNX_REQUIRE(cap_blocks >= nblk, "coefficient capacity");
+    if (8ull * n < nblk) return jpeg_corrupt("the file is too short for the image's blocks");       // (as fnx_jpeg_decode: before anything is sized by the header)
+    std::memset(coef, 0, sizeof(int16_t) * 64 * static_cast<size_t>(nblk));
+    return jpeg_progressive_coefficients(data, n, &f, coef);
+}
+
+int fnx_jpeg_recompress(fnx_ctx *ctx, const uint8_t *data, size_t n, double target_ssim, const double *window, uint8_t *out, size_t cap,
+                        size_t *nbytes, int *quality, double *ssim, int *steps, int *w, int *h)
+{
+    FNX_ENTER(ctx);
+    FNX_REQUIRE(data && window && nbytes && quality && ssim && w && h, "recompress arguments");
+    *nbytes = 0;
+    JpegFile f;
+    uint8_t *pl[4] = {nullptr, nullptr, nullptr, nullptr};
+    int ys = 0, cs = 0;
+    FNX_TRY(jpeg_decode_planes(ctx, data, n, &f, pl, &ys, &cs));
+    *w = f.w; *h = f.h;
+    JpegPlanes orig;
+    FNX_TRY(jpeg_planes(ctx, SLOT_JPEG0, f.w, f.h, &orig));
+    fnx_prepared ref;
+    bool from_planes = false;
+    if (f.ncomp == 3) {
+        // r3: toNRGBARef's image of the decoded planes (33 MB at 4K) was written for two readers only -- the encoder's colour
+        // conversion and the reference plane's box sums; both take the planes themselves now (same per-pixel arithmetic), the
+        // box sums where launch_box_downsample_ycc takes the planes' layout (else the image is made after all)
+        FNX_TRY(launch_jpeg_ycc_planes(ctx, pl[0], ys, pl[1], pl[2], cs, f.ratio, f.w, f.h, orig.p[0], orig.p[1], orig.p[2]));
+        FNX_TRY(jpeg_prepared(ctx, f.w, f.h, &ref));
+        if (ref.pw != f.w || ref.ph != f.h)
+            FNX_TRY(launch_box_downsample_ycc(ctx, pl[0], ys, pl[1], pl[2], cs, f.ratio, f.w, f.h, ref.pix, ref.pw * 4, ref.pw, ref.ph,
+                                              &from_planes));
+    }
+    if (!from_planes) {
+        void *t = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_JPEG_DEC_IMG, static_cast<size_t>(f.w) * f.h * 4 + 16, &t));
+        uint8_t *img = static_cast<uint8_t *>(t);
+        const int istride = f.w * 4;
+        const bool grey = f.ncomp == 1;
+        if (f.ncomp == 4) FNX_TRY(launch_cmyk_to_nrgba(ctx, pl, ys, f.adobe, f.w, f.h, img, istride));
+        else FNX_TRY(launch_ycbcr_to_nrgba(ctx, pl[0], ys, grey ? nullptr : pl[1], grey ? nullptr : pl[2], cs, grey ? 0 : f.ratio, f.w, f.h, img, istride));
+        FNX_TRY(jpeg_ycc_planes(ctx, SLOT_JPEG0, img, istride, f.w, f.h, &orig));
+        FNX_TRY(jpeg_prepared(ctx, f.w, f.h, &ref));
+        FNX_TRY(prepared_plane(ctx, img, istride, ref));
+    }
+    FNX_TRY(jpeg_search_device(ctx, ref, orig, f.w, f.h, target_ssim, window, quality, ssim, steps));
+    return jpeg_file_from_planes(ctx, orig, f.w, f.h, *quality, out, cap, nbytes);
+}
+}  // extern "C"
