@@ -2243,6 +2243,7 @@ int launch_msssim_fused(fnx_ctx *ctx, const uint8_t *a, int astride, const uint8
             wm.windows[i] = defer.item[i].windows;
         }
     }
+    note_route(ctx, FNX_PROF_SSIM, "windowed_ssim_sep_multi_kernel");
     hipLaunchKernelGGL(windowed_ssim_sep_multi_kernel, dim3(maxt, levels * nz), dim3(256), 0, ctx->stream, wm);
     FNX_HIP(hipGetLastError());
     if (!fold) FNX_TRY(launch_ssim_finish_deferred(ctx, defer, d_out, static_cast<int>(nz), nz > 1 ? SSIM_DEFER_DOUBLES : 0, nz > 1 ? 5 : 0));
