@@ -1,4 +1,5 @@
 // fnx_* entry points: argument checks, host<->device staging, table upload, kernel launches.
+#include <algorithm>
 #include <atomic>
 #include <limits>
 #include <cmath>
@@ -15,15 +16,13 @@ inline size_t pix_len(int w, int h, int stride)
     return (w > 0 && h > 0) ? static_cast<size_t>(h - 1) * stride + static_cast<size_t>(w) * 4 : 0;
 }
 
-// SSIMFast of n device image pairs (single pointers or device pointer arrays) -> d_out[n].
-// Image i of the single-pointer form lives at a + i*a_img (used by MSSSIM with n == 1).
-// defer (n == 1 only): windowed paths leave their final mean to launch_ssim_finish_deferred, which writes
-// d_out_base[defer_index]; d_out is then d_out_base + defer_index
-int ssim_fast_device(fnx_ctx *ctx, int n, const uint8_t *a, const uint8_t *const *as, int astride,
-                     const uint8_t *b, const uint8_t *const *bs, int bstride, int w, int h,
-                     const double *h_window, const double *d_window, double *d_out,
-                     SsimDeferred *defer = nullptr, int defer_index = 0)
+// SSIMFast of n device image pairs -> d_out[n].  Image i of the single-pointer form lives at a.p + i*a.image_bytes (used by
+// MSSSIM with n == 1).  opt.defer (n == 1 only): windowed paths leave their final mean to launch_ssim_finish_deferred, which
+// writes d_out_base[defer_index]; d_out is then d_out_base + defer_index
+int ssim_fast_device(fnx_ctx *ctx, const ImgPairs &im, const double *h_window, const double *d_window, double *d_out, const SsimOpts &opt = SsimOpts())
 {
+    const int n = im.n, w = im.w, h = im.h;
+    double *d_base = opt.defer ? d_out - opt.defer_index : d_out;
     int nw, nh;
     if (ssim_fast_dims(w, h, &nw, &nh)) {
         // boxDownsample both sides (ssim.go:57-58) into tight planes: [a0..an-1][b0..bn-1]
@@ -31,23 +30,84 @@ int ssim_fast_device(fnx_ctx *ctx, int n, const uint8_t *a, const uint8_t *const
         void *t = nullptr;
         FNX_TRY(scratch(ctx, SLOT_TMP2, plane * 2 * n + 16, &t));
         uint8_t *da = static_cast<uint8_t *>(t), *db = da + plane * n;
-        FNX_TRY(launch_box_downsample_pair(ctx, n, a, as, astride, b, bs, bstride, w, h, da, nw * 4, plane, nw, nh));
+        FNX_TRY(launch_box_downsample_pair(ctx, im, da, nw * 4, plane, nw, nh));
         if (nw < 8 || nh < 8) {
             for (int i = 0; i < n; i++)
                 FNX_TRY(launch_pixel_ssim(ctx, da + plane * i, db + plane * i, nw, nh, plane, d_out + i));
             return FNX_OK;
         }
-        return launch_windowed_ssim(ctx, n, da, nw * 4, plane, db, nw * 4, plane, nw, nh, h_window, d_window,
-                                    defer ? d_out - defer_index : d_out, defer, defer_index);
+        return launch_windowed_ssim(ctx, plane_pairs(n, da, db, plane, nw, nh), h_window, d_window, d_base, opt);
     }
-    if (as || bs) {
+    if (im.a.ptrs || im.b.ptrs) {
         set_error("batched SSIMFast needs images larger than 512 px (the downsample path)");
         return FNX_ERR_INVALID;
     }
-    if (w < 8 || h < 8) return launch_pixel_ssim(ctx, a, b, w, h, pix_len(w, h, astride), d_out);
-    return launch_windowed_ssim(ctx, 1, a, astride, 0, b, bstride, 0, w, h, h_window, d_window,
-                                defer ? d_out - defer_index : d_out, defer, defer_index);
+    if (w < 8 || h < 8) return launch_pixel_ssim(ctx, im.a.p, im.b.p, w, h, pix_len(w, h, im.a.stride), d_out);
+    return launch_windowed_ssim(ctx, one_pair(im.a.p, im.a.stride, im.b.p, im.b.stride, w, h), h_window, d_window, d_base, opt);
 }
+
+// Two host arrays of n device pointers each -> the ctx's device copies (batched launches index them by image)
+template <typename Second>   // const uint8_t (both sides read) or uint8_t (sources, destinations)
+int upload_ptr_pair(fnx_ctx *ctx, int n, const uint8_t *const *first, Second *const *second, const uint8_t *const **d_first, Second *const **d_second)
+{
+    const void *hosts[2] = {first, second};
+    const size_t sizes[2] = {sizeof(void *) * size_t(n), sizeof(void *) * size_t(n)};
+    void *dp[2];
+    FNX_TRY(upload_tables(ctx, SLOT_PTRS, hosts, sizes, 2, dp));
+    *d_first = static_cast<const uint8_t *const *>(dp[0]);
+    *d_second = static_cast<Second *const *>(dp[1]);
+    return FNX_OK;
+}
+
+bool all_aligned16(int n, const uint8_t *const *ptrs, int stride)
+{
+    bool al = true;
+    for (int i = 0; i < n; i++) al = al && aligned16(ptrs[i], stride);
+    return al;
+}
+
+// What the round 6 batch entry points ask of their arguments: the call's own conditions and the batch size, then -- once the
+// caller has dealt with n == 0 and its dims -- every image of both arrays.  (The blur, SSIMFast and one-pass batches keep their
+// older checks: they take n > FNX_BATCH_MAX and refuse null arrays at n == 0, so sharing these would change an answer.)
+int check_batch(int n, bool arrays, bool args_ok = true)
+{
+    FNX_REQUIRE(n >= 0 && (n == 0 || arrays) && args_ok, "batch arguments");
+    FNX_REQUIRE(n <= FNX_BATCH_MAX, "more than FNX_BATCH_MAX (65535) images in one batch call: the image is a grid dimension");
+    return FNX_OK;
+}
+
+struct BatchSide { const uint8_t *const *p; int stride, w, h; const char *what; };
+int check_batch_images(int n, const BatchSide &x, const BatchSide &y, const char *distinct_msg = nullptr)
+{
+    for (int i = 0; i < n; i++) {
+        if (distinct_msg) FNX_REQUIRE(x.p[i] && y.p[i] && x.p[i] != y.p[i], distinct_msg);
+        else FNX_REQUIRE(x.p[i] && y.p[i], "null image in batch");
+        FNX_TRY(check_img(x.p[i], x.stride, x.w, x.h, x.what));
+        FNX_TRY(check_img(y.p[i], y.stride, y.w, y.h, y.what));
+    }
+    return FNX_OK;
+}
+
+int check_pix_lens(int w, int h, int astride, int bstride)   // pixelSSIM walks a.Pix and indexes b.Pix with it (ssim.go:178)
+{
+    FNX_REQUIRE(pix_len(w, h, bstride) >= pix_len(w, h, astride), "b.Pix shorter than a.Pix (the reference would panic)");
+    return FNX_OK;
+}
+
+// Both sides of a host- or device-space comparison on the device: `flat` (pixelSSIM's sizes) as the flat Pix slices they are,
+// stride kept, else by rows
+int stage_pair(fnx_ctx *ctx, int space, const uint8_t *a, int astride, const uint8_t *b, int bstride, int w, int h, bool flat, DevImg *da, DevImg *db)
+{
+    if (flat) FNX_TRY(check_pix_lens(w, h, astride, bstride));
+    const auto stage = flat ? stage_in_flat : stage_in;
+    FNX_TRY(stage(ctx, space, a, astride, w, h, SLOT_IN_A, da));
+    return stage(ctx, space, b, bstride, w, h, SLOT_IN_B, db);
+}
+
+void nan_fill(double *d, int n) { std::fill_n(d, n, std::numeric_limits<double>::quiet_NaN()); }
+
+// The FIFO position the next *_enqueue call fills (free while res_count < RES_DEPTH: can_enqueue)
+int res_tail(const fnx_ctx *ctx) { return (ctx->res_head + ctx->res_count) % fnx_ctx::RES_DEPTH; }
 
 // Result slots of an *_enqueue call: the batch's OWN pinned buffer (one per FIFO position), so that nothing
 // a later call does to the pinned ring (growth frees it, wrap-around reuses it) can touch results that were
@@ -55,7 +115,7 @@ int ssim_fast_device(fnx_ctx *ctx, int n, const uint8_t *a, const uint8_t *const
 // res_count < RES_DEPTH, and a fetched batch has been copied out.
 int result_slot_queued(fnx_ctx *ctx, int n, double **d)
 {
-    fnx_ctx::ResBuf &rb = ctx->res_buf[(ctx->res_head + ctx->res_count) % fnx_ctx::RES_DEPTH];
+    fnx_ctx::ResBuf &rb = ctx->res_buf[res_tail(ctx)];
     const size_t need = sizeof(double) * static_cast<size_t>(n > 16 ? n : 16);
     if (need > rb.cap) {
         if (rb.p) FNX_HIP(hipHostFree(rb.p));
@@ -65,35 +125,40 @@ int result_slot_queued(fnx_ctx *ctx, int n, double **d)
         rb.cap = need * 2;
     }
     *d = rb.p;
-    for (int i = 0; i < n; i++) (*d)[i] = std::numeric_limits<double>::quiet_NaN();
+    nan_fill(*d, n);
     return FNX_OK;
 }
 
-// Wait until the n result slots hold values.  The result kernels are the last work of a call and write
-// straight into (uncached) pinned host memory, so the values arrive a PCIe write after the kernel stores
-// them, while hipStreamSynchronize / hipEventSynchronize return 10-20 us later; the stream (or the event)
-// is still queried now and then, which also ends the wait if a value really is NaN or the GPU faulted.
-template <typename Done>
-int poll_results(const double *pinned, int n, Done done)
+// Spin until ready() holds: on words in pinned host memory that the call's last kernel writes.  They arrive a PCIe write
+// after the kernel stores them, while hipStreamSynchronize / hipEventSynchronize return 10-20 us later; the stream (or the
+// event) is still queried now and then (done), which also ends the wait if the words never change or the GPU faulted.
+template <typename Ready, typename Done>
+int poll_until(Ready ready, Done done)
 {
-    const volatile double *v = pinned;
-    for (unsigned spin = 1;; spin++) {
-        bool all = true;
-        for (int i = 0; i < n; i++) {
-            const double x = v[i];
-            if (x != x) { all = false; break; }
-        }
-        if (all) {
-            std::atomic_thread_fence(std::memory_order_acquire);
-            return FNX_OK;
-        }
+    for (unsigned spin = 1; !ready(); spin++) {
         if ((spin & 127u) == 0) {
             const hipError_t q = done();
-            if (q == hipSuccess) return FNX_OK;
+            if (q == hipSuccess) break;
             if (q != hipErrorNotReady) FNX_HIP(q);
         }
         __builtin_ia32_pause();
     }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return FNX_OK;
+}
+
+// Wait until the n result slots hold values (a NaN slot is one not written yet, or a value that really is NaN)
+template <typename Done>
+int poll_results(const double *pinned, int n, Done done)
+{
+    const volatile double *v = pinned;
+    return poll_until([=] {
+        for (int i = 0; i < n; i++) {
+            const double x = v[i];
+            if (x != x) return false;
+        }
+        return true;
+    }, done);
 }
 
 // ssim.go:344-352: exp(sum_i weights[i] * log(max(level_i, 1e-10)))
@@ -104,15 +169,21 @@ double msssim_combine(const double *lv, const double *weights, int nlev)
     return std::exp(result);
 }
 
-// An event right behind the result kernels, and the batch joins the ctx's FIFO of unfetched results:
-// fnx_results_fetch then never waits for work that was queued on this stream after the batch.
-int publish_results(fnx_ctx *ctx, const double *pinned, int n)
+int can_enqueue(fnx_ctx *ctx)
 {
     if (ctx->res_count == fnx_ctx::RES_DEPTH) {
         set_error("invalid argument: %d enqueued batches are waiting for fnx_results_fetch on this ctx", ctx->res_count);
         return FNX_ERR_INVALID;
     }
-    fnx_ctx::Pending &q = ctx->res_q[(ctx->res_head + ctx->res_count) % fnx_ctx::RES_DEPTH];
+    return FNX_OK;
+}
+
+// An event right behind the result kernels, and the batch joins the ctx's FIFO of unfetched results (*filled: its entry):
+// fnx_results_fetch then never waits for work that was queued on this stream after the batch.
+int publish_results(fnx_ctx *ctx, const double *pinned, int n, fnx_ctx::Pending **filled = nullptr)
+{
+    FNX_TRY(can_enqueue(ctx));
+    fnx_ctx::Pending &q = ctx->res_q[res_tail(ctx)];
     if (!q.ev) FNX_HIP(hipEventCreateWithFlags(&q.ev, hipEventDisableTiming));
     FNX_HIP(hipEventRecord(q.ev, ctx->stream));
     q.pinned = pinned;
@@ -121,16 +192,74 @@ int publish_results(fnx_ctx *ctx, const double *pinned, int n)
     q.nimg = 1;
     q.tail_parity = -1;
     ctx->res_count++;
+    if (filled) *filled = &q;
     return FNX_OK;
 }
 
-int can_enqueue(fnx_ctx *ctx)
+// MSSSIM's entry: five slots per image, `nlev` of them written; the fetch combines them with `weights` into nimg numbers
+int publish_msssim(fnx_ctx *ctx, const double *pinned, int nimg, int nlev, const double (&weights)[5])
 {
-    if (ctx->res_count == fnx_ctx::RES_DEPTH) {
-        set_error("invalid argument: %d enqueued batches are waiting for fnx_results_fetch on this ctx", ctx->res_count);
-        return FNX_ERR_INVALID;
-    }
+    fnx_ctx::Pending *q = nullptr;
+    FNX_TRY(publish_results(ctx, pinned, nimg, &q));
+    q->nraw = nlev;
+    q->nimg = nimg;
+    for (int i = 0; i < 5; i++) q->weights[i] = weights[i];
     return FNX_OK;
+}
+
+// While one lives, launch_windowed_ssim takes its partial sums from `partial_slot` (-1: the ctx's usual one) and, with
+// on_tail, every launcher works on the ctx's second stream: the ctx is put back on every way out of the scope
+class LaunchScope {
+public:
+    LaunchScope(fnx_ctx *ctx, int partial_slot, bool on_tail) : ctx_(ctx), main_(ctx->stream)
+    {
+        if (on_tail) ctx->stream = ctx->stream2;
+        ctx->partial_slot = partial_slot;
+    }
+    ~LaunchScope() { ctx_->partial_slot = -1; ctx_->stream = main_; }
+    LaunchScope(const LaunchScope &) = delete;
+    LaunchScope &operator=(const LaunchScope &) = delete;
+private:
+    fnx_ctx *ctx_;
+    hipStream_t main_;
+};
+
+// The tail stream waits for everything enqueued on `stream` so far (the one-pass batches' hand-over events, same use, in turn)
+int tail_follows_main(fnx_ctx *ctx)
+{
+    hipEvent_t ev = ctx->ev_blur[ctx->ev_toggle];
+    FNX_HIP(hipEventRecord(ev, ctx->stream));
+    FNX_HIP(hipStreamWaitEvent(ctx->stream2, ev, 0));
+    ctx->stream2_used = true;
+    ctx->ev_toggle ^= 1;
+    return FNX_OK;
+}
+
+// SSIM (ssim.go:35-42) of im.n device pairs into dres: pixelSSIM below 8 px, else toLuminance x2 + windowedSSIM at full resolution.
+// as / bs: the HOST arrays of a batch's image pointers (uploaded for the windowed launch), or nullptr: the one pair im names.
+// The values are left for result_wait (THEN_WAIT) or published as one FIFO entry.  THEN_PUBLISH_TAIL: the windowed SSIM runs on the
+// ctx's second stream, behind everything enqueued so far (the images were produced on `stream`): what the caller enqueues next --
+// the next image's AdaptiveSharpen in config 4 -- does not wait for it, so one kernel's last workgroups and the next one's first
+// share the chip instead of each launch draining it (three launch boundaries per image, ~5 us each, at 8K).  The partial sums
+// use the tail's own slot: other calls on `stream` may use SLOT_PARTIAL meanwhile.
+enum SsimThen { THEN_WAIT, THEN_PUBLISH, THEN_PUBLISH_TAIL };
+int ssim_pairs(fnx_ctx *ctx, ImgPairs im, const uint8_t *const *as, const uint8_t *const *bs, const double *window, const double *dwin, double *dres, SsimThen then)
+{
+    if (im.w < 8 || im.h < 8) {
+        FNX_TRY(check_pix_lens(im.w, im.h, im.a.stride, im.b.stride));
+        for (int i = 0; i < im.n; i++)
+            FNX_TRY(launch_pixel_ssim(ctx, as ? as[i] : im.a.p, bs ? bs[i] : im.b.p, im.w, im.h, pix_len(im.w, im.h, im.a.stride), dres + i));
+    } else {
+        if (as) FNX_TRY(upload_ptr_pair(ctx, im.n, as, bs, &im.a.ptrs, &im.b.ptrs));
+        if (then == THEN_PUBLISH_TAIL) {
+            FNX_TRY(tail_follows_main(ctx));
+            LaunchScope tail(ctx, SLOT_PART0, true);
+            FNX_TRY(launch_windowed_ssim(ctx, im, window, dwin, dres));
+            return publish_results(ctx, dres, im.n);          // the result's event: behind the score, on the second stream
+        }
+        FNX_TRY(launch_windowed_ssim(ctx, im, window, dwin, dres));
+    }
+    return then == THEN_WAIT ? FNX_OK : publish_results(ctx, dres, im.n);
 }
 
 }  // namespace
@@ -194,7 +323,15 @@ int result_slot(fnx_ctx *ctx, int n, double **d)
     void *p = nullptr;
     FNX_TRY(pinned_alloc(ctx, sizeof(double) * static_cast<size_t>(n > 16 ? n : 16), &p));
     *d = static_cast<double *>(p);
-    for (int i = 0; i < n; i++) (*d)[i] = std::numeric_limits<double>::quiet_NaN();
+    nan_fill(*d, n);
+    return FNX_OK;
+}
+
+int upload_window(fnx_ctx *ctx, const double *window, const double **d_window)
+{
+    void *d = nullptr;
+    FNX_TRY(upload_table(ctx, SLOT_TABLE0, window, sizeof(double) * 64, &d));
+    *d_window = static_cast<const double *>(d);
     return FNX_OK;
 }
 
@@ -211,8 +348,8 @@ int against_device(fnx_ctx *ctx, const fnx_prepared *ref, const uint8_t *b, int 
                    double *out, bool b_is_plane)
 {
     const int w = ref->w, h = ref->h, pw = ref->pw, ph = ref->ph;
-    void *dwin = nullptr;
-    FNX_TRY(upload_table(ctx, SLOT_TABLE0, window, sizeof(double) * 64, &dwin));
+    const double *dwin = nullptr;
+    FNX_TRY(upload_window(ctx, window, &dwin));
     double *dres;
     FNX_TRY(result_slot(ctx, 1, &dres));
     const uint8_t *cb = b;
@@ -234,8 +371,7 @@ int against_device(fnx_ctx *ctx, const fnx_prepared *ref, const uint8_t *b, int 
         }
         FNX_TRY(launch_pixel_ssim(ctx, ref->pix, cb, pw, ph, static_cast<size_t>(pw) * ph * 4, dres));
     } else {
-        FNX_TRY(launch_windowed_ssim(ctx, 1, ref->pix, pw * 4, 0, cb, cbs, 0, pw, ph, window,
-                                     static_cast<const double *>(dwin), dres));
+        FNX_TRY(launch_windowed_ssim(ctx, one_pair(ref->pix, pw * 4, cb, cbs, pw, ph), window, dwin, dres));
     }
     return result_wait(ctx, dres, out, 1);
 }
@@ -302,23 +438,16 @@ int lanczos_resize_tables_batch(fnx_ctx *ctx, int n, const uint8_t *const *srcs,
                                 const TapTable &th, const TapTable &tv, uint8_t *const *dsts, int dstride, int dstW, int dstH)
 {
     FNX_ENTER(ctx);
-    FNX_REQUIRE(n >= 0 && (n == 0 || (srcs && dsts)), "batch arguments");
-    FNX_REQUIRE(n <= FNX_BATCH_MAX, "more than FNX_BATCH_MAX (65535) images in one batch call: the image is a grid dimension");
+    FNX_TRY(check_batch(n, srcs && dsts));
     if (n == 0) return FNX_OK;
     if (srcW <= 0 || srcH <= 0 || dstW <= 0 || dstH <= 0) return FNX_EMPTY;   // resize.go:41-43
     FNX_REQUIRE((srcW == dstW && srcH == dstH) || (th.off && th.idx && th.wt && tv.off && tv.idx && tv.wt), "tap table is null");
-    for (int i = 0; i < n; i++) {
-        FNX_REQUIRE(srcs[i] && dsts[i], "null image in batch");
-        FNX_TRY(check_img(srcs[i], sstride, srcW, srcH, "src"));
-        FNX_TRY(check_img(dsts[i], dstride, dstW, dstH, "dst"));
-    }
+    FNX_TRY(check_batch_images(n, {srcs, sstride, srcW, srcH, "src"}, {dsts, dstride, dstW, dstH, "dst"}));
     if (n > 1 && !(srcW == dstW && srcH == dstH)) {
-        const void *hosts[2] = {srcs, dsts};
-        const size_t sizes[2] = {sizeof(void *) * size_t(n), sizeof(void *) * size_t(n)};
-        void *dp[2];
-        FNX_TRY(upload_tables(ctx, SLOT_PTRS, hosts, sizes, 2, dp));
-        const int rc = resize_fused(ctx, th, tv, srcs[0], sstride, srcW, srcH, dsts[0], dstride, n,
-                                    static_cast<const uint8_t *const *>(dp[0]), static_cast<uint8_t *const *>(dp[1]));
+        const uint8_t *const *d_srcs;
+        uint8_t *const *d_dsts;
+        FNX_TRY(upload_ptr_pair(ctx, n, srcs, dsts, &d_srcs, &d_dsts));
+        const int rc = resize_fused(ctx, th, tv, srcs[0], sstride, srcW, srcH, dsts[0], dstride, n, d_srcs, d_dsts);
         if (rc < 0) return rc;
         if (rc != FNX_NOOP) return FNX_OK;
     }
@@ -373,10 +502,9 @@ static int blur_batch_body(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int 
     if (n == 0 || w <= 0 || h <= 0) return FNX_OK;
     FNX_REQUIRE(sstride >= 4 * w && dstride >= 4 * w && !(sstride & 3) && !(dstride & 3), "stride");
     for (int i = 0; i < n; i++) FNX_REQUIRE(srcs[i] && dsts[i] && srcs[i] != dsts[i], "null image in batch, or dst aliases src (the blur is not in-place)");
-    const void *hosts[2] = {srcs, dsts};
-    const size_t sizes[2] = {sizeof(void *) * size_t(n), sizeof(void *) * size_t(n)};
-    void *dp[2];
-    FNX_TRY(upload_tables(ctx, SLOT_PTRS, hosts, sizes, 2, dp));
+    const uint8_t *const *d_srcs;
+    uint8_t *const *d_dsts;
+    FNX_TRY(upload_ptr_pair(ctx, n, srcs, dsts, &d_srcs, &d_dsts));
     const bool keep = (flags & FNX_BLUR_KEEP_BOX_SUMS) != 0;
     flags &= ~FNX_BLUR_KEEP_BOX_SUMS;
     ctx->kept.valid = false;
@@ -391,8 +519,8 @@ static int blur_batch_body(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int 
         FNX_TRY(scratch(ctx, p ? SLOT_PLANES1 : SLOT_PLANES0, plane * 2 * n + 16, &t));
         if (ctx->tail_pending[p]) FNX_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_tail[p], 0));
         ctx->boxes_on_main = true;               // blur, box planes and (next call) the windowed SSIM back to back on `stream`
-        const int st = launch_blur_scored(ctx, n, static_cast<const uint8_t *const *>(dp[0]), sstride, w, h, kernel, radius, flags,
-                                          static_cast<uint8_t *const *>(dp[1]), dstride, static_cast<uint8_t *>(t), plane, nw, nh);
+        const int st = launch_blur_scored(ctx, n, d_srcs, sstride, w, h, kernel, radius, flags, d_dsts, dstride,
+                                          static_cast<uint8_t *>(t), plane, nw, nh);
         ctx->boxes_on_main = false;
         if (st < 0) return st;
         if (st == FNX_OK) {
@@ -408,8 +536,7 @@ static int blur_batch_body(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int 
         }
         // FNX_NOOP: a shape the one-pass kernel is not built for -- the plain blur, nothing kept
     }
-    return launch_blur(ctx, n, nullptr, static_cast<const uint8_t *const *>(dp[0]), sstride, w, h, kernel,
-                       radius, flags, nullptr, static_cast<uint8_t *const *>(dp[1]), dstride);
+    return launch_blur(ctx, n, nullptr, d_srcs, sstride, w, h, kernel, radius, flags, nullptr, d_dsts, dstride);
 }
 
 // The effects read a SubImage (sstride != 4w) two ways: by rows, and as the flat front of its Pix slice
@@ -470,22 +597,15 @@ static int sharpen_batch_common(fnx_ctx *ctx, bool adaptive, int n, const uint8_
                                 uint8_t *const *dsts, int dstride)
 {
     FNX_ENTER(ctx);
-    FNX_REQUIRE(n >= 0 && (n == 0 || (srcs && dsts)), "batch arguments");
-    FNX_REQUIRE(n <= FNX_BATCH_MAX, "more than FNX_BATCH_MAX (65535) images in one batch call: the image is a grid dimension");
+    FNX_TRY(check_batch(n, srcs && dsts));
     if (n == 0) return FNX_OK;
     FNX_REQUIRE(w >= 3 && h >= 3, "sharpen needs w,h >= 3 (the reference returns the input below that)");
-    for (int i = 0; i < n; i++) {
-        FNX_REQUIRE(srcs[i] && dsts[i] && srcs[i] != dsts[i], "null image in batch, or dst aliases src");
-        FNX_TRY(check_img(srcs[i], sstride, w, h, "src"));
-        FNX_TRY(check_img(dsts[i], dstride, w, h, "dst"));
-    }
+    FNX_TRY(check_batch_images(n, {srcs, sstride, w, h, "src"}, {dsts, dstride, w, h, "dst"}, "null image in batch, or dst aliases src"));
     if (n > 1) {
-        const void *hosts[2] = {srcs, dsts};
-        const size_t sizes[2] = {sizeof(void *) * size_t(n), sizeof(void *) * size_t(n)};
-        void *dp[2];
-        FNX_TRY(upload_tables(ctx, SLOT_PTRS, hosts, sizes, 2, dp));
-        const int rc = launch_sharpen_batch(ctx, adaptive, n, srcs[0], static_cast<const uint8_t *const *>(dp[0]), sstride, w, h, amount,
-                                            dsts[0], static_cast<uint8_t *const *>(dp[1]), dstride);
+        const uint8_t *const *d_srcs;
+        uint8_t *const *d_dsts;
+        FNX_TRY(upload_ptr_pair(ctx, n, srcs, dsts, &d_srcs, &d_dsts));
+        const int rc = launch_sharpen_batch(ctx, adaptive, n, srcs[0], d_srcs, sstride, w, h, amount, dsts[0], d_dsts, dstride);
         if (rc < 0) return rc;
         if (rc != FNX_NOOP) return FNX_OK;
     }
@@ -594,11 +714,10 @@ static bool kept_matches(fnx_ctx *ctx, int n, const uint8_t *const *as, int astr
 static int kept_score(fnx_ctx *ctx, int n, const double *window, const double *dwin, double *dres, bool batch_form)
 {
     fnx_ctx::KeptBoxes &k = ctx->kept;
-    const int p = k.parity;
-    if (batch_form) ctx->partial_slot = p ? SLOT_PART1 : SLOT_PART0;    // (the one-pass entry's arithmetic; a single call keeps its own)
-    const int rc = launch_windowed_ssim(ctx, n, k.planes, k.nw * 4, k.plane, k.planes + k.plane * n, k.nw * 4, k.plane, k.nw, k.nh, window, dwin, dres);
-    ctx->partial_slot = -1;
-    if (rc < 0) return rc;
+    {   // (the one-pass entry's arithmetic; a single call keeps its own)
+        LaunchScope own(ctx, !batch_form ? -1 : k.parity ? SLOT_PART1 : SLOT_PART0, false);
+        FNX_TRY(launch_windowed_ssim(ctx, plane_pairs(n, k.planes, k.planes + k.plane * n, k.plane, k.nw, k.nh), window, dwin, dres));
+    }
     note_route(ctx, FNX_PROF_SSIM, "kept box planes + windowed SSIM");
     ctx->parity ^= 1;
     return FNX_OK;
@@ -616,28 +735,21 @@ int fnx_ssim_fast(fnx_ctx *ctx, int space, const uint8_t *a, int astride, const 
         *out = 1.0;
         return FNX_OK;
     }
-    void *dwin = nullptr;
-    FNX_TRY(upload_table(ctx, SLOT_TABLE0, window, sizeof(double) * 64, &dwin));
+    const double *dwin = nullptr;
+    FNX_TRY(upload_window(ctx, window, &dwin));
     if (kept_matches(ctx, 1, &a, astride, &b, bstride, w, h) && space == FNX_DEVICE) {
         double *dres;
         FNX_TRY(result_slot(ctx, 1, &dres));
-        FNX_TRY(kept_score(ctx, 1, window, static_cast<const double *>(dwin), dres, false));
+        FNX_TRY(kept_score(ctx, 1, window, dwin, dres, false));
         return result_wait(ctx, dres, out, 1);
     }
     DevImg da, db;
     int nw, nh;
-    if (!ssim_fast_dims(w, h, &nw, &nh) && (w < 8 || h < 8)) {   // pixelSSIM on the inputs themselves
-        FNX_REQUIRE(pix_len(w, h, bstride) >= pix_len(w, h, astride), "b.Pix shorter than a.Pix (the reference would panic)");
-        FNX_TRY(stage_in_flat(ctx, space, a, astride, w, h, SLOT_IN_A, &da));
-        FNX_TRY(stage_in_flat(ctx, space, b, bstride, w, h, SLOT_IN_B, &db));
-    } else {
-        FNX_TRY(stage_in(ctx, space, a, astride, w, h, SLOT_IN_A, &da));
-        FNX_TRY(stage_in(ctx, space, b, bstride, w, h, SLOT_IN_B, &db));
-    }
+    const bool pixel = !ssim_fast_dims(w, h, &nw, &nh) && (w < 8 || h < 8);   // pixelSSIM on the inputs themselves
+    FNX_TRY(stage_pair(ctx, space, a, astride, b, bstride, w, h, pixel, &da, &db));
     double *dres;
     FNX_TRY(result_slot(ctx, 1, &dres));
-    FNX_TRY(ssim_fast_device(ctx, 1, da.p, nullptr, da.stride, db.p, nullptr, db.stride, w, h, window,
-                             static_cast<const double *>(dwin), dres));
+    FNX_TRY(ssim_fast_device(ctx, one_pair(da.p, da.stride, db.p, db.stride, w, h), window, dwin, dres));
     return result_wait(ctx, dres, out, 1);
 }
 
@@ -686,32 +798,23 @@ int fnx_ssim_fast_batch_enqueue(fnx_ctx *ctx, int n, const uint8_t *const *as, i
     if (n == 0) return FNX_OK;
     FNX_REQUIRE(w > 0 && h > 0 && astride >= 4 * w && bstride >= 4 * w, "dims");
     FNX_TRY(can_enqueue(ctx));
-    void *dwin = nullptr;
-    FNX_TRY(upload_table(ctx, SLOT_TABLE0, window, sizeof(double) * 64, &dwin));
+    const double *dwin = nullptr;
+    FNX_TRY(upload_window(ctx, window, &dwin));
     double *dres;
     FNX_TRY(result_slot_queued(ctx, n, &dres));
     if (kept_matches(ctx, n, as, astride, bs, bstride, w, h)) {
-        FNX_TRY(kept_score(ctx, n, window, static_cast<const double *>(dwin), dres, true));
+        FNX_TRY(kept_score(ctx, n, window, dwin, dres, true));
         return publish_results(ctx, dres, n);
     }
     int nw, nh;
-    bool al = !(astride & 15) && !(bstride & 15);
-    for (int i = 0; i < n; i++) {
-        FNX_REQUIRE(as[i] && bs[i], "null image in batch");
-        al = al && !(reinterpret_cast<uintptr_t>(as[i]) & 15) && !(reinterpret_cast<uintptr_t>(bs[i]) & 15);
-    }
-    if (ssim_fast_dims(w, h, &nw, &nh) && al) {
-        const void *hosts[2] = {as, bs};
-        const size_t sizes[2] = {sizeof(void *) * size_t(n), sizeof(void *) * size_t(n)};
-        void *dp[2];
-        FNX_TRY(upload_tables(ctx, SLOT_PTRS, hosts, sizes, 2, dp));
-        FNX_TRY(ssim_fast_device(ctx, n, nullptr, static_cast<const uint8_t *const *>(dp[0]), astride, nullptr,
-                                 static_cast<const uint8_t *const *>(dp[1]), bstride, w, h, window,
-                                 static_cast<const double *>(dwin), dres));
+    for (int i = 0; i < n; i++) FNX_REQUIRE(as[i] && bs[i], "null image in batch");
+    if (ssim_fast_dims(w, h, &nw, &nh) && all_aligned16(n, as, astride) && all_aligned16(n, bs, bstride)) {
+        const uint8_t *const *d_as, *const *d_bs;
+        FNX_TRY(upload_ptr_pair(ctx, n, as, bs, &d_as, &d_bs));
+        FNX_TRY(ssim_fast_device(ctx, pairs_by_pointer(n, d_as, astride, d_bs, bstride, w, h), window, dwin, dres));
     } else {
         for (int i = 0; i < n; i++)
-            FNX_TRY(ssim_fast_device(ctx, 1, as[i], nullptr, astride, bs[i], nullptr, bstride, w, h, window,
-                                     static_cast<const double *>(dwin), dres + i));
+            FNX_TRY(ssim_fast_device(ctx, one_pair(as[i], astride, bs[i], bstride, w, h), window, dwin, dres + i));
     }
     return publish_results(ctx, dres, n);
 }
@@ -735,44 +838,30 @@ int fnx_gaussian_blur_ssim_fast_batch_enqueue(fnx_ctx *ctx, int n, const uint8_t
         // step's own tail -- box_from_slabs, windowed SSIM, finish -- runs on the second stream, i.e. under the
         // blur of whatever step the caller enqueues next.
         const int p = ctx->parity;
-        const void *hosts[2] = {srcs, dsts};
-        const size_t sizes[2] = {sizeof(void *) * size_t(n), sizeof(void *) * size_t(n)};
-        void *dp[2];
-        FNX_TRY(upload_tables(ctx, SLOT_PTRS, hosts, sizes, 2, dp));
-        void *dwin = nullptr;
-        FNX_TRY(upload_table(ctx, SLOT_TABLE0, window, sizeof(double) * 64, &dwin));   // before the blur: uploads ride on `stream`
+        const uint8_t *const *d_srcs;
+        uint8_t *const *d_dsts;
+        FNX_TRY(upload_ptr_pair(ctx, n, srcs, dsts, &d_srcs, &d_dsts));
+        const double *dwin = nullptr;
+        FNX_TRY(upload_window(ctx, window, &dwin));   // before the blur: uploads ride on `stream`
         const size_t plane = static_cast<size_t>(nw) * nh * 4;
         void *t = nullptr;
         FNX_TRY(scratch(ctx, p ? SLOT_PLANES1 : SLOT_PLANES0, plane * 2 * n + 16, &t));
         uint8_t *planes = static_cast<uint8_t *>(t);
         if (ctx->tail_pending[p]) FNX_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_tail[p], 0));
-        const int st = launch_blur_scored(ctx, n, static_cast<const uint8_t *const *>(dp[0]), sstride, w, h, kernel,
-                                          radius, flags, static_cast<uint8_t *const *>(dp[1]), dstride, planes, plane, nw, nh);
+        const int st = launch_blur_scored(ctx, n, d_srcs, sstride, w, h, kernel, radius, flags, d_dsts, dstride, planes, plane, nw, nh);
         if (st < 0) return st;
         if (st == FNX_OK) {
             double *dres;
             FNX_TRY(result_slot_queued(ctx, n, &dres));
-            // the windowed-SSIM launcher works on ctx->stream: point it at the tail stream for this call
-            hipStream_t main_stream = ctx->stream;
-            ctx->stream = ctx->stream2;
-            ctx->partial_slot = p ? SLOT_PART1 : SLOT_PART0;
-            int rc = launch_windowed_ssim(ctx, n, planes, nw * 4, plane, planes + plane * n, nw * 4, plane, nw, nh,
-                                          window, static_cast<const double *>(dwin), dres);
-            if (rc >= 0) {
-                rc = publish_results(ctx, dres, n);      // the batch's event: behind the tail
-                if (rc >= 0) {
-                    fnx_ctx::Pending &q = ctx->res_q[(ctx->res_head + ctx->res_count - 1) % fnx_ctx::RES_DEPTH];
-                    q.tail_parity = p;
-                    q.tail_gen = ++ctx->tail_gen[p];
-                }
+            {
+                LaunchScope tail(ctx, p ? SLOT_PART1 : SLOT_PART0, true);   // the windowed-SSIM launcher works on ctx->stream
+                FNX_TRY(launch_windowed_ssim(ctx, plane_pairs(n, planes, planes + plane * n, plane, nw, nh), window, dwin, dres));
+                fnx_ctx::Pending *q = nullptr;
+                FNX_TRY(publish_results(ctx, dres, n, &q));      // the batch's event: behind the tail
+                q->tail_parity = p;
+                q->tail_gen = ++ctx->tail_gen[p];
+                FNX_HIP(hipEventRecord(ctx->ev_tail[p], ctx->stream2));
             }
-            if (rc >= 0 && hipEventRecord(ctx->ev_tail[p], ctx->stream2) != hipSuccess) {
-                set_error("hipEventRecord (tail) failed");
-                rc = FNX_ERR_HIP;
-            }
-            ctx->partial_slot = -1;
-            ctx->stream = main_stream;
-            if (rc < 0) return rc;
             ctx->tail_pending[p] = true;
             ctx->parity ^= 1;
             return FNX_OK;
@@ -817,8 +906,8 @@ int fnx_gaussian_blur_ssim_fast(fnx_ctx *ctx, int space, const uint8_t *src, int
         return fnx_ssim_fast(ctx, space, src, sstride, dst, dstride, w, h, window, ssim);
     }
     FNX_REQUIRE(space != FNX_DEVICE || src != dst, "dst aliases src (the blur is not in-place)");
-    void *dwin = nullptr;
-    FNX_TRY(upload_table(ctx, SLOT_TABLE0, window, sizeof(double) * 64, &dwin));
+    const double *dwin = nullptr;
+    FNX_TRY(upload_window(ctx, window, &dwin));
     DevImg s;
     DevOut d;
     FNX_TRY(stage_in(ctx, space, src, sstride, w, h, SLOT_IN_A, &s));
@@ -826,7 +915,7 @@ int fnx_gaussian_blur_ssim_fast(fnx_ctx *ctx, int space, const uint8_t *src, int
     FNX_TRY(launch_blur(ctx, 1, s.p, nullptr, s.stride, w, h, kernel, radius, flags, d.p, nullptr, d.stride));
     double *dres;
     FNX_TRY(result_slot(ctx, 1, &dres));
-    FNX_TRY(ssim_fast_device(ctx, 1, s.p, nullptr, s.stride, d.p, nullptr, d.stride, w, h, window, static_cast<const double *>(dwin), dres));
+    FNX_TRY(ssim_fast_device(ctx, one_pair(s.p, s.stride, d.p, d.stride, w, h), window, dwin, dres));
     FNX_TRY(finish_enqueue(ctx, space, &d));                     // the blurred image starts back behind the score's kernels
     FNX_TRY(result_wait(ctx, dres, ssim, 1));
     if (space != FNX_DEVICE) FNX_HIP(hipStreamSynchronize(ctx->stream));
@@ -845,25 +934,13 @@ int fnx_ssim(fnx_ctx *ctx, int space, const uint8_t *a, int astride, const uint8
         *out = 1.0;
         return FNX_OK;
     }
-    void *dwin = nullptr;
-    FNX_TRY(upload_table(ctx, SLOT_TABLE0, window, sizeof(double) * 64, &dwin));
+    const double *dwin = nullptr;
+    FNX_TRY(upload_window(ctx, window, &dwin));
     DevImg da, db;
-    if (w < 8 || h < 8) {
-        FNX_REQUIRE(pix_len(w, h, bstride) >= pix_len(w, h, astride), "b.Pix shorter than a.Pix (the reference would panic)");
-        FNX_TRY(stage_in_flat(ctx, space, a, astride, w, h, SLOT_IN_A, &da));
-        FNX_TRY(stage_in_flat(ctx, space, b, bstride, w, h, SLOT_IN_B, &db));
-    } else {
-        FNX_TRY(stage_in(ctx, space, a, astride, w, h, SLOT_IN_A, &da));
-        FNX_TRY(stage_in(ctx, space, b, bstride, w, h, SLOT_IN_B, &db));
-    }
+    FNX_TRY(stage_pair(ctx, space, a, astride, b, bstride, w, h, w < 8 || h < 8, &da, &db));
     double *dres;
     FNX_TRY(result_slot(ctx, 1, &dres));
-    if (w < 8 || h < 8) {   // ssim.go:35-37
-        FNX_TRY(launch_pixel_ssim(ctx, da.p, db.p, w, h, pix_len(w, h, da.stride), dres));
-    } else {                // toLuminance x2 + windowedSSIM at full resolution (ssim.go:39-42)
-        FNX_TRY(launch_windowed_ssim(ctx, 1, da.p, da.stride, 0, db.p, db.stride, 0, w, h, window,
-                                     static_cast<const double *>(dwin), dres));
-    }
+    FNX_TRY(ssim_pairs(ctx, one_pair(da.p, da.stride, db.p, db.stride, w, h), nullptr, nullptr, window, dwin, dres, THEN_WAIT));
     return result_wait(ctx, dres, out, 1);
 }
 
@@ -875,38 +952,14 @@ int fnx_ssim_enqueue(fnx_ctx *ctx, const uint8_t *a, int astride, const uint8_t 
     FNX_TRY(check_img(a, astride, w, h, "a"));
     FNX_TRY(check_img(b, bstride, w, h, "b"));
     FNX_TRY(can_enqueue(ctx));
-    void *dwin = nullptr;
-    FNX_TRY(upload_table(ctx, SLOT_TABLE0, window, sizeof(double) * 64, &dwin));
+    const double *dwin = nullptr;
+    FNX_TRY(upload_window(ctx, window, &dwin));
     double *dres;
     FNX_TRY(result_slot_queued(ctx, 1, &dres));
-    if (w < 8 || h < 8) {   // ssim.go:35-37
-        FNX_REQUIRE(pix_len(w, h, bstride) >= pix_len(w, h, astride), "b.Pix shorter than a.Pix (the reference would panic)");
-        FNX_TRY(launch_pixel_ssim(ctx, a, b, w, h, pix_len(w, h, astride), dres));
-        return publish_results(ctx, dres, 1);
-    }
-    // The score's kernels run on the ctx's second stream, behind everything enqueued so far (the images were
-    // produced on `stream`): what the caller enqueues next -- the next image's AdaptiveSharpen in config 4 -- does
-    // not wait for them, so one kernel's last workgroups and the next one's first share the chip instead of each
-    // launch draining it (three launch boundaries per image, ~5 us each, at 8K).  The partial sums use the tail's
-    // own slot: other calls on `stream` may use SLOT_PARTIAL meanwhile.  a and b stay the caller's until the fetch.
+    // the score's kernels on the second stream (ssim_pairs); a and b stay the caller's until the fetch
     static const bool same_stream = [] { const char *e = dev_env("FNX_SSIM_ENQUEUE_INLINE"); return e && e[0] == '1'; }();
-    if (same_stream) {
-        FNX_TRY(launch_windowed_ssim(ctx, 1, a, astride, 0, b, bstride, 0, w, h, window, static_cast<const double *>(dwin), dres));
-        return publish_results(ctx, dres, 1);
-    }
-    hipEvent_t ev = ctx->ev_blur[ctx->ev_toggle];                 // the one-pass batches' hand-over events, same use
-    FNX_HIP(hipEventRecord(ev, ctx->stream));
-    FNX_HIP(hipStreamWaitEvent(ctx->stream2, ev, 0));
-    ctx->stream2_used = true;
-    hipStream_t main_stream = ctx->stream;
-    ctx->stream = ctx->stream2;
-    ctx->partial_slot = SLOT_PART0;
-    int rc = launch_windowed_ssim(ctx, 1, a, astride, 0, b, bstride, 0, w, h, window, static_cast<const double *>(dwin), dres);
-    if (rc >= 0) rc = publish_results(ctx, dres, 1);              // the result's event: behind the score, on the second stream
-    ctx->partial_slot = -1;
-    ctx->stream = main_stream;
-    ctx->ev_toggle ^= 1;
-    return rc;
+    return ssim_pairs(ctx, one_pair(a, astride, b, bstride, w, h), nullptr, nullptr, window, dwin, dres,
+                      same_stream ? THEN_PUBLISH : THEN_PUBLISH_TAIL);
 }
 
 // MSSSIM's weights, trimmed while a level's min dim < 8 (ssim.go:324-342)
@@ -935,8 +988,8 @@ static int msssim_weights(int w, int h, double (&weights)[5])
 static int msssim_levels_device(fnx_ctx *ctx, const uint8_t *ap, int astride, const uint8_t *bp, int bstride, int w, int h,
                                 int nweights, const double *window, double *dres, int *nlev_out)
 {
-    void *dwin = nullptr;
-    FNX_TRY(upload_table(ctx, SLOT_TABLE0, window, sizeof(double) * 64, &dwin));
+    const double *dwin = nullptr;
+    FNX_TRY(upload_window(ctx, window, &dwin));
     int nlev = 0;
     const int fused = launch_msssim_fused(ctx, ap, astride, bp, bstride, w, h, nweights, window, dres, &nlev);
     if (fused < 0) return fused;
@@ -952,16 +1005,15 @@ static int msssim_levels_device(fnx_ctx *ctx, const uint8_t *ap, int astride, co
         void *reserve = nullptr;
         FNX_TRY(scratch(ctx, SLOT_PARTIAL, sizeof(double) * SSIM_DEFER_DOUBLES, &reserve));
         for (int i = 0; i < nweights; i++) {
-            FNX_TRY(ssim_fast_device(ctx, 1, ca, nullptr, cas, cb, nullptr, cbs, cw, ch, window,
-                                     static_cast<const double *>(dwin), dres + i, &defer, i));
+            const ImgPairs level = one_pair(ca, cas, cb, cbs, cw, ch);
+            FNX_TRY(ssim_fast_device(ctx, level, window, dwin, dres + i, SsimOpts::deferred(&defer, i)));
             nlev = i + 1;
             if (i < nweights - 1) {
                 const int nw = cw / 2, nh = ch / 2;
                 if (nw < 8 || nh < 8) break;              // ssim.go:354-358
                 uint8_t *na = static_cast<uint8_t *>(pyr) + (i & 1) * 2 * lvl_bytes;
                 uint8_t *nb = na + lvl_bytes;
-                FNX_TRY(launch_box_downsample_pair(ctx, 1, ca, nullptr, cas, cb, nullptr, cbs, cw, ch, na, nw * 4,
-                                                   lvl_bytes, nw, nh));
+                FNX_TRY(launch_box_downsample_pair(ctx, level, na, nw * 4, lvl_bytes, nw, nh));
                 ca = na; cb = nb; cas = cbs = nw * 4; cw = nw; ch = nh;
             }
         }
@@ -1037,6 +1089,33 @@ int fnx_msssim(fnx_ctx *ctx, int space, const uint8_t *a, int astride, const uin
     return FNX_OK;
 }
 
+// n checked same-geometry device pairs -> one FIFO entry of n MSSSIMs (fnx_msssim_enqueue: n == 1)
+static int msssim_enqueue_body(fnx_ctx *ctx, int n, const uint8_t *const *as, const uint8_t *const *bs, int w, int h, const double *window)
+{
+    FNX_TRY(can_enqueue(ctx));
+    double weights[5];
+    const int nweights = msssim_weights(w, h, weights);
+    double *dres;
+    FNX_TRY(result_slot_queued(ctx, 5 * n, &dres));
+    int nlev = 0;
+    bool batched = false;
+    // the five launches of the fused form with the image as a grid dimension of each (ssim.hip); shapes it does not cover
+    // (odd dims, a pair that is not 16-byte aligned -- the pointers: the levels are read flat, stride 4w -- the non-default
+    // forms) take the loop below
+    if (n > 1 && all_aligned16(n, as, 0) && all_aligned16(n, bs, 0)) {
+        const uint8_t *const *d_as, *const *d_bs;
+        FNX_TRY(upload_ptr_pair(ctx, n, as, bs, &d_as, &d_bs));
+        const double *dwin = nullptr;
+        FNX_TRY(upload_window(ctx, window, &dwin));
+        const int rc = launch_msssim_fused(ctx, as[0], w * 4, bs[0], w * 4, w, h, nweights, window, dres, &nlev, n, d_as, d_bs);
+        if (rc < 0) return rc;
+        batched = rc == FNX_OK;
+    }
+    for (int i = 0; i < n && !batched; i++)      // (every image has the same levels: the dims decide)
+        FNX_TRY(msssim_levels_device(ctx, as[i], w * 4, bs[i], w * 4, w, h, nweights, window, dres + 5 * i, &nlev));   // toNRGBA: flat (see fnx_msssim)
+    return publish_msssim(ctx, dres, n, nlev, weights);
+}
+
 int fnx_msssim_enqueue(fnx_ctx *ctx, const uint8_t *a, int astride, const uint8_t *b, int bstride, int w, int h,
                        const double *window)
 {
@@ -1044,18 +1123,7 @@ int fnx_msssim_enqueue(fnx_ctx *ctx, const uint8_t *a, int astride, const uint8_
     FNX_REQUIRE(window != nullptr && w > 0 && h > 0, "enqueue arguments");
     FNX_TRY(check_img(a, astride, w, h, "a"));
     FNX_TRY(check_img(b, bstride, w, h, "b"));
-    FNX_TRY(can_enqueue(ctx));
-    double weights[5];
-    const int nweights = msssim_weights(w, h, weights);
-    double *dres;
-    FNX_TRY(result_slot_queued(ctx, 5, &dres));
-    int nlev = 0;
-    FNX_TRY(msssim_levels_device(ctx, a, w * 4, b, w * 4, w, h, nweights, window, dres, &nlev));   // toNRGBA: flat (see fnx_msssim)
-    fnx_ctx::Pending &q = ctx->res_q[(ctx->res_head + ctx->res_count) % fnx_ctx::RES_DEPTH];
-    FNX_TRY(publish_results(ctx, dres, 1));
-    q.nraw = nlev;
-    for (int i = 0; i < 5; i++) q.weights[i] = weights[i];
-    return FNX_OK;
+    return msssim_enqueue_body(ctx, 1, &a, &b, w, h, window);
 }
 
 // n same-geometry device pairs scored by ONE launch of the window kernel (the image is its second grid dimension), on the
@@ -1064,89 +1132,27 @@ int fnx_ssim_batch_enqueue(fnx_ctx *ctx, int n, const uint8_t *const *as, int as
                            int w, int h, const double *window)
 {
     FNX_ENTER(ctx);
-    FNX_REQUIRE(n >= 0 && (n == 0 || (as && bs)) && window != nullptr && w > 0 && h > 0, "batch arguments");
-    FNX_REQUIRE(n <= FNX_BATCH_MAX, "more than FNX_BATCH_MAX (65535) images in one batch call: the image is a grid dimension");
+    FNX_TRY(check_batch(n, as && bs, window != nullptr && w > 0 && h > 0));
     if (n == 0) return FNX_OK;
-    for (int i = 0; i < n; i++) {
-        FNX_REQUIRE(as[i] && bs[i], "null image in batch");
-        FNX_TRY(check_img(as[i], astride, w, h, "a"));
-        FNX_TRY(check_img(bs[i], bstride, w, h, "b"));
-    }
+    FNX_TRY(check_batch_images(n, {as, astride, w, h, "a"}, {bs, bstride, w, h, "b"}));
     FNX_TRY(can_enqueue(ctx));
-    void *dwin = nullptr;
-    FNX_TRY(upload_table(ctx, SLOT_TABLE0, window, sizeof(double) * 64, &dwin));
+    const double *dwin = nullptr;
+    FNX_TRY(upload_window(ctx, window, &dwin));
     double *dres;
     FNX_TRY(result_slot_queued(ctx, n, &dres));
-    if (w < 8 || h < 8) {   // ssim.go:35-37: pixelSSIM, pair by pair
-        FNX_REQUIRE(pix_len(w, h, bstride) >= pix_len(w, h, astride), "b.Pix shorter than a.Pix (the reference would panic)");
-        for (int i = 0; i < n; i++) FNX_TRY(launch_pixel_ssim(ctx, as[i], bs[i], w, h, pix_len(w, h, astride), dres + i));
-        return publish_results(ctx, dres, n);
-    }
-    const void *hosts[2] = {as, bs};
-    const size_t sizes[2] = {sizeof(void *) * size_t(n), sizeof(void *) * size_t(n)};
-    void *dp[2];
-    FNX_TRY(upload_tables(ctx, SLOT_PTRS, hosts, sizes, 2, dp));
-    hipEvent_t ev = ctx->ev_blur[ctx->ev_toggle];                 // (see fnx_ssim_enqueue)
-    FNX_HIP(hipEventRecord(ev, ctx->stream));
-    FNX_HIP(hipStreamWaitEvent(ctx->stream2, ev, 0));
-    ctx->stream2_used = true;
-    hipStream_t main_stream = ctx->stream;
-    ctx->stream = ctx->stream2;
-    ctx->partial_slot = SLOT_PART0;
-    int rc = launch_windowed_ssim(ctx, n, as[0], astride, 0, bs[0], bstride, 0, w, h, window, static_cast<const double *>(dwin), dres, nullptr, 0,
-                                  static_cast<const uint8_t *const *>(dp[0]), static_cast<const uint8_t *const *>(dp[1]));
-    if (rc >= 0) rc = publish_results(ctx, dres, n);
-    ctx->partial_slot = -1;
-    ctx->stream = main_stream;
-    ctx->ev_toggle ^= 1;
-    return rc;
+    ImgPairs im = one_pair(as[0], astride, bs[0], bstride, w, h);
+    im.n = n;
+    return ssim_pairs(ctx, im, as, bs, window, dwin, dres, THEN_PUBLISH_TAIL);
 }
 
 int fnx_msssim_batch_enqueue(fnx_ctx *ctx, int n, const uint8_t *const *as, int astride, const uint8_t *const *bs, int bstride,
                              int w, int h, const double *window)
 {
     FNX_ENTER(ctx);
-    FNX_REQUIRE(n >= 0 && (n == 0 || (as && bs)) && window != nullptr && w > 0 && h > 0, "batch arguments");
-    FNX_REQUIRE(n <= FNX_BATCH_MAX, "more than FNX_BATCH_MAX (65535) images in one batch call: the image is a grid dimension");
+    FNX_TRY(check_batch(n, as && bs, window != nullptr && w > 0 && h > 0));
     if (n == 0) return FNX_OK;
-    for (int i = 0; i < n; i++) {
-        FNX_REQUIRE(as[i] && bs[i], "null image in batch");
-        FNX_TRY(check_img(as[i], astride, w, h, "a"));
-        FNX_TRY(check_img(bs[i], bstride, w, h, "b"));
-    }
-    FNX_TRY(can_enqueue(ctx));
-    double weights[5];
-    const int nweights = msssim_weights(w, h, weights);
-    double *dres;
-    FNX_TRY(result_slot_queued(ctx, 5 * n, &dres));
-    int nlev = 0;
-    bool batched = false;
-    if (n > 1) {
-        // the five launches of the fused form with the image as a grid dimension of each (ssim.hip); shapes it does not cover
-        // (odd dims, a pair that is not 16-byte aligned, the non-default forms) take the loop below
-        bool al = true;
-        for (int i = 0; i < n; i++) al = al && !(reinterpret_cast<uintptr_t>(as[i]) & 15) && !(reinterpret_cast<uintptr_t>(bs[i]) & 15);
-        if (al) {
-            const void *hosts[2] = {as, bs};
-            const size_t sizes[2] = {sizeof(void *) * size_t(n), sizeof(void *) * size_t(n)};
-            void *dp[2];
-            FNX_TRY(upload_tables(ctx, SLOT_PTRS, hosts, sizes, 2, dp));
-            void *dwin = nullptr;
-            FNX_TRY(upload_table(ctx, SLOT_TABLE0, window, sizeof(double) * 64, &dwin));
-            const int rc = launch_msssim_fused(ctx, as[0], w * 4, bs[0], w * 4, w, h, nweights, window, dres, &nlev, n,
-                                               static_cast<const uint8_t *const *>(dp[0]), static_cast<const uint8_t *const *>(dp[1]));
-            if (rc < 0) return rc;
-            batched = rc == FNX_OK;
-        }
-    }
-    for (int i = 0; i < n && !batched; i++)      // (every image has the same levels: the dims decide)
-        FNX_TRY(msssim_levels_device(ctx, as[i], w * 4, bs[i], w * 4, w, h, nweights, window, dres + 5 * i, &nlev));   // toNRGBA: flat (see fnx_msssim)
-    fnx_ctx::Pending &q = ctx->res_q[(ctx->res_head + ctx->res_count) % fnx_ctx::RES_DEPTH];
-    FNX_TRY(publish_results(ctx, dres, n));
-    q.nraw = nlev;
-    q.nimg = n;
-    for (int i = 0; i < 5; i++) q.weights[i] = weights[i];
-    return FNX_OK;
+    FNX_TRY(check_batch_images(n, {as, astride, w, h, "a"}, {bs, bstride, w, h, "b"}));
+    return msssim_enqueue_body(ctx, n, as, bs, w, h, window);
 }
 
 // ---- prepared reference ------------------------------------------------------------------
@@ -1318,19 +1324,11 @@ static int analyze_direct(fnx_ctx *ctx, int n, const uint8_t *src, const uint8_t
     for (int i = 0; i < nr; i++) ready[i] = 0u;
     std::atomic_thread_fence(std::memory_order_release);
     FNX_TRY(launch_analyze_one(ctx, n, src, srcs, sstride, w, h, al, hres, hvar, const_cast<uint32_t *>(ready)));
-    for (unsigned spin = 1;; spin++) {
-        bool all = true;
+    FNX_TRY(poll_until([=] {
         for (int i = 0; i < nr; i++)
-            if (ready[i] != 1u) { all = false; break; }
-        if (all) break;
-        if ((spin & 127u) == 0) {
-            const hipError_t q = hipStreamQuery(ctx->stream);
-            if (q == hipSuccess) break;                         // the stream is empty: the words are there
-            if (q != hipErrorNotReady) FNX_HIP(q);
-        }
-        __builtin_ia32_pause();
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
+            if (ready[i] != 1u) return false;
+        return true;
+    }, [&] { return hipStreamQuery(ctx->stream); }));           // (the stream is empty: the words are there)
     for (int i = 0; i < nr; i++) FNX_REQUIRE(ready[i] == 1u, "Analyze: the launch finished without a result");
     std::memcpy(out, hres, sizeof(fnx_analysis) * static_cast<size_t>(n));
     for (int i = 0; i < n; i++) {                                   // the contrast workgroups' sums, in order: bit-reproducible
@@ -1377,11 +1375,8 @@ int fnx_analyze_batch(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstri
     FNX_REQUIRE(n >= 0 && srcs && out, "batch arguments");
     if (n == 0) return FNX_OK;
     FNX_REQUIRE(w > 0 && h > 0 && sstride >= 4 * w && !(sstride & 3), "dims");
-    bool al = true;
-    for (int i = 0; i < n; i++) {
-        FNX_REQUIRE(srcs[i], "null image in batch");
-        al = al && !(reinterpret_cast<uintptr_t>(srcs[i]) & 15);
-    }
+    for (int i = 0; i < n; i++) FNX_REQUIRE(srcs[i], "null image in batch");
+    const bool al = all_aligned16(n, srcs, 0);
     void *dp = nullptr;
     FNX_TRY(upload_table(ctx, SLOT_PTRS, srcs, sizeof(void *) * size_t(n), &dp));
     if (!analyze_staged() && n <= 4096) {
@@ -1422,21 +1417,12 @@ int fnx_scan_flags(fnx_ctx *ctx, int space, const uint8_t *pix, size_t pix_len, 
         int nslots = 0;
         FNX_TRY(launch_scan_flags_direct(ctx, d, pix_len, static_cast<uint32_t *>(pin), &nslots));
         int first = 0;                                             // slots below it have reported
-        for (unsigned spin = 1;; spin++) {
+        const auto drain = [&] {
             while (first < nslots && hf[first] != 0xffffffffu) { flags |= hf[first]; first++; }
-            if (first == nslots) break;
-            if ((spin & 127u) == 0) {
-                const hipError_t q = hipStreamQuery(ctx->stream);
-                if (q != hipSuccess && q != hipErrorNotReady) FNX_HIP(q);
-                if (q == hipSuccess) {                             // the stream is empty: every word is there
-                    while (first < nslots && hf[first] != 0xffffffffu) { flags |= hf[first]; first++; }
-                    FNX_REQUIRE(first == nslots, "scan_flags: the kernel finished without all of its results");
-                    break;
-                }
-            }
-            __builtin_ia32_pause();
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
+            return first == nslots;
+        };
+        FNX_TRY(poll_until(drain, [&] { return hipStreamQuery(ctx->stream); }));
+        FNX_REQUIRE(drain(), "scan_flags: the kernel finished without all of its results");   // (the stream is empty: every word is there)
         flags &= 3u;
     }
     if (is_opaque) *is_opaque = (flags & 1u) ? 0 : 1;

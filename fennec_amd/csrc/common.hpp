@@ -329,6 +329,8 @@ int check_space(int space);
 int check_space_io(int space);
 // SSIMFast's dims (ssim.go:52-56): true when the w x h image is compared box-downsampled, at *nw x *nh (<= 512 px)
 bool ssim_fast_dims(int w, int h, int *nw, int *nh);
+// the 8 x 8 SSIM window (64 doubles, host) as the ctx's device table
+int upload_window(fnx_ctx *ctx, const double *window, const double **d_window);
 // n result doubles in pinned memory that the result kernels write (NaN until then), and the wait for them (-> out)
 int result_slot(fnx_ctx *ctx, int n, double **d);
 int result_wait(fnx_ctx *ctx, const double *pinned, double *out, int n);
@@ -337,6 +339,18 @@ int against_device(fnx_ctx *ctx, const fnx_prepared *ref, const uint8_t *b, int 
                    bool b_is_plane = false);
 // the reference's own plane from the device image src into ref.pix (ref.w, ref.h, ref.pw, ref.ph as ssim_fast_dims set them)
 int prepared_plane(fnx_ctx *ctx, const uint8_t *src, int sstride, const fnx_prepared &ref);
+
+// n same-geometry w x h image pairs on the device, as the SSIM and boxDownsample launchers take them.  Image i of a side is
+// ptrs[i] where ptrs (a DEVICE array) is given, else p + i * image_bytes.
+struct ImgSide { const uint8_t *p = nullptr; const uint8_t *const *ptrs = nullptr; int stride = 0; size_t image_bytes = 0; };
+struct ImgPairs { int n = 0, w = 0, h = 0; ImgSide a, b; };
+// one pair; n pairs of tight planes, `plane` bytes apart on each side; n pairs by device pointer arrays
+inline ImgPairs one_pair(const uint8_t *a, int astride, const uint8_t *b, int bstride, int w, int h) { return {1, w, h, {a, nullptr, astride, 0}, {b, nullptr, bstride, 0}}; }
+inline ImgPairs plane_pairs(int n, const uint8_t *a, const uint8_t *b, size_t plane, int w, int h) { return {n, w, h, {a, nullptr, w * 4, plane}, {b, nullptr, w * 4, plane}}; }
+inline ImgPairs pairs_by_pointer(int n, const uint8_t *const *d_as, int astride, const uint8_t *const *d_bs, int bstride, int w, int h)
+{
+    return {n, w, h, {nullptr, d_as, astride, 0}, {nullptr, d_bs, bstride, 0}};
+}
 
 // ---- kernel launchers (each enqueues on ctx->stream; device pointers only) ----
 int launch_blur(fnx_ctx *ctx, int n, const uint8_t *src, const uint8_t *const *srcs, int sstride,
@@ -427,12 +441,9 @@ int launch_resize_v(fnx_ctx *ctx, const uint8_t *src, int sstride, int srcW, int
 int launch_box_downsample(fnx_ctx *ctx, int n, const uint8_t *src, const uint8_t *const *srcs,
                           int sstride, int srcW, int srcH, uint8_t *dst, int dstride,
                           size_t dst_image_bytes, int dstW, int dstH);
-int launch_box_downsample_pair(fnx_ctx *ctx, int n, const uint8_t *src, const uint8_t *const *srcs,
-                               int sstride, const uint8_t *src_b, const uint8_t *const *srcs_b, int sstride_b,
-                               int srcW, int srcH, uint8_t *dst, int dstride, size_t dst_image_bytes,
-                               int dstW, int dstH);
-// Windowed SSIM of n image pairs (tight or strided NRGBA, w x h >= 8): image i of a at
-// a + i*a_image_bytes (same for b); writes n doubles to d_out.
+// both sides of n SSIM comparisons in one launch: dst holds [a0..an-1][b0..bn-1] (src.b.p == src.b.ptrs == nullptr: a only)
+int launch_box_downsample_pair(fnx_ctx *ctx, const ImgPairs &src, uint8_t *dst, int dstride, size_t dst_image_bytes, int dstW, int dstH);
+// Windowed SSIM of n image pairs (tight or strided NRGBA, w x h >= 8); writes n doubles to d_out.
 // Windowed-SSIM launches whose final means are taken later by ONE finish launch (MSSSIM: five levels,
 // each finish is ~4.5 us of latency for a few hundred additions).  The caller reserves SLOT_PARTIAL
 // for all of them first (SSIM_DEFER_DOUBLES) so that the partial pointers stay valid.
@@ -442,14 +453,14 @@ struct SsimDeferred {
     size_t used = 0;                       // doubles of SLOT_PARTIAL handed out
     struct Item { size_t offset; int tiles; double windows; int out_index; } item[8];
 };
-// defer != nullptr (n must be 1): no finish launch; the result goes to d_out[defer_out_index] when
-// launch_ssim_finish_deferred runs
-int launch_windowed_ssim(fnx_ctx *ctx, int n, const uint8_t *a, int astride, size_t a_image_bytes,
-                         const uint8_t *b, int bstride, size_t b_image_bytes, int w, int h,
-                         const double *h_window, const double *d_window, double *d_out,
-                         SsimDeferred *defer = nullptr, int defer_out_index = 0,
-                         const uint8_t *const *d_as = nullptr, const uint8_t *const *d_bs = nullptr,    // device pointer arrays: image z = d_as[z] / d_bs[z]
-                         bool select_as_one = false);   // kernel, tiling and reduction order of a call with n == 1
+struct SsimOpts {
+    SsimDeferred *defer = nullptr;   // (n must be 1): no finish launch; d_out[defer_index] is written when
+    int defer_index = 0;             // launch_ssim_finish_deferred runs
+    bool select_as_one = false;      // kernel, tiling and reduction order of a call with n == 1
+    static SsimOpts deferred(SsimDeferred *d, int index) { SsimOpts o; o.defer = d; o.defer_index = index; return o; }
+    static SsimOpts as_one() { SsimOpts o; o.select_as_one = true; return o; }
+};
+int launch_windowed_ssim(fnx_ctx *ctx, const ImgPairs &im, const double *h_window, const double *d_window, double *d_out, const SsimOpts &opt = SsimOpts());
 int launch_ssim_finish_deferred(fnx_ctx *ctx, const SsimDeferred &d, double *d_out, int nimg = 1, size_t part_img = 0, int out_img = 0);
 // MSSSIM's levels in five launches (ssim.hip); FNX_NOOP (nothing launched) for shapes it does not cover.
 // d_out[i] = SSIMFast of level i; *nlev = levels the reference's loop visits.

@@ -364,8 +364,9 @@ int fnx_jpeg_compress_batch(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int
     const size_t chunk_cap = JPEG_BATCH_SCRATCH / per_item;
     const int chunk = static_cast<int>(chunk_cap < 1 ? 1 : (chunk_cap > static_cast<size_t>(n) ? n : chunk_cap));
 
-    void *dwin = nullptr, *dq = nullptr;
-    FNX_TRY(upload_table(ctx, SLOT_TABLE0, window, sizeof(double) * 64, &dwin));
+    const double *dwin = nullptr;
+    void *dq = nullptr;
+    FNX_TRY(upload_window(ctx, window, &dwin));
     FNX_TRY(upload_table(ctx, SLOT_JPEG_QTAB, jpeg_qtab_host(), sizeof(uint32_t) * JPEG_QTAB_WORDS, &dq));
     const uint32_t *d_qtab = static_cast<const uint32_t *>(dq);
 
@@ -443,8 +444,7 @@ int fnx_jpeg_compress_batch(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int
             double *dres;
             FNX_TRY(result_slot(ctx, nj, &dres));
             if (pixel) FNX_TRY(launch_pixel_ssim_batch(ctx, nj, d_as, d_bs, pw, ph, static_cast<size_t>(pw) * ph * 4, dres));
-            else FNX_TRY(launch_windowed_ssim(ctx, nj, nullptr, pw * 4, 0, nullptr, pw * 4, 0, pw, ph, window,
-                                              static_cast<const double *>(dwin), dres, nullptr, 0, d_as, d_bs, true));
+            else FNX_TRY(launch_windowed_ssim(ctx, pairs_by_pointer(nj, d_as, pw * 4, d_bs, pw * 4, pw, ph), window, dwin, dres, SsimOpts::as_one()));
             FNX_TRY(result_wait(ctx, dres, vals.data(), nj));
             for (int j = 0; j < nj; j++) st[act[j]].record(jobs[j].y, vals[j]);
         }

@@ -465,27 +465,24 @@ int launch_box_downsample(fnx_ctx *ctx, int n, const uint8_t *src, const uint8_t
                           int sstride, int srcW, int srcH, uint8_t *dst, int dstride,
                           size_t dst_image_bytes, int dstW, int dstH)
 {
-    return launch_box_downsample_pair(ctx, n, src, srcs, sstride, nullptr, nullptr, 0, srcW, srcH, dst, dstride,
-                                      dst_image_bytes, dstW, dstH);
+    return launch_box_downsample_pair(ctx, {n, srcW, srcH, {src, srcs, sstride, 0}, {}}, dst, dstride, dst_image_bytes, dstW, dstH);
 }
 
 // Both sides of an SSIM comparison in ONE launch: images a (z < n) and b (z >= n), same geometry;
 // dst image z lives at dst + z*dst_image_bytes.  b == bs == nullptr: a only.
-int launch_box_downsample_pair(fnx_ctx *ctx, int n, const uint8_t *src, const uint8_t *const *srcs,
-                               int sstride, const uint8_t *src_b, const uint8_t *const *srcs_b, int sstride_b,
-                               int srcW, int srcH, uint8_t *dst, int dstride, size_t dst_image_bytes,
-                               int dstW, int dstH)
+int launch_box_downsample_pair(fnx_ctx *ctx, const ImgPairs &im, uint8_t *dst, int dstride, size_t dst_image_bytes, int dstW, int dstH)
 {
+    const int n = im.n, srcW = im.w, srcH = im.h;
     if (srcW <= 0 || srcH <= 0 || dstW <= 0 || dstH <= 0 || n <= 0) return FNX_OK;
-    const bool pair = src_b || srcs_b;
+    const bool pair = im.b.p || im.b.ptrs;
     BoxArgs a{};
-    a.src = src; a.srcs = srcs; a.dst = dst; a.dst_image_bytes = dst_image_bytes;
-    a.src_b = src_b; a.srcs_b = srcs_b; a.sstride_b = sstride_b; a.nimg = n;
-    a.sstride = sstride; a.srcW = srcW; a.srcH = srcH; a.dstride = dstride; a.dstW = dstW; a.dstH = dstH;
+    a.src = im.a.p; a.srcs = im.a.ptrs; a.dst = dst; a.dst_image_bytes = dst_image_bytes;
+    a.src_b = im.b.p; a.srcs_b = im.b.ptrs; a.sstride_b = im.b.stride; a.nimg = n;
+    a.sstride = im.a.stride; a.srcW = srcW; a.srcH = srcH; a.dstride = dstride; a.dstW = dstW; a.dstH = dstH;
     a.xRatio = static_cast<double>(srcW) / static_cast<double>(dstW);   // ssim.go:251-252
     a.yRatio = static_cast<double>(srcH) / static_cast<double>(dstH);
-    a.vec_in = srcs ? ((sstride & 15) == 0) : aligned16(src, sstride);
-    if (pair) a.vec_in = a.vec_in && (srcs_b ? ((sstride_b & 15) == 0) : aligned16(src_b, sstride_b));
+    const auto vec_in = [](const ImgSide &s) { return s.ptrs ? (s.stride & 15) == 0 : aligned16(s.p, s.stride); };
+    a.vec_in = vec_in(im.a) && (!pair || vec_in(im.b));
     const int nz = pair ? 2 * n : n;
     const bool tiled = srcW >= dstW && srcH >= dstH && a.yRatio + 1.0 < BOX_MAXROWS &&
                        a.xRatio + 1.0 < BOX_MAXROWS && a.xRatio * 2 + 8 < 4 * BOX_CHUNKS;
@@ -1684,16 +1681,22 @@ static bool ssim_use_tiled()
     return v;
 }
 
-int launch_windowed_ssim(fnx_ctx *ctx, int n, const uint8_t *a, int astride, size_t a_image_bytes,
-                         const uint8_t *b, int bstride, size_t b_image_bytes, int w, int h,
-                         const double *h_window, const double *d_window, double *d_out,
-                         SsimDeferred *defer, int defer_out_index, const uint8_t *const *d_as, const uint8_t *const *d_bs,
-                         bool select_as_one)
+// the image fields that every window kernel's argument struct carries
+template <typename Args>
+static void set_pairs(Args &k, const ImgPairs &im)
 {
-    const int ww = w - 8, wh = h - 8;     // window grid
+    k.a = im.a.p; k.b = im.b.p; k.as = im.a.ptrs; k.bs = im.b.ptrs; k.a_image_bytes = im.a.image_bytes; k.b_image_bytes = im.b.image_bytes;
+    k.astride = im.a.stride; k.bstride = im.b.stride; k.w = im.w; k.h = im.h;
+}
+
+int launch_windowed_ssim(fnx_ctx *ctx, const ImgPairs &im, const double *h_window, const double *d_window, double *d_out, const SsimOpts &opt)
+{
+    const int n = im.n;
+    SsimDeferred *const defer = opt.defer;
+    const int ww = im.w - 8, wh = im.h - 8;     // window grid
     // select_as_one: the kernel, its tiling and its reduction order are those of a call with n == 1 (every image's score is
     // then bit for bit the single call's: fnx_jpeg_compress_batch); n only widens the grid
-    const long nsel = select_as_one ? 1L : static_cast<long>(n);
+    const long nsel = opt.select_as_one ? 1L : static_cast<long>(n);
     const bool have = ww > 0 && wh > 0;
     WinSepArgs sa{};
     const bool sep = have && window_rank1(h_window, sa.col, sa.row);
@@ -1749,8 +1752,7 @@ int launch_windowed_ssim(fnx_ctx *ctx, int n, const uint8_t *a, int astride, siz
         FNX_TRY(scratch(ctx, ps, sizeof(double) * (static_cast<size_t>(tiles) * n + 2), &part));
     }
     if (march) {
-        ma.a = a; ma.b = b; ma.as = d_as; ma.bs = d_bs; ma.a_image_bytes = a_image_bytes; ma.b_image_bytes = b_image_bytes;
-        ma.astride = astride; ma.bstride = bstride; ma.w = w; ma.h = h;
+        set_pairs(ma, im);
         ma.partial = static_cast<double *>(part);
         for (int i = 0; i < 8; i++) { ma.col[i] = sa.col[i]; ma.row[i] = sa.row[i]; }
         // the image's last workgroup takes the mean itself (no finish launch).  Counters: 2 x 4096, one half per
@@ -1784,8 +1786,7 @@ int launch_windowed_ssim(fnx_ctx *ctx, int n, const uint8_t *a, int astride, siz
         FNX_HIP(hipGetLastError());
         FNX_TRY(prof_end(ctx));
     } else if (sep) {
-        sa.a = a; sa.b = b; sa.as = d_as; sa.bs = d_bs; sa.a_image_bytes = a_image_bytes; sa.b_image_bytes = b_image_bytes;
-        sa.astride = astride; sa.bstride = bstride; sa.w = w; sa.h = h;
+        set_pairs(sa, im);
         sa.tiles_x = tiles_x; sa.tiles = tiles; sa.partial = static_cast<double *>(part);
         static const bool nofold = [] { const char *e = dev_env("FNX_SSIM_NOFOLD"); return e && e[0] == '1'; }();
         if (!big && !defer && !nofold && n <= 4096) {
@@ -1802,8 +1803,8 @@ int launch_windowed_ssim(fnx_ctx *ctx, int n, const uint8_t *a, int astride, siz
         FNX_HIP(hipGetLastError());
     } else if (have) {
         WinArgs wa{};
-        wa.a = a; wa.b = b; wa.as = d_as; wa.bs = d_bs; wa.a_image_bytes = a_image_bytes; wa.b_image_bytes = b_image_bytes;
-        wa.astride = astride; wa.bstride = bstride; wa.w = w; wa.h = h; wa.window = d_window;
+        set_pairs(wa, im);
+        wa.window = d_window;
         wa.tiles_x = tiles_x; wa.tiles = tiles; wa.partial = static_cast<double *>(part);
         note_route(ctx, FNX_PROF_SSIM, "windowed_ssim_kernel");
         hipLaunchKernelGGL(windowed_ssim_kernel, dim3(tiles, n), dim3(256), 0, ctx->stream, wa);
@@ -1811,7 +1812,7 @@ int launch_windowed_ssim(fnx_ctx *ctx, int n, const uint8_t *a, int astride, siz
     }
     const double count = have ? static_cast<double>(ww) * static_cast<double>(wh) : 0.0;
     if (defer) {
-        defer->item[defer->count++] = {defer->used, tiles, count, defer_out_index};
+        defer->item[defer->count++] = {defer->used, tiles, count, opt.defer_index};
         defer->used += static_cast<size_t>(tiles) + 2;
         return FNX_OK;
     }
