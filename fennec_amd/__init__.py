@@ -164,6 +164,12 @@ def load_library() -> C.CDLL:
         _sig(L, "fnx_resize_v", i, [ctx, i] + img + [i, i, _i32p, _i32p, _f64p] + img + [i])
         _sig(L, "fnx_lanczos_resize", i, [ctx, i] + img + [i, i, _i32p, _i32p, _f64p, _i32p, _i32p, _f64p] + img + [i, i])
         _sig(L, "fnx_box_downsample", i, [ctx, i] + img + [i, i] + img + [i, i])
+        tabs = [_i32p, _i32p, _f64p, _i32p, _i32p, _f64p]   # offH, idxH, wH, offV, idxV, wV
+        _sig(L, "fnx_lanczos_box_downsample", i, [ctx, i] + img + [i, i] + tabs + [i, i] + img + [i, i])
+        _sig(L, "fnx_lanczos_box_fused", i, [i, i] + tabs + [i, i, i, i])
+        _sig(L, "fnx_ssim_fast_resized", i, [ctx, i] + img + [i, i] + img + [i, i] + tabs + [_f64p, _f64p])
+        _sig(L, "fnx_ssim_resized", i, [ctx, i] + img + [i, i] + img + [i, i] + tabs + [_f64p, _f64p])
+        _sig(L, "fnx_msssim_resized", i, [ctx, i] + img + [i, i] + img + [i, i] + tabs + [_f64p, _f64p, _f64p])
         _sig(L, "fnx_ssim_fast", i, [ctx, i] + img + img + [i, i, _f64p, _f64p])
         _sig(L, "fnx_ssim", i, [ctx, i] + img + img + [i, i, _f64p, _f64p])
         _sig(L, "fnx_pixel_ssim", i, [ctx, i, _u8p, C.c_size_t, _u8p, C.c_size_t, i, i, _f64p])
@@ -247,6 +253,7 @@ def load_library() -> C.CDLL:
         _sig(L, "fennec_SSIM", i, [ctx, i] + img + [i, i] + img + [i, i, _f64p])
         _sig(L, "fennec_SSIMFast", i, [ctx, i] + img + img + [i, i, _f64p])
         _sig(L, "fennec_MSSSIM", i, [ctx, i] + img + [i, i] + img + [i, i, _f64p])
+        _sig(L, "fennec_computeSSIMNRGBA", i, [ctx, i] + img + [i, i] + img + [i, i, _f64p])
         _sig(L, "fennec_GaussianBlur", i, [ctx, i] + img + [i, i, d] + img)
         _sig(L, "fennec_Sharpen", i, [ctx, i] + img + [i, i, d] + img)
         _sig(L, "fennec_AdaptiveSharpen", i, [ctx, i] + img + [i, i, d] + img)
@@ -627,6 +634,79 @@ class Context:
             self._chk(self._lib.fennec_MSSSIM(self._h, a.space, a.ptr, a.stride, a.w, a.h, b.ptr, b.stride,
                                               b.w, b.h, C.byref(out)), "MSSSIM")
         return out.value
+
+    def computeSSIMNRGBA(self, img1, img2) -> float:
+        """targetsize.go:563 -- SSIMFast(img1, lanczosResize(img2, img1's dims)).  img2 goes to the device at its own size;
+        under set_form("resize_box", 1), where SSIMFast downsamples (img1 above 512 px) and img2 is the smaller image, the resized
+        image is never stored."""
+        a, b = self._pair(img1, img2)
+        out = C.c_double()
+        with self._ordered(img1, img2):
+            self._chk(self._lib.fennec_computeSSIMNRGBA(self._h, a.space, a.ptr, a.stride, a.w, a.h, b.ptr, b.stride,
+                                                        b.w, b.h, C.byref(out)), "computeSSIMNRGBA")
+        return out.value
+
+    def _resized_args(self, a, b, tables):
+        """(keep-alive arrays, the six table pointers) of a *_resized call: `tables` = (table_h, table_v) as precomputeWeights
+        returns them (b.w -> a.w, b.h -> a.h), None: computed here; NULL pointers when the dims are equal."""
+        if tables is None:
+            if (a.w, a.h) == (b.w, b.h) or min(a.w, a.h, b.w, b.h) <= 0:
+                return [], [None] * 6
+            tables = (self.precomputeWeights(a.w, b.w), self.precomputeWeights(a.h, b.h))
+        keep, ptrs = [], []
+        for off, idx, wt in tables:
+            for arr, conv in ((off, _i32), (idx, _i32), (wt, _f64)):
+                if arr is None:
+                    ptrs.append(None)
+                    continue
+                k, ptr = conv(arr)
+                keep.append(k)
+                ptrs.append(ptr)
+        return keep, ptrs
+
+    def _scored_resized(self, name, img1, img2, tables, window, levels=False):
+        a, b = self._pair(img1, img2)
+        keep, t = self._resized_args(a, b, tables)
+        k, pk = _f64(self.gaussianKernel() if window is None else window)
+        out = C.c_double()
+        extra = []
+        if levels:
+            lv = np.empty(5, dtype=np.float64)
+            extra = [lv.ctypes.data_as(_f64p)]
+        with self._ordered(img1, img2):
+            self._chk(getattr(self._lib, name)(self._h, a.space, a.ptr, a.stride, a.w, a.h, b.ptr, b.stride, b.w, b.h, *t, pk,
+                                               C.byref(out), *extra), name)
+        return (out.value, lv) if levels else out.value
+
+    def ssim_fast_resized(self, img1, img2, tables=None, window=None) -> float:
+        """fnx_ssim_fast_resized: computeSSIMNRGBA with the CALLER's tap tables ((table_h, table_v), None: precomputeWeights')."""
+        return self._scored_resized("fnx_ssim_fast_resized", img1, img2, tables, window)
+
+    def ssim_resized(self, img1, img2, tables=None, window=None) -> float:
+        """fnx_ssim_resized: SSIM (ssim.go:24) of differently sized images with the caller's tap tables."""
+        return self._scored_resized("fnx_ssim_resized", img1, img2, tables, window)
+
+    def msssim_resized(self, img1, img2, tables=None, window=None):
+        """fnx_msssim_resized: MSSSIM (ssim.go:313) of differently sized images -> (value, the five per-level values)."""
+        return self._scored_resized("fnx_msssim_resized", img1, img2, tables, window, levels=True)
+
+    def lanczosBoxDownsample(self, img, midW: int, midH: int, dstW: int, dstH: int, to_host: bool = False, tables=None):
+        """boxDownsample(lanczosResize(img, midW, midH), dstW, dstH) (resize.go:37, ssim.go:244) in one call
+        (fnx_lanczos_box_downsample): under set_form("resize_box", 1), where the fused kernel applies, the midW x midH image is
+        never stored.
+        to_host: see boxDownsample."""
+        s = _Img(img)
+        if min(s.w, s.h, midW, midH, dstW, dstH) <= 0:
+            return self._out_for(s, 0, 0, to_host)[1]
+        if tables is None and (s.w, s.h) != (midW, midH):
+            tables = (self.precomputeWeights(midW, s.w), self.precomputeWeights(midH, s.h))
+        keep, t = self._resized_args(s, s, tables)
+        space, dst = self._out_for(s, dstW, dstH, to_host)
+        d = _Img(dst)
+        with self._ordered(img, dst):
+            self._chk(self._lib.fnx_lanczos_box_downsample(self._h, space, s.ptr, s.stride, s.w, s.h, *t, midW, midH,
+                                                           d.ptr, d.stride, dstW, dstH), "fnx_lanczos_box_downsample")
+        return dst
 
     def msssim_levels(self, img1, img2, window=None):
         """fnx_msssim with per-level SSIMFast values (equal dims)."""
@@ -1467,6 +1547,7 @@ def _dev_of(x):
 def SSIM(img1, img2): return default_context(_dev_of(img1)).SSIM(img1, img2)
 def SSIMFast(img1, img2): return default_context(_dev_of(img1)).SSIMFast(img1, img2)
 def MSSSIM(img1, img2): return default_context(_dev_of(img1)).MSSSIM(img1, img2)
+def computeSSIMNRGBA(img1, img2): return default_context(_dev_of(img1)).computeSSIMNRGBA(img1, img2)
 def GaussianBlur(img, sigma): return default_context(_dev_of(img)).GaussianBlur(img, sigma, exact=None)
 def Sharpen(img, strength): return default_context(_dev_of(img)).Sharpen(img, strength)
 def AdaptiveSharpen(img, strength): return default_context(_dev_of(img)).AdaptiveSharpen(img, strength)
@@ -1474,6 +1555,7 @@ def ApplyOrientation(img, orient): return default_context(_dev_of(img)).ApplyOri
 def lanczosResize(img, dstW, dstH): return default_context(_dev_of(img)).lanczosResize(img, dstW, dstH)
 def smartResize(img, maxW, maxH): return default_context(_dev_of(img)).smartResize(img, maxW, maxH)
 def boxDownsample(img, dstW, dstH): return default_context(_dev_of(img)).boxDownsample(img, dstW, dstH)
+def lanczosBoxDownsample(img, midW, midH, dstW, dstH): return default_context(_dev_of(img)).lanczosBoxDownsample(img, midW, midH, dstW, dstH)
 def Analyze(img): return default_context(_dev_of(img)).Analyze(img)
 
 
@@ -1481,6 +1563,15 @@ def gaussianKernel(size=8, sigma=1.5):
     k = np.empty(size * size, dtype=np.float64)
     load_library().fennec_gaussianKernel(size, sigma, k.ctypes.data_as(_f64p))
     return k
+
+
+def lanczos_box_fused(srcW, srcH, midW, midH, dstW, dstH, tables=None) -> bool:
+    """fnx_lanczos_box_fused: would boxDownsample(lanczosResize(srcW x srcH -> midW x midH), dstW, dstH) take resize_box_kernel?
+    tables = (table_h, table_v), None: precomputeWeights'.  Host arithmetic only."""
+    th, tv = tables if tables is not None else (precomputeWeights(midW, srcW), precomputeWeights(midH, srcH))
+    oh, poh = _i32(th[0]); ih, pih = _i32(th[1]); wh, pwh = _f64(th[2])
+    ov, pov = _i32(tv[0]); iv, piv = _i32(tv[1]); wv, pwv = _f64(tv[2])
+    return bool(load_library().fnx_lanczos_box_fused(srcW, srcH, poh, pih, pwh, pov, piv, pwv, midW, midH, dstW, dstH))
 
 
 def blur_fixed_point(kernel):

@@ -458,6 +458,152 @@ int lanczos_resize_tables_batch(fnx_ctx *ctx, int n, const uint8_t *const *srcs,
     return FNX_OK;
 }
 
+// boxDownsample(lanczosResize(src, midW, midH), dstW, dstH) of a device image: lanczosResize into `up_slot` and the box
+// kernel, or -- form "resize_box" "1", where it applies -- resize_box_kernel.  The fused kernel is not the default: it has
+// not been timed against the resize kernels + box kernel it would replace (fp64 reference-order arithmetic against fp32 /
+// matrix-pipe kernels plus a round trip of the image through memory)
+int lanczos_box_device(fnx_ctx *ctx, const uint8_t *src, int sstride, int srcW, int srcH, const TapTable &th, const TapTable &tv,
+                       int midW, int midH, uint8_t *dst, int dstride, int dstW, int dstH, Slot up_slot)
+{
+    const char *form = form_value(ctx, FORM_RESIZE_BOX);
+    if (form && form[0] == '1' && !(srcW == midW && srcH == midH)) {
+        const int rc = launch_resize_box(ctx, src, sstride, srcW, srcH, th, tv, midW, midH, dst, dstride, dstW, dstH);
+        if (rc < 0) return rc;
+        if (rc != FNX_NOOP) return FNX_OK;
+    }
+    void *up = nullptr;
+    FNX_TRY(scratch(ctx, up_slot, static_cast<size_t>(midW) * midH * 4 + 16, &up));
+    FNX_TRY(lanczos_resize_tables(ctx, FNX_DEVICE, src, sstride, srcW, srcH, th, tv, static_cast<uint8_t *>(up), midW * 4, midW, midH));
+    return launch_box_downsample(ctx, 1, static_cast<const uint8_t *>(up), nullptr, midW * 4, midW, midH, dst, dstride, 0, dstW, dstH);
+}
+
+// computeSSIMNRGBA's tail (targetsize.go:563-568) against a prepared `a`: where SSIMFast downsamples, only the box plane of
+// lanczosResize(b) is made (SLOT_TMP2, where against_device would put it); an `a` of at most 512 px is compared at full size
+int ssim_fast_resized_device(fnx_ctx *ctx, const fnx_prepared *ref, const uint8_t *b, int bstride, int bw, int bh,
+                             const TapTable &th, const TapTable &tv, const double *window, double *out)
+{
+    const int w = ref->w, h = ref->h, pw = ref->pw, ph = ref->ph;
+    if (bw == w && bh == h) return against_device(ctx, ref, b, bstride, window, out);
+    if (pw != w || ph != h) {
+        void *t = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_TMP2, static_cast<size_t>(pw) * ph * 4 + 16, &t));
+        FNX_TRY(lanczos_box_device(ctx, b, bstride, bw, bh, th, tv, w, h, static_cast<uint8_t *>(t), pw * 4, pw, ph, SLOT_TS_UP));
+        return against_device(ctx, ref, static_cast<const uint8_t *>(t), pw * 4, window, out, true);
+    }
+    void *up = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_TS_UP, static_cast<size_t>(w) * h * 4 + 16, &up));
+    FNX_TRY(lanczos_resize_tables(ctx, FNX_DEVICE, b, bstride, bw, bh, th, tv, static_cast<uint8_t *>(up), w * 4, w, h));
+    return against_device(ctx, ref, static_cast<const uint8_t *>(up), w * 4, window, out);
+}
+
+// What the *_resized entry points share before any work (ssim.go:31-33 with an empty side): *done = true with the call's
+// status when there is nothing left to do
+static int resized_guard(int space, int aw, int ah, int bw, int bh, const void *a, int astride, const void *b, int bstride,
+                         const TapTable &th, const TapTable &tv, const char *what, bool *empty_a)
+{
+    FNX_TRY(check_space(space));
+    *empty_a = aw <= 0 || ah <= 0;
+    if (*empty_a) return FNX_OK;
+    if (bw <= 0 || bh <= 0) {
+        // lanczosResize hands back a 0x0 image; pixelSSIM / the windows then index past it for a non-empty `a`
+        set_error("%s: second image is empty (the reference panics)", what);
+        return FNX_ERR_INVALID;
+    }
+    FNX_TRY(check_img(a, astride, aw, ah, "a"));
+    FNX_TRY(check_img(b, bstride, bw, bh, "b"));
+    FNX_REQUIRE(th.off && th.idx && th.wt && tv.off && tv.idx && tv.wt, "tap table is null");
+    return FNX_OK;
+}
+
+int resize_b_device(fnx_ctx *ctx, int space, const uint8_t *b, int bstride, int bw, int bh, const TapTable &th, const TapTable &tv,
+                           int w, int h, const uint8_t **out, int *ostride)
+{
+    void *d = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_TMP3, static_cast<size_t>(w) * h * 4 + 16, &d));
+    DevImg s;
+    FNX_TRY(stage_in(ctx, space, b, bstride, bw, bh, SLOT_IN_B, &s));
+    FNX_TRY(lanczos_resize_tables(ctx, FNX_DEVICE, s.p, s.stride, bw, bh, th, tv, static_cast<uint8_t *>(d), w * 4, w, h));
+    *out = static_cast<const uint8_t *>(d);
+    *ostride = w * 4;
+    return FNX_OK;
+}
+
+int ssim_resized_tables(fnx_ctx *ctx, int space, const uint8_t *a, int astride, int aw, int ah, const uint8_t *b, int bstride, int bw, int bh,
+                        const TapTable &th, const TapTable &tv, const double *window, double *out)
+{
+    if (aw == bw && ah == bh) return fnx_ssim(ctx, space, a, astride, b, bstride, aw, ah, window, out);
+    FNX_ENTER(ctx);
+    FNX_REQUIRE(window && out, "window/out is null");
+    bool empty_a;
+    FNX_TRY(resized_guard(space, aw, ah, bw, bh, a, astride, b, bstride, th, tv, "SSIM", &empty_a));
+    if (empty_a) { *out = 1.0; return FNX_OK; }     // pixelSSIM: n == 0 (ssim.go:172-175)
+    const uint8_t *rb;
+    int rbs;
+    FNX_TRY(resize_b_device(ctx, space, b, bstride, bw, bh, th, tv, aw, ah, &rb, &rbs));
+    DevImg da;
+    FNX_TRY(stage_in(ctx, space, a, astride, aw, ah, SLOT_IN_A, &da));
+    return fnx_ssim(ctx, FNX_DEVICE, da.p, da.stride, rb, rbs, aw, ah, window, out);
+}
+
+int msssim_resized_tables(fnx_ctx *ctx, int space, const uint8_t *a, int astride, int aw, int ah, const uint8_t *b, int bstride, int bw, int bh,
+                          const TapTable &th, const TapTable &tv, const double *window, double *out, double *per_level)
+{
+    if (aw == bw && ah == bh) return fnx_msssim(ctx, space, a, astride, b, bstride, aw, ah, window, out, per_level);
+    FNX_ENTER(ctx);
+    FNX_REQUIRE(window && out, "window/out is null");
+    bool empty_a;
+    FNX_TRY(resized_guard(space, aw, ah, bw, bh, a, astride, b, bstride, th, tv, "MSSSIM", &empty_a));
+    if (empty_a) return fnx_msssim(ctx, space, a, astride, a, astride, aw, ah, window, out, per_level);
+    const uint8_t *rb;
+    int rbs;
+    FNX_TRY(resize_b_device(ctx, space, b, bstride, bw, bh, th, tv, aw, ah, &rb, &rbs));
+    DevImg da;
+    FNX_TRY(stage_in_front(ctx, space, a, aw, ah, SLOT_IN_A, &da));      // toNRGBA(a): the flat front of a.Pix (ssim.go:345)
+    return fnx_msssim(ctx, FNX_DEVICE, da.p, da.stride, rb, rbs, aw, ah, window, out, per_level);
+}
+
+int ssim_fast_resized_tables(fnx_ctx *ctx, int space, const uint8_t *a, int astride, int aw, int ah, const uint8_t *b, int bstride, int bw,
+                             int bh, const TapTable &th, const TapTable &tv, const double *window, double *out)
+{
+    if (aw == bw && ah == bh) return fnx_ssim_fast(ctx, space, a, astride, b, bstride, aw, ah, window, out);
+    FNX_ENTER(ctx);
+    FNX_REQUIRE(window && out, "window/out is null");
+    bool empty_a;
+    FNX_TRY(resized_guard(space, aw, ah, bw, bh, a, astride, b, bstride, th, tv, "computeSSIMNRGBA", &empty_a));
+    if (empty_a) { *out = 1.0; return FNX_OK; }
+    // pixelSSIM walks a's flat Pix slice and indexes the resized b (a fresh tight image) with it (ssim.go:178)
+    FNX_REQUIRE((aw >= 8 && ah >= 8) || astride == aw * 4, "a under 8 px must be tight (the reference indexes past the resized image)");
+    DevImg da, db;
+    FNX_TRY(stage_in(ctx, space, a, astride, aw, ah, SLOT_IN_A, &da));
+    FNX_TRY(stage_in(ctx, space, b, bstride, bw, bh, SLOT_IN_B, &db));
+    fnx_prepared ref;
+    ref.w = aw;
+    ref.h = ah;
+    ssim_fast_dims(aw, ah, &ref.pw, &ref.ph);
+    void *rp = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_TMP1, static_cast<size_t>(ref.pw) * ref.ph * 4 + 16, &rp));
+    ref.pix = static_cast<uint8_t *>(rp);
+    FNX_TRY(prepared_plane(ctx, da.p, da.stride, ref));
+    return ssim_fast_resized_device(ctx, &ref, db.p, db.stride, bw, bh, th, tv, window, out);
+}
+
+int lanczos_box_tables(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int srcW, int srcH, const TapTable &th, const TapTable &tv,
+                       int midW, int midH, uint8_t *dst, int dstride, int dstW, int dstH)
+{
+    FNX_ENTER(ctx);
+    FNX_TRY(check_space_io(space));
+    if (srcW <= 0 || srcH <= 0 || midW <= 0 || midH <= 0 || dstW <= 0 || dstH <= 0) return FNX_EMPTY;   // resize.go:41-43, ssim.go:246-248
+    FNX_TRY(check_img(src, sstride, srcW, srcH, "src"));
+    FNX_TRY(check_img(dst, dstride, dstW, dstH, "dst"));
+    FNX_REQUIRE((srcW == midW && srcH == midH) || (th.off && th.idx && th.wt && tv.off && tv.idx && tv.wt), "tap table is null");
+    DevImg s;
+    DevOut d;
+    FNX_TRY(stage_in(ctx, space, src, sstride, srcW, srcH, SLOT_IN_A, &s));
+    FNX_TRY(stage_out(ctx, space, dst, dstride, dstW, dstH, SLOT_OUT, &d));
+    FNX_TRY(lanczos_box_device(ctx, s.p, s.stride, srcW, srcH, th, tv, midW, midH, d.p, d.stride, dstW, dstH, SLOT_TS_UP));
+    return finish(ctx, space, &d);
+}
+
 }  // namespace fnx
 
 extern "C" {
@@ -1153,6 +1299,47 @@ int fnx_msssim_batch_enqueue(fnx_ctx *ctx, int n, const uint8_t *const *as, int 
     if (n == 0) return FNX_OK;
     FNX_TRY(check_batch_images(n, {as, astride, w, h, "a"}, {bs, bstride, w, h, "b"}));
     return msssim_enqueue_body(ctx, n, as, bs, w, h, window);
+}
+
+// ---- resize, then score (ssim.go:31-33, 320-322; targetsize.go:563-568): b goes up at its own size, nothing comes down ----
+int fnx_lanczos_box_downsample(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int srcW, int srcH,
+                               const int32_t *offH, const int32_t *idxH, const double *wH,
+                               const int32_t *offV, const int32_t *idxV, const double *wV,
+                               int midW, int midH, uint8_t *dst, int dstride, int dstW, int dstH)
+{
+    const TapTable th{offH, idxH, wH, midW, 0}, tv{offV, idxV, wV, midH, 0};
+    return fnx::lanczos_box_tables(ctx, space, src, sstride, srcW, srcH, th, tv, midW, midH, dst, dstride, dstW, dstH);
+}
+
+int fnx_lanczos_box_fused(int srcW, int srcH, const int32_t *offH, const int32_t *idxH, const double *wH,
+                          const int32_t *offV, const int32_t *idxV, const double *wV, int midW, int midH, int dstW, int dstH)
+{
+    const TapTable th{offH, idxH, wH, midW, 0}, tv{offV, idxV, wV, midH, 0};
+    return fnx::resize_box_covers(th, tv, srcW, srcH, midW, midH, dstW, dstH) ? 1 : 0;
+}
+
+int fnx_ssim_fast_resized(fnx_ctx *ctx, int space, const uint8_t *a, int astride, int aw, int ah, const uint8_t *b, int bstride, int bw, int bh,
+                          const int32_t *offH, const int32_t *idxH, const double *wH,
+                          const int32_t *offV, const int32_t *idxV, const double *wV, const double *window, double *out)
+{
+    const TapTable th{offH, idxH, wH, aw, 0}, tv{offV, idxV, wV, ah, 0};
+    return fnx::ssim_fast_resized_tables(ctx, space, a, astride, aw, ah, b, bstride, bw, bh, th, tv, window, out);
+}
+
+int fnx_ssim_resized(fnx_ctx *ctx, int space, const uint8_t *a, int astride, int aw, int ah, const uint8_t *b, int bstride, int bw, int bh,
+                     const int32_t *offH, const int32_t *idxH, const double *wH,
+                     const int32_t *offV, const int32_t *idxV, const double *wV, const double *window, double *out)
+{
+    const TapTable th{offH, idxH, wH, aw, 0}, tv{offV, idxV, wV, ah, 0};
+    return fnx::ssim_resized_tables(ctx, space, a, astride, aw, ah, b, bstride, bw, bh, th, tv, window, out);
+}
+
+int fnx_msssim_resized(fnx_ctx *ctx, int space, const uint8_t *a, int astride, int aw, int ah, const uint8_t *b, int bstride, int bw, int bh,
+                       const int32_t *offH, const int32_t *idxH, const double *wH,
+                       const int32_t *offV, const int32_t *idxV, const double *wV, const double *window, double *out, double *per_level)
+{
+    const TapTable th{offH, idxH, wH, aw, 0}, tv{offV, idxV, wV, ah, 0};
+    return fnx::msssim_resized_tables(ctx, space, a, astride, aw, ah, b, bstride, bw, bh, th, tv, window, out, per_level);
 }
 
 // ---- prepared reference ------------------------------------------------------------------

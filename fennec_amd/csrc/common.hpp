@@ -42,6 +42,7 @@ enum Form {
     FORM_MSSSIM_FOLD,        // "msssim_fold":     "0" = a finish launch instead of the fold in the window kernel
     FORM_MSSSIM_BOXFLY,      // "msssim_boxfly":   "1" = levels 1..4's boxes taken on the fly
     FORM_PALETTE_GRID,       // "palette_grid":    "0" every image walks the whole palette / "1" every image takes the grid
+    FORM_RESIZE_BOX,         // "resize_box":      "1" = resize_box_kernel where its domain allows (default: the resize kernels, then the box kernel)
     FORM_COUNT
 };
 
@@ -104,6 +105,7 @@ enum Slot {
     SLOT_AN_HASH0, SLOT_AN_HASH1,   // analyze.hip: the colour-set tables of this call and the next (the launch that uses one zeroes the other)
     SLOT_TS_SCALED, SLOT_TS_UP,    // jpeg_api.cpp: fnx_jpeg_target_size's Lanczos-scaled image and its upscale back to the source's size
     SLOT_JPEG_QTAB, SLOT_JPEG_JOBS,  // fnx_jpeg_compress_batch: the quantiser tables of qualities 1..100, a search step's job list
+    SLOT_RZBOX_TABLES, SLOT_RZBOX_SUMS,   // resize_box.hip: both tap tables + the box maps, the image-wide integer box sums
     SLOT_DONE,       // workgroup counters of the kernels that finish their own reduction (ssim.hip), zero between launches
     SLOT_COUNT
 };
@@ -427,6 +429,35 @@ int lanczos_resize_tables(fnx_ctx *ctx, int space, const uint8_t *src, int sstri
                           const TapTable &th, const TapTable &tv, uint8_t *dst, int dstride, int dstW, int dstH);
 int lanczos_resize_tables_batch(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstride, int srcW, int srcH,
                                 const TapTable &th, const TapTable &tv, uint8_t *const *dsts, int dstride, int dstW, int dstH);
+// resize_box.hip: dst = boxDownsample(lanczosResize(src, midW, midH), dstW, dstH) in one pass, the midW x midH image never
+// stored (device pointers); FNX_NOOP (nothing launched) for pairs outside the kernel's domain (see there)
+int launch_resize_box(fnx_ctx *ctx, const uint8_t *src, int sstride, int srcW, int srcH, const TapTable &th, const TapTable &tv,
+                      int midW, int midH, uint8_t *dst, int dstride, int dstW, int dstH);
+bool resize_box_covers(const TapTable &th, const TapTable &tv, int srcW, int srcH, int midW, int midH, int dstW, int dstH,
+                       std::vector<int32_t> *map = nullptr, int *maxbw = nullptr);
+// the same for a device image: lanczosResize into `up_slot` and the box kernel, or the fused kernel where it applies and
+// the ctx asks for it ("resize_box" "1")
+int lanczos_box_device(fnx_ctx *ctx, const uint8_t *src, int sstride, int srcW, int srcH, const TapTable &th, const TapTable &tv,
+                       int midW, int midH, uint8_t *dst, int dstride, int dstW, int dstH, Slot up_slot);
+// computeSSIMNRGBA's tail (targetsize.go:563-568): SSIMFast(prepared reference, lanczosResize(b -> ref's dims)), b on the device
+int ssim_fast_resized_device(fnx_ctx *ctx, const fnx_prepared *ref, const uint8_t *b, int bstride, int bw, int bh,
+                             const TapTable &th, const TapTable &tv, const double *window, double *out);
+// b (bw x bh in `space`) staged at its own size (SLOT_IN_B) and resized to w x h on the device into SLOT_TMP3 (ssim.go:31-33, 320-322)
+int resize_b_device(fnx_ctx *ctx, int space, const uint8_t *b, int bstride, int bw, int bh, const TapTable &th, const TapTable &tv,
+                    int w, int h, const uint8_t **out, int *ostride);
+// the same with the tables of host_api.cpp's cache (make_taps), as fennec_lanczosResize takes them
+int ssim_fast_resized_prepared(fnx_ctx *ctx, const fnx_prepared *ref, const uint8_t *b, int bstride, int bw, int bh,
+                               const double *window, double *out);
+// the bodies of fnx_ssim_fast_resized / fnx_ssim_resized / fnx_msssim_resized / fnx_lanczos_box_downsample: images in `space`,
+// both tables given (an id != 0 keeps the plan look-up by id)
+int ssim_fast_resized_tables(fnx_ctx *ctx, int space, const uint8_t *a, int astride, int aw, int ah, const uint8_t *b, int bstride, int bw,
+                             int bh, const TapTable &th, const TapTable &tv, const double *window, double *out);
+int ssim_resized_tables(fnx_ctx *ctx, int space, const uint8_t *a, int astride, int aw, int ah, const uint8_t *b, int bstride, int bw, int bh,
+                        const TapTable &th, const TapTable &tv, const double *window, double *out);
+int msssim_resized_tables(fnx_ctx *ctx, int space, const uint8_t *a, int astride, int aw, int ah, const uint8_t *b, int bstride, int bw, int bh,
+                          const TapTable &th, const TapTable &tv, const double *window, double *out, double *per_level);
+int lanczos_box_tables(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int srcW, int srcH, const TapTable &th, const TapTable &tv,
+                       int midW, int midH, uint8_t *dst, int dstride, int dstW, int dstH);
 // contig_taps: resize_contiguous_taps() of the (host) H table -- most taps of any output when every
 // output's tap indices are consecutive, else 0
 int launch_resize_h(fnx_ctx *ctx, const uint8_t *src, int sstride, int srcW, int srcH,

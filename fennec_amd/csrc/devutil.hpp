@@ -122,6 +122,16 @@ __device__ __forceinline__ double u8_to_f64(uint32_t v)
     return __hiloint2double(0x43300000, static_cast<int>(v)) - 4503599627370496.0;
 }
 
+// one tap of a resize pass (resize.hip, resize_box.hip): aw = sa*w; r += R*aw; g += G*aw; b += B*aw; a += aw   (resize.go:95-103)
+__device__ __forceinline__ void resize_tap(uint32_t p, double w, double &r, double &g, double &b, double &al)
+{
+    const double aw = u8_to_f64(p >> 24) * w;
+    r += u8_to_f64(p & 0xffu) * aw;
+    g += u8_to_f64((p >> 8) & 0xffu) * aw;
+    b += u8_to_f64((p >> 16) & 0xffu) * aw;
+    al += aw;
+}
+
 // sum over a 256-lane workgroup, result valid in thread 0 (s_red: 4 doubles of LDS)
 __device__ __forceinline__ double block_sum_256(double v, double *s_red)
 {

@@ -72,32 +72,27 @@ const double *ssim_window()
     return k.data();
 }
 
-// b resized to a's dims on the device when dims differ (ssim.go:31-33, 320-322).
-// Returns device pointer/stride of the image to compare against.
+// b resized to a's dims on the device (ssim.go:31-33, 320-322) with the cache's tables: resize_b_device
 int resize_b_to(fnx_ctx *ctx, int space, const uint8_t *b, int bstride, int bw, int bh, int w, int h,
                 const uint8_t **out, int *ostride)
 {
     const auto pth = make_taps(w, bw), ptv = make_taps(h, bh);
-    const Taps &th = *pth, &tv = *ptv;
-    void *d = nullptr;
-    FNX_TRY(scratch(ctx, SLOT_TMP3, static_cast<size_t>(w) * h * 4 + 16, &d));
-    const uint8_t *src = b;
-    int sstride = bstride;
-    if (space == FNX_HOST) {   // stage b ourselves; the resize then runs device -> device
-        DevImg s;
-        FNX_TRY(stage_in(ctx, FNX_HOST, b, bstride, bw, bh, SLOT_IN_B, &s));
-        src = s.p;
-        sstride = s.stride;
-    }
-    int rc = lanczos_resize_tables(ctx, FNX_DEVICE, src, sstride, bw, bh, th.table(w), tv.table(h),
-                                   static_cast<uint8_t *>(d), w * 4, w, h);
-    if (rc < 0) return rc;
-    *out = static_cast<const uint8_t *>(d);
-    *ostride = w * 4;
-    return FNX_OK;
+    return resize_b_device(ctx, space, b, bstride, bw, bh, pth->table(w), ptv->table(h), w, h, out, ostride);
 }
 
 }  // namespace
+
+namespace fnx {
+
+int ssim_fast_resized_prepared(fnx_ctx *ctx, const fnx_prepared *ref, const uint8_t *b, int bstride, int bw, int bh,
+                               const double *window, double *out)
+{
+    if (bw == ref->w && bh == ref->h) return ssim_fast_resized_device(ctx, ref, b, bstride, bw, bh, TapTable{}, TapTable{}, window, out);
+    const auto pth = make_taps(ref->w, bw), ptv = make_taps(ref->h, bh);
+    return ssim_fast_resized_device(ctx, ref, b, bstride, bw, bh, pth->table(ref->w), ptv->table(ref->h), window, out);
+}
+
+}  // namespace fnx
 
 extern "C" {
 
@@ -212,26 +207,10 @@ int fennec_ssimFastDims(int w, int h, int *newW, int *newH)
 int fennec_SSIM(fnx_ctx *ctx, int space, const uint8_t *a, int astride, int aw, int ah,
                 const uint8_t *b, int bstride, int bw, int bh, double *out)
 {
-    if (aw == bw && ah == bh) return fnx_ssim(ctx, space, a, astride, b, bstride, aw, ah, ssim_window(), out);
-    FNX_ENTER(ctx);
-    if (space != FNX_HOST && space != FNX_DEVICE) {
-        set_error("invalid argument: space must be FNX_HOST or FNX_DEVICE");
-        return FNX_ERR_INVALID;
-    }
-    if (aw <= 0 || ah <= 0 || bw <= 0 || bh <= 0) {
-        // lanczosResize hands back a 0x0 image; pixelSSIM then indexes past it for a non-empty
-        // `a` (the reference panics) or returns 1.0 for an empty `a`.
-        if (aw <= 0 || ah <= 0) { *out = 1.0; return FNX_OK; }
-        set_error("SSIM: second image is empty (the reference panics)");
-        return FNX_ERR_INVALID;
-    }
-    const uint8_t *rb;
-    int rbs;
-    FNX_TRY(resize_b_to(ctx, space, b, bstride, bw, bh, aw, ah, &rb, &rbs));
-    if (space == FNX_DEVICE) return fnx_ssim(ctx, FNX_DEVICE, a, astride, rb, rbs, aw, ah, ssim_window(), out);
-    DevImg da;
-    FNX_TRY(stage_in(ctx, FNX_HOST, a, astride, aw, ah, SLOT_IN_A, &da));
-    return fnx_ssim(ctx, FNX_DEVICE, da.p, da.stride, rb, rbs, aw, ah, ssim_window(), out);
+    if ((aw == bw && ah == bh) || aw <= 0 || ah <= 0 || bw <= 0 || bh <= 0)     // no resize: no tables
+        return ssim_resized_tables(ctx, space, a, astride, aw, ah, b, bstride, bw, bh, TapTable{}, TapTable{}, ssim_window(), out);
+    const auto pth = make_taps(aw, bw), ptv = make_taps(ah, bh);
+    return ssim_resized_tables(ctx, space, a, astride, aw, ah, b, bstride, bw, bh, pth->table(aw), ptv->table(ah), ssim_window(), out);
 }
 
 int fennec_SSIMFast(fnx_ctx *ctx, int space, const uint8_t *a, int astride, const uint8_t *b,
@@ -243,26 +222,20 @@ int fennec_SSIMFast(fnx_ctx *ctx, int space, const uint8_t *a, int astride, cons
 int fennec_MSSSIM(fnx_ctx *ctx, int space, const uint8_t *a, int astride, int aw, int ah,
                   const uint8_t *b, int bstride, int bw, int bh, double *out)
 {
-    if (aw == bw && ah == bh)
-        return fnx_msssim(ctx, space, a, astride, b, bstride, aw, ah, ssim_window(), out, nullptr);
-    FNX_ENTER(ctx);
-    if (space != FNX_HOST && space != FNX_DEVICE) {
-        set_error("invalid argument: space must be FNX_HOST or FNX_DEVICE");
-        return FNX_ERR_INVALID;
-    }
-    if (aw <= 0 || ah <= 0 || bw <= 0 || bh <= 0) {
-        if (aw <= 0 || ah <= 0) return fnx_msssim(ctx, space, a, astride, a, astride, aw, ah, ssim_window(), out, nullptr);
-        set_error("MSSSIM: second image is empty (the reference panics)");
-        return FNX_ERR_INVALID;
-    }
-    const uint8_t *rb;
-    int rbs;
-    FNX_TRY(resize_b_to(ctx, space, b, bstride, bw, bh, aw, ah, &rb, &rbs));
-    if (space == FNX_DEVICE)
-        return fnx_msssim(ctx, FNX_DEVICE, a, astride, rb, rbs, aw, ah, ssim_window(), out, nullptr);
-    DevImg da;
-    FNX_TRY(stage_in_front(ctx, FNX_HOST, a, aw, ah, SLOT_IN_A, &da));      // toNRGBA(a): the flat front of a.Pix (ssim.go:345)
-    return fnx_msssim(ctx, FNX_DEVICE, da.p, da.stride, rb, rbs, aw, ah, ssim_window(), out, nullptr);
+    if ((aw == bw && ah == bh) || aw <= 0 || ah <= 0 || bw <= 0 || bh <= 0)
+        return msssim_resized_tables(ctx, space, a, astride, aw, ah, b, bstride, bw, bh, TapTable{}, TapTable{}, ssim_window(), out, nullptr);
+    const auto pth = make_taps(aw, bw), ptv = make_taps(ah, bh);
+    return msssim_resized_tables(ctx, space, a, astride, aw, ah, b, bstride, bw, bh, pth->table(aw), ptv->table(ah), ssim_window(), out, nullptr);
+}
+
+// computeSSIMNRGBA (targetsize.go:563-568)
+int fennec_computeSSIMNRGBA(fnx_ctx *ctx, int space, const uint8_t *a, int astride, int aw, int ah,
+                            const uint8_t *b, int bstride, int bw, int bh, double *out)
+{
+    if ((aw == bw && ah == bh) || aw <= 0 || ah <= 0 || bw <= 0 || bh <= 0)
+        return ssim_fast_resized_tables(ctx, space, a, astride, aw, ah, b, bstride, bw, bh, TapTable{}, TapTable{}, ssim_window(), out);
+    const auto pth = make_taps(aw, bw), ptv = make_taps(ah, bh);
+    return ssim_fast_resized_tables(ctx, space, a, astride, aw, ah, b, bstride, bw, bh, pth->table(aw), ptv->table(ah), ssim_window(), out);
 }
 
 int fennec_MSSSIM_enqueue(fnx_ctx *ctx, const uint8_t *a, int astride, int aw, int ah, const uint8_t *b, int bstride,

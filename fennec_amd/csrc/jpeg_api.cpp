@@ -524,8 +524,9 @@ int fnx_jpeg_encode_scaled(fnx_ctx *ctx, int space, const uint8_t *src, int sstr
 // The source is staged once; every scale step's planes come from jpeg_box_ycc_kernel and only its file sizes (8 bytes
 // a query) come back.  Slots: the source SLOT_IN_A, its planes SLOT_JPEG0, a scale step's planes SLOT_JPEG1, strategy 1's
 // decoded winner SLOT_JPEG2, the prepared SSIMFast side of the source SLOT_JPEG3, the Lanczos-scaled image SLOT_TS_SCALED
-// and its upscale for computeSSIMNRGBA SLOT_TS_UP.  At most one scaled candidate exists per call (strategy 4 runs only
-// when strategy 3 found none), so SLOT_TS_SCALED still holds the winner's image at the end.
+// and -- unless the ctx runs resize_box_kernel ("resize_box" "1") -- its upscale for computeSSIMNRGBA SLOT_TS_UP.  At most one scaled
+// candidate exists per call (strategy 4 runs only when strategy 3 found none), so SLOT_TS_SCALED still holds the winner's
+// image at the end.
 namespace {
 
 constexpr int TS_MIN_QUALITY = 20;     // minJPEGQuality (targetsize.go:14)
@@ -560,14 +561,7 @@ struct TsRun {
     int ssim_against(const uint8_t *b, int bstride, int bw, int bh, double *out)
     {
         FNX_TRY(prepared());
-        if (bw != w || bh != h) {
-            void *up = nullptr;
-            FNX_TRY(scratch(ctx, SLOT_TS_UP, static_cast<size_t>(w) * h * 4 + 16, &up));
-            FNX_TRY(fennec_lanczosResize(ctx, FNX_DEVICE, b, bstride, bw, bh, static_cast<uint8_t *>(up), w * 4, w, h));
-            b = static_cast<const uint8_t *>(up);
-            bstride = w * 4;
-        }
-        return against_device(ctx, &ref, b, bstride, window, out);
+        return ssim_fast_resized_prepared(ctx, &ref, b, bstride, bw, bh, window, out);
     }
 
     // jpegQualitySearchFast(boxDownsample(src, dw, dh)) (targetsize.go:236, 260, 306): the scaled image never exists

@@ -24,16 +24,6 @@ struct ResizeArgs {
     const double *wt;
 };
 
-// one tap: aw = sa*w; r += R*aw; g += G*aw; b += B*aw; a += aw   (resize.go:95-103)
-__device__ __forceinline__ void resize_tap(uint32_t p, double w, double &r, double &g, double &b, double &al)
-{
-    const double aw = u8_to_f64(p >> 24) * w;
-    r += u8_to_f64(p & 0xffu) * aw;
-    g += u8_to_f64((p >> 8) & 0xffu) * aw;
-    b += u8_to_f64((p >> 16) & 0xffu) * aw;
-    al += aw;
-}
-
 template <bool VERT>
 __global__ __launch_bounds__(256) void resize_pass_kernel(ResizeArgs a)
 {

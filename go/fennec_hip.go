@@ -179,11 +179,54 @@ func pixelSSIMHIP(c *C.fnx_ctx, a, b *image.NRGBA, w, h int, out *C.double) C.in
 	return C.fnx_pixel_ssim(c, C.FNX_HOST, pix(a), C.size_t(len(a.Pix)), pix(b), C.size_t(len(b.Pix)), C.int(w), C.int(h), out)
 }
 
+// Which score resizedHIP asks for.
+const (
+	resizedSSIM = iota
+	resizedMSSSIM
+	resizedFast
+)
+
+// resizedHIP scores a against b Lanczos-resized to a's size (ssim.go:31-33, 320-322, targetsize.go:564-566) in ONE call:
+// b crosses the bus at its own size, is resized on the device with Go's own tables, and only the score comes back.
+// ok == false: nothing was computed (no device, a refused argument, an `a` the pixelSSIM branch takes) -- the caller
+// composes lanczosResize and the equal-dims call as before.
+func resizedHIP(kind int, a, b *image.NRGBA) (float64, bool) {
+	w, h := a.Bounds().Dx(), a.Bounds().Dy()
+	bw, bh := b.Bounds().Dx(), b.Bounds().Dy()
+	c := poolGetIf(w >= 8 && h >= 8 && bw > 0 && bh > 0)
+	if c == nil {
+		return 0, false
+	}
+	defer pool.put(c)
+	offH, idxH, wH := lanczosTable(w, bw)
+	offV, idxV, wV := lanczosTable(h, bh)
+	win := (*C.double)(unsafe.Pointer(&ssimWindow[0]))
+	var out C.double
+	var st C.int
+	switch kind {
+	case resizedSSIM:
+		st = C.fnx_ssim_resized(c, C.FNX_HOST, pix(a), C.int(a.Stride), C.int(w), C.int(h), pix(b), C.int(b.Stride), C.int(bw), C.int(bh),
+			&offH[0], &idxH[0], &wH[0], &offV[0], &idxV[0], &wV[0], win, &out)
+	case resizedMSSSIM:
+		st = C.fnx_msssim_resized(c, C.FNX_HOST, pix(a), C.int(a.Stride), C.int(w), C.int(h), pix(b), C.int(b.Stride), C.int(bw), C.int(bh),
+			&offH[0], &idxH[0], &wH[0], &offV[0], &idxV[0], &wV[0], win, &out, nil)
+	default:
+		st = C.fnx_ssim_fast_resized(c, C.FNX_HOST, pix(a), C.int(a.Stride), C.int(w), C.int(h), pix(b), C.int(b.Stride), C.int(bw), C.int(bh),
+			&offH[0], &idxH[0], &wH[0], &offV[0], &idxV[0], &wV[0], win, &out)
+	}
+	runtime.KeepAlive(a)
+	runtime.KeepAlive(b)
+	return float64(out), st == C.FNX_OK
+}
+
 // SSIM replaces ssim.go:24.
 func SSIM(img1, img2 image.Image) float64 {
 	a, b := toNRGBARef(img1), toNRGBARef(img2)
 	w, h := a.Bounds().Dx(), a.Bounds().Dy()
 	if w != b.Bounds().Dx() || h != b.Bounds().Dy() {
+		if v, ok := resizedHIP(resizedSSIM, a, b); ok { // ssim.go:31-33 and the score in one call
+			return v
+		}
 		b = lanczosResize(b, w, h) // ssim.go:31-33 (itself on the GPU)
 	}
 	if c := pool.get(); c != nil {
@@ -211,6 +254,9 @@ func MSSSIM(img1, img2 image.Image) float64 {
 	a, b := toNRGBARef(img1), toNRGBARef(img2)
 	w, h := a.Bounds().Dx(), a.Bounds().Dy()
 	if w != b.Bounds().Dx() || h != b.Bounds().Dy() {
+		if v, ok := resizedHIP(resizedMSSSIM, a, b); ok { // ssim.go:320-322 and the score in one call
+			return v
+		}
 		b = lanczosResize(b, w, h) // ssim.go:320-322
 	}
 	if c := pool.get(); c != nil {
@@ -226,6 +272,20 @@ func MSSSIM(img1, img2 image.Image) float64 {
 	}
 	fellBack("MSSSIM")
 	return msssimGo(a, b)
+}
+
+// computeSSIMNRGBA replaces targetsize.go:563: where the dims differ, the resize and SSIMFast are one call
+// (fnx_ssim_fast_resized): b crosses the bus at its own size and the resized image stays on the device.  When that call is not made or refused,
+// the reference's own body runs on the shadowed lanczosResize and SSIMFast, each of which counts its own fallback.
+func computeSSIMNRGBA(a, b *image.NRGBA) float64 {
+	w, h := a.Bounds().Dx(), a.Bounds().Dy()
+	if w != b.Bounds().Dx() || h != b.Bounds().Dy() {
+		if v, ok := resizedHIP(resizedFast, a, b); ok {
+			return v
+		}
+		b = lanczosResize(b, w, h)
+	}
+	return SSIMFast(a, b)
 }
 
 // boxDownsample replaces ssim.go:244.

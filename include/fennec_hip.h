@@ -173,6 +173,8 @@ int fnx_ctx_set_ssim_mode(fnx_ctx *ctx, int mode);
  *   "resize_fused" "0"     the two-pass resize kernels
  *   "msssim_levelwise" "1", "msssim_nofuse0" "1", "msssim_fold" "0", "msssim_boxfly" "1"   MSSSIM's launch structure
  *   "palette_grid" "0|1"   applyPalette: whole-palette walk for every image / the candidate grid for every image
+ *   "resize_box" "1"       fnx_lanczos_box_downsample, fnx_ssim_fast_resized, target-size mode: resize_box_kernel where its
+ *                          domain allows ("0" and the default: lanczosResize into scratch, then the box kernel)
  * value NULL: back to the default.  Unknown name or a value longer than 7 characters: FNX_ERR_INVALID.  No reference counterpart. */
 int fnx_ctx_set_form(fnx_ctx *ctx, const char *name, const char *value);
 
@@ -269,8 +271,8 @@ int fnx_ssim_fast(fnx_ctx *ctx, int space, const uint8_t *a, int astride, const 
  * the loop's last iteration reads it (and must then fit).  Divides by w*h like the reference; w*h == 0 -> 1.0. */
 int fnx_pixel_ssim(fnx_ctx *ctx, int space, const uint8_t *a_pix, size_t a_pix_len, const uint8_t *b_pix,
                    size_t b_pix_len, int w, int h, double *out);
-/* SSIM (ssim.go:24-43) for equal dims (the dims-differ resize is composed by
- * the caller, as fennec_SSIM does). */
+/* SSIM (ssim.go:24-43) for equal dims (differing dims: fnx_ssim_resized;
+ * fennec_SSIM routes both). */
 int fnx_ssim(fnx_ctx *ctx, int space, const uint8_t *a, int astride, const uint8_t *b,
              int bstride, int w, int h, const double *window, double *out);
 /* MSSSIM (ssim.go:313-365) for equal dims; per_level (NULL or 5 doubles)
@@ -278,6 +280,51 @@ int fnx_ssim(fnx_ctx *ctx, int space, const uint8_t *a, int astride, const uint8
  * toNRGBA copies the first 4*w*h flat bytes (convert.go:16, ssim.go:345) -- see the SubImage note at fnx_blur3x3. */
 int fnx_msssim(fnx_ctx *ctx, int space, const uint8_t *a, int astride, const uint8_t *b,
                int bstride, int w, int h, const double *window, double *out, double *per_level);
+
+/* ---- resize, then score: the pairs of steps the reference makes when two images differ in size ----
+ * Tables as fnx_lanczos_resize takes them: offH / idxH / wH for bw -> aw, offV / idxV / wV for bh -> ah; they may be NULL
+ * when the dims are equal (the call is then exactly the plain entry point's).  Guards as fennec_SSIM: an empty `a` scores
+ * 1.0, an empty `b` beside a non-empty `a` is FNX_ERR_INVALID (the reference panics), differing dims with a NULL table are
+ * FNX_ERR_INVALID.  All of them block and return a scalar, so they follow the other blocking forms' rules about the
+ * result FIFO.  In either space each image crosses PCIe once -- `a` at its size, `b` at ITS OWN size -- and nothing comes
+ * back but the score: the resized image lives and dies in the ctx's scratch memory. */
+/* boxDownsample(lanczosResize(src, midW, midH), dstW, dstH) (resize.go:37-53, then ssim.go:244-309), bit-exact.  On the
+ * fused route (form "resize_box" "1"; csrc/resize_box.hip: resize_box_kernel, reported by fnx_ctx_last_kernel(ctx, FNX_PROF_RESIZE)) the
+ * midW x midH image never exists in memory: a workgroup resizes a tile into registers and adds its bytes to integer box
+ * sums.  Fused domain: an upscale or equal size on both axes whose tables have contiguous tap indices and at most 8 taps
+ * per output (every precomputeWeights table for src <= mid), dst <= mid on both axes with boxes at most 32 px wide -- every
+ * pair target-size mode makes (b = int(aw s) x int(ah s), 0.05 <= s < 1, both dims >= 8, a's long side from 513 to beyond
+ * 8192 px).  Everything else -- a downscale on either axis, tables with gaps, dst above mid -- is composed from
+ * fnx_lanczos_resize into scratch and fnx_box_downsample, same bytes.  The fused route is OPT-IN, fnx_ctx_set_form(ctx,
+ * "resize_box", "1"): it has not been timed against the composed one (tools/time_ssim_resized.py is the script; no table
+ * is committed), so the default stays with the kernels target-size mode has run so far. */
+int fnx_lanczos_box_downsample(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int srcW, int srcH,
+                               const int32_t *offH, const int32_t *idxH, const double *wH,
+                               const int32_t *offV, const int32_t *idxV, const double *wV,
+                               int midW, int midH, uint8_t *dst, int dstride, int dstW, int dstH);
+/* Would fnx_lanczos_box_downsample take the fused route for these tables and dims under "resize_box" "1" (the domain above)?  1 / 0.  Host arithmetic
+ * only, no device, no ctx: what the library itself asks before every such call.  No reference counterpart. */
+int fnx_lanczos_box_fused(int srcW, int srcH, const int32_t *offH, const int32_t *idxH, const double *wH,
+                          const int32_t *offV, const int32_t *idxV, const double *wV, int midW, int midH, int dstW, int dstH);
+/* computeSSIMNRGBA(a, b) (targetsize.go:563-568): SSIMFast(a, lanczosResize(b, aw, ah)).  Where SSIMFast downsamples (a's
+ * long side above 512 px) only the box plane of the resized b is needed: fnx_lanczos_box_downsample's routes make it; a smaller `a`
+ * is compared against the whole resized image.  An `a` under 8 px (pixelSSIM) must be tight. */
+int fnx_ssim_fast_resized(fnx_ctx *ctx, int space, const uint8_t *a, int astride, int aw, int ah,
+                          const uint8_t *b, int bstride, int bw, int bh,
+                          const int32_t *offH, const int32_t *idxH, const double *wH,
+                          const int32_t *offV, const int32_t *idxV, const double *wV, const double *window, double *out);
+/* SSIM with differing dims (ssim.go:24-43, the resize of lines 31-33 included): b is resized on the device into scratch
+ * and scored there at full resolution. */
+int fnx_ssim_resized(fnx_ctx *ctx, int space, const uint8_t *a, int astride, int aw, int ah,
+                     const uint8_t *b, int bstride, int bw, int bh,
+                     const int32_t *offH, const int32_t *idxH, const double *wH,
+                     const int32_t *offV, const int32_t *idxV, const double *wV, const double *window, double *out);
+/* MSSSIM with differing dims (ssim.go:313-365, the resize of lines 320-322 included); per_level as fnx_msssim's. */
+int fnx_msssim_resized(fnx_ctx *ctx, int space, const uint8_t *a, int astride, int aw, int ah,
+                       const uint8_t *b, int bstride, int bw, int bh,
+                       const int32_t *offH, const int32_t *idxH, const double *wH,
+                       const int32_t *offV, const int32_t *idxV, const double *wV, const double *window, double *out,
+                       double *per_level);
 
 /* Binary-search form of SSIMFast (compress.go:45-74 calls SSIMFast(src, decoded)
  * with the same src every iteration): downsample + luminance of the reference
@@ -581,6 +628,9 @@ int fennec_SSIMFast(fnx_ctx *ctx, int space, const uint8_t *a, int astride, cons
                     int bstride, int w, int h, double *out);                      /* ssim.go:48 */
 int fennec_MSSSIM(fnx_ctx *ctx, int space, const uint8_t *a, int astride, int aw, int ah,
                   const uint8_t *b, int bstride, int bw, int bh, double *out);   /* ssim.go:313 */
+/* computeSSIMNRGBA (targetsize.go:563-568): fnx_ssim_fast_resized with precomputeWeights' tables and the 8 x 8 window. */
+int fennec_computeSSIMNRGBA(fnx_ctx *ctx, int space, const uint8_t *a, int astride, int aw, int ah,
+                            const uint8_t *b, int bstride, int bw, int bh, double *out);
 /* MSSSIM of a device-resident pair through the ctx's result FIFO (fnx_msssim_enqueue), img2 resized to img1's
  * dims first when they differ (ssim.go:320-322); fnx_results_fetch(ctx, 1, &v) returns the value. */
 int fennec_MSSSIM_enqueue(fnx_ctx *ctx, const uint8_t *a, int astride, int aw, int ah, const uint8_t *b, int bstride,
