@@ -40,6 +40,7 @@ LIB_PATH = os.environ.get("FENNEC_HIP_LIB") or os.path.join(_HERE, "libfennec_hi
 FNX_OK, FNX_NOOP, FNX_EMPTY = 0, 1, 2
 FNX_HOST, FNX_DEVICE, FNX_DEVICE_SRC = 0, 1, 2
 FNX_BLUR_FAST, FNX_BLUR_EXACT, FNX_BLUR_KEEP_BOX_SUMS = 0, 1, 2
+FNX_PNG_PALETTED, FNX_PNG_GRAY, FNX_PNG_NRGBA = 1, 2, 3      # fnx_png_reduce's kinds (compress.go:90-108)
 PROF_MAIN, PROF_SSIM, PROF_RESIZE, PROF_FX, PROF_JPEG = 1, 2, 4, 8, 16
 
 _u8p = C.c_void_p
@@ -244,6 +245,9 @@ def load_library() -> C.CDLL:
         _sig(L, "fnx_ycbcr_to_nrgba", i, [ctx, i, _u8p, i, _u8p, _u8p, i, i, i, i] + img)
         _sig(L, "fnx_ssim_fast_against_ycbcr", i, [ctx, C.c_void_p, i, _u8p, i, _u8p, _u8p, i, i, _f64p, _f64p])
         _sig(L, "fnx_apply_palette", i, [ctx, i] + img + [i, i, _u8p, i, _u8p, i, _u8p, i])
+        _sig(L, "fnx_png_reduce", i, [ctx, i] + img + [i, i, i, C.POINTER(i), _u8p, C.POINTER(i), _u8p, i])
+        _sig(L, "fennec_CompressFilePNGReduce", i, [ctx, _u8p, C.c_size_t, C.POINTER(FileOptions), C.POINTER(i), _u8p, C.POINTER(i), _u8p,
+                                                     C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i)])
         _sig(L, "fennec_gaussianKernel", None, [i, d, _f64p])
         _sig(L, "fennec_blurKernel", i, [d, _f64p])
         _sig(L, "fennec_lanczosKernel", d, [d])
@@ -1306,6 +1310,76 @@ class Context:
                       "applyPalette")
         return idx, q
 
+    def png_reduce(self, img, max_colors: int = 256, want_plane: bool = True, plane=None):
+        """compressPNG's decision and reduced image (compress.go:90-153; fnx_png_reduce) -> (kind, palette (n, 4) uint8, plane):
+        FNX_PNG_PALETTED with tryPalettize's palette (first-occurrence order) and index plane, FNX_PNG_GRAY with toGray's
+        plane, or FNX_PNG_NRGBA (plane None: the image is the image).  want_plane=False: classify only.  plane: an (h, >= w)
+        uint8 array to write into (rows contiguous) -- numpy beside a device image is the device-source / host-plane form;
+        it is returned as it is, and left untouched for FNX_PNG_NRGBA."""
+        v = _Img(img)
+        space = v.space
+        pptr, pstride = None, 0
+        if want_plane:
+            if plane is None:
+                if v.space == FNX_DEVICE:
+                    import torch
+                    plane = torch.empty((v.h, v.w), dtype=torch.uint8, device=img.device)
+                else:
+                    plane = np.empty((v.h, v.w), dtype=np.uint8)
+            on_device = _is_torch(plane)
+            if on_device and v.space != FNX_DEVICE:
+                raise FennecError("a device plane needs a device image")
+            if tuple(plane.shape[:1]) != (v.h,) or plane.ndim != 2 or plane.shape[1] < v.w:
+                raise FennecError("plane must be (h, >= w) uint8")
+            if on_device:
+                pptr, pstride = plane.data_ptr(), int(plane.stride(0)) if v.h > 1 else int(plane.shape[1])
+                ok = plane.stride(1) == 1
+            else:
+                pptr, pstride = plane.ctypes.data, int(plane.strides[0]) if v.h > 1 else int(plane.shape[1])
+                ok = plane.dtype == np.uint8 and plane.strides[1] == 1
+                if v.space == FNX_DEVICE:
+                    space = FNX_DEVICE_SRC
+            if not ok:
+                raise FennecError("plane rows must be contiguous uint8")
+        kind, n = C.c_int(0), C.c_int(0)
+        pal = np.zeros((256, 4), dtype=np.uint8)
+        with self._ordered(img, plane if want_plane and _is_torch(plane) else None):
+            self._chk(self._lib.fnx_png_reduce(self._h, space, v.ptr, v.stride, v.w, v.h, int(max_colors), C.byref(kind),
+                                               pal.ctypes.data, C.byref(n), pptr, pstride),
+                      "fnx_png_reduce")
+        out = plane if want_plane and kind.value != FNX_PNG_NRGBA else None
+        return kind.value, pal[:n.value].copy(), out
+
+    def tryPalettize(self, img, max_colors: int = 256):
+        """tryPalettize (compress.go:112-153) -> (palette (n, 4), indices (h, w)), or None when the image holds more than
+        max_colors colours.  The palette is in first-occurrence order (the reference's is a Go map's: any order)."""
+        v = _Img(img)
+        if v.space == FNX_DEVICE:
+            import torch
+            keep = torch.empty((v.h, v.w), dtype=torch.uint8, device=img.device)
+        else:
+            keep = np.empty((v.h, v.w), dtype=np.uint8)
+        kind, pal, plane = self.png_reduce(img, max_colors, True, keep)
+        return (pal, plane) if kind == FNX_PNG_PALETTED else None
+
+    def compress_file_png_reduce(self, data: bytes, orient: int = 1, max_w: int = 0, max_h: int = 0, cap: int | None = None):
+        """CompressFile's PNG branch for a JPEG source up to the encoder (fennec_CompressFilePNGReduce): decode,
+        ApplyOrientation(orient), smartResize(max_w, max_h), then compressPNG's reduction on the resident image ->
+        (kind, palette (n, 4), image, original (w, h), final (w, h)); image: (h, w) uint8 indices or grays, or (h, w, 4) NRGBA."""
+        src = np.frombuffer(data, dtype=np.uint8)
+        o = FileOptions(int(orient), int(max_w), int(max_h), 0, 0.0)
+        kind, nc, n = C.c_int(0), C.c_int(0), C.c_size_t(0)
+        pal = np.zeros((256, 4), dtype=np.uint8)
+        dims = (C.c_int * 4)()
+        rc, buf = _into_buffer(lambda b, c: self._lib.fennec_CompressFilePNGReduce(self._h, src.ctypes.data_as(_u8p), len(data), C.byref(o),
+                                                                                   C.byref(kind), pal.ctypes.data, C.byref(nc),
+                                                                                   b.ctypes.data_as(_u8p), c, C.byref(n), dims),
+                               1 << 16 if cap is None else int(cap), n)
+        self._chk(rc, "fennec_CompressFilePNGReduce")
+        w, h = dims[2], dims[3]
+        image = buf[:n.value].reshape((h, w, 4) if kind.value == FNX_PNG_NRGBA else (h, w))
+        return kind.value, pal[:nc.value].copy(), image, (dims[0], dims[1]), (w, h)
+
     # -- batched forms (device tensors) ---------------------------------------------------
     # Contract of the plan_* objects: creating a plan synchronises torch's current stream once (the inputs
     # exist from then on); run() / enqueue() only touch the stream the ctx launches on (its own unless a per-image
@@ -1557,6 +1631,8 @@ def smartResize(img, maxW, maxH): return default_context(_dev_of(img)).smartResi
 def boxDownsample(img, dstW, dstH): return default_context(_dev_of(img)).boxDownsample(img, dstW, dstH)
 def lanczosBoxDownsample(img, midW, midH, dstW, dstH): return default_context(_dev_of(img)).lanczosBoxDownsample(img, midW, midH, dstW, dstH)
 def Analyze(img): return default_context(_dev_of(img)).Analyze(img)
+def png_reduce(img, max_colors=256, want_plane=True): return default_context(_dev_of(img)).png_reduce(img, max_colors, want_plane)
+def tryPalettize(img, max_colors=256): return default_context(_dev_of(img)).tryPalettize(img, max_colors)
 
 
 def gaussianKernel(size=8, sigma=1.5):

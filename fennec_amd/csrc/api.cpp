@@ -1674,3 +1674,82 @@ int fnx_orient(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, 
 }
 
 }  // extern "C"
+
+// ---- compressPNG's pixel stages: tryPalettize, isGrayscale + toGray (compress.go:90-153, convert.go:76-100) ----------
+namespace fnx {
+
+int png_reduce_device(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, int max_colors, uint8_t *d_plane, int pstride,
+                      int *kind, uint8_t *palette, int *ncolors)
+{
+    const void *dres = nullptr;
+    FNX_TRY(launch_png_palettize(ctx, src, sstride, w, h, max_colors, d_plane, pstride, &dres));
+    std::vector<uint32_t> res(png_result_bytes() / sizeof(uint32_t));
+    FNX_TRY(fetch_bytes(ctx, dres, res.data(), png_result_bytes()));
+    *ncolors = 0;
+    if (!res[0]) {                                                   // compress.go:92-96
+        *kind = FNX_PNG_PALETTED;
+        *ncolors = static_cast<int>(res[2]);
+        std::memcpy(palette, &res[4], sizeof(uint32_t) * res[2]);    // r, g, b, a: the words' bytes in memory order
+        if (d_plane) note_route(ctx, FNX_PROF_MAIN, "png_plane_kernel");
+        return FNX_OK;
+    }
+    // compress.go:98: isGrayscale walks the flat Pix, row padding included.  A non-grey VISIBLE pixel met by the colours
+    // pass already answers it (every photograph); otherwise the flat scan decides.
+    bool gray = false;
+    if (!res[1]) {
+        void *df = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_RESULT, 16, &df));
+        FNX_TRY(launch_scan_flags(ctx, src, static_cast<size_t>(h - 1) * sstride + static_cast<size_t>(w) * 4, static_cast<uint32_t *>(df)));
+        uint32_t flags = 0;
+        FNX_TRY(fetch_bytes(ctx, df, &flags, sizeof(flags)));
+        gray = !(flags & 2u);
+    }
+    *kind = gray ? FNX_PNG_GRAY : FNX_PNG_NRGBA;
+    if (gray && d_plane) {                                           // compress.go:99-103: toGray
+        FNX_TRY(launch_png_plane(ctx, src, sstride, w, h, true, d_plane, pstride));
+        note_route(ctx, FNX_PROF_MAIN, "png_plane_kernel");
+    }
+    return FNX_OK;
+}
+
+}  // namespace fnx
+
+extern "C" {
+
+int fnx_png_reduce(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int max_colors, int *kind, uint8_t *palette,
+                   int *ncolors, uint8_t *plane, int pstride)
+{
+    FNX_ENTER(ctx);
+    FNX_TRY(check_space_io(space));
+    FNX_REQUIRE(max_colors >= 1 && max_colors <= 256, "max_colors: 1..256 (image.Paletted indices are uint8)");
+    FNX_REQUIRE(kind != nullptr && palette != nullptr && ncolors != nullptr, "kind, palette and ncolors are outputs");
+    FNX_REQUIRE(w <= 65535 && h <= 65535, "dims: at most 65535 (first-occurrence indices are 32-bit)");
+    FNX_TRY(check_img(src, sstride, w, h, "src"));
+    if (plane) FNX_REQUIRE(pstride >= w, "plane stride");
+    if (w <= 0 || h <= 0) {                                           // an empty colorMap: a palette of no colours (compress.go:116-141)
+        *kind = FNX_PNG_PALETTED;
+        *ncolors = 0;
+        return FNX_OK;
+    }
+    DevImg s;
+    FNX_TRY(stage_in_flat(ctx, space, src, sstride, w, h, SLOT_IN_A, &s));
+    uint8_t *dplane = plane;
+    int dpitch = pstride;
+    if (plane && space != FNX_DEVICE) {
+        dpitch = (w + 3) & ~3;
+        void *t = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_OUT, static_cast<size_t>(dpitch) * h + 16, &t));
+        dplane = static_cast<uint8_t *>(t);
+    }
+    FNX_TRY(png_reduce_device(ctx, s.p, s.stride, w, h, max_colors, dplane, dpitch, kind, palette, ncolors));
+    if (*kind == FNX_PNG_NRGBA) return FNX_OK;                        // the plane stays as it was
+    if (plane && space != FNX_DEVICE) {
+        FNX_HIP(hipMemcpy2DAsync(plane, pstride, dplane, dpitch, w, h, hipMemcpyDeviceToHost, ctx->stream));
+        FNX_HIP(hipStreamSynchronize(ctx->stream));
+    } else if (plane && *kind == FNX_PNG_GRAY) {
+        FNX_HIP(hipStreamSynchronize(ctx->stream));                   // (the gray plane was launched after the last wait)
+    }
+    return FNX_OK;
+}
+
+}  // extern "C"

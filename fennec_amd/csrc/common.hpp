@@ -106,6 +106,7 @@ enum Slot {
     SLOT_TS_SCALED, SLOT_TS_UP,    // jpeg_api.cpp: fnx_jpeg_target_size's Lanczos-scaled image and its upscale back to the source's size
     SLOT_JPEG_QTAB, SLOT_JPEG_JOBS,  // fnx_jpeg_compress_batch: the quantiser tables of qualities 1..100, a search step's job list
     SLOT_RZBOX_TABLES, SLOT_RZBOX_SUMS,   // resize_box.hip: both tap tables + the box maps, the image-wide integer box sums
+    SLOT_PNG,        // png_reduce.hip: the colour set's result (over, count, palette) and the colour -> index table of the plane pass
     SLOT_DONE,       // workgroup counters of the kernels that finish their own reduction (ssim.hip), zero between launches
     SLOT_COUNT
 };
@@ -520,6 +521,18 @@ int ssim_done_counters(fnx_ctx *ctx, unsigned **out);   // ssim.hip: zeroed "wor
 constexpr int DONE_SCAN = 2 * 4096 + 16;                // first of the 16 words of analyze.hip's scans
 // analyzeFormat's samples: pixels at row-major indices 0, step, 2 step, ... (nsamples of them) as packed NRGBA words
 int launch_sample_pixels(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, long long step, uint32_t *d_out, int nsamples);
+// png_reduce.hip: compressPNG's pixel stages (compress.go:90-153).  launch_png_palettize: tryPalettize's colour set, palette
+// and (d_plane != nullptr) index plane of a device image, w, h <= 65535; *d_result (device, png_result_bytes()): words
+// 0 over (more than max_colors colours), 1 nongray (with over: a non-grey visible pixel was met on the way), 2 ncolors,
+// 3 unused, then the palette words in first-occurrence order.  launch_png_plane: that index plane later, or toGray's plane.
+size_t png_result_bytes();
+int launch_png_palettize(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, int max_colors, uint8_t *d_plane, int pstride,
+                         const void **d_result);
+int launch_png_plane(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, bool gray, uint8_t *d_plane, int pstride);
+// the body of fnx_png_reduce for a device image (flat Pix readable: (h-1) sstride + 4w bytes); d_plane: device, or nullptr
+// (classify only).  Blocks; kind / palette / ncolors are host memory.
+int png_reduce_device(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, int max_colors, uint8_t *d_plane, int pstride,
+                      int *kind, uint8_t *palette, int *ncolors);
 // applyPalette (+ palettedToNRGBA): palette = n x 4 host bytes (opaque); idx and/or quant may be null
 int launch_apply_palette(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, const uint8_t *palette, int n,
                          uint8_t *idx, int istride, uint8_t *quant, int qstride);

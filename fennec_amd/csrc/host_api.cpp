@@ -413,24 +413,12 @@ void fennec_pool_release(void)
     for (auto &e : all) fnx_ctx_destroy(e.second);
 }
 
-// CompressFile for a JPEG source in standard mode (fennec.go:30-76 -> compressImageInternal :107-141 -> handleStandardMode
-// :162-205) from the file's bytes, every pixel stage on the device: image.Decode + toNRGBA, ApplyOrientation (AutoOrient;
-// the caller read the tag, exif.go), smartResize (MaxWidth / MaxHeight), analyzeFormat (Format: Auto), compressJPEGOptimal.
-int fennec_CompressFileJPEG(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_FileOptions *o, uint8_t *out, size_t cap,
-                            size_t *nbytes, int *quality, double *ssim, int *steps, int dims[4])
+// What CompressFile does to a decoded JPEG before it looks at the format (fennec.go:107-129), on the device: image.Decode +
+// toNRGBA of a file whose dimensions (w x h) the caller has read, ApplyOrientation (AutoOrient; the caller read the tag,
+// exif.go), smartResize (MaxWidth / MaxHeight).  *img: the resident tight *pw x *ph image (SLOT_FILE0 or SLOT_FILE1).
+static int file_stages(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_FileOptions *o, int w, int h, const uint8_t **pimg,
+                       int *pw, int *ph, int dims[4])
 {
-    if (!ctx || !data || !o || !nbytes || !quality || !ssim || !dims) {
-        set_error("invalid argument: CompressFileJPEG");
-        return FNX_ERR_INVALID;
-    }
-    *nbytes = 0;
-    int w = 0, h = 0;
-    FNX_TRY(fnx_jpeg_decode(ctx, data, n, FNX_HOST, nullptr, 0, &w, &h));          // dimensions; refuses what the device decoder does not take
-    if (!(o->orient > 1 && o->orient <= 8) && o->max_w <= 0 && o->max_h <= 0 && !o->auto_format) {
-        // nothing between the decode and the search: the item body without the decoded image (fnx_jpeg_recompress, r3)
-        dims[0] = dims[2] = w; dims[1] = dims[3] = h;
-        return fnx_jpeg_recompress(ctx, data, n, o->target_ssim, ssim_window(), out, cap, nbytes, quality, ssim, steps, &w, &h);
-    }
     void *b0 = nullptr;
     FNX_TRY(scratch(ctx, SLOT_FILE0, static_cast<size_t>(w) * h * 4 + 16, &b0));
     FNX_TRY(fnx_jpeg_decode(ctx, data, n, FNX_DEVICE, static_cast<uint8_t *>(b0), w * 4, &w, &h));
@@ -451,10 +439,34 @@ int fennec_CompressFileJPEG(fnx_ctx *ctx, const uint8_t *data, size_t n, const f
             void *b = nullptr;
             FNX_TRY(scratch(ctx, in0 ? SLOT_FILE1 : SLOT_FILE0, static_cast<size_t>(nw) * nh * 4 + 16, &b));
             FNX_TRY(fennec_lanczosResize(ctx, FNX_DEVICE, img, w * 4, w, h, static_cast<uint8_t *>(b), nw * 4, nw, nh));
-            img = static_cast<const uint8_t *>(b); w = nw; h = nh; in0 = !in0;
+            img = static_cast<const uint8_t *>(b); w = nw; h = nh;
         }
     }
     dims[2] = w; dims[3] = h;                                                      // FinalDimensions
+    *pimg = img; *pw = w; *ph = h;
+    return FNX_OK;
+}
+
+// CompressFile for a JPEG source in standard mode (fennec.go:30-76 -> compressImageInternal :107-141 -> handleStandardMode
+// :162-205) from the file's bytes, every pixel stage on the device: image.Decode + toNRGBA, ApplyOrientation (AutoOrient;
+// the caller read the tag, exif.go), smartResize (MaxWidth / MaxHeight), analyzeFormat (Format: Auto), compressJPEGOptimal.
+int fennec_CompressFileJPEG(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_FileOptions *o, uint8_t *out, size_t cap,
+                            size_t *nbytes, int *quality, double *ssim, int *steps, int dims[4])
+{
+    if (!ctx || !data || !o || !nbytes || !quality || !ssim || !dims) {
+        set_error("invalid argument: CompressFileJPEG");
+        return FNX_ERR_INVALID;
+    }
+    *nbytes = 0;
+    int w = 0, h = 0;
+    FNX_TRY(fnx_jpeg_decode(ctx, data, n, FNX_HOST, nullptr, 0, &w, &h));          // dimensions; refuses what the device decoder does not take
+    if (!(o->orient > 1 && o->orient <= 8) && o->max_w <= 0 && o->max_h <= 0 && !o->auto_format) {
+        // nothing between the decode and the search: the item body without the decoded image (fnx_jpeg_recompress, r3)
+        dims[0] = dims[2] = w; dims[1] = dims[3] = h;
+        return fnx_jpeg_recompress(ctx, data, n, o->target_ssim, ssim_window(), out, cap, nbytes, quality, ssim, steps, &w, &h);
+    }
+    const uint8_t *img = nullptr;
+    FNX_TRY(file_stages(ctx, data, n, o, w, h, &img, &w, &h, dims));
     if (o->auto_format) {
         // analyzeFormat (convert.go:105-146) on what a JPEG decodes to (opaque): PNG when fewer than 256 distinct colours
         // among the sampled pixels.  The samples come to the host (<= 80 KB); the set is the reference's, early stop included.
@@ -479,6 +491,41 @@ int fennec_CompressFileJPEG(fnx_ctx *ctx, const uint8_t *data, size_t n, const f
         if (alpha || seen.size() < 256) return FNX_NOOP;                          // Format PNG: the caller's compressPNG
     }
     return fnx_jpeg_compress(ctx, FNX_DEVICE, img, w * 4, w, h, o->target_ssim, ssim_window(), out, cap, nbytes, quality, ssim, steps);
+}
+
+// CompressFile's PNG branch for a JPEG source up to the encoder (fennec.go:107-141 -> compressPNG, compress.go:90-153): the
+// same stages, then tryPalettize / isGrayscale + toGray on the resident image; `out` is what png.Encoder is handed.
+int fennec_CompressFilePNGReduce(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_FileOptions *o, int *kind, uint8_t *palette,
+                                 int *ncolors, uint8_t *out, size_t cap, size_t *nbytes, int dims[4])
+{
+    if (!ctx || !data || !o || !kind || !palette || !ncolors || !nbytes || !dims || (!out && cap)) {
+        set_error("invalid argument: CompressFilePNGReduce");
+        return FNX_ERR_INVALID;
+    }
+    *nbytes = 0;
+    *kind = 0;
+    *ncolors = 0;
+    int w = 0, h = 0;
+    FNX_TRY(fnx_jpeg_decode(ctx, data, n, FNX_HOST, nullptr, 0, &w, &h));          // dimensions; refuses what the device decoder does not take
+    const uint8_t *img = nullptr;
+    FNX_TRY(file_stages(ctx, data, n, o, w, h, &img, &w, &h, dims));
+    if (w > 65535 || h > 65535) {
+        set_error("invalid argument: CompressFilePNGReduce takes images of at most 65535 x 65535");
+        return FNX_ERR_INVALID;
+    }
+    void *dp = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_OUT, static_cast<size_t>(w) * h + 16, &dp));
+    FNX_TRY(png_reduce_device(ctx, img, w * 4, w, h, 256, static_cast<uint8_t *>(dp), w, kind, palette, ncolors));
+    const size_t px = static_cast<size_t>(w) * h;
+    *nbytes = *kind == FNX_PNG_NRGBA ? px * 4 : px;
+    if (cap < *nbytes) {
+        set_error("invalid argument: CompressFilePNGReduce needs %zu bytes of output, cap is %zu", *nbytes, cap);
+        return FNX_ERR_INVALID;
+    }
+    const void *reduced = *kind == FNX_PNG_NRGBA ? static_cast<const void *>(img) : dp;
+    FNX_HIP(hipMemcpyAsync(out, reduced, *nbytes, hipMemcpyDeviceToHost, ctx->stream));
+    FNX_HIP(hipStreamSynchronize(ctx->stream));
+    return FNX_OK;
 }
 
 }  // extern "C"

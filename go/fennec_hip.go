@@ -727,6 +727,75 @@ func applyPalette(src *image.NRGBA, palette color.Palette) *image.Paletted {
 	return applyPaletteGo(src, palette)
 }
 
+// ---- compress.go: compressPNG's pixel stages (compress.go:90-153) ---------------------------
+
+// palettedFrom wraps fnx_png_reduce's palette bytes (r,g,b,a per entry, first-occurrence order) as a color.Palette.
+func palettedFrom(pal []C.uint8_t, n int) color.Palette {
+	out := make(color.Palette, n)
+	for i := 0; i < n; i++ {
+		out[i] = color.NRGBA{uint8(pal[4*i]), uint8(pal[4*i+1]), uint8(pal[4*i+2]), uint8(pal[4*i+3])}
+	}
+	return out
+}
+
+// tryPalettize replaces compress.go:112: nil when the image holds more than maxColors colours.  The reference's palette is
+// in a Go map's (random) order; the device's is in first-occurrence order -- Palette[Pix[i]] is the source pixel either way.
+func tryPalettize(img *image.NRGBA, maxColors int) *image.Paletted {
+	w, h := img.Bounds().Dx(), img.Bounds().Dy()
+	if maxColors < 1 || maxColors > 256 || w <= 0 || h <= 0 || w > 65535 || h > 65535 {
+		return tryPalettizeGo(img, maxColors)
+	}
+	if c := pool.get(); c != nil {
+		defer pool.put(c)
+		var kind, n C.int
+		pal := make([]C.uint8_t, 256*4)
+		indexed := image.NewPaletted(image.Rect(0, 0, w, h), nil)
+		st := C.fnx_png_reduce(c, C.FNX_HOST, pix(img), C.int(img.Stride), C.int(w), C.int(h), C.int(maxColors), &kind,
+			&pal[0], &n, (*C.uint8_t)(unsafe.Pointer(&indexed.Pix[0])), C.int(indexed.Stride))
+		runtime.KeepAlive(img)
+		if st == C.FNX_OK {
+			if kind != C.FNX_PNG_PALETTED {
+				return nil
+			}
+			indexed.Palette = palettedFrom(pal, int(n))
+			return indexed
+		}
+	}
+	fellBack("tryPalettize")
+	return tryPalettizeGo(img, maxColors)
+}
+
+// compressFilePNGReduceHIP is CompressFile's PNG branch for a .jpg source up to the encoder (fennec.go:107-141 ->
+// compressPNG, compress.go:90-107) on the context that has just answered FNX_NOOP for the same file and options: decode,
+// orientation and resize run on the device again, tryPalettize / isGrayscale + toGray on the resident image, and the
+// reduced image comes back as the type compressPNG hands png.Encoder.  nil: the device refused; decode on the host.
+func compressFilePNGReduceHIP(c *C.fnx_ctx, file []byte, fo *C.fennec_FileOptions) image.Image {
+	buf := make([]byte, 1<<20)
+	pal := make([]C.uint8_t, 256*4)
+	for try := 0; try < 2; try++ {
+		var kind, ncolors C.int
+		var n C.size_t
+		var dims [4]C.int
+		st := C.fennec_CompressFilePNGReduce(c, (*C.uint8_t)(unsafe.Pointer(&file[0])), C.size_t(len(file)), fo, &kind, &pal[0], &ncolors,
+			(*C.uint8_t)(unsafe.Pointer(&buf[0])), C.size_t(len(buf)), &n, &dims[0])
+		runtime.KeepAlive(file)
+		rect := image.Rect(0, 0, int(dims[2]), int(dims[3]))
+		switch {
+		case st == C.FNX_OK && kind == C.FNX_PNG_PALETTED:
+			return &image.Paletted{Pix: buf[:int(n)], Stride: rect.Dx(), Rect: rect, Palette: palettedFrom(pal, int(ncolors))}
+		case st == C.FNX_OK && kind == C.FNX_PNG_GRAY:
+			return &image.Gray{Pix: buf[:int(n)], Stride: rect.Dx(), Rect: rect}
+		case st == C.FNX_OK:
+			return &image.NRGBA{Pix: buf[:int(n)], Stride: 4 * rect.Dx(), Rect: rect}
+		case st == C.FNX_ERR_INVALID && int(n) > len(buf):
+			buf = make([]byte, int(n))
+		default:
+			return nil
+		}
+	}
+	return nil
+}
+
 // ---- compress.go: the whole quality search on the device (opt-in; DESIGN.md 3.11) -----------
 
 // jpegQualitySearchHIP runs compressJPEGOptimal's binary search (compress.go:24-74) with every candidate quality
@@ -891,12 +960,15 @@ func jpegRecompressHIP(data []byte, targetSSIM float64) (out []byte, quality int
 // one call: decode, ApplyOrientation (opts.AutoOrient, orient as openWithOrientation read it), smartResize (MaxWidth /
 // MaxHeight), analyzeFormat (Format == Auto), compressJPEGOptimal -- every pixel stage on the device.
 //   ok == false            the device was not used or refuses the file: the reference's own path
-//   ok && data == nil      analyzeFormat chose PNG: the caller's compressPNG (orig / final dims are set)
+//   ok && data == nil      analyzeFormat chose PNG (orig / final dims are set): reduced is what compressPNG would hand
+//                          png.Encoder (*image.Paletted, *image.Gray or *image.NRGBA), made on the device without a second
+//                          decode on the host -- `png.Encoder{CompressionLevel: png.BestCompression}.Encode(w, reduced)`;
+//                          reduced == nil: the caller's own decode and compressPNG
 func compressFileJPEGHIP(file []byte, orient Orientation, opts Options, targetSSIM float64) (data []byte, quality int, ssim float64,
-	orig, final image.Point, ok bool) {
+	orig, final image.Point, reduced image.Image, ok bool) {
 	c := poolGetIf(useDeviceSearch && len(file) > 4 && opts.TargetSize == 0 && (opts.Format == JPEG || opts.Format == Auto))
 	if c == nil {
-		return nil, 0, 0, image.Point{}, image.Point{}, false
+		return nil, 0, 0, image.Point{}, image.Point{}, nil, false
 	}
 	defer pool.put(c)
 	var fo C.fennec_FileOptions
@@ -922,16 +994,16 @@ func compressFileJPEGHIP(file []byte, orient Orientation, opts Options, targetSS
 		orig, final = image.Pt(int(dims[0]), int(dims[1])), image.Pt(int(dims[2]), int(dims[3]))
 		switch {
 		case st == C.FNX_OK:
-			return buf[:int(n)], int(q), float64(s), orig, final, true
+			return buf[:int(n)], int(q), float64(s), orig, final, nil, true
 		case st == C.FNX_NOOP:
-			return nil, 0, 1.0, orig, final, true
+			return nil, 0, 1.0, orig, final, compressFilePNGReduceHIP(c, file, &fo), true
 		case st == C.FNX_ERR_INVALID && int(n) > len(buf):
 			buf = make([]byte, int(n))
 		default:
-			return nil, 0, 0, image.Point{}, image.Point{}, false
+			return nil, 0, 0, image.Point{}, image.Point{}, nil, false
 		}
 	}
-	return nil, 0, 0, image.Point{}, image.Point{}, false
+	return nil, 0, 0, image.Point{}, image.Point{}, nil, false
 }
 
 // jpegQualitySearchOptHIP is jpegQualitySearchOpt (targetsize.go:125-176) on the device: every candidate's size from the

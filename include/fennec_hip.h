@@ -584,6 +584,32 @@ int fnx_apply_palette(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, 
                       const uint8_t *palette, int ncolors, uint8_t *indices, int istride,
                       uint8_t *quantized, int qstride);
 
+/* ---- compressPNG's pixel stages (compress.go:90-153, convert.go:76-100) ------------------- */
+/* What compressPNG decides and builds before png.Encoder sees a byte, for an NRGBA w x h image (w, h <= 65535):
+ *   FNX_PNG_PALETTED  at most max_colors distinct (r,g,b,a) among the w visible pixels of the h rows (alpha is part of the
+ *                     key, row padding is not visited: compress.go:116-128; the count is exact).  palette[0 .. *ncolors)
+ *                     holds them, plane[y*pstride + x] the palette position of pixel (x, y) (compress.go:141-150).
+ *   FNX_PNG_GRAY      else, when isGrayscale says so -- the flat walk of convert.go:76-84 over (h-1)*sstride + 4w bytes,
+ *                     row padding INCLUDED, which must be readable: plane[y*pstride + x] = R(x, y), alpha dropped as
+ *                     toGray drops it (convert.go:86-100).  An opaque grey image never gets here (at most 256 greys
+ *                     always palettise); a translucent one with more than max_colors (v, a) pairs does -- the reference's
+ *                     behaviour, kept.
+ *   FNX_PNG_NRGBA     else: the image as it is; plane is not written.
+ * Palette order: the reference builds its palette by ranging over a Go map (compress.go:134-138), an order the language
+ * leaves random, so ANY order is a reference answer and parity is palette[plane] == source with a duplicate-free
+ * palette.  This library fixes one: ascending row-major index of each colour's first occurrence (what an insertion-
+ * ordered map would give) -- independent of launch geometry and timing, so two calls return identical bytes.
+ * space: FNX_HOST, FNX_DEVICE, or FNX_DEVICE_SRC (device source, host plane).  *ncolors: the palette's length when
+ * PALETTED, else 0.  plane == NULL: classify only (kind, palette, ncolors).  The encoder -- deflate, row filters -- stays
+ * the caller's.  Kernels: csrc/png_reduce.hip (png_colors_kernel / png_plane_kernel in fnx_ctx_last_kernel(ctx,
+ * FNX_PROF_MAIN)).  Integers: bit-exact. */
+#define FNX_PNG_PALETTED 1   /* tryPalettize(img, max_colors) != nil     compress.go:92-96, 112-153 */
+#define FNX_PNG_GRAY     2   /* else isGrayscale(img): toGray(img)       compress.go:98-103, convert.go:76-100 */
+#define FNX_PNG_NRGBA    3   /* else the image as it is                  compress.go:105-107 */
+int fnx_png_reduce(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int max_colors /* 1..256 */,
+                   int *kind, uint8_t *palette /* HOST, 256 x 4: r,g,b,a */, int *ncolors,
+                   uint8_t *plane /* w x h bytes, stride pstride >= w; may be NULL: classify only */, int pstride);
+
 /* ======================================================================= */
 /* fennec_* : the reference's function set (names and argument meaning as in
  * the Go source), mirrored above fnx_*.                                     */
@@ -698,6 +724,17 @@ typedef struct fennec_FileOptions {
 } fennec_FileOptions;
 int fennec_CompressFileJPEG(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_FileOptions *opts, uint8_t *out, size_t cap,
                             size_t *nbytes, int *quality, double *ssim, int *steps /* may be NULL */, int dims[4]);
+/* CompressFile's PNG branch for a JPEG source, up to the encoder (fennec.go:107-141 -> compressPNG, compress.go:90-153 with
+ * convert.go:76-100): decode, ApplyOrientation and smartResize staged exactly as fennec_CompressFileJPEG stages them, then
+ * fnx_png_reduce (max_colors 256) on the resident image -- for the item that came back FNX_NOOP there, or under Format:
+ * PNG, without a second decode on the host.  opts->target_ssim and opts->auto_format are ignored: the caller has decided.
+ * out: the tight reduced image the caller hands to png.Encoder -- w*h bytes (image.Paletted.Pix with `palette` in this
+ * library's first-occurrence order, or image.Gray.Pix) or w*h*4 NRGBA bytes; *nbytes its size; dims as
+ * fennec_CompressFileJPEG's.  cap too small: FNX_ERR_INVALID with *nbytes, *kind, *ncolors and dims set (call again).
+ * FNX_ERR_UNSUPPORTED as fnx_jpeg_decode. */
+int fennec_CompressFilePNGReduce(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_FileOptions *opts,
+                                 int *kind, uint8_t *palette /* 256 x 4 */, int *ncolors,
+                                 uint8_t *out, size_t cap, size_t *nbytes, int dims[4]);
 /* The same pool over JPEG FILES in host memory (what CompressBatch reads for a .jpg item, batch.go:88-101): per item
  * fnx_jpeg_recompress -- decoder, search and encoder on the device, no host codec.  A file the device decoder does not
  * take comes back with failed != 0 and status == FNX_ERR_UNSUPPORTED: the caller decodes it on the host and sends it
