@@ -248,6 +248,9 @@ def load_library() -> C.CDLL:
         _sig(L, "fnx_png_reduce", i, [ctx, i] + img + [i, i, i, C.POINTER(i), _u8p, C.POINTER(i), _u8p, i])
         _sig(L, "fennec_CompressFilePNGReduce", i, [ctx, _u8p, C.c_size_t, C.POINTER(FileOptions), C.POINTER(i), _u8p, C.POINTER(i), _u8p,
                                                      C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i)])
+        _sig(L, "fnx_png_filter", i, [ctx, i, i, _u8p, i, i, i, i, i, _u8p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i), C.POINTER(i)])
+        _sig(L, "fennec_CompressFilePNGStream", i, [ctx, _u8p, C.c_size_t, C.POINTER(FileOptions), C.POINTER(i), _u8p, C.POINTER(i),
+                                                     C.POINTER(i), C.POINTER(i), _u8p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i)])
         _sig(L, "fennec_gaussianKernel", None, [i, d, _f64p])
         _sig(L, "fennec_blurKernel", i, [d, _f64p])
         _sig(L, "fennec_lanczosKernel", d, [d])
@@ -1380,6 +1383,91 @@ class Context:
         image = buf[:n.value].reshape((h, w, 4) if kind.value == FNX_PNG_NRGBA else (h, w))
         return kind.value, pal[:nc.value].copy(), image, (dims[0], dims[1]), (w, h)
 
+    def png_filter(self, src, kind: int | None = None, ncolors: int = 0, opaque: int = -1, out=None):
+        """The PNG encoder's row stage (fnx_png_filter; compress.go:94-107) -> (stream (h, 1 + n) uint8, color_type, bit_depth):
+        every row packed, filtered by the cheapest of the five PNG filters and led by its type byte -- the bytes zlib reads.
+        src: an (h, w, 4) NRGBA image (kind FNX_PNG_NRGBA; opaque 1 / 0 states whether RGB or RGBA rows are written, -1 decides
+        as image.NRGBA.Opaque() does) or an (h, w) uint8 plane: toGray's (FNX_PNG_GRAY, the default for a plane) or an index
+        plane (FNX_PNG_PALETTED with ncolors, which sets the bit depth).  numpy in, numpy out; a device tensor gives a device
+        tensor, or fills `out` -- a flat uint8 numpy array (the device-source / host-stream form) or device tensor of at least
+        h * (1 + n) bytes, of which the stream's bytes are returned as an (h, 1 + n) view."""
+        torch_src = _is_torch(src)
+        if src.ndim == 3:
+            v = _Img(src)
+            kind = FNX_PNG_NRGBA if kind is None else kind
+            if kind != FNX_PNG_NRGBA:
+                raise FennecError("an (h, w, 4) image is FNX_PNG_NRGBA")
+            space, ptr, stride, w, h = v.space, v.ptr, v.stride, v.w, v.h
+        else:
+            kind = FNX_PNG_GRAY if kind is None else kind
+            if kind not in (FNX_PNG_GRAY, FNX_PNG_PALETTED) or src.ndim != 2:
+                raise FennecError("an (h, w) plane is FNX_PNG_GRAY or FNX_PNG_PALETTED")
+            h, w = int(src.shape[0]), int(src.shape[1])
+            if torch_src:
+                import torch
+                if not src.is_cuda or src.dtype != torch.uint8 or (w > 0 and src.stride(1) != 1):
+                    raise FennecError("device planes must be uint8 CUDA/HIP tensors with contiguous rows")
+                space, ptr, stride = FNX_DEVICE, src.data_ptr(), int(src.stride(0)) if h > 1 else w
+            else:
+                if not isinstance(src, np.ndarray) or src.dtype != np.uint8 or (w > 0 and src.strides[1] != 1):
+                    raise FennecError("host planes must be numpy uint8 arrays with contiguous rows")
+                space, ptr, stride = FNX_HOST, src.ctypes.data, int(src.strides[0]) if h > 1 else w
+        n, ct, bd = C.c_size_t(0), C.c_int(0), C.c_int(0)
+
+        def call(sp, optr, cap):
+            return self._lib.fnx_png_filter(self._h, sp, int(kind), ptr, stride, w, h, int(ncolors), int(opaque), optr, cap, C.byref(n),
+                                            C.byref(ct), C.byref(bd))
+        if out is not None:
+            on_device = _is_torch(out)
+            if on_device and space != FNX_DEVICE:
+                raise FennecError("a device stream needs a device source")
+            if out.ndim != 1 or not (out.is_contiguous() if on_device else (out.dtype == np.uint8 and out.flags.c_contiguous)):
+                raise FennecError("out must be a flat contiguous uint8 buffer")
+            optr = out.data_ptr() if on_device else out.ctypes.data
+            with self._ordered(src, out):
+                self._chk(call(space if on_device or space == FNX_HOST else FNX_DEVICE_SRC, optr, int(out.shape[0])), "fnx_png_filter")
+            return out[:n.value].reshape(h, n.value // h), ct.value, bd.value
+        # one call: an image whose opacity the call itself finds gets room for RGBA rows, and the stream is a view of its front
+        cap = h * (1 + (4 * w if kind == FNX_PNG_NRGBA and opaque != 1 else 3 * w if kind == FNX_PNG_NRGBA else w))
+        with self._ordered(src):
+            if space == FNX_DEVICE:
+                import torch
+                buf = torch.empty(cap, dtype=torch.uint8, device=src.device)
+                optr = buf.data_ptr()
+            else:
+                buf = np.empty(cap, dtype=np.uint8)
+                optr = buf.ctypes.data
+            self._chk(call(space, optr, cap), "fnx_png_filter")
+        return buf[:n.value].reshape(h, n.value // h), ct.value, bd.value
+
+    def compress_png(self, img, level: int = 9) -> bytes:
+        """compressPNG (compress.go:90-108) end to end -> the PNG file: the reduction (png_reduce), the encoder's row stage
+        (png_filter) on the reduced image where it lives, then zlib and the chunks on the host (png_file).  The file differs
+        from Go's in the deflate bytes only (Python's zlib is not Go's compress/flate) and decodes to the same pixels."""
+        v = _Img(img)
+        kind, pal, plane = self.png_reduce(img)
+        src = img if kind == FNX_PNG_NRGBA else plane
+        host = np.empty(v.h * (1 + (4 * v.w if kind == FNX_PNG_NRGBA else v.w)), dtype=np.uint8) if v.space == FNX_DEVICE else None
+        stream, ct, bd = self.png_filter(src, kind, len(pal), -1, host)
+        return png_file(stream, v.w, v.h, ct, bd, pal if kind == FNX_PNG_PALETTED else None, level)
+
+    def compress_file_png_stream(self, data: bytes, orient: int = 1, max_w: int = 0, max_h: int = 0, cap: int | None = None):
+        """CompressFile's PNG branch for a JPEG source up to the bytes deflate reads (fennec_CompressFilePNGStream): decode,
+        ApplyOrientation(orient), smartResize(max_w, max_h), compressPNG's reduction, the encoder's row stage ->
+        (kind, palette (n, 4), stream (h, 1 + n) uint8, color_type, bit_depth, original (w, h), final (w, h))."""
+        src = np.frombuffer(data, dtype=np.uint8)
+        o = FileOptions(int(orient), int(max_w), int(max_h), 0, 0.0)
+        kind, nc, ct, bd, n = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_size_t(0)
+        pal = np.zeros((256, 4), dtype=np.uint8)
+        dims = (C.c_int * 4)()
+        rc, buf = _into_buffer(lambda b, c: self._lib.fennec_CompressFilePNGStream(self._h, src.ctypes.data_as(_u8p), len(data), C.byref(o),
+                                                                                   C.byref(kind), pal.ctypes.data, C.byref(nc), C.byref(ct),
+                                                                                   C.byref(bd), b.ctypes.data_as(_u8p), c, C.byref(n), dims),
+                               1 << 16 if cap is None else int(cap), n)
+        self._chk(rc, "fennec_CompressFilePNGStream")
+        w, h = dims[2], dims[3]
+        return (kind.value, pal[:nc.value].copy(), buf[:n.value].reshape(h, n.value // h), ct.value, bd.value, (dims[0], dims[1]), (w, h))
+
     # -- batched forms (device tensors) ---------------------------------------------------
     # Contract of the plan_* objects: creating a plan synchronises torch's current stream once (the inputs
     # exist from then on); run() / enqueue() only touch the stream the ctx launches on (its own unless a per-image
@@ -1631,8 +1719,34 @@ def smartResize(img, maxW, maxH): return default_context(_dev_of(img)).smartResi
 def boxDownsample(img, dstW, dstH): return default_context(_dev_of(img)).boxDownsample(img, dstW, dstH)
 def lanczosBoxDownsample(img, midW, midH, dstW, dstH): return default_context(_dev_of(img)).lanczosBoxDownsample(img, midW, midH, dstW, dstH)
 def Analyze(img): return default_context(_dev_of(img)).Analyze(img)
+def png_filter(src, kind=None, ncolors=0, opaque=-1): return default_context(_dev_of(src)).png_filter(src, kind, ncolors, opaque)
+def compress_png(img, level=9): return default_context(_dev_of(img)).compress_png(img, level)
 def png_reduce(img, max_colors=256, want_plane=True): return default_context(_dev_of(img)).png_reduce(img, max_colors, want_plane)
 def tryPalettize(img, max_colors=256): return default_context(_dev_of(img)).tryPalettize(img, max_colors)
+
+
+def png_file(stream, w, h, color_type, bit_depth, palette=None, level=9) -> bytes:
+    """The PNG file around fnx_png_filter's stream (host only): signature, IHDR, PLTE (3 bytes per palette entry), tRNS (the
+    alphas up to and including the last entry whose alpha != 255; omitted when there is none), one IDAT holding
+    zlib.compress(stream, level), IEND.  palette: (n, 4) r,g,b,a for colour type 3.  Python's zlib is not Go's compress/flate:
+    the file differs from the reference's in the deflate bytes only."""
+    import struct
+    import zlib
+
+    def chunk(tag: bytes, body: bytes) -> bytes:
+        return struct.pack(">I", len(body)) + tag + body + struct.pack(">I", zlib.crc32(tag + body) & 0xffffffff)
+    raw = np.ascontiguousarray(stream, dtype=np.uint8).tobytes()
+    parts = [b"\x89PNG\r\n\x1a\n", chunk(b"IHDR", struct.pack(">IIBBBBB", int(w), int(h), int(bit_depth), int(color_type), 0, 0, 0))]
+    if int(color_type) == 3:
+        pal = np.asarray(palette, dtype=np.uint8).reshape(-1, 4)
+        if not 1 <= len(pal) <= 1 << int(bit_depth):
+            raise FennecError("a paletted PNG needs a palette of 1 .. 2^bit_depth entries")
+        parts.append(chunk(b"PLTE", pal[:, :3].tobytes()))
+        translucent = np.flatnonzero(pal[:, 3] != 255)
+        if len(translucent):
+            parts.append(chunk(b"tRNS", pal[:translucent[-1] + 1, 3].tobytes()))
+    parts += [chunk(b"IDAT", zlib.compress(raw, int(level))), chunk(b"IEND", b"")]
+    return b"".join(parts)
 
 
 def gaussianKernel(size=8, sigma=1.5):

@@ -107,6 +107,7 @@ enum Slot {
     SLOT_JPEG_QTAB, SLOT_JPEG_JOBS,  // fnx_jpeg_compress_batch: the quantiser tables of qualities 1..100, a search step's job list
     SLOT_RZBOX_TABLES, SLOT_RZBOX_SUMS,   // resize_box.hip: both tap tables + the box maps, the image-wide integer box sums
     SLOT_PNG,        // png_reduce.hip: the colour set's result (over, count, palette) and the colour -> index table of the plane pass
+    SLOT_PNG_STREAM, // png_filter.hip: the filtered scanlines on their way to a host buffer
     SLOT_DONE,       // workgroup counters of the kernels that finish their own reduction (ssim.hip), zero between launches
     SLOT_COUNT
 };
@@ -533,6 +534,18 @@ int launch_png_plane(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h
 // (classify only).  Blocks; kind / palette / ncolors are host memory.
 int png_reduce_device(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, int max_colors, uint8_t *d_plane, int pstride,
                       int *kind, uint8_t *palette, int *ncolors);
+// png_filter.hip: the encoder's per-row stage (compress.go:94-107, targetsize.go:189, 342) -- rows of 1 + n bytes, the filter
+// type and the filtered row, as zlib reads them.  Row forms: RGB / RGBA from an NRGBA image (4-byte aligned), GRAY from a
+// byte plane, PALETTED from an index plane at `depth` 8, 4, 2 or 1 bits (type 0, packed MSB first; depth is ignored otherwise).
+enum PngRowForm { PNG_ROW_RGB = 0, PNG_ROW_RGBA = 1, PNG_ROW_GRAY = 2, PNG_ROW_PALETTED = 3 };
+int png_row_bytes(int form, int w, int depth);          // n
+int launch_png_filter(fnx_ctx *ctx, int form, const uint8_t *src, int sstride, int w, int h, int depth, uint8_t *d_out);
+// image.NRGBA.Opaque(): *d_flag = 1 when a visible pixel has alpha != 255, else 0
+int launch_png_alpha(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, uint32_t *d_flag);
+// the body of fnx_png_filter for a DEVICE image or plane; out: device (out_on_device) or host memory.  Blocks unless the
+// opacity is stated and the stream stays on the device.
+int png_filter_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors, int opaque, bool out_on_device,
+                      uint8_t *out, size_t cap, size_t *nbytes, int *color_type, int *bit_depth);
 // applyPalette (+ palettedToNRGBA): palette = n x 4 host bytes (opaque); idx and/or quant may be null
 int launch_apply_palette(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, const uint8_t *palette, int n,
                          uint8_t *idx, int istride, uint8_t *quant, int qstride);

@@ -36,9 +36,15 @@ package fennec
 import "C"
 
 import (
+	"bufio"
+	"compress/zlib"
 	"context"
+	"encoding/binary"
+	"hash/crc32"
 	"image"
 	"image/color"
+	"image/png"
+	"io"
 	"log"
 	"math"
 	"os"
@@ -794,6 +800,133 @@ func compressFilePNGReduceHIP(c *C.fnx_ctx, file []byte, fo *C.fennec_FileOption
 		}
 	}
 	return nil
+}
+
+// ---- the PNG encoder: its row stage on the device (compress.go:94-107, targetsize.go:189, 342) ----
+
+// pngFilterHIP runs what png.Encoder does to every row before zlib -- pack, the five filters, the smallest sum of
+// |residual| (the rule is stated above fnx_png_filter in fennec_hip.h) -- on the device, for the three image types compressPNG
+// hands the encoder.  stream: h rows of 1 + n bytes, the bytes zlib is fed.  ok == false: not taken; encode in Go.
+func pngFilterHIP(m image.Image) (stream []byte, colorType, depth int, pal color.Palette, ok bool) {
+	w, h := m.Bounds().Dx(), m.Bounds().Dy()
+	if w <= 0 || h <= 0 || w > 65535 || h > 65535 {
+		return nil, 0, 0, nil, false
+	}
+	var kind, stride, ncolors C.int
+	var src *C.uint8_t
+	rowBytes := w
+	switch img := m.(type) {
+	case *image.NRGBA:
+		kind, stride, src = C.FNX_PNG_NRGBA, C.int(img.Stride), pix(img)
+		rowBytes = 4 * w // RGBA rows unless Opaque(), which the call decides
+	case *image.Gray:
+		kind, stride, src = C.FNX_PNG_GRAY, C.int(img.Stride), (*C.uint8_t)(unsafe.Pointer(&img.Pix[0]))
+	case *image.Paletted:
+		if len(img.Palette) < 1 || len(img.Palette) > 256 {
+			return nil, 0, 0, nil, false
+		}
+		kind, stride, src = C.FNX_PNG_PALETTED, C.int(img.Stride), (*C.uint8_t)(unsafe.Pointer(&img.Pix[0]))
+		ncolors, pal = C.int(len(img.Palette)), img.Palette
+	default:
+		return nil, 0, 0, nil, false
+	}
+	c := pool.get()
+	if c == nil {
+		return nil, 0, 0, nil, false
+	}
+	defer pool.put(c)
+	buf := make([]byte, h*(1+rowBytes))
+	var n C.size_t
+	var ct, bd C.int
+	st := C.fnx_png_filter(c, C.FNX_HOST, kind, src, stride, C.int(w), C.int(h), ncolors, -1,
+		(*C.uint8_t)(unsafe.Pointer(&buf[0])), C.size_t(len(buf)), &n, &ct, &bd)
+	runtime.KeepAlive(m)
+	if st != C.FNX_OK {
+		return nil, 0, 0, nil, false
+	}
+	return buf[:int(n)], int(ct), int(bd), pal, true
+}
+
+// pngChunkWriter writes every Write as one chunk of its tag: length, tag, body, CRC-32 over tag and body.
+type pngChunkWriter struct {
+	w   io.Writer
+	tag string
+}
+
+func (c pngChunkWriter) Write(body []byte) (int, error) {
+	var head [8]byte
+	var tail [4]byte
+	binary.BigEndian.PutUint32(head[:4], uint32(len(body)))
+	copy(head[4:], c.tag)
+	crc := crc32.NewIEEE()
+	crc.Write(head[4:])
+	crc.Write(body)
+	binary.BigEndian.PutUint32(tail[:], crc.Sum32())
+	for _, part := range [][]byte{head[:], body, tail[:]} {
+		if _, err := c.w.Write(part); err != nil {
+			return 0, err
+		}
+	}
+	return len(body), nil
+}
+
+// encodePNG is `(&png.Encoder{CompressionLevel: png.BestCompression}).Encode(w, m)` -- what compressPNG (compress.go:94-107)
+// and target-size mode (targetsize.go:189, 342) call -- with the per-row stage on the device: the chunks and deflate at
+// zlib.BestCompression stay here, IDAT cut at 32 KiB as the encoder's buffered writer cuts it.  Any other image type, or
+// any refusal of the device, runs the encoder in Go (counted).
+func encodePNG(w io.Writer, m image.Image) error {
+	stream, colorType, depth, pal, ok := pngFilterHIP(m)
+	if !ok {
+		fellBack("encodePNG")
+		return (&png.Encoder{CompressionLevel: png.BestCompression}).Encode(w, m)
+	}
+	if _, err := io.WriteString(w, "\x89PNG\r\n\x1a\n"); err != nil {
+		return err
+	}
+	var ihdr [13]byte
+	binary.BigEndian.PutUint32(ihdr[0:4], uint32(m.Bounds().Dx()))
+	binary.BigEndian.PutUint32(ihdr[4:8], uint32(m.Bounds().Dy()))
+	ihdr[8], ihdr[9] = uint8(depth), uint8(colorType) // compression, filter and interlace methods: 0
+	if _, err := (pngChunkWriter{w, "IHDR"}).Write(ihdr[:]); err != nil {
+		return err
+	}
+	if len(pal) > 0 {
+		plte := make([]byte, 0, 3*len(pal))
+		trns := make([]byte, len(pal))
+		last := -1 // tRNS runs up to the last entry that is not opaque
+		for i, entry := range pal {
+			v := color.NRGBAModel.Convert(entry).(color.NRGBA)
+			plte = append(plte, v.R, v.G, v.B)
+			trns[i] = v.A
+			if v.A != 0xff {
+				last = i
+			}
+		}
+		if _, err := (pngChunkWriter{w, "PLTE"}).Write(plte); err != nil {
+			return err
+		}
+		if last >= 0 {
+			if _, err := (pngChunkWriter{w, "tRNS"}).Write(trns[:last+1]); err != nil {
+				return err
+			}
+		}
+	}
+	idat := bufio.NewWriterSize(pngChunkWriter{w, "IDAT"}, 1<<15)
+	zw, err := zlib.NewWriterLevel(idat, zlib.BestCompression)
+	if err != nil {
+		return err
+	}
+	if _, err := zw.Write(stream); err != nil {
+		return err
+	}
+	if err := zw.Close(); err != nil {
+		return err
+	}
+	if err := idat.Flush(); err != nil {
+		return err
+	}
+	_, err = (pngChunkWriter{w, "IEND"}).Write(nil)
+	return err
 }
 
 // ---- compress.go: the whole quality search on the device (opt-in; DESIGN.md 3.11) -----------

@@ -610,6 +610,44 @@ int fnx_png_reduce(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int
                    int *kind, uint8_t *palette /* HOST, 256 x 4: r,g,b,a */, int *ncolors,
                    uint8_t *plane /* w x h bytes, stride pstride >= w; may be NULL: classify only */, int pstride);
 
+/* ---- the PNG encoder's per-row stage: pack, five filters, smallest sum (compress.go:94-107, targetsize.go:189, 342) ---- */
+/* What png.Encoder{CompressionLevel: png.BestCompression} does to every row of the image it is handed, before zlib sees a
+ * byte -- by compressPNG (compress.go:94-107), the quantize strategy (targetsize.go:189) and scaleSearch (targetsize.go:342).
+ * Go's image/png/writer.go is not part of the reference tree, so the rule is restated here and parity with
+ * Go is unpinned in the sense of DESIGN.md section 1; a numpy restatement of exactly this text is the tests' reference.
+ *   kind, input                          colour type / depth   raw row of n bytes                              bpp
+ *   FNX_PNG_NRGBA, every visible a==255  2 (RGB)  / 8          r,g,b per pixel, n = 3w                         3
+ *   FNX_PNG_NRGBA otherwise              6 (RGBA) / 8          the 4w bytes as stored (non-premultiplied)      4
+ *   FNX_PNG_GRAY (toGray's plane)        0        / 8          the w bytes                                     1
+ *   FNX_PNG_PALETTED, ncolors > 16       3        / 8          the w bytes                                     -
+ *   FNX_PNG_PALETTED, ncolors <= 16/4/2  3        / 4, 2, 1    indices packed MSB first, the last partial byte
+ *                                                              shifted left to fill; n = ceil(w*depth / 8)     -
+ * "Opaque" is image.NRGBA.Opaque(): the w visible pixels of the h rows; row padding is not looked at (unlike convert.go's
+ * flat isOpaque).  opaque = 1 / 0 states it, -1 asks this call to decide that way first.
+ * out: h rows of 1 + n bytes -- the filter type, then the filtered row -- exactly the stream zlib is fed.
+ * Paletted rows always get type 0 and the raw bytes.  Otherwise, with cur the raw row, prev the RAW row above (zeros for
+ * row 0), left[i] = cur[i-bpp] and ul[i] = prev[i-bpp] (both 0 for i < bpp), all arithmetic mod 256:
+ *   0 None     cur[i]
+ *   1 Sub      cur[i] - left[i]
+ *   2 Up       cur[i] - prev[i]
+ *   3 Average  cur[i] - ((left[i] + prev[i]) >> 1), the sum in at least 9 bits
+ *   4 Paeth    cur[i] - paeth(left[i], prev[i], ul[i]);  p = a + b - c, pa = |p-a|, pb = |p-b|, pc = |p-c|:
+ *              a if pa <= pb && pa <= pc, else b if pb <= pc, else c
+ * The cost of a filter is the sum over the row of abs8(residual), abs8(d) = d < 128 ? d : 256 - d (abs8(128) = 128).  The
+ * filters are tried in the order Up, Paeth, None, Sub, Average and a later one replaces the best only when its sum is
+ * strictly smaller.  (Go leaves a filter's loop once its running sum reaches the best so far: that only abandons a filter
+ * that can no longer win, full sums give the same choice.  Sums fit 32 bits: n <= 262 140, times 128.)
+ * space: FNX_HOST, FNX_DEVICE, or FNX_DEVICE_SRC (device image, host stream: the product route).  src: the NRGBA image
+ * (sstride >= 4w, a multiple of 4, the pointer 4-byte aligned in the device spaces) or the byte plane (sstride >= w, any
+ * alignment).  w, h: 1..65535.  ncolors: 1..256 for FNX_PNG_PALETTED, ignored otherwise; opaque: ignored for planes.
+ * *nbytes = h * (1 + n), *color_type and *bit_depth are set whenever the arguments are good; cap < *nbytes:
+ * FNX_ERR_INVALID with the three set (call again), nothing written.  Bad arguments are refused before anything is
+ * launched.  Integers: bit-exact, independent of launch geometry.  Deflate stays the caller's.  Kernels:
+ * csrc/png_filter.hip (png_filter_kernel / png_pack_kernel in fnx_ctx_last_kernel(ctx, FNX_PROF_MAIN)). */
+int fnx_png_filter(fnx_ctx *ctx, int space, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors /* paletted: 1..256 */,
+                   int opaque /* 1, 0, or -1: decide as Opaque() does */, uint8_t *out, size_t cap, size_t *nbytes,
+                   int *color_type, int *bit_depth);
+
 /* ======================================================================= */
 /* fennec_* : the reference's function set (names and argument meaning as in
  * the Go source), mirrored above fnx_*.                                     */
@@ -734,6 +772,16 @@ int fennec_CompressFileJPEG(fnx_ctx *ctx, const uint8_t *data, size_t n, const f
  * FNX_ERR_UNSUPPORTED as fnx_jpeg_decode. */
 int fennec_CompressFilePNGReduce(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_FileOptions *opts,
                                  int *kind, uint8_t *palette /* 256 x 4 */, int *ncolors,
+                                 uint8_t *out, size_t cap, size_t *nbytes, int dims[4]);
+/* CompressFile's PNG branch for a JPEG source up to the bytes deflate reads (fennec.go:107-141 -> compressPNG,
+ * compress.go:90-153 with convert.go:76-100, then the encoder's row stage, compress.go:94-107): fennec_CompressFilePNGReduce's
+ * stages, then fnx_png_filter (opacity decided as Opaque() does) on the resident reduced image.  out: the h rows of 1 + n bytes
+ * zlib is fed; *nbytes their size; *kind, palette, *ncolors as fennec_CompressFilePNGReduce's; *color_type, *bit_depth for
+ * IHDR; dims as fennec_CompressFileJPEG's (dims[2], dims[3]: the PNG's width and height).  What is left to the caller:
+ * zlib at BestCompression and the chunks (IHDR, PLTE from `palette`, tRNS from its alphas, IDAT, IEND).  cap too small:
+ * FNX_ERR_INVALID with every result but the stream set (call again).  FNX_ERR_UNSUPPORTED as fnx_jpeg_decode. */
+int fennec_CompressFilePNGStream(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_FileOptions *opts,
+                                 int *kind, uint8_t *palette /* 256 x 4 */, int *ncolors, int *color_type, int *bit_depth,
                                  uint8_t *out, size_t cap, size_t *nbytes, int dims[4]);
 /* The same pool over JPEG FILES in host memory (what CompressBatch reads for a .jpg item, batch.go:88-101): per item
  * fnx_jpeg_recompress -- decoder, search and encoder on the device, no host codec.  A file the device decoder does not
