@@ -218,6 +218,11 @@ def load_library() -> C.CDLL:
                                                         C.POINTER(i), C.POINTER(i), C.POINTER(i)])
         _sig(L, "fnx_jpeg_recompress", i, [ctx, _u8p, C.c_size_t, d, _f64p, _u8p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i), _f64p,
                                             C.POINTER(i), C.POINTER(i), C.POINTER(i)])
+        _sig(L, "fnx_jpeg_decode_batch", i, [ctx, i, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(i), C.POINTER(i),
+                                             C.POINTER(i), C.POINTER(i)])
+        _sig(L, "fnx_jpeg_recompress_batch", i, [ctx, i, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), _f64p, _f64p, C.POINTER(C.c_void_p),
+                                                 C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(i), _f64p, C.POINTER(i), C.POINTER(i),
+                                                 C.POINTER(i), C.POINTER(i)])
         _sig(L, "fnx_jpeg_quality_search", i, [ctx, i] + img + [i, i, d, _f64p, C.POINTER(i), _f64p, C.POINTER(i)])
         _sig(L, "fnx_jpeg_encode_scaled", i, [ctx, i] + img + [i, i, i, i, i, _u8p, C.c_size_t, C.POINTER(C.c_size_t)])
         _sig(L, "fnx_jpeg_target_size", i, [ctx, i] + img + [i, i, C.c_longlong, i, _f64p, C.POINTER(C.c_int), C.POINTER(SizeCandidate),
@@ -987,6 +992,78 @@ class Context:
         if rc == FNX_OK:
             return buf[:n.value].tobytes(), q.value, v.value, st.value, (w.value, h.value)
         self._chk(rc, "fnx_jpeg_recompress")
+
+    def _item_error(self, rc: int, what: str):
+        """the exception the single call raises for a batch item's status (the message is the status: a batch keeps one text)"""
+        kind = FennecUnsupported if rc == FNX_ERR_UNSUPPORTED else FennecError
+        return kind(f"{what}: status {rc}")
+
+    def jpeg_decode_batch(self, files, device: bool = False):
+        """toNRGBARef(jpeg.Decode(f)) of every file of a list in one call (fnx_jpeg_decode_batch: one set of launches per chunk of
+        baseline files) -> (images, statuses).  images[i] is an (h, w, 4) uint8 array -- with device=True a torch tensor on the
+        ctx's device -- and what jpeg_decode(files[i]) returns, or None where statuses[i] != FNX_OK."""
+        import torch
+        files = [bytes(f) for f in files]
+        n = len(files)
+        if n == 0:
+            raise FennecError("jpeg_decode_batch takes a non-empty list of files")
+        bufs = [np.frombuffer(f, dtype=np.uint8) if len(f) else np.zeros(1, dtype=np.uint8) for f in files]
+        dsts = []
+        for f in files:                                   # a file whose config fails goes in with no destination
+            try:
+                w, h = self.jpeg_decode_config(f)
+                dsts.append(torch.empty((h, w, 4), dtype=torch.uint8, device=f"cuda:{self.device}"))
+            except FennecError:
+                dsts.append(None)
+        views = [None if t is None else _Img(t) for t in dsts]
+        pf = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+        ps = (C.c_size_t * n)(*[len(f) for f in files])
+        pd = (C.c_void_p * n)(*[None if v is None else v.ptr for v in views])
+        pst = (C.c_int * n)(*[0 if v is None else v.stride for v in views])
+        ws, hs, status = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        with self._ordered(*[t for t in dsts if t is not None]):
+            self._chk(self._lib.fnx_jpeg_decode_batch(self._h, n, pf, ps, pd, pst, ws, hs, status), "fnx_jpeg_decode_batch")
+            images = [dsts[i] if status[i] == FNX_OK else None for i in range(n)]
+            if not device:
+                images = [None if t is None else t.cpu().numpy() for t in images]
+        return images, list(status)
+
+    def jpeg_recompress_batch(self, files, target_ssim, window=None):
+        """CompressBatch's item body for a list of JPEG files in one call (fnx_jpeg_recompress_batch) -> a list with, per item,
+        what jpeg_recompress(files[i], target_ssim[i]) returns -- (bytes, quality, ssim, steps, (w, h)) -- or the FennecError /
+        FennecUnsupported instance it would raise.  target_ssim: one float for every item, or a sequence of n."""
+        files = [bytes(f) for f in files]
+        n = len(files)
+        if n == 0:
+            raise FennecError("jpeg_recompress_batch takes a non-empty list of files")
+        if isinstance(target_ssim, (int, float)):
+            targets = [float(target_ssim)] * n
+        else:
+            targets = [float(t) for t in target_ssim]
+            if len(targets) != n:
+                raise FennecError(f"jpeg_recompress_batch: {len(targets)} targets for {n} files")
+        k, pk = _f64(self.gaussianKernel() if window is None else window)
+        tg, ptg = _f64(targets)
+        bufs = [np.frombuffer(f, dtype=np.uint8) if len(f) else np.zeros(1, dtype=np.uint8) for f in files]
+        outs = [np.empty(len(f) + 4096, dtype=np.uint8) for f in files]          # as jpeg_recompress
+        pf = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+        ps = (C.c_size_t * n)(*[len(f) for f in files])
+        po = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        caps = (C.c_size_t * n)(*[len(o) for o in outs])
+        nb, q, st, status = (C.c_size_t * n)(), (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        ws, hs = (C.c_int * n)(), (C.c_int * n)()
+        v = (C.c_double * n)()
+        self._chk(self._lib.fnx_jpeg_recompress_batch(self._h, n, pf, ps, ptg, pk, po, caps, nb, q, v, st, ws, hs, status),
+                  "fnx_jpeg_recompress_batch")
+        res = []
+        for i in range(n):
+            if status[i] == FNX_OK:
+                res.append((outs[i][:nb[i]].tobytes(), q[i], v[i], st[i], (ws[i], hs[i])))
+            elif status[i] == FNX_ERR_INVALID and nb[i] > caps[i]:          # the buffer was small: that item through the single call
+                res.append(self.jpeg_recompress(files[i], targets[i], window))
+            else:
+                res.append(self._item_error(status[i], f"fnx_jpeg_recompress_batch: file {i}"))
+        return res
 
     def compress_file_jpeg(self, data: bytes, target_ssim: float, orient: int = 1, max_w: int = 0, max_h: int = 0, auto_format: bool = False):
         """CompressFile for a JPEG source in standard mode, every pixel stage on the device (fennec_CompressFileJPEG): decode,

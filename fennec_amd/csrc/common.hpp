@@ -651,6 +651,19 @@ int jpeg_corrupt(const char *what);         // set_error + FNX_ERR_INVALID
 // rst: the byte offsets (in dst) at which restart intervals 1, 2, ... start
 int jpeg_unstuff(const uint8_t *data, size_t n, const JpegFile &f, uint8_t *dst, size_t *nbytes, std::vector<uint32_t> *rst);
 int jpeg_decode_planes(fnx_ctx *ctx, const uint8_t *data, size_t n, JpegFile *f, uint8_t *planes[4], int *ystride, int *cstride);
+// a chunk of BASELINE files (jpeg_parse'd, !progressive) through one set of launches: per item its status (what
+// jpeg_decode_planes answers for the file) and, when that is FNX_OK, its planes in SLOT_JPEG_DEC_PLANES.  The return value is
+// below 0 only where the chunk could not run at all.
+struct JpegBatchItem {
+    const uint8_t *data = nullptr;
+    size_t n = 0;
+    JpegFile f;
+    int status = 0;
+    uint8_t *planes[3] = {nullptr, nullptr, nullptr};
+    int ystride = 0, cstride = 0;
+};
+size_t jpeg_decode_chunk_bytes(const JpegFile &f, size_t n);      // device scratch the file adds to a chunk (an upper estimate, from its bytes)
+int jpeg_decode_planes_chunk(fnx_ctx *ctx, int m, JpegBatchItem *items);
 int launch_scan(fnx_ctx *ctx, const uint32_t *in, unsigned long long *out, unsigned long long *totals, int n, unsigned long long *grand);
 
 }  // namespace fnx

@@ -330,6 +330,11 @@ const uint32_t *jpeg_qtab_host()
     return t.data();
 }
 
+// the body of fnx_jpeg_compress_batch behind its argument checks (fnx_jpeg_recompress_batch: once per geometry of its files)
+int jpeg_compress_group(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstride, int w, int h, const double *target_ssim,
+                        const double *window, uint8_t *const *outs, const size_t *caps, size_t *nbytes, int *quality, double *ssim,
+                        int *steps, int *status);
+
 }  // namespace
 
 int fnx_jpeg_compress_batch(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstride, int w, int h, const double *target_ssim,
@@ -349,7 +354,15 @@ int fnx_jpeg_compress_batch(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int
         }
     }
     FNX_REQUIRE(ctx->res_count == 0, "enqueued batches are waiting for fnx_results_fetch: fetch them before a blocking batch call");
+    return jpeg_compress_group(ctx, n, srcs, sstride, w, h, target_ssim, window, outs, caps, nbytes, quality, ssim, steps, status);
+}
 
+namespace {
+
+int jpeg_compress_group(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstride, int w, int h, const double *target_ssim,
+                        const double *window, uint8_t *const *outs, const size_t *caps, size_t *nbytes, int *quality, double *ssim,
+                        int *steps, int *status)
+{
     // the route is the single call's for this geometry: tested once, taken for every item
     int pw, ph, ys, yh, cs, chh;
     const bool ds = ssim_fast_dims(w, h, &pw, &ph);
@@ -503,6 +516,8 @@ int fnx_jpeg_compress_batch(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int
     }
     return FNX_OK;
 }
+
+}  // namespace
 
 int fnx_jpeg_encode_scaled(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int dw, int dh, int quality,
                            uint8_t *out, size_t cap, size_t *nbytes)
@@ -776,7 +791,30 @@ int fnx_jpeg_target_size(fnx_ctx *ctx, int space, const uint8_t *src, int sstrid
 }
 
 // ---- image.Decode of a baseline JPEG on the device (third slice: jpeg_dec.hip) ----------------
-// toNRGBARef(jpeg.Decode(data)) into SLOT_JPEG_DEC_IMG (tight rows); *f describes the file
+namespace {
+
+// toNRGBARef's image of a decoded file's planes
+int jpeg_planes_image(fnx_ctx *ctx, const JpegFile &f, const uint8_t *const pl[4], int ys, int cs, uint8_t *dst, int dstride)
+{
+    const bool grey = f.ncomp == 1;
+    if (f.ncomp == 4) return launch_cmyk_to_nrgba(ctx, pl, ys, f.adobe, f.w, f.h, dst, dstride);
+    return launch_ycbcr_to_nrgba(ctx, pl[0], ys, grey ? nullptr : pl[1], grey ? nullptr : pl[2], cs, grey ? 0 : f.ratio, f.w, f.h, dst, dstride);
+}
+
+// fnx_jpeg_decode behind its parse and its argument checks
+int jpeg_decode_image(fnx_ctx *ctx, const uint8_t *data, size_t n, JpegFile *f, int space, uint8_t *dst, int dstride)
+{
+    DevOut d;
+    FNX_TRY(stage_out(ctx, space, dst, dstride, f->w, f->h, SLOT_OUT, &d));
+    uint8_t *pl[4] = {nullptr, nullptr, nullptr, nullptr};
+    int ys = 0, cs = 0;
+    FNX_TRY(jpeg_decode_planes(ctx, data, n, f, pl, &ys, &cs));
+    FNX_TRY(jpeg_planes_image(ctx, *f, pl, ys, cs, d.p, d.stride));
+    return finish(ctx, space, &d);
+}
+
+}  // namespace
+
 int fnx_jpeg_decode(fnx_ctx *ctx, const uint8_t *data, size_t n, int space, uint8_t *dst, int dstride, int *w, int *h)
 {
     FNX_REQUIRE(data != nullptr && w != nullptr && h != nullptr, "decode arguments");
@@ -791,15 +829,90 @@ int fnx_jpeg_decode(fnx_ctx *ctx, const uint8_t *data, size_t n, int space, uint
     FNX_TRY(jpeg_parse(data, n, &f));
     *w = f.w; *h = f.h;
     FNX_TRY(check_img(dst, dstride, f.w, f.h, "dst"));
-    DevOut d;
-    FNX_TRY(stage_out(ctx, space, dst, dstride, f.w, f.h, SLOT_OUT, &d));
-    uint8_t *pl[4] = {nullptr, nullptr, nullptr, nullptr};
-    int ys = 0, cs = 0;
-    FNX_TRY(jpeg_decode_planes(ctx, data, n, &f, pl, &ys, &cs));
-    const bool grey = f.ncomp == 1;
-    if (f.ncomp == 4) FNX_TRY(launch_cmyk_to_nrgba(ctx, pl, ys, f.adobe, f.w, f.h, d.p, d.stride));
-    else FNX_TRY(launch_ycbcr_to_nrgba(ctx, pl[0], ys, grey ? nullptr : pl[1], grey ? nullptr : pl[2], cs, grey ? 0 : f.ratio, f.w, f.h, d.p, d.stride));
-    return finish(ctx, space, &d);
+    return jpeg_decode_image(ctx, data, n, &f, space, dst, dstride);
+}
+
+// ---- the same for a batch of files (fnx_jpeg_decode_batch; jpeg_dec.hip: jpeg_decode_planes_chunk) ------------------------
+namespace {
+
+// The files' images into dsts (DEVICE), per item what fnx_jpeg_decode(files[i], FNX_DEVICE, dsts[i]) gives.  Baseline files go
+// through the decoder in chunks -- at most FNX_JPEG_DECODE_CHUNK files and JPEG_BATCH_SCRATCH of device scratch each (a file
+// that alone needs more is a chunk of one) --, a refused file leaves its destination untouched (the images are made after the
+// chunk's verdicts are in: launches, no wait); the host-route files follow one at a time.
+int jpeg_decode_batch_device(fnx_ctx *ctx, int n, const uint8_t *const *files, const size_t *sizes, uint8_t *const *dsts, const int *dstrides,
+                             int *ws, int *hs, int *status)
+{
+    std::vector<JpegBatchItem> chunk;
+    std::vector<int> at, host;
+    chunk.reserve(FNX_JPEG_DECODE_CHUNK);
+    size_t bytes = 0;
+    auto flush = [&]() -> int {
+        if (chunk.empty()) return FNX_OK;
+        FNX_TRY(jpeg_decode_planes_chunk(ctx, static_cast<int>(chunk.size()), chunk.data()));
+        for (size_t j = 0; j < chunk.size(); j++) {
+            const JpegBatchItem &it = chunk[j];
+            const int k = at[j];
+            status[k] = it.status;
+            if (it.status != FNX_OK) continue;
+            const uint8_t *pl[4] = {it.planes[0], it.planes[1], it.planes[2], nullptr};
+            FNX_TRY(jpeg_planes_image(ctx, it.f, pl, it.ystride, it.cstride, dsts[k], dstrides[k]));
+        }
+        chunk.clear();
+        at.clear();
+        bytes = 0;
+        return FNX_OK;
+    };
+    for (int i = 0; i < n; i++) {
+        ws[i] = hs[i] = 0;
+        status[i] = FNX_ERR_INVALID;
+        if (!files[i]) {
+            set_error("invalid argument: decode batch: files[%d] is NULL", i);
+            continue;
+        }
+        JpegBatchItem it;
+        it.data = files[i];
+        it.n = sizes[i];
+        const int rc = jpeg_parse(it.data, it.n, &it.f);
+        if (rc < 0) {
+            status[i] = rc;
+            continue;
+        }
+        ws[i] = it.f.w; hs[i] = it.f.h;
+        if (!dsts[i]) {
+            set_error("invalid argument: decode batch: dsts[%d] is NULL", i);
+            continue;
+        }
+        if (check_img(dsts[i], dstrides[i], it.f.w, it.f.h, "dst") < 0) continue;
+        if (it.f.progressive) {
+            host.push_back(i);
+            continue;
+        }
+        const size_t cost = jpeg_decode_chunk_bytes(it.f, it.n);
+        if (!chunk.empty() && (chunk.size() >= FNX_JPEG_DECODE_CHUNK || bytes + cost > JPEG_BATCH_SCRATCH)) FNX_TRY(flush());
+        bytes += cost;
+        chunk.push_back(it);
+        at.push_back(i);
+    }
+    FNX_TRY(flush());
+    for (int i : host) {
+        JpegFile f;
+        FNX_TRY(jpeg_parse(files[i], sizes[i], &f));
+        status[i] = jpeg_decode_image(ctx, files[i], sizes[i], &f, FNX_DEVICE, dsts[i], dstrides[i]);
+        if (status[i] == FNX_ERR_HIP || status[i] == FNX_ERR_OOM) return status[i];
+    }
+    return FNX_OK;
+}
+
+}  // namespace
+
+int fnx_jpeg_decode_batch(fnx_ctx *ctx, int n, const uint8_t *const *files, const size_t *sizes, uint8_t *const *dsts, const int *dstrides,
+                          int *ws, int *hs, int *status)
+{
+    FNX_ENTER(ctx);
+    FNX_REQUIRE(n >= 1 && n <= FNX_BATCH_MAX, "decode batch: n must be 1..FNX_BATCH_MAX (65535)");
+    FNX_REQUIRE(files && sizes && dsts && dstrides && ws && hs && status, "decode batch: NULL array");
+    FNX_REQUIRE(ctx->res_count == 0, "enqueued batches are waiting for fnx_results_fetch: fetch them before a blocking batch call");
+    return jpeg_decode_batch_device(ctx, n, files, sizes, dsts, dstrides, ws, hs, status);
 }
 
 // host only: jpeg_prog.cpp's output as the tests and the sanitizer runs read it
@@ -859,5 +972,89 @@ int fnx_jpeg_recompress(fnx_ctx *ctx, const uint8_t *data, size_t n, double targ
     }
     FNX_TRY(jpeg_search_device(ctx, ref, orig, f.w, f.h, target_ssim, window, quality, ssim, steps));
     return jpeg_file_from_planes(ctx, orig, f.w, f.h, *quality, out, cap, nbytes);
+}
+
+// CompressBatch's item body for n JPEG files: fnx_jpeg_decode_batch into tight images in SLOT_JPEG_DEC_IMG, then
+// fnx_jpeg_compress_batch's body once per geometry.  Per item the single call's results, by two equalities the tests pin:
+// fnx_jpeg_recompress == fnx_jpeg_compress of the decoded image, and fnx_jpeg_compress_batch's item == fnx_jpeg_compress.
+int fnx_jpeg_recompress_batch(fnx_ctx *ctx, int n, const uint8_t *const *files, const size_t *sizes, const double *target_ssim,
+                              const double *window, uint8_t *const *outs, const size_t *caps, size_t *nbytes, int *quality, double *ssim,
+                              int *steps, int *ws, int *hs, int *status)
+{
+    FNX_ENTER(ctx);
+    FNX_REQUIRE(n >= 1 && n <= FNX_BATCH_MAX, "recompress batch: n must be 1..FNX_BATCH_MAX (65535)");
+    FNX_REQUIRE(files && sizes && target_ssim && outs && caps && nbytes && quality && ssim && ws && hs && status, "recompress batch: NULL array");
+    FNX_REQUIRE(window != nullptr, "recompress batch: NULL window");
+    for (int i = 0; i < n; i++) {
+        if (!outs[i]) {
+            set_error("invalid argument: recompress batch: outs[%d] is NULL", i);
+            return FNX_ERR_INVALID;
+        }
+    }
+    FNX_REQUIRE(ctx->res_count == 0, "enqueued batches are waiting for fnx_results_fetch: fetch them before a blocking batch call");
+    std::vector<uint8_t *> dst;
+    std::vector<int> dstride, idx;
+    std::vector<size_t> off;
+    std::vector<const uint8_t *> g_src;
+    std::vector<uint8_t *> g_out;
+    std::vector<double> g_target, g_ssim;
+    std::vector<size_t> g_cap, g_nbytes;
+    std::vector<int> g_quality, g_steps, g_status;
+    // spans of the batch whose decoded images fit JPEG_BATCH_SCRATCH together (at least one file each)
+    for (int s0 = 0; s0 < n;) {
+        int s1 = s0;
+        size_t total = 0;
+        off.clear();
+        for (; s1 < n; s1++) {
+            int w = 0, h = 0;
+            JpegFile f;
+            if (files[s1] && jpeg_parse(files[s1], sizes[s1], &f) >= 0) { w = f.w; h = f.h; }
+            const size_t b = al256(static_cast<size_t>(w) * h * 4 + 16);
+            if (s1 > s0 && total + b > JPEG_BATCH_SCRATCH) break;
+            off.push_back(total);
+            total += b;
+            ws[s1] = w; hs[s1] = h;
+        }
+        const int m = s1 - s0;
+        void *t = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_JPEG_DEC_IMG, total, &t));
+        dst.assign(m, nullptr);
+        dstride.assign(m, 0);
+        for (int i = 0; i < m; i++) {
+            nbytes[s0 + i] = 0;
+            if (ws[s0 + i] <= 0) continue;                   // (the decoder answers for a file that does not parse)
+            dst[i] = static_cast<uint8_t *>(t) + off[i];
+            dstride[i] = ws[s0 + i] * 4;
+        }
+        FNX_TRY(jpeg_decode_batch_device(ctx, m, files + s0, sizes + s0, dst.data(), dstride.data(), ws + s0, hs + s0, status + s0));
+        // every geometry's items that decoded, in the batch's order
+        std::vector<char> taken(m, 0);
+        for (int i = 0; i < m; i++) {
+            if (taken[i] || status[s0 + i] != FNX_OK) continue;
+            const int w = ws[s0 + i], h = hs[s0 + i];
+            idx.clear();
+            for (int j = i; j < m; j++)
+                if (!taken[j] && status[s0 + j] == FNX_OK && ws[s0 + j] == w && hs[s0 + j] == h) {
+                    taken[j] = 1;
+                    idx.push_back(j);
+                }
+            const int g = static_cast<int>(idx.size());
+            g_src.resize(g); g_out.resize(g); g_target.resize(g); g_ssim.resize(g); g_cap.resize(g); g_nbytes.resize(g);
+            g_quality.resize(g); g_steps.resize(g); g_status.resize(g);
+            for (int j = 0; j < g; j++) {
+                const int k = s0 + idx[j];
+                g_src[j] = dst[idx[j]]; g_out[j] = outs[k]; g_target[j] = target_ssim[k]; g_cap[j] = caps[k];
+            }
+            FNX_TRY(jpeg_compress_group(ctx, g, g_src.data(), w * 4, w, h, g_target.data(), window, g_out.data(), g_cap.data(), g_nbytes.data(),
+                                        g_quality.data(), g_ssim.data(), g_steps.data(), g_status.data()));
+            for (int j = 0; j < g; j++) {
+                const int k = s0 + idx[j];
+                nbytes[k] = g_nbytes[j]; quality[k] = g_quality[j]; ssim[k] = g_ssim[j]; status[k] = g_status[j];
+                if (steps) steps[k] = g_steps[j];
+            }
+        }
+        s0 = s1;
+    }
+    return FNX_OK;
 }
 }  // extern "C"

@@ -268,11 +268,11 @@ __device__ __forceinline__ void dec_stage(DecShared &sh, const DecArgs &a, long 
 
 // <false>: workgroup g owns spans [g OWN, (g + 1) OWN) and decodes the WARM spans before them as well (their results
 // are dropped).  <true>: the same ownership, no warm-up -- only a workgroup whose predecessor ended elsewhere runs.
+// The body of both launches: g is the workgroup's number INSIDE ITS FILE (a's arrays are that file's), flag the round's word.
 template <bool FIX, bool RST>
-__global__ __launch_bounds__(256) void jpeg_dsync_kernel(DecArgs a)
+__device__ __forceinline__ void dec_sync_body(DecShared &sh, const DecArgs &a, const int g, uint32_t *flag)
 {
-    __shared__ DecShared sh;
-    const int g = blockIdx.x, t = threadIdx.x;
+    const int t = threadIdx.x;
     const long long span0 = static_cast<long long>(g) * DEC_OWN - (FIX ? 0 : DEC_WARM);
     const long long gs = span0 + t;
     const bool live = gs >= 0 && gs < a.nlanes && (!FIX || t < DEC_OWN);
@@ -370,7 +370,7 @@ __global__ __launch_bounds__(256) void jpeg_dsync_kernel(DecArgs a)
         __hip_atomic_store(&a.s_out[gs], my_out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         a.cnt[gs] = my_cnt;
     }
-    if (FIX && t == 0) a.flag[0] = 1u;
+    if (FIX && t == 0) flag[0] = 1u;
     if (a.dbg) {
         if (t == 0) {
             atomicMax(&a.dbg[0], passes);
@@ -380,16 +380,44 @@ __global__ __launch_bounds__(256) void jpeg_dsync_kernel(DecArgs a)
     }
 }
 
-template <bool RST>
-__global__ __launch_bounds__(256) void jpeg_dwrite_kernel(DecArgs a)
+template <bool FIX, bool RST>
+__global__ __launch_bounds__(256) void jpeg_dsync_kernel(DecArgs a)
 {
     __shared__ DecShared sh;
-    const int g = blockIdx.x, t = threadIdx.x, gt = g * 256 + t;
+    dec_sync_body<FIX, RST>(sh, a, blockIdx.x, a.flag);
+}
+
+// ---- a chunk of files per launch (fnx_jpeg_decode_batch) ----
+// One file's scan is ~215 workgroups at 4K and a handful for a thumbnail: a chunk of files shares every launch.  The files'
+// DecArgs sit in a device array, each with ITS slice of the chunk's arrays (its own scan with its own zero look-ahead and
+// limits, tables, restart offsets; lanes and blocks laid end to end without gaps), and blockIdx.x finds (file, workgroup in
+// the file) in a flattened table -- a grid of "largest file x files" would park a DecShared on workgroups that have nothing
+// to do.  The body is the single file's: a workgroup never looks outside its file's slice.
+struct DecWg {
+    int file, wg;
+};
+
+template <bool FIX, bool RST>
+__global__ __launch_bounds__(256) void jpeg_dsync_batch_kernel(const DecArgs *__restrict__ files, const DecWg *__restrict__ wgs, uint32_t *flag)
+{
+    __shared__ DecShared sh;
+    const DecWg w = wgs[blockIdx.x];
+    const DecArgs a = files[w.file];
+    dec_sync_body<FIX, RST>(sh, a, w.wg, flag);
+}
+
+// BATCH: first_blk is the file's slice of a prefix sum over the whole chunk's lanes -- a lane's first block is its prefix
+// minus the prefix at the file's first lane
+template <bool RST, bool BATCH>
+__device__ __forceinline__ void dec_write_body(DecShared &sh, const DecArgs &a, const int g)
+{
+    const int t = threadIdx.x, gt = g * 256 + t;
     dec_stage(sh, a, static_cast<long long>(g) * 256, a.tab, static_cast<int>(sizeof(DecTables)));
     __syncthreads();
     if (gt >= a.nlanes) return;
     const unsigned long long st = a.s_in[gt];
-    long long blk = static_cast<long long>(a.first_blk[gt]);
+    const unsigned long long fb0 = BATCH ? a.first_blk[0] : 0ull;
+    long long blk = static_cast<long long>(a.first_blk[gt] - fb0);
     if (RST && a.nrst > 0) {
         // Block numbers are counted from the restart interval's start, not from the file's: the sync passes go by position and
         // cannot know when an interval's blocks are complete, so the <= 7 bits a DAMAGED interval leaves before its boundary
@@ -406,7 +434,7 @@ __global__ __launch_bounds__(256) void jpeg_dwrite_kernel(DecArgs a)
         const int j = lo_k - 1;
         if (j >= 0) {
             const unsigned long long rec = a.rst_rec[j];
-            const long long before = static_cast<long long>(a.first_blk[rec >> 32]) + static_cast<long long>(rec & 0xffffffffull);
+            const long long before = static_cast<long long>(a.first_blk[rec >> 32] - fb0) + static_cast<long long>(rec & 0xffffffffull);
             blk = static_cast<long long>(j + 1) * a.ri_blocks + (blk - before);
         }
     }
@@ -419,6 +447,30 @@ __global__ __launch_bounds__(256) void jpeg_dwrite_kernel(DecArgs a)
     dec_span<true, RST>(sh, a, rel, z, slot, static_cast<uint32_t>(t + 1) * DEC_SPAN, cnt, blk, bad, static_cast<long long>(wg_bit),
                         left > 0xfffffff0ull ? 0xfffffff0u : static_cast<uint32_t>(left));
     if (bad) atomicOr(a.err, bad);
+}
+
+template <bool RST>
+__global__ __launch_bounds__(256) void jpeg_dwrite_kernel(DecArgs a)
+{
+    __shared__ DecShared sh;
+    dec_write_body<RST, false>(sh, a, blockIdx.x);
+}
+
+// what the host reads of a file when the chunk is done (the single file's d_flag + 64: err, then the blocks finished)
+struct DecResult {
+    uint32_t err, pad;
+    unsigned long long blocks;
+};
+
+template <bool RST>
+__global__ __launch_bounds__(256) void jpeg_dwrite_batch_kernel(const DecArgs *__restrict__ files, const DecWg *__restrict__ wgs)
+{
+    __shared__ DecShared sh;
+    const DecWg w = wgs[blockIdx.x];
+    const DecArgs a = files[w.file];
+    // the blocks finished inside the file's string: the difference of two bases (the prefix sum runs one lane past the chunk's last)
+    if (w.wg == 0 && threadIdx.x == 0) reinterpret_cast<DecResult *>(a.err)->blocks = a.first_blk[a.nlanes] - a.first_blk[0];
+    dec_write_body<RST, true>(sh, a, w.wg);
 }
 
 // ---- DC prediction and the blocks ----
@@ -435,11 +487,22 @@ __device__ __forceinline__ int dc_place(int b, int nmcu, int ny, int nc)
     return j < ny ? m * ny + j : (ny + (j - ny)) * nmcu + m;
 }
 
-__global__ __launch_bounds__(256) void jpeg_dc_gather_kernel(DcArgs a)
+__device__ __forceinline__ void dc_gather_body(const DcArgs &a, const int b)
 {
-    const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= a.nblk) return;
     a.dcb[dc_place(b, a.nmcu, a.ny, a.nc)] = static_cast<uint32_t>(static_cast<int32_t>(a.coef[static_cast<size_t>(b) * 64]) + 2048);
+}
+
+__global__ __launch_bounds__(256) void jpeg_dc_gather_kernel(DcArgs a)
+{
+    dc_gather_body(a, blockIdx.x * 256 + threadIdx.x);
+}
+
+// (coef and dcb: the file's slices of the chunk's arrays)
+__global__ __launch_bounds__(256) void jpeg_dc_gather_batch_kernel(const DcArgs *__restrict__ files, const DecWg *__restrict__ wgs)
+{
+    const DecWg w = wgs[blockIdx.x];
+    dc_gather_body(files[w.file], w.wg * 256 + threadIdx.x);
 }
 
 struct IdctArgs {
@@ -454,10 +517,8 @@ struct IdctArgs {
     uint16_t q[4][64];                   // natural order (a fourth plane -- the black of a CMYK file -- only with abs_dc)
 };
 
-__global__ __launch_bounds__(256) void jpeg_didct_kernel(IdctArgs a)
+__device__ __forceinline__ void dec_idct_body(const IdctArgs &a, const int plane, const int i)
 {
-    const int plane = blockIdx.y;
-    const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.nblocks[plane]) return;
     const int by = i / a.nbx[plane], bx = i - by * a.nbx[plane];
     const int ny = a.hy * a.vy, per = ny + a.nc;
@@ -510,6 +571,19 @@ __global__ __launch_bounds__(256) void jpeg_didct_kernel(IdctArgs a)
     }
 }
 
+__global__ __launch_bounds__(256) void jpeg_didct_kernel(IdctArgs a)
+{
+    dec_idct_body(a, blockIdx.y, blockIdx.x * 256 + threadIdx.x);
+}
+
+// coef, dcb and dcsum are the file's slices: the DC is a DIFFERENCE of two prefix sums inside the file's own blocks, so a
+// prefix sum over the whole chunk's blocks serves every file.  nblocks[c] = 0 for a plane the file does not have.
+__global__ __launch_bounds__(256) void jpeg_didct_batch_kernel(const IdctArgs *__restrict__ files, const DecWg *__restrict__ wgs)
+{
+    const DecWg w = wgs[blockIdx.x];
+    dec_idct_body(files[w.file], blockIdx.y, w.wg * 256 + threadIdx.x);
+}
+
 // ---- the host side (segments, tables, the scan without its stuffing: jpeg_parse.cpp) and the launches ----
 constexpr int SCAN_PER_WG_D = 2048;
 
@@ -558,6 +632,74 @@ static int jpeg_decode_planes_progressive(fnx_ctx *ctx, const uint8_t *data, siz
     FNX_HIP(hipGetLastError());
     FNX_TRY(prof_end(ctx));
     f->rounds = 0;
+    return FNX_OK;
+}
+
+// the sync passes' form of a file's tables (common.hpp: DecSyncTables)
+static void dec_sync_tables(const DecTables &tab, DecSyncTables *ts)
+{
+    std::memcpy(ts->limit, tab.limit, sizeof(ts->limit));
+    std::memcpy(ts->delta, tab.delta, sizeof(ts->delta));
+    std::memcpy(ts->value, tab.value, sizeof(ts->value));
+    auto effect = [](uint32_t e, bool ac, uint32_t *bits, uint32_t *step) {        // one symbol of the write pass's table
+        const uint32_t len = e >> 8, sym = e & 0xffu, sz = sym & 15u, r = sym >> 4;
+        *bits = len + sz;
+        *step = !ac ? 1u : ((sz == 0 && r != 15) ? 64u : r + 1u);
+    };
+    for (int t = 0; t < 2; t++)
+        for (int i = 0; i < (1 << DEC_FAST_BITS); i++) {
+            const uint32_t e = tab.fast[t][i];
+            uint32_t b1 = 0, s1 = 0;
+            if (e) effect(e, false, &b1, &s1);
+            ts->st[t][i] = e ? (b1 | (s1 << 8)) : 0u;
+        }
+    for (int t = 0; t < 2; t++)
+        for (int i = 0; i < (1 << DEC_FAST_BITS); i++) {
+            const uint32_t e = tab.fast[2 + t][i];
+            uint32_t v = 0;
+            if (e) {
+                uint32_t b1, s1;
+                effect(e, true, &b1, &s1);
+                v = b1 | (s1 << 8);
+                // a second symbol: the block goes on, and the code after symbol 1's bits lies inside the prefix
+                if (s1 < 64 && b1 < static_cast<uint32_t>(DEC_FAST_BITS)) {
+                    const uint32_t rest = (static_cast<uint32_t>(i) << b1) & ((1u << DEC_FAST_BITS) - 1u);   // what is known of the bits behind it
+                    const uint32_t e2 = tab.fast[2 + t][rest];
+                    if (e2 && (e2 >> 8) <= static_cast<uint32_t>(DEC_FAST_BITS) - b1) {      // every prefix with these known bits holds this code
+                        uint32_t b2, s2;
+                        effect(e2, true, &b2, &s2);
+                        v |= ((b1 + b2) << 16) | ((s1 + s2) << 24);
+                    }
+                }
+            }
+            ts->st[2 + t][i] = v;
+        }
+}
+
+// a baseline file's dequantisation + IDCT launch: coef / dcb / dcsum are its blocks', planes its Y, Cb, Cr (MCU-padded)
+static IdctArgs dec_idct_args(const JpegFile &f, const int16_t *coef, const uint32_t *dcb, const unsigned long long *dcsum, uint8_t *const planes[3])
+{
+    const int ys = 8 * f.hy * f.mx, yh = 8 * f.vy * f.my, cs = 8 * f.mx, chh = 8 * f.my;
+    IdctArgs ia{};
+    ia.coef = coef; ia.dcb = dcb; ia.dcsum = dcsum;
+    for (int c = 0; c < 3; c++) {
+        ia.out[c] = planes[c];
+        ia.stride[c] = c ? cs : ys;
+        ia.nbx[c] = (c ? cs : ys) / 8;
+        ia.nblocks[c] = ia.nbx[c] * ((c ? chh : yh) / 8);
+        for (int k = 0; k < 64; k++) ia.q[c][k] = f.q[c][k];
+    }
+    ia.mx = f.mx; ia.nmcu = f.mx * f.my; ia.hy = f.hy; ia.vy = f.vy; ia.nc = f.ncomp - 1; ia.ri = f.ri; ia.abs_dc = 0;
+    return ia;
+}
+
+// the write pass's complaints and the blocks the scan held, as fnx_jpeg_decode answers them
+static int dec_verdict(uint32_t err, unsigned long long blocks, int nblk)
+{
+    if (blocks < static_cast<unsigned long long>(nblk)) return jpeg_corrupt("the scan ends before the last block");
+    if (err & 8u) return jpeg_corrupt("the scan ends before the last block");
+    if (err & 16u) return jpeg_corrupt("a restart interval does not hold the blocks it should");
+    if (err) return jpeg_corrupt("the scan holds a code outside its Huffman table or a run past the end of a block");
     return FNX_OK;
 }
 
@@ -623,45 +765,7 @@ int jpeg_decode_planes(fnx_ctx *ctx, const uint8_t *data, size_t n, JpegFile *f,
     *ystride = ys; *cstride = cs;
 
     std::memcpy(tpin, &f->tab, sizeof(DecTables));
-    {   // the sync passes' form of the tables (common.hpp: DecSyncTables)
-        DecSyncTables *ts = reinterpret_cast<DecSyncTables *>(static_cast<uint8_t *>(tpin) + sizeof(DecTables));
-        std::memcpy(ts->limit, f->tab.limit, sizeof(ts->limit));
-        std::memcpy(ts->delta, f->tab.delta, sizeof(ts->delta));
-        std::memcpy(ts->value, f->tab.value, sizeof(ts->value));
-        auto effect = [](uint32_t e, bool ac, uint32_t *bits, uint32_t *step) {        // one symbol of the write pass's table
-            const uint32_t len = e >> 8, sym = e & 0xffu, sz = sym & 15u, r = sym >> 4;
-            *bits = len + sz;
-            *step = !ac ? 1u : ((sz == 0 && r != 15) ? 64u : r + 1u);
-        };
-        for (int t = 0; t < 2; t++)
-            for (int i = 0; i < (1 << DEC_FAST_BITS); i++) {
-                const uint32_t e = f->tab.fast[t][i];
-                uint32_t b1 = 0, s1 = 0;
-                if (e) effect(e, false, &b1, &s1);
-                ts->st[t][i] = e ? (b1 | (s1 << 8)) : 0u;
-            }
-        for (int t = 0; t < 2; t++)
-            for (int i = 0; i < (1 << DEC_FAST_BITS); i++) {
-                const uint32_t e = f->tab.fast[2 + t][i];
-                uint32_t v = 0;
-                if (e) {
-                    uint32_t b1, s1;
-                    effect(e, true, &b1, &s1);
-                    v = b1 | (s1 << 8);
-                    // a second symbol: the block goes on, and the code after symbol 1's bits lies inside the prefix
-                    if (s1 < 64 && b1 < static_cast<uint32_t>(DEC_FAST_BITS)) {
-                        const uint32_t rest = (static_cast<uint32_t>(i) << b1) & ((1u << DEC_FAST_BITS) - 1u);   // what is known of the bits behind it
-                        const uint32_t e2 = f->tab.fast[2 + t][rest];
-                        if (e2 && (e2 >> 8) <= static_cast<uint32_t>(DEC_FAST_BITS) - b1) {      // every prefix with these known bits holds this code
-                            uint32_t b2, s2;
-                            effect(e2, true, &b2, &s2);
-                            v |= ((b1 + b2) << 16) | ((s1 + s2) << 24);
-                        }
-                    }
-                }
-                ts->st[2 + t][i] = v;
-            }
-    }
+    dec_sync_tables(f->tab, reinterpret_cast<DecSyncTables *>(static_cast<uint8_t *>(tpin) + sizeof(DecTables)));
     FNX_HIP(hipMemcpyAsync(d_ecs, pin, nwords * 4, hipMemcpyHostToDevice, ctx->stream));
     FNX_HIP(hipMemcpyAsync(d_tab, tpin, sizeof(DecTables) + sizeof(DecSyncTables) + 4 * rst.size(), hipMemcpyHostToDevice, ctx->stream));
     FNX_HIP(hipMemsetAsync(d_flag, 0, b_flag, ctx->stream));
@@ -715,16 +819,7 @@ int jpeg_decode_planes(fnx_ctx *ctx, const uint8_t *data, size_t n, JpegFile *f,
     DcArgs da{d_coef, d_dcb, nblk, static_cast<int>(nmcu), f->hy * f->vy, f->ncomp - 1};
     hipLaunchKernelGGL(jpeg_dc_gather_kernel, dim3((nblk + 255) / 256), dim3(256), 0, ctx->stream, da);
     FNX_TRY(launch_scan(ctx, d_dcb, d_dcs, d_tot2, nblk, nullptr));
-    IdctArgs ia{};
-    ia.coef = d_coef; ia.dcb = d_dcb; ia.dcsum = d_dcs;
-    for (int c = 0; c < 3; c++) {
-        ia.out[c] = planes[c];
-        ia.stride[c] = c ? cs : ys;
-        ia.nbx[c] = (c ? cs : ys) / 8;
-        ia.nblocks[c] = ia.nbx[c] * ((c ? chh : yh) / 8);
-        for (int k = 0; k < 64; k++) ia.q[c][k] = f->q[c][k];
-    }
-    ia.mx = f->mx; ia.nmcu = static_cast<int>(nmcu); ia.hy = f->hy; ia.vy = f->vy; ia.nc = f->ncomp - 1; ia.ri = f->ri; ia.abs_dc = 0;
+    const IdctArgs ia = dec_idct_args(*f, d_coef, d_dcb, d_dcs, planes);
     hipLaunchKernelGGL(jpeg_didct_kernel, dim3((ia.nblocks[0] + 255) / 256, f->ncomp), dim3(256), 0, ctx->stream, ia);
     FNX_HIP(hipGetLastError());
     // what the scan held: blocks finished inside the string, and the write pass's complaints
@@ -736,10 +831,220 @@ int jpeg_decode_planes(fnx_ctx *ctx, const uint8_t *data, size_t n, JpegFile *f,
         std::fprintf(stderr, "[fennec jpeg] %d x %d, %zu scan bytes, %d lanes in %d workgroups: passes max %u avg %.1f, lane-decodes %u (%.2f per lane), "
                              "cross-workgroup rounds %d\n", f->w, f->h, nb, nlanes, nwg, dbg[0], double(dbg[1]) / nwg, dbg[2], double(dbg[2]) / nlanes, f->rounds);
     }
-    if (chk.blocks < static_cast<unsigned long long>(nblk)) return jpeg_corrupt("the scan ends before the last block");
-    if (chk.err & 8u) return jpeg_corrupt("the scan ends before the last block");
-    if (chk.err & 16u) return jpeg_corrupt("a restart interval does not hold the blocks it should");
-    if (chk.err) return jpeg_corrupt("the scan holds a code outside its Huffman table or a run past the end of a block");
+    return dec_verdict(chk.err, chk.blocks, nblk);
+}
+
+// ---- a chunk of baseline files in one set of launches (fnx_jpeg_decode_batch) ----
+// Device layout of a chunk (SLOT_JPEG_DEC), m files of which the live ones passed the host's refusals:
+//   uploaded slice 1   every file's scan without its stuffing (own slice, own four words of zero look-ahead), then every
+//                      file's DecTables | DecSyncTables | restart offsets -- ONE pinned slice, one copy
+//   uploaded slice 2   DecArgs[m] | DcArgs[m] | IdctArgs[m] | the five workgroup tables -- one copy
+//   per lane           s_in, s_out, first_blk: the live files' lanes end to end, NO gaps, one lane more at the end (whose count
+//                      is zero: first_blk there is the chunk's total, so every file's blocks are a difference of two bases)
+//   zeroed at once     64 round flags | DecResult[m] | cnt (per lane)
+//   per block          coef (zeroed), dcb, dcsum: the live files' blocks end to end; rst_rec: their boundaries end to end
+// Host waits: one per pair of repair rounds (shared by every file: quiet = no workgroup of ANY file decoded again), one for
+// every file's DecResult.  Nothing else -- unless the pinned ring wraps (runtime.cpp), which waits for the stream first.
+size_t jpeg_decode_chunk_bytes(const JpegFile &f, size_t n)
+{
+    const size_t scan = n - f.scan;
+    const unsigned long long hdr = static_cast<unsigned long long>(f.mx) * f.my * f.nslots;
+    const unsigned long long nblk = hdr < 4ull * scan ? hdr : 4ull * scan;          // (a scan holds at most 4 blocks a byte)
+    const size_t lanes = scan * 8 / DEC_SPAN + 2;
+    return scan + 4 * (scan / 2 + 1 < hdr ? scan / 2 + 1 : static_cast<size_t>(hdr)) + sizeof(DecTables) + sizeof(DecSyncTables) + sizeof(DecArgs) + sizeof(DcArgs) +
+           sizeof(IdctArgs) + 1024 + 28 * lanes + static_cast<size_t>(nblk) * (128 + 4 + 8 + 8 + 64);
+}
+
+int jpeg_decode_planes_chunk(fnx_ctx *ctx, int m, JpegBatchItem *it)
+{
+    auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+    struct Plan {
+        size_t o_ecs = 0, o_tab = 0, nb = 0, nwords = 0, nrst = 0;
+        size_t lane0 = 0, blk0 = 0, rec0 = 0, o_planes = 0, b_y = 0, b_c = 0;
+        int nlanes = 0, nblk = 0;
+        bool live = false;
+    };
+    std::vector<Plan> pl(m);
+    // slice 1, sized by the files' bytes (never by a header): scans, then tables + restart offsets
+    size_t up = 0;
+    for (int i = 0; i < m; i++) {
+        pl[i].o_ecs = up;
+        up += al((it[i].n - it[i].f.scan + 64 + 63) & ~size_t(63));                // >= the scan + 4 words of zeros
+    }
+    for (int i = 0; i < m; i++) {
+        const JpegFile &f = it[i].f;
+        const size_t by_file = (it[i].n - f.scan) / 2 + 1;                          // a restart marker is two bytes
+        const unsigned long long by_hdr = f.ri > 0 ? (static_cast<unsigned long long>(f.mx) * f.my + f.ri - 1) / f.ri : 0;
+        pl[i].o_tab = up;
+        up += al(sizeof(DecTables) + sizeof(DecSyncTables) + 4 * (by_hdr < by_file ? static_cast<size_t>(by_hdr) : by_file) + 16);
+    }
+    void *pin = nullptr;
+    FNX_TRY(pinned_alloc(ctx, up, &pin));
+    uint8_t *hp = static_cast<uint8_t *>(pin);
+    std::vector<uint32_t> rst;
+    size_t L = 0, NB = 0, NR = 0, PB = 0;
+    size_t n_sync = 0, n_fix = 0, n_write = 0, n_gather = 0, n_idct = 0;
+    bool any_rst = false;
+    for (int i = 0; i < m; i++) {
+        JpegFile &f = it[i].f;
+        Plan &p = pl[i];
+        it[i].status = jpeg_unstuff(it[i].data, it[i].n, f, hp + p.o_ecs, &p.nb, &rst);
+        if (it[i].status < 0) continue;
+        p.nwords = (p.nb + 3) / 4 + 4;
+        std::memset(hp + p.o_ecs + p.nb, 0, p.nwords * 4 - p.nb);
+        // the single file's refusals (jpeg_decode_planes), before anything is sized by the header
+        const unsigned long long nbits = 8ull * p.nb;
+        const size_t nlanes_z = static_cast<size_t>((nbits + DEC_SPAN - 1) / DEC_SPAN);
+        const long long nblk_ll = static_cast<long long>(f.mx) * f.my * f.nslots;
+        if (nlanes_z == 0) it[i].status = jpeg_corrupt("an empty scan");
+        else if (nlanes_z >= (size_t(1) << 30) || nblk_ll >= (1ll << 30)) it[i].status = jpeg_unsupported("a file this large");
+        else if (nbits < 2ull * static_cast<unsigned long long>(nblk_ll)) it[i].status = jpeg_corrupt("the scan is too short for the image's blocks");
+        if (it[i].status < 0) continue;
+        uint8_t *tp = hp + p.o_tab;
+        std::memcpy(tp, &f.tab, sizeof(DecTables));
+        dec_sync_tables(f.tab, reinterpret_cast<DecSyncTables *>(tp + sizeof(DecTables)));
+        if (!rst.empty()) std::memcpy(tp + sizeof(DecTables) + sizeof(DecSyncTables), rst.data(), 4 * rst.size());
+        p.nrst = rst.size();
+        p.nlanes = static_cast<int>(nlanes_z);
+        p.nblk = static_cast<int>(nblk_ll);
+        p.b_y = al(static_cast<size_t>(8 * f.hy * f.mx) * (8 * f.vy * f.my));
+        p.b_c = al(static_cast<size_t>(8 * f.mx) * (8 * f.my));
+        p.lane0 = L; L += p.nlanes;
+        p.blk0 = NB; NB += p.nblk;
+        p.rec0 = NR; NR += p.nrst;
+        p.o_planes = PB; PB += p.b_y + 2 * p.b_c;
+        const size_t nwg = (p.nlanes + DEC_OWN - 1) / DEC_OWN;
+        n_sync += nwg;
+        n_fix += nwg - 1;                                                            // (a file's workgroup 0 has no predecessor: never repaired)
+        n_write += (p.nlanes + 255) / 256;
+        n_gather += (p.nblk + 255) / 256;
+        n_idct += (static_cast<size_t>(f.hy * f.mx) * (f.vy * f.my) + 255) / 256;
+        any_rst = any_rst || p.nrst > 0;
+        p.live = true;
+    }
+    if (L == 0) return FNX_OK;                                                       // every file refused
+    FNX_REQUIRE(L + 1 < (size_t(1) << 30) && NB < (size_t(1) << 30), "decode batch: a chunk of more than 2^30 lanes or blocks");
+    const size_t lanes = L + 1;
+
+    const size_t o_args = 0, o_dc = o_args + al(sizeof(DecArgs) * m), o_idct = o_dc + al(sizeof(DcArgs) * m), o_wgs = o_idct + al(sizeof(IdctArgs) * m);
+    const size_t n_wgs = n_sync + n_fix + n_write + n_gather + n_idct;
+    const size_t up2 = o_wgs + al(sizeof(DecWg) * n_wgs);
+    const size_t b_state = al(8 * lanes), b_tot = al(8 * (lanes / SCAN_PER_WG_D + 2)), b_flag = al(4 * 64), b_res = al(sizeof(DecResult) * m), b_cnt = al(4 * lanes),
+                 b_coef = al(sizeof(int16_t) * 64 * NB), b_dcb = al(4 * NB), b_dcs = al(8 * NB), b_tot2 = al(8 * (NB / SCAN_PER_WG_D + 2)), b_rec = al(8 * (NR + 1));
+    void *sc = nullptr, *plv = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_JPEG_DEC, up + up2 + 3 * b_state + b_tot + b_flag + b_res + b_cnt + b_coef + b_dcb + b_dcs + b_tot2 + b_rec, &sc));
+    FNX_TRY(scratch(ctx, SLOT_JPEG_DEC_PLANES, PB, &plv));
+    unsigned char *q = static_cast<unsigned char *>(sc);
+    unsigned char *d_up = q; q += up;
+    unsigned char *d_up2 = q; q += up2;
+    unsigned long long *d_in = reinterpret_cast<unsigned long long *>(q); q += b_state;
+    unsigned long long *d_out = reinterpret_cast<unsigned long long *>(q); q += b_state;
+    unsigned long long *d_first = reinterpret_cast<unsigned long long *>(q); q += b_state;
+    unsigned long long *d_tot = reinterpret_cast<unsigned long long *>(q); q += b_tot;
+    uint32_t *d_flag = reinterpret_cast<uint32_t *>(q); q += b_flag;
+    DecResult *d_res = reinterpret_cast<DecResult *>(q); q += b_res;
+    uint32_t *d_cnt = reinterpret_cast<uint32_t *>(q); q += b_cnt;
+    int16_t *d_coef = reinterpret_cast<int16_t *>(q); q += b_coef;
+    uint32_t *d_dcb = reinterpret_cast<uint32_t *>(q); q += b_dcb;
+    unsigned long long *d_dcs = reinterpret_cast<unsigned long long *>(q); q += b_dcs;
+    unsigned long long *d_tot2 = reinterpret_cast<unsigned long long *>(q); q += b_tot2;
+    unsigned long long *d_rec = reinterpret_cast<unsigned long long *>(q);
+    // slice 1 goes up before slice 2 is asked for: should the ring wrap there, it waits for this copy first
+    FNX_HIP(hipMemcpyAsync(d_up, hp, up, hipMemcpyHostToDevice, ctx->stream));
+    FNX_HIP(hipMemsetAsync(d_flag, 0, b_flag + b_res + b_cnt, ctx->stream));
+    FNX_HIP(hipMemsetAsync(d_coef, 0, sizeof(int16_t) * 64 * NB, ctx->stream));
+    if (NR) FNX_HIP(hipMemsetAsync(d_rec, 0, 8 * NR, ctx->stream));
+
+    void *pin2 = nullptr;
+    FNX_TRY(pinned_alloc(ctx, up2, &pin2));
+    uint8_t *hp2 = static_cast<uint8_t *>(pin2);
+    std::memset(hp2, 0, o_wgs);
+    DecArgs *h_args = reinterpret_cast<DecArgs *>(hp2 + o_args);
+    DcArgs *h_dc = reinterpret_cast<DcArgs *>(hp2 + o_dc);
+    IdctArgs *h_idct = reinterpret_cast<IdctArgs *>(hp2 + o_idct);
+    DecWg *h_wgs = reinterpret_cast<DecWg *>(hp2 + o_wgs);
+    DecWg *w_sync = h_wgs, *w_fix = w_sync + n_sync, *w_write = w_fix + n_fix, *w_gather = w_write + n_write, *w_idct = w_gather + n_gather;
+    for (int i = 0; i < m; i++) {
+        const Plan &p = pl[i];
+        if (!p.live) continue;
+        const JpegFile &f = it[i].f;
+        DecArgs a{};
+        const unsigned char *d_tab = d_up + p.o_tab;
+        a.ecs = reinterpret_cast<const uint32_t *>(d_up + p.o_ecs);
+        a.tab = reinterpret_cast<const DecTables *>(d_tab);
+        a.tab_sync = reinterpret_cast<const DecSyncTables *>(d_tab + sizeof(DecTables));
+        a.s_in = d_in + p.lane0; a.s_out = d_out + p.lane0; a.cnt = d_cnt + p.lane0; a.flag = d_flag;
+        a.first_blk = d_first + p.lane0; a.coef = d_coef + 64 * p.blk0; a.err = &d_res[i].err; a.dbg = nullptr;
+        a.nwords = static_cast<long long>(p.nwords); a.nbits = 8ull * p.nb; a.nlanes = p.nlanes; a.nblk = p.nblk; a.nslots = f.nslots;
+        a.dcpack = f.dcpack; a.acpack = f.acpack;
+        a.rst = reinterpret_cast<const uint32_t *>(d_tab + sizeof(DecTables) + sizeof(DecSyncTables)); a.nrst = static_cast<int>(p.nrst);
+        a.ri_blocks = f.ri * f.nslots;
+        a.rst_rec = d_rec + p.rec0;
+        h_args[i] = a;
+        h_dc[i] = DcArgs{a.coef, d_dcb + p.blk0, p.nblk, f.mx * f.my, f.hy * f.vy, f.ncomp - 1};
+        uint8_t *y = static_cast<uint8_t *>(plv) + p.o_planes;
+        it[i].planes[0] = y; it[i].planes[1] = y + p.b_y; it[i].planes[2] = y + p.b_y + p.b_c;
+        it[i].ystride = 8 * f.hy * f.mx; it[i].cstride = 8 * f.mx;
+        h_idct[i] = dec_idct_args(f, a.coef, d_dcb + p.blk0, d_dcs + p.blk0, it[i].planes);
+        for (int c = f.ncomp; c < 3; c++) h_idct[i].nblocks[c] = 0;
+        const int nwg = (p.nlanes + DEC_OWN - 1) / DEC_OWN, nwg_write = (p.nlanes + 255) / 256, nwg_gather = (p.nblk + 255) / 256,
+                  nwg_idct = (h_idct[i].nblocks[0] + 255) / 256;
+        for (int g = 0; g < nwg; g++) *w_sync++ = DecWg{i, g};
+        for (int g = 1; g < nwg; g++) *w_fix++ = DecWg{i, g};
+        for (int g = 0; g < nwg_write; g++) *w_write++ = DecWg{i, g};
+        for (int g = 0; g < nwg_gather; g++) *w_gather++ = DecWg{i, g};
+        for (int g = 0; g < nwg_idct; g++) *w_idct++ = DecWg{i, g};
+    }
+    FNX_HIP(hipMemcpyAsync(d_up2, hp2, up2, hipMemcpyHostToDevice, ctx->stream));
+    const DecArgs *d_args = reinterpret_cast<const DecArgs *>(d_up2 + o_args);
+    const DecWg *d_wsync = reinterpret_cast<const DecWg *>(d_up2 + o_wgs), *d_wfix = d_wsync + n_sync, *d_wwrite = d_wfix + n_fix,
+                *d_wgather = d_wwrite + n_write, *d_widct = d_wgather + n_gather;
+
+    // the RST forms when any file of the chunk has intervals (a file without them meets no boundary there: same states, same blocks)
+    FNX_TRY(prof_begin(ctx, FNX_PROF_JPEG));
+    if (any_rst) hipLaunchKernelGGL((jpeg_dsync_batch_kernel<false, true>), dim3(static_cast<unsigned>(n_sync)), dim3(256), 0, ctx->stream, d_args, d_wsync, d_flag);
+    else hipLaunchKernelGGL((jpeg_dsync_batch_kernel<false, false>), dim3(static_cast<unsigned>(n_sync)), dim3(256), 0, ctx->stream, d_args, d_wsync, d_flag);
+    FNX_HIP(hipGetLastError());
+    note_route(ctx, FNX_PROF_JPEG, "jpeg_dsync_batch_kernel");
+    FNX_TRY(prof_end(ctx));
+    int rounds = 0;
+    if (n_fix > 0) {
+        uint32_t flags[64];
+        int r = 0;
+        for (;;) {
+            const int r0 = r;
+            for (int k = 0; k < 2 && r < 64; k++, r++) {
+                if (any_rst) hipLaunchKernelGGL((jpeg_dsync_batch_kernel<true, true>), dim3(static_cast<unsigned>(n_fix)), dim3(256), 0, ctx->stream, d_args, d_wfix, d_flag + r);
+                else hipLaunchKernelGGL((jpeg_dsync_batch_kernel<true, false>), dim3(static_cast<unsigned>(n_fix)), dim3(256), 0, ctx->stream, d_args, d_wfix, d_flag + r);
+            }
+            FNX_HIP(hipGetLastError());
+            FNX_TRY(fetch_bytes(ctx, d_flag, flags, sizeof(uint32_t) * static_cast<size_t>(r)));
+            bool quiet = false;
+            for (int k = r0; k < r; k++) quiet = quiet || flags[k] == 0;
+            rounds = r;
+            if (quiet) break;
+            if (r >= 64) {
+                FNX_HIP(hipMemsetAsync(d_flag, 0, 4 * 64, ctx->stream));
+                r = 0;
+            }
+        }
+    }
+    FNX_TRY(launch_scan(ctx, d_cnt, d_first, d_tot, static_cast<int>(lanes), nullptr));
+    if (any_rst) hipLaunchKernelGGL(jpeg_dwrite_batch_kernel<true>, dim3(static_cast<unsigned>(n_write)), dim3(256), 0, ctx->stream, d_args, d_wwrite);
+    else hipLaunchKernelGGL(jpeg_dwrite_batch_kernel<false>, dim3(static_cast<unsigned>(n_write)), dim3(256), 0, ctx->stream, d_args, d_wwrite);
+    hipLaunchKernelGGL(jpeg_dc_gather_batch_kernel, dim3(static_cast<unsigned>(n_gather)), dim3(256), 0, ctx->stream,
+                       reinterpret_cast<const DcArgs *>(d_up2 + o_dc), d_wgather);
+    FNX_TRY(launch_scan(ctx, d_dcb, d_dcs, d_tot2, static_cast<int>(NB), nullptr));
+    hipLaunchKernelGGL(jpeg_didct_batch_kernel, dim3(static_cast<unsigned>(n_idct), 3), dim3(256), 0, ctx->stream,
+                       reinterpret_cast<const IdctArgs *>(d_up2 + o_idct), d_widct);
+    FNX_HIP(hipGetLastError());
+    std::vector<DecResult> res(m);
+    FNX_TRY(fetch_bytes(ctx, d_res, res.data(), sizeof(DecResult) * m));
+    for (int i = 0; i < m; i++) {
+        if (!pl[i].live) continue;
+        it[i].f.rounds = rounds;
+        it[i].status = dec_verdict(res[i].err, res[i].blocks, pl[i].nblk);
+    }
     return FNX_OK;
 }
 

@@ -498,6 +498,29 @@ int fnx_jpeg_compress_batch(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int
                             const double *target_ssim /* n */, const double *window /* 64 */,
                             uint8_t *const *outs, const size_t *caps, size_t *nbytes /* n */, int *quality /* n */,
                             double *ssim /* n */, int *steps /* n, may be NULL */, int *status /* n */);
+/* image.Decode + toNRGBA of n JPEG files in host memory (the loadImage of CompressBatch's items, batch.go:88-122 ->
+ * io.go:60-95) in one call: dsts[i] (DEVICE, stride dstrides[i]) and status[i] are what fnx_jpeg_decode(ctx, files[i], sizes[i],
+ * FNX_DEVICE, dsts[i], dstrides[i], ..) gives, byte for byte, FNX_ERR_UNSUPPORTED / FNX_ERR_INVALID included (a refused file
+ * leaves its destination untouched); ws[i] / hs[i] are set whenever the frame parses (else 0).  The files may differ in every
+ * respect.  Baseline files share ONE set of launches per chunk of at most FNX_JPEG_DECODE_CHUNK files (fewer where their
+ * scratch would pass 1 GiB): every synchronisation round, prefix sum, write pass and IDCT runs once for the chunk, and the
+ * host waits once per pair of repair rounds and once for the chunk's verdicts -- where fnx_jpeg_decode waits at least twice
+ * per file.  Files of the host route (progressive, SOF1, a component per scan, four components) follow one at a time.
+ * dsts[i] == NULL or a stride fnx_jpeg_decode refuses: FNX_ERR_INVALID for that item only.  Returns FNX_OK when the batch ran,
+ * an error for bad arguments (n outside 1..FNX_BATCH_MAX, a NULL array) before anything is launched.  Blocking; needs an empty
+ * result FIFO.  The images are enqueued on the ctx's stream when it returns (as fnx_jpeg_decode with FNX_DEVICE). */
+#define FNX_JPEG_DECODE_CHUNK 32   /* files per set of launches, at most */
+int fnx_jpeg_decode_batch(fnx_ctx *ctx, int n, const uint8_t *const *files, const size_t *sizes, uint8_t *const *dsts,
+                          const int *dstrides, int *ws /* n */, int *hs /* n */, int *status /* n */);
+/* CompressBatch's item body (fnx_jpeg_recompress; batch.go:88-122 -> compress.go:21-87) for n JPEG files in host memory:
+ * fnx_jpeg_decode_batch into images that stay on the device, then fnx_jpeg_compress_batch's search and files once per
+ * geometry among them.  Per item, (file bytes, quality, ssim, steps, w, h) are fnx_jpeg_recompress's for the same file and
+ * target.  status[i]: FNX_OK; the decoder's answer for a file it refused (nbytes[i] = 0); FNX_ERR_INVALID when caps[i] is too
+ * small, with nbytes[i] and quality[i] set as in fnx_jpeg_compress_batch.  Return value as fnx_jpeg_decode_batch. */
+int fnx_jpeg_recompress_batch(fnx_ctx *ctx, int n, const uint8_t *const *files, const size_t *sizes,
+                              const double *target_ssim /* n */, const double *window /* 64 */, uint8_t *const *outs,
+                              const size_t *caps, size_t *nbytes /* n */, int *quality /* n */, double *ssim /* n */,
+                              int *steps /* n, may be NULL */, int *ws /* n */, int *hs /* n */, int *status /* n */);
 
 /* dsts[i] = GaussianBlur(srcs[i]) AND out[i] = SSIMFast(srcs[i], dsts[i]) -- the pair of calls
  * the reference makes whenever it scores a processed image against its source (effects.go:146
