@@ -41,6 +41,7 @@ FNX_OK, FNX_NOOP, FNX_EMPTY = 0, 1, 2
 FNX_HOST, FNX_DEVICE, FNX_DEVICE_SRC = 0, 1, 2
 FNX_BLUR_FAST, FNX_BLUR_EXACT, FNX_BLUR_KEEP_BOX_SUMS = 0, 1, 2
 FNX_PNG_PALETTED, FNX_PNG_GRAY, FNX_PNG_NRGBA = 1, 2, 3      # fnx_png_reduce's kinds (compress.go:90-108)
+FNX_DEFLATE_CHUNK, FNX_DEFLATE_SUB = 32768, 128               # deflate.hip: bytes per chunk (= per workgroup, per block) and per lane
 PROF_MAIN, PROF_SSIM, PROF_RESIZE, PROF_FX, PROF_JPEG = 1, 2, 4, 8, 16
 
 _u8p = C.c_void_p
@@ -256,6 +257,11 @@ def load_library() -> C.CDLL:
         _sig(L, "fnx_png_filter", i, [ctx, i, i, _u8p, i, i, i, i, i, _u8p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i), C.POINTER(i)])
         _sig(L, "fennec_CompressFilePNGStream", i, [ctx, _u8p, C.c_size_t, C.POINTER(FileOptions), C.POINTER(i), _u8p, C.POINTER(i),
                                                      C.POINTER(i), C.POINTER(i), _u8p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i)])
+        _sig(L, "fnx_deflate_bound", C.c_size_t, [C.c_size_t])
+        _sig(L, "fnx_deflate", i, [ctx, i, _u8p, C.c_size_t, i, _u8p, C.c_size_t, C.POINTER(C.c_size_t)])
+        _sig(L, "fnx_png_encode", i, [ctx, i, i, _u8p, i, i, i, i, i, _u8p, _u8p, C.c_size_t, C.POINTER(C.c_size_t)])
+        _sig(L, "fennec_CompressFilePNG", i, [ctx, _u8p, C.c_size_t, C.POINTER(FileOptions), _u8p, C.c_size_t, C.POINTER(C.c_size_t),
+                                               C.POINTER(i), C.POINTER(i)])
         _sig(L, "fennec_gaussianKernel", None, [i, d, _f64p])
         _sig(L, "fennec_blurKernel", i, [d, _f64p])
         _sig(L, "fennec_lanczosKernel", d, [d])
@@ -1460,14 +1466,9 @@ class Context:
         image = buf[:n.value].reshape((h, w, 4) if kind.value == FNX_PNG_NRGBA else (h, w))
         return kind.value, pal[:nc.value].copy(), image, (dims[0], dims[1]), (w, h)
 
-    def png_filter(self, src, kind: int | None = None, ncolors: int = 0, opaque: int = -1, out=None):
-        """The PNG encoder's row stage (fnx_png_filter; compress.go:94-107) -> (stream (h, 1 + n) uint8, color_type, bit_depth):
-        every row packed, filtered by the cheapest of the five PNG filters and led by its type byte -- the bytes zlib reads.
-        src: an (h, w, 4) NRGBA image (kind FNX_PNG_NRGBA; opaque 1 / 0 states whether RGB or RGBA rows are written, -1 decides
-        as image.NRGBA.Opaque() does) or an (h, w) uint8 plane: toGray's (FNX_PNG_GRAY, the default for a plane) or an index
-        plane (FNX_PNG_PALETTED with ncolors, which sets the bit depth).  numpy in, numpy out; a device tensor gives a device
-        tensor, or fills `out` -- a flat uint8 numpy array (the device-source / host-stream form) or device tensor of at least
-        h * (1 + n) bytes, of which the stream's bytes are returned as an (h, 1 + n) view."""
+    @staticmethod
+    def _png_src(src, kind):
+        """(kind, space, pointer, stride, w, h) of png_filter's / png_encode's source: an (h, w, 4) image or an (h, w) plane"""
         torch_src = _is_torch(src)
         if src.ndim == 3:
             v = _Img(src)
@@ -1489,6 +1490,17 @@ class Context:
                 if not isinstance(src, np.ndarray) or src.dtype != np.uint8 or (w > 0 and src.strides[1] != 1):
                     raise FennecError("host planes must be numpy uint8 arrays with contiguous rows")
                 space, ptr, stride = FNX_HOST, src.ctypes.data, int(src.strides[0]) if h > 1 else w
+        return kind, space, ptr, stride, w, h
+
+    def png_filter(self, src, kind: int | None = None, ncolors: int = 0, opaque: int = -1, out=None):
+        """The PNG encoder's row stage (fnx_png_filter; compress.go:94-107) -> (stream (h, 1 + n) uint8, color_type, bit_depth):
+        every row packed, filtered by the cheapest of the five PNG filters and led by its type byte -- the bytes zlib reads.
+        src: an (h, w, 4) NRGBA image (kind FNX_PNG_NRGBA; opaque 1 / 0 states whether RGB or RGBA rows are written, -1 decides
+        as image.NRGBA.Opaque() does) or an (h, w) uint8 plane: toGray's (FNX_PNG_GRAY, the default for a plane) or an index
+        plane (FNX_PNG_PALETTED with ncolors, which sets the bit depth).  numpy in, numpy out; a device tensor gives a device
+        tensor, or fills `out` -- a flat uint8 numpy array (the device-source / host-stream form) or device tensor of at least
+        h * (1 + n) bytes, of which the stream's bytes are returned as an (h, 1 + n) view."""
+        kind, space, ptr, stride, w, h = self._png_src(src, kind)
         n, ct, bd = C.c_size_t(0), C.c_int(0), C.c_int(0)
 
         def call(sp, optr, cap):
@@ -1517,16 +1529,98 @@ class Context:
             self._chk(call(space, optr, cap), "fnx_png_filter")
         return buf[:n.value].reshape(h, n.value // h), ct.value, bd.value
 
-    def compress_png(self, img, level: int = 9) -> bytes:
+    def compress_png(self, img, level: int = 9, device_deflate: bool = False) -> bytes:
         """compressPNG (compress.go:90-108) end to end -> the PNG file: the reduction (png_reduce), the encoder's row stage
         (png_filter) on the reduced image where it lives, then zlib and the chunks on the host (png_file).  The file differs
-        from Go's in the deflate bytes only (Python's zlib is not Go's compress/flate) and decodes to the same pixels."""
+        from Go's in the deflate bytes only (Python's zlib is not Go's compress/flate) and decodes to the same pixels.
+        device_deflate=True: the row stage and the deflate on the device (png_encode; `level` does not apply) -- a larger
+        file, no scanline on the host."""
         v = _Img(img)
         kind, pal, plane = self.png_reduce(img)
         src = img if kind == FNX_PNG_NRGBA else plane
+        if device_deflate:
+            return self.png_encode(src, kind, len(pal), -1, pal if kind == FNX_PNG_PALETTED else None)
         host = np.empty(v.h * (1 + (4 * v.w if kind == FNX_PNG_NRGBA else v.w)), dtype=np.uint8) if v.space == FNX_DEVICE else None
         stream, ct, bd = self.png_filter(src, kind, len(pal), -1, host)
         return png_file(stream, v.w, v.h, ct, bd, pal if kind == FNX_PNG_PALETTED else None, level)
+
+    def deflate(self, buf, row: int = 0, out=None):
+        """The zlib stream of `buf` (fnx_deflate; deflate.hip): independent chunks of FNX_DEFLATE_CHUNK bytes, one workgroup
+        and one deflate block each; zlib.decompress reads it back.  buf: bytes or a flat uint8 numpy array -> bytes; a flat
+        uint8 device tensor -> a device tensor (the front of a buffer of deflate_bound(len) bytes), or fills `out`: a flat
+        uint8 numpy array (device source, host stream) or device tensor, of which the stream's bytes are returned as a view.
+        row: the stream's row length (1 + n of png_filter) as a match-distance hint, 0 for none."""
+        if _is_torch(buf):
+            import torch
+            if not buf.is_cuda or buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous():
+                raise FennecError("a device buffer must be a flat contiguous uint8 CUDA/HIP tensor")
+            space, ptr, n, keep = FNX_DEVICE, buf.data_ptr(), int(buf.shape[0]), buf
+        else:
+            keep = np.frombuffer(buf, dtype=np.uint8) if isinstance(buf, (bytes, bytearray, memoryview)) else buf
+            if not isinstance(keep, np.ndarray) or keep.dtype != np.uint8 or keep.ndim != 1 or not keep.flags.c_contiguous:
+                raise FennecError("a host buffer must be bytes or a flat contiguous uint8 numpy array")
+            space, ptr, n = FNX_HOST, keep.ctypes.data, int(keep.shape[0])
+        if n < 1:
+            raise FennecError("deflate takes at least one byte")
+        size = C.c_size_t(0)
+        if out is None:
+            cap = int(self._lib.fnx_deflate_bound(n))
+            if space == FNX_DEVICE:
+                import torch
+                out = torch.empty(cap, dtype=torch.uint8, device=buf.device)
+            else:
+                out = np.empty(cap, dtype=np.uint8)
+            fresh = True
+        else:
+            fresh = False
+        on_device = _is_torch(out)
+        if on_device and space != FNX_DEVICE:
+            raise FennecError("a device stream needs a device source")
+        if out.ndim != 1 or not (out.is_contiguous() if on_device else (out.dtype == np.uint8 and out.flags.c_contiguous)):
+            raise FennecError("out must be a flat contiguous uint8 buffer")
+        optr = out.data_ptr() if on_device else out.ctypes.data
+        sp = space if on_device or space == FNX_HOST else FNX_DEVICE_SRC
+        with self._ordered(buf if space == FNX_DEVICE else None, out if on_device else None):
+            self._chk(self._lib.fnx_deflate(self._h, sp, ptr, n, int(row), optr, int(out.shape[0]), C.byref(size)), "fnx_deflate")
+        view = out[:size.value]
+        return view.tobytes() if fresh and not on_device else view
+
+    def png_encode(self, src, kind: int | None = None, ncolors: int = 0, opaque: int = -1, palette=None) -> bytes:
+        """The complete PNG file of `src` (fnx_png_encode): png_filter's row stage and the deflate on the device, the chunks
+        (signature, IHDR, PLTE and tRNS for paletted kinds, one IDAT, IEND: png_file's layout) and their CRCs on the host.
+        src, kind, ncolors, opaque: as png_filter's; palette: (ncolors, 4) r,g,b,a for FNX_PNG_PALETTED."""
+        kind, space, ptr, stride, w, h = self._png_src(src, kind)
+        pal = None
+        if kind == FNX_PNG_PALETTED:
+            if palette is None:
+                raise FennecError("a paletted image needs its palette")
+            pal = np.ascontiguousarray(palette, dtype=np.uint8).reshape(-1, 4)
+            ncolors = ncolors or len(pal)
+            if len(pal) < ncolors:
+                raise FennecError("the palette is shorter than ncolors")
+        n = C.c_size_t(0)
+        sp = FNX_DEVICE_SRC if space == FNX_DEVICE else FNX_HOST
+        with self._ordered(src):
+            rc, buf = _into_buffer(lambda b, c: self._lib.fnx_png_encode(self._h, sp, int(kind), ptr, stride, w, h, int(ncolors), int(opaque),
+                                                                         pal.ctypes.data if pal is not None else None,
+                                                                         b.ctypes.data, c, C.byref(n)),
+                                   max(1 << 16, (w * h) // 2), n)
+            self._chk(rc, "fnx_png_encode")
+        return buf[:n.value].tobytes()
+
+    def compress_file_png(self, data: bytes, orient: int = 1, max_w: int = 0, max_h: int = 0, cap: int | None = None):
+        """CompressFile's PNG branch for a JPEG source in one call (fennec_CompressFilePNG): decode, ApplyOrientation(orient),
+        smartResize(max_w, max_h), compressPNG's reduction, the encoder's row stage and the deflate on the device ->
+        (PNG file bytes, kind, original (w, h), final (w, h))."""
+        src = np.frombuffer(data, dtype=np.uint8)
+        o = FileOptions(int(orient), int(max_w), int(max_h), 0, 0.0)
+        kind, n = C.c_int(0), C.c_size_t(0)
+        dims = (C.c_int * 4)()
+        rc, buf = _into_buffer(lambda b, c: self._lib.fennec_CompressFilePNG(self._h, src.ctypes.data_as(_u8p), len(data), C.byref(o),
+                                                                             b.ctypes.data_as(_u8p), c, C.byref(n), dims, C.byref(kind)),
+                               1 << 16 if cap is None else int(cap), n)
+        self._chk(rc, "fennec_CompressFilePNG")
+        return buf[:n.value].tobytes(), kind.value, (dims[0], dims[1]), (dims[2], dims[3])
 
     def compress_file_png_stream(self, data: bytes, orient: int = 1, max_w: int = 0, max_h: int = 0, cap: int | None = None):
         """CompressFile's PNG branch for a JPEG source up to the bytes deflate reads (fennec_CompressFilePNGStream): decode,
@@ -1797,7 +1891,10 @@ def boxDownsample(img, dstW, dstH): return default_context(_dev_of(img)).boxDown
 def lanczosBoxDownsample(img, midW, midH, dstW, dstH): return default_context(_dev_of(img)).lanczosBoxDownsample(img, midW, midH, dstW, dstH)
 def Analyze(img): return default_context(_dev_of(img)).Analyze(img)
 def png_filter(src, kind=None, ncolors=0, opaque=-1): return default_context(_dev_of(src)).png_filter(src, kind, ncolors, opaque)
-def compress_png(img, level=9): return default_context(_dev_of(img)).compress_png(img, level)
+def compress_png(img, level=9, device_deflate=False): return default_context(_dev_of(img)).compress_png(img, level, device_deflate)
+def deflate(buf, row=0): return default_context(_dev_of(buf)).deflate(buf, row)
+def png_encode(src, kind=None, ncolors=0, opaque=-1, palette=None): return default_context(_dev_of(src)).png_encode(src, kind, ncolors, opaque, palette)
+def deflate_bound(n): return int(load_library().fnx_deflate_bound(int(n)))
 def png_reduce(img, max_colors=256, want_plane=True): return default_context(_dev_of(img)).png_reduce(img, max_colors, want_plane)
 def tryPalettize(img, max_colors=256): return default_context(_dev_of(img)).tryPalettize(img, max_colors)
 

@@ -108,6 +108,7 @@ enum Slot {
     SLOT_RZBOX_TABLES, SLOT_RZBOX_SUMS,   // resize_box.hip: both tap tables + the box maps, the image-wide integer box sums
     SLOT_PNG,        // png_reduce.hip: the colour set's result (over, count, palette) and the colour -> index table of the plane pass
     SLOT_PNG_STREAM, // png_filter.hip: the filtered scanlines on their way to a host buffer
+    SLOT_DEFLATE_TOK, SLOT_DEFLATE_SLOTS, SLOT_DEFLATE_OUT,   // deflate.hip: the chunks' tokens; the result word, the chunks' sizes and output slots; the stream on its way to a host buffer
     SLOT_DONE,       // workgroup counters of the kernels that finish their own reduction (ssim.hip), zero between launches
     SLOT_COUNT
 };
@@ -546,6 +547,16 @@ int launch_png_alpha(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h
 // opacity is stated and the stream stays on the device.
 int png_filter_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors, int opaque, bool out_on_device,
                       uint8_t *out, size_t cap, size_t *nbytes, int *color_type, int *bit_depth);
+// deflate.hip: the zlib stream of n >= 1 device bytes into d_out (device, cap bytes; a larger stream writes nothing);
+// *d_size: the device word that holds the stream's size once both kernels have run.  row: a match-distance hint, 0 for none.
+size_t deflate_chunks(size_t n);
+size_t deflate_bound(size_t n);
+int launch_deflate(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, uint8_t *d_out, size_t cap, const unsigned long long **d_size);
+// png_api.cpp: the body of fnx_deflate for device bytes (out: device or host memory), and of fnx_png_encode for a DEVICE image or
+// plane (out: host memory; palette: host)
+int deflate_device(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, bool out_on_device, uint8_t *out, size_t cap, size_t *nbytes);
+int png_encode_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors, int opaque, const uint8_t *palette,
+                      uint8_t *out, size_t cap, size_t *nbytes);
 // applyPalette (+ palettedToNRGBA): palette = n x 4 host bytes (opaque); idx and/or quant may be null
 int launch_apply_palette(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, const uint8_t *palette, int n,
                          uint8_t *idx, int istride, uint8_t *quant, int qstride);

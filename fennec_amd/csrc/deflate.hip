@@ -1,0 +1,614 @@
+// A chunk-parallel deflate for gfx950: a zlib stream (RFC 1950) of deflate blocks (RFC 1951) from bytes that are already on
+// the device -- the filtered scanlines of png_filter.hip above all.  No library code; the format, restated:
+//
+//  * RFC 1950: CMF = 0x78 (deflate, 32 KiB window), FLG = 0x01 (no dictionary, level 0, (CMF * 256 + FLG) % 31 == 0), the
+//    deflate blocks, then Adler-32 of the input, big-endian: a = 1 + sum x[i], b = n + sum (n - i) x[i], both mod 65521,
+//    b << 16 | a.
+//  * RFC 1951: bits are packed from bit 0 of each byte upwards; Huffman codes go in most significant bit first (the code
+//    tables below hold them bit-reversed), everything else least significant bit first.  A block starts with BFINAL (1 bit)
+//    and BTYPE (2 bits): 00 stored (pad to a byte, LEN, ~LEN as 16-bit little-endian words, LEN bytes), 01 the fixed codes
+//    (literal/length lengths 8 for 0..143, 9 for 144..255, 7 for 256..279, 8 for 280..287; distance codes 5 bits), 10
+//    dynamic codes: HLIT - 257 (5 bits), HDIST - 1 (5), HCLEN - 4 (4), HCLEN code-length-code lengths of 3 bits in the order
+//    16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15, then the HLIT + HDIST code lengths in that code: 0..15 a length, 16
+//    repeat the previous length 3..6 times (2 extra bits), 17 / 18 a run of 3..10 / 11..138 zeros (3 / 7 extra bits).
+//    Symbol 256 ends a block.  Length l = 3..258: symbol 257 + (l - 3) below 11; 285 for 258; else with e = msb(l - 3) - 2,
+//    265 + 4 (e - 1) + (((l - 3) >> e) & 3) and e extra bits.  Distance d = 1..32768: symbol d - 1 below 5; else with
+//    m = msb(d - 1), 2 m + (((d - 1) >> (m - 1)) & 1) and m - 1 extra bits.  Codes are canonical: within a length in symbol
+//    order, lengths ascending.
+//
+// deflate_chunk_kernel: one workgroup of 256 lanes per chunk of FNX_DEFLATE_CHUNK = 32 KiB, the chunk's bytes in LDS.
+//  * No match reaches behind its chunk's start; every chunk is ONE block and every chunk but the last ends with an empty
+//    stored block (3 header bits, padding, 00 00 ff ff), so each chunk's output is whole bytes and the chunks concatenate by
+//    a byte copy.  The last chunk carries BFINAL.
+//  * Candidates for position p: the PNG distances 1, 2, 3, 4, 6, 8 and `row` (the stream's row length, 0: none), and one
+//    hash candidate.  The hash table (4096 words of LDS, three bytes hashed) is filled segment by segment, 256 positions at
+//    a time: every lane looks up, barrier, atomicMax of its own position, barrier -- a lookup sees positions of EARLIER
+//    segments only, and the largest of them, so the candidate is a function of the input alone.  The longest match wins,
+//    the smaller distance on ties; 3..258 bytes (a 3-byte match further than 4096 back costs more than its literals and
+//    is not taken).
+//  * Parse: lane t owns the sub-chunk [t S, (t + 1) S), S = FNX_DEFLATE_SUB = 128, and parses it greedily; sub-chunk starts
+//    are token boundaries, a match is cut at its sub-chunk's end (it may START before it).  Tokens go to the chunk's region
+//    of global scratch, one word each -- the region first holds the hash candidates of the chunk's positions: a lane reads
+//    position p's word before it writes token k <= p - t S over a word in front of it.
+//  * Codes: both histograms by LDS atomics while parsing; symbols ranked by (count, symbol) in parallel; the Huffman trees by
+//    the two-queue merge on one lane each (literal/length on lane 0, distance on lane 64); depths above 15 (7 for the
+//    code-length code) are folded into the limit and the Kraft sum repaired by moving one code down a level at a time;
+//    lengths are handed out by rank.  A block without a match still sends one distance code (symbol 0, one bit); a code with
+//    a single symbol gets one bit (the code-length code, which inflate wants complete, a second unused one).
+//    The block takes the smallest of dynamic, fixed and stored; stored is one block (LEN is 16 bits: static_assert below).
+//  * Emit: lanes add up their tokens' bits, an exclusive prefix sum over the workgroup gives each lane its bit offset, lanes
+//    OR their bits into the LDS words that held the chunk (zeroed; integer OR: any order gives the same bytes), and the
+//    words go to the chunk's slot (sized by the stored bound) as dword vector stores.  Each chunk writes its byte count and
+//    its Adler-32 partial (a, b, len).
+// deflate_gather_kernel: one workgroup per chunk: the sum of the byte counts in front of it (the prefix sum, every
+// workgroup for itself), the two header bytes, the byte copy into the caller's buffer (aligned dwords by v_alignbyte), the
+// combined Adler-32 behind the last chunk, the total size in a result word.  A total above `cap` writes nothing.
+//
+// Resources (hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage): no scratch in either kernel;
+// VGPRs: see DESIGN.md section 5.7 (the figures are the compiler's and are restated there with the LDS sizes).
+#include "common.hpp"
+#include "devutil.hpp"
+
+#include <algorithm>
+
+namespace fnx {
+
+constexpr int DF_T = 256;                          // lanes per workgroup
+constexpr int DF_C = FNX_DEFLATE_CHUNK;
+constexpr int DF_S = FNX_DEFLATE_SUB;              // a lane's sub-chunk
+constexpr int DF_HBITS = 12;
+constexpr int DF_SLOT = DF_C + 32;                 // a chunk's output slot: stored bound C + 10, dword reads one past the end
+constexpr uint32_t DF_ADLER = 65521u;
+constexpr int DF_STORED = 0, DF_FIXED = 1, DF_DYNAMIC = 2;   // BTYPE
+static_assert(DF_S * DF_T == DF_C && DF_S >= 64, "equal sub-chunks of at least 64 bytes");
+static_assert(DF_C <= 32768, "distances are at most 32768; a stored block's LEN is 16 bits");
+
+__device__ const uint8_t DF_CLORD[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+
+struct DeflateArgs {
+    const uint8_t *src;
+    size_t n;
+    int row;
+    uint32_t nchunks;
+    uint32_t *tok;                       // DF_C words per chunk
+    uint8_t *slots;                      // DF_SLOT bytes per chunk, 16-byte aligned
+    uint32_t *meta;                      // per chunk: bytes, adler a, adler b, len
+};
+
+// one Huffman build's work arrays (LDS: the hash table's words, which are dead by then)
+struct HuffWork {
+    uint32_t ifreq[288];                 // internal nodes: weight, later depth
+    uint16_t iparent[288];
+    uint16_t lparent[288];
+    uint16_t order[288];                 // symbols with a count, ascending by (count, symbol)
+    uint32_t count[16];                  // codes per length
+};
+
+// symbol and extra bits of a match length / distance
+__device__ __forceinline__ void df_len_sym(int l, int &sym, int &ebits, int &eval)
+{
+    const int l3 = l - 3;
+    if (l3 < 8) { sym = 257 + l3; ebits = 0; eval = 0; return; }
+    if (l3 == 255) { sym = 285; ebits = 0; eval = 0; return; }
+    const int e = 29 - __clz(l3);
+    sym = 261 + 4 * e + ((l3 >> e) & 3);
+    ebits = e;
+    eval = l3 & ((1 << e) - 1);
+}
+__device__ __forceinline__ void df_dist_sym(int d, int &sym, int &ebits, int &eval)
+{
+    const int d1 = d - 1;
+    if (d1 < 4) { sym = d1; ebits = 0; eval = 0; return; }
+    const int m = 31 - __clz(d1);
+    sym = 2 * m + ((d1 >> (m - 1)) & 1);
+    ebits = m - 1;
+    eval = d1 & ((1 << (m - 1)) - 1);
+}
+__device__ __forceinline__ int df_len_ebits(int sym) { return sym >= 265 && sym < 285 ? (sym - 261) >> 2 : 0; }
+__device__ __forceinline__ int df_dist_ebits(int sym) { return sym >= 4 ? (sym >> 1) - 1 : 0; }
+__device__ __forceinline__ int df_fixed_len(int sym) { return sym < 144 ? 8 : (sym < 256 ? 9 : (sym < 280 ? 7 : 8)); }
+
+// a token: a literal byte, or 1 << 31 | (len - 3) << 16 | (dist - 1)
+__device__ __forceinline__ uint32_t df_match_tok(int len, int dist) { return 0x80000000u | (static_cast<uint32_t>(len - 3) << 16) | static_cast<uint32_t>(dist - 1); }
+
+// order[r] = the symbol of rank r among those with a count, by (count, symbol); every lane of the workgroup
+__device__ __forceinline__ void df_rank(const uint32_t *freq, int n, uint16_t *order, int tid)
+{
+    for (int s = tid; s < n; s += DF_T) {
+        const uint32_t f = freq[s];
+        if (!f) continue;
+        int r = 0;
+        for (int j = 0; j < n; j++) {
+            const uint32_t g = freq[j];
+            r += (g != 0 && (g < f || (g == f && j < s))) ? 1 : 0;
+        }
+        order[r] = static_cast<uint16_t>(s);
+    }
+}
+
+// code lengths of at most maxbits from counts and their ranking; ONE lane
+__device__ void df_build_lengths(const uint32_t *freq, int n, int maxbits, uint8_t *lens, HuffWork &w)
+{
+    int m = 0;
+    for (int j = 0; j < n; j++) {
+        lens[j] = 0;
+        m += freq[j] != 0 ? 1 : 0;
+    }
+    if (m == 0) return;
+    if (m == 1) { lens[w.order[0]] = 1; return; }
+    // the two-queue merge: leaves in rank order, internal nodes in the order they are made (their weights never decrease)
+    int li = 0, ii = 0;
+    for (int k = 0; k < m - 1; k++) {
+        uint32_t f = 0;
+        for (int t = 0; t < 2; t++) {
+            const uint32_t lf = li < m ? freq[w.order[li]] : 0u;
+            if (li < m && (ii >= k || lf <= w.ifreq[ii])) { w.lparent[li] = static_cast<uint16_t>(k); f += lf; li++; }
+            else { w.iparent[ii] = static_cast<uint16_t>(k); f += w.ifreq[ii]; ii++; }
+        }
+        w.ifreq[k] = f;
+    }
+    w.ifreq[m - 2] = 0;                                              // the root's depth; a parent is made after its children
+    for (int k = m - 3; k >= 0; k--) w.ifreq[k] = w.ifreq[w.iparent[k]] + 1;
+    for (int l = 0; l < 16; l++) w.count[l] = 0;
+    for (int i = 0; i < m; i++) {
+        const int d = static_cast<int>(w.ifreq[w.lparent[i]]) + 1;
+        w.count[min(d, maxbits)]++;                                  // deeper than the limit: folded into it
+    }
+    uint32_t total = 0;
+    for (int l = 1; l <= maxbits; l++) total += w.count[l] << (maxbits - l);
+    while (total > (1u << maxbits)) {                                // each round takes 2^-maxbits off the Kraft sum
+        w.count[maxbits]--;
+        for (int l = maxbits - 1; l > 0; l--) {
+            if (w.count[l]) { w.count[l]--; w.count[l + 1] += 2; break; }
+        }
+        total--;
+    }
+    int i = m - 1;                                                   // the most frequent symbol takes the shortest code
+    for (int l = 1; l <= maxbits; l++) {
+        for (uint32_t c = w.count[l]; c > 0; c--) lens[w.order[i--]] = static_cast<uint8_t>(l);
+    }
+}
+
+// canonical codes, bit-reversed for the stream; every lane of the workgroup
+__device__ __forceinline__ void df_assign_codes(const uint8_t *lens, int n, uint16_t *codes, int tid)
+{
+    for (int s = tid; s < n; s += DF_T) {
+        const int L = lens[s];
+        uint32_t code = 0;
+        if (L) {
+            for (int j = 0; j < n; j++) {
+                const int lj = lens[j];
+                if (lj && lj < L) code += 1u << (L - lj);            // the first code of length L
+                else if (lj == L && j < s) code++;
+            }
+            code = __brev(code) >> (32 - L);
+        }
+        codes[s] = static_cast<uint16_t>(code);
+    }
+}
+
+// a lane's bit writer into the workgroup's LDS words
+struct DfBits {
+    uint32_t *w;
+    uint64_t acc;
+    int nacc;                            // < 32 between calls
+    uint32_t word;
+    __device__ __forceinline__ DfBits(uint32_t *words, uint32_t bitpos) : w(words), acc(0), nacc(static_cast<int>(bitpos & 31u)), word(bitpos >> 5) {}
+    __device__ __forceinline__ void put(uint32_t v, int n)           // n <= 31
+    {
+        acc |= static_cast<uint64_t>(v) << nacc;
+        nacc += n;
+        if (nacc >= 32) {
+            atomicOr(&w[word++], static_cast<uint32_t>(acc));
+            acc >>= 32;
+            nacc -= 32;
+        }
+    }
+    __device__ __forceinline__ uint32_t pos() const { return (word << 5) + static_cast<uint32_t>(nacc); }
+    __device__ __forceinline__ void align8() { put(0u, (8 - (nacc & 7)) & 7); }
+    __device__ __forceinline__ void flush() { if (nacc > 0) atomicOr(&w[word], static_cast<uint32_t>(acc)); }
+};
+
+__global__ __launch_bounds__(DF_T) void deflate_chunk_kernel(DeflateArgs a)
+{
+    __shared__ uint32_t s_w[(DF_C + 64) / 4];                        // the chunk's bytes, later its output bits
+    __shared__ uint32_t s_hash[1 << DF_HBITS];                       // position + 1; later three HuffWork
+    __shared__ uint32_t s_llf[288], s_df[32], s_clf[20];
+    __shared__ uint8_t s_lll[288], s_dl[32], s_cll[20];
+    __shared__ uint16_t s_llc[288], s_dc[32], s_clc[20];
+    __shared__ uint16_t s_cltok[320];                                // symbol | extra value << 8
+    __shared__ uint32_t s_scan[DF_T];
+    __shared__ uint32_t s_adler[2];
+    __shared__ uint32_t s_form, s_hlit, s_hdist, s_hclen, s_ncl, s_hdr_bits, s_nbytes;
+    static_assert(3 * sizeof(HuffWork) <= sizeof(uint32_t) << DF_HBITS, "the Huffman work arrays take the hash table's words");
+
+    const int tid = threadIdx.x;
+    const uint32_t c = blockIdx.x;
+    const size_t base = static_cast<size_t>(c) * DF_C;
+    const int len = static_cast<int>(std::min<size_t>(DF_C, a.n - base));
+    const bool last = c + 1 == a.nchunks;
+    const uint8_t *src = a.src + base;
+    uint8_t *s_b = reinterpret_cast<uint8_t *>(s_w);
+    uint32_t *tok = a.tok + static_cast<size_t>(c) * DF_C;
+    HuffWork *hw = reinterpret_cast<HuffWork *>(s_hash);
+
+    // ---- the chunk into LDS
+    if ((reinterpret_cast<uintptr_t>(src) & 3u) == 0) {
+        const int nd = len >> 2;
+        for (int i = tid; i < nd; i += DF_T) s_w[i] = *(g_u32 *)(src + 4 * i);
+        for (int i = 4 * nd + tid; i < len; i += DF_T) s_b[i] = src[i];
+    } else {
+        for (int i = tid; i < len; i += DF_T) s_b[i] = src[i];
+    }
+    for (int i = tid; i < (1 << DF_HBITS); i += DF_T) s_hash[i] = 0;
+    for (int i = tid; i < 288; i += DF_T) s_llf[i] = i == 256 ? 1u : 0u;   // one end-of-block
+    if (tid < 32) s_df[tid] = 0;
+    if (tid < 20) s_clf[tid] = 0;
+    if (tid < 2) s_adler[tid] = 0;
+    __syncthreads();
+
+    // ---- the hash candidate of every position, segment by segment: tok[p] = its distance, 0 for none
+    for (int seg = 0; seg < len; seg += DF_T) {
+        const int p = seg + tid;
+        const bool hashed = p + 2 < len;
+        uint32_t h = 0;
+        if (hashed) {
+            const uint32_t v = s_b[p] | (static_cast<uint32_t>(s_b[p + 1]) << 8) | (static_cast<uint32_t>(s_b[p + 2]) << 16);
+            h = (v * 0x9e3779b1u) >> (32 - DF_HBITS);
+            const uint32_t seen = s_hash[h];
+            tok[p] = seen ? static_cast<uint32_t>(p) + 1u - seen : 0u;
+        } else if (p < len) {
+            tok[p] = 0;
+        }
+        __syncthreads();
+        if (hashed) atomicMax(&s_hash[h], static_cast<uint32_t>(p) + 1u);
+        __syncthreads();
+    }
+
+    // ---- the greedy parse of this lane's sub-chunk
+    const int s0 = tid * DF_S, e0 = min(s0 + DF_S, len);
+    int ntok = 0;
+    {
+        uint32_t asum = 0, bsum = 0;
+        for (int p = s0; p < e0;) {
+            const int maxl = min(258, e0 - p);
+            int best = 0, bestd = 0;
+            if (maxl >= 3) {
+                const int hd = static_cast<int>(tok[p]);
+#pragma unroll
+                for (int k = 0; k < 8; k++) {
+                    const int d = k == 0 ? 1 : k == 1 ? 2 : k == 2 ? 3 : k == 3 ? 4 : k == 4 ? 6 : k == 5 ? 8 : k == 6 ? a.row : hd;
+                    if (d <= 0 || d > p) continue;
+                    int l = 0;
+                    while (l < maxl && s_b[p + l] == s_b[p - d + l]) l++;
+                    if (l == 3 && d > 4096) continue;
+                    if (l > best || (l == best && d < bestd)) { best = l; bestd = d; }
+                }
+            }
+            if (best >= 3) {
+                int sym, eb, ev;
+                df_len_sym(best, sym, eb, ev);
+                atomicAdd(&s_llf[sym], 1u);
+                df_dist_sym(bestd, sym, eb, ev);
+                atomicAdd(&s_df[sym], 1u);
+                tok[s0 + ntok++] = df_match_tok(best, bestd);
+                p += best;
+            } else {
+                const uint32_t b = s_b[p];
+                atomicAdd(&s_llf[b], 1u);
+                tok[s0 + ntok++] = b;
+                p++;
+            }
+        }
+        // Adler-32's sums of the sub-chunk, b against the CHUNK's end: at most 128 * 255 * 32768 < 2^32
+        for (int i = s0; i < e0; i++) {
+            const uint32_t x = s_b[i];
+            asum += x;
+            bsum += x * static_cast<uint32_t>(len - i);
+        }
+        if (s0 < e0) {
+            atomicAdd(&s_adler[0], asum);                            // at most 32768 * 255
+            atomicAdd(&s_adler[1], bsum % DF_ADLER);                 // at most 256 * 65520
+        }
+    }
+    __syncthreads();
+
+    // ---- the codes
+    df_rank(s_llf, 286, hw[0].order, tid);
+    df_rank(s_df, 30, hw[1].order, tid);
+    __syncthreads();
+    if (tid == 0) df_build_lengths(s_llf, 286, 15, s_lll, hw[0]);
+    if (tid == 64) {
+        df_build_lengths(s_df, 30, 15, s_dl, hw[1]);
+        bool any = false;
+        for (int j = 0; j < 30; j++) any = any || s_dl[j] != 0;
+        if (!any) s_dl[0] = 1;                                       // no match in the block: one distance code all the same
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int hlit = 286, hdist = 30;
+        while (hlit > 257 && s_lll[hlit - 1] == 0) hlit--;
+        while (hdist > 1 && s_dl[hdist - 1] == 0) hdist--;
+        // the HLIT + HDIST lengths as one sequence in the code-length code
+        int ncl = 0;
+        const int nseq = hlit + hdist;
+        for (int i = 0; i < nseq;) {
+            const int v = i < hlit ? s_lll[i] : s_dl[i - hlit];
+            int r = 1;
+            while (i + r < nseq && (i + r < hlit ? s_lll[i + r] : s_dl[i + r - hlit]) == v) r++;
+            i += r;
+            if (v == 0) {
+                while (r >= 11) { const int t = min(r, 138); s_cltok[ncl++] = static_cast<uint16_t>(18 | ((t - 11) << 8)); s_clf[18]++; r -= t; }
+                if (r >= 3) { s_cltok[ncl++] = static_cast<uint16_t>(17 | ((r - 3) << 8)); s_clf[17]++; r = 0; }
+            } else {
+                s_cltok[ncl++] = static_cast<uint16_t>(v); s_clf[v]++; r--;
+                while (r >= 3) { const int t = min(r, 6); s_cltok[ncl++] = static_cast<uint16_t>(16 | ((t - 3) << 8)); s_clf[16]++; r -= t; }
+            }
+            for (; r > 0; r--) { s_cltok[ncl++] = static_cast<uint16_t>(v); s_clf[v]++; }
+        }
+        int m = 0;
+        for (int s = 0; s < 19; s++) {
+            const uint32_t f = s_clf[s];
+            if (!f) continue;
+            int r = 0;
+            for (int j = 0; j < 19; j++) {
+                const uint32_t g = s_clf[j];
+                r += (g != 0 && (g < f || (g == f && j < s))) ? 1 : 0;
+            }
+            hw[2].order[r] = static_cast<uint16_t>(s);
+            m++;
+        }
+        df_build_lengths(s_clf, 19, 7, s_cll, hw[2]);
+        if (m == 1) s_cll[hw[2].order[0] == 0 ? 1 : 0] = 1;         // inflate refuses an incomplete code-length code
+        int hclen = 19;
+        while (hclen > 4 && s_cll[DF_CLORD[hclen - 1]] == 0) hclen--;
+        uint32_t hdr = 3 + 5 + 5 + 4 + 3 * static_cast<uint32_t>(hclen);
+        for (int i = 0; i < ncl; i++) {
+            const int s = s_cltok[i] & 0xff;
+            hdr += s_cll[s] + (s == 16 ? 2 : (s == 17 ? 3 : (s == 18 ? 7 : 0)));
+        }
+        uint32_t dyn = hdr, fix = 3;
+        for (int s = 0; s < 286; s++) {
+            const uint32_t f = s_llf[s];
+            dyn += f * (s_lll[s] + df_len_ebits(s));
+            fix += f * (df_fixed_len(s) + df_len_ebits(s));
+        }
+        for (int s = 0; s < 30; s++) {
+            const uint32_t f = s_df[s];
+            dyn += f * (s_dl[s] + df_dist_ebits(s));
+            fix += f * (5 + df_dist_ebits(s));
+        }
+        int form = DF_DYNAMIC;
+        uint32_t bits = dyn;
+        if (fix < bits) { form = DF_FIXED; bits = fix; }
+        if (8u * (5u + static_cast<uint32_t>(len)) <= bits) form = DF_STORED;
+        s_form = form; s_hlit = hlit; s_hdist = hdist; s_hclen = hclen; s_ncl = ncl;
+        s_hdr_bits = form == DF_DYNAMIC ? hdr : 3;
+    }
+    __syncthreads();
+    const int form = static_cast<int>(s_form);
+    uint32_t *slot = reinterpret_cast<uint32_t *>(a.slots + static_cast<size_t>(c) * DF_SLOT);
+
+    if (form == DF_STORED) {
+        // header, LEN, ~LEN, the bytes, and behind every chunk but the last the empty stored block (whose header byte is zero too)
+        const int nb = 5 + len + (last ? 0 : 5);
+        for (int j = tid; 4 * j < nb; j += DF_T) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const int k = 4 * j + e;
+                uint32_t b = 0;
+                if (k == 0) b = last ? 1u : 0u;
+                else if (k < 3) b = (static_cast<uint32_t>(len) >> (8 * (k - 1))) & 0xffu;
+                else if (k < 5) b = (~static_cast<uint32_t>(len) >> (8 * (k - 3))) & 0xffu;
+                else if (k < 5 + len) b = s_b[k - 5];
+                else if (k < nb) b = k >= 5 + len + 3 ? 0xffu : 0u;
+                v |= b << (8 * e);
+            }
+            *(g_u32w *)(slot + j) = v;
+        }
+        if (tid == 0) s_nbytes = nb;
+    } else {
+        if (form == DF_DYNAMIC) {
+            df_assign_codes(s_lll, 286, s_llc, tid);
+            df_assign_codes(s_dl, 30, s_dc, tid);
+            df_assign_codes(s_cll, 19, s_clc, tid);
+        } else {
+            for (int s = tid; s < 288; s += DF_T) {
+                const int L = df_fixed_len(s);
+                const uint32_t code = s < 144 ? 0x30u + s : (s < 256 ? 0x190u + (s - 144) : (s < 280 ? s - 256u : 0xc0u + (s - 280)));
+                s_lll[s] = static_cast<uint8_t>(L);
+                s_llc[s] = static_cast<uint16_t>(__brev(code) >> (32 - L));
+            }
+            if (tid < 32) {
+                s_dl[tid] = 5;
+                s_dc[tid] = static_cast<uint16_t>(__brev(static_cast<uint32_t>(tid)) >> 27);
+            }
+        }
+        for (int i = tid; i < (DF_C + 64) / 4; i += DF_T) s_w[i] = 0;    // the chunk's bytes are not read again
+        __syncthreads();
+        uint32_t mybits = 0;
+        for (int k = 0; k < ntok; k++) {
+            const uint32_t t = tok[s0 + k];
+            if (t & 0x80000000u) {
+                int sym, eb, ev;
+                df_len_sym(static_cast<int>((t >> 16) & 0xffu) + 3, sym, eb, ev);
+                mybits += s_lll[sym] + eb;
+                df_dist_sym(static_cast<int>(t & 0xffffu) + 1, sym, eb, ev);
+                mybits += s_dl[sym] + eb;
+            } else {
+                mybits += s_lll[t];
+            }
+        }
+        s_scan[tid] = mybits;
+        __syncthreads();
+        uint32_t off = s_hdr_bits;
+        for (int j = 0; j < tid; j++) off += s_scan[j];
+        if (tid == 0) {
+            DfBits hb(s_w, 0);
+            hb.put(last ? 1u : 0u, 1);
+            hb.put(static_cast<uint32_t>(form), 2);
+            if (form == DF_DYNAMIC) {
+                hb.put(s_hlit - 257, 5);
+                hb.put(s_hdist - 1, 5);
+                hb.put(s_hclen - 4, 4);
+                for (uint32_t i = 0; i < s_hclen; i++) hb.put(s_cll[DF_CLORD[i]], 3);
+                for (uint32_t i = 0; i < s_ncl; i++) {
+                    const int s = s_cltok[i] & 0xff;
+                    hb.put(s_clc[s], s_cll[s]);
+                    if (s >= 16) hb.put(s_cltok[i] >> 8, s == 16 ? 2 : (s == 17 ? 3 : 7));
+                }
+            }
+            hb.flush();
+        }
+        DfBits bw(s_w, off);
+        for (int k = 0; k < ntok; k++) {
+            const uint32_t t = tok[s0 + k];
+            if (t & 0x80000000u) {
+                int sym, eb, ev;
+                df_len_sym(static_cast<int>((t >> 16) & 0xffu) + 3, sym, eb, ev);
+                bw.put(s_llc[sym], s_lll[sym]);
+                if (eb) bw.put(static_cast<uint32_t>(ev), eb);
+                df_dist_sym(static_cast<int>(t & 0xffffu) + 1, sym, eb, ev);
+                bw.put(s_dc[sym], s_dl[sym]);
+                if (eb) bw.put(static_cast<uint32_t>(ev), eb);
+            } else {
+                bw.put(s_llc[t], s_lll[t]);
+            }
+        }
+        if (tid == DF_T - 1) {                                       // behind the last lane's tokens: the block's end
+            bw.put(s_llc[256], s_lll[256]);
+            if (!last) {
+                bw.put(0u, 3);
+                bw.align8();
+                bw.put(0u, 16);
+                bw.put(0xffffu, 16);
+            } else {
+                bw.align8();
+            }
+            s_nbytes = bw.pos() >> 3;
+        }
+        bw.flush();
+        __syncthreads();
+        const int nb = static_cast<int>(s_nbytes);
+        for (int j = tid; 4 * j < nb; j += DF_T) *(g_u32w *)(slot + j) = s_w[j];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t *m = a.meta + 4 * static_cast<size_t>(c);
+        m[0] = s_nbytes;
+        m[1] = s_adler[0] % DF_ADLER;
+        m[2] = s_adler[1] % DF_ADLER;
+        m[3] = static_cast<uint32_t>(len);
+    }
+}
+
+struct GatherArgs {
+    const uint8_t *slots;
+    const uint32_t *meta;
+    uint32_t nchunks;
+    size_t n;
+    uint8_t *out;
+    size_t cap;
+    unsigned long long *result;          // the stream's size
+};
+
+// the sum of v over the workgroup, in every lane (s_red: 4 words; two barriers)
+__device__ __forceinline__ unsigned long long df_block_sum(unsigned long long v, unsigned long long *s_red)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    __syncthreads();                                                 // the previous sum has been read
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return s_red[0] + s_red[1] + s_red[2] + s_red[3];
+}
+
+__global__ __launch_bounds__(DF_T) void deflate_gather_kernel(GatherArgs a)
+{
+    __shared__ unsigned long long s_red[4];
+    const int tid = threadIdx.x;
+    const uint32_t c = blockIdx.x;
+    unsigned long long before = 0, all = 0;
+    for (uint32_t j = tid; j < a.nchunks; j += DF_T) {
+        const unsigned long long nb = a.meta[4 * static_cast<size_t>(j)];
+        all += nb;
+        if (j < c) before += nb;
+    }
+    before = df_block_sum(before, s_red);
+    all = df_block_sum(all, s_red);
+    const unsigned long long size = 2 + all + 4;
+    if (c == 0 && tid == 0) *a.result = size;
+    if (size > a.cap) return;                                        // the caller is told the size and nothing is written
+    if (c == 0 && tid == 0) { a.out[0] = 0x78; a.out[1] = 0x01; }
+
+    const int nb = static_cast<int>(a.meta[4 * static_cast<size_t>(c)]);
+    const uint8_t *s = a.slots + static_cast<size_t>(c) * DF_SLOT;
+    uint8_t *dst = a.out + 2 + before;
+    const int head = min(nb, static_cast<int>((4u - (reinterpret_cast<uintptr_t>(dst) & 3u)) & 3u));
+    const int nd = (nb - head) >> 2;
+    if (tid < head) dst[tid] = s[tid];
+    for (int i = tid; i < nd; i += DF_T) {
+        const int j = head + 4 * i;                                  // dst + j is dword aligned; the slot's dwords j >> 2 and the next hold it
+        const uint32_t lo = *(g_u32 *)(s + (j & ~3)), hi = *(g_u32 *)(s + (j & ~3) + 4);
+        *(g_u32w *)(dst + j) = __builtin_amdgcn_alignbyte(hi, lo, j & 3);
+    }
+    for (int k = head + 4 * nd + tid; k < nb; k += DF_T) dst[k] = s[k];
+
+    if (c + 1 == a.nchunks) {
+        // Adler-32 of the whole: a = 1 + sum a_j, b = n + sum (b_j + (n - end_j) a_j), end_j the input offset behind chunk j
+        unsigned long long sa = 0, sb = 0;
+        for (uint32_t j = tid; j < a.nchunks; j += DF_T) {
+            const uint32_t *m = a.meta + 4 * static_cast<size_t>(j);
+            const unsigned long long end = static_cast<unsigned long long>(j) * DF_C + m[3];
+            sa += m[1];
+            sb += m[2] + ((a.n - end) % DF_ADLER) * m[1];            // below 2^33 a term
+        }
+        sa = df_block_sum(sa, s_red);
+        sb = df_block_sum(sb, s_red);
+        if (tid == 0) {
+            const uint32_t av = static_cast<uint32_t>((1 + sa) % DF_ADLER);
+            const uint32_t bv = static_cast<uint32_t>((a.n % DF_ADLER + sb) % DF_ADLER);
+            uint8_t *t = a.out + 2 + all;
+            t[0] = static_cast<uint8_t>(bv >> 8); t[1] = static_cast<uint8_t>(bv);
+            t[2] = static_cast<uint8_t>(av >> 8); t[3] = static_cast<uint8_t>(av);
+        }
+    }
+}
+
+size_t deflate_chunks(size_t n) { return n ? (n + DF_C - 1) / DF_C : 1; }
+
+// every chunk stored (5 bytes of block header) and closed by the empty stored block (5), the zlib header and the Adler-32
+size_t deflate_bound(size_t n) { return n + 10 * deflate_chunks(n) + 6; }
+
+int launch_deflate(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, uint8_t *d_out, size_t cap, const unsigned long long **d_size)
+{
+    const size_t nchunks = deflate_chunks(n);
+    void *dt = nullptr, *ds = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_DEFLATE_TOK, nchunks * DF_C * sizeof(uint32_t) + 16, &dt));
+    // the result word, the chunks' (bytes, a, b, len), the chunks' slots
+    const size_t meta_bytes = (16 * nchunks + 16 + 15) & ~size_t(15);
+    FNX_TRY(scratch(ctx, SLOT_DEFLATE_SLOTS, meta_bytes + nchunks * DF_SLOT + 16, &ds));
+    uint8_t *p = static_cast<uint8_t *>(ds);
+    DeflateArgs da{};
+    da.src = d_src; da.n = n; da.row = row > 0 && row < DF_C ? row : 0; da.nchunks = static_cast<uint32_t>(nchunks);
+    da.tok = static_cast<uint32_t *>(dt);
+    da.meta = reinterpret_cast<uint32_t *>(p + 16);
+    da.slots = p + meta_bytes;
+    note_route(ctx, FNX_PROF_MAIN, "deflate_chunk_kernel");
+    FNX_TRY(prof_begin(ctx));
+    hipLaunchKernelGGL(deflate_chunk_kernel, dim3(da.nchunks), dim3(DF_T), 0, ctx->stream, da);
+    FNX_HIP(hipGetLastError());
+    FNX_TRY(prof_end(ctx));
+    GatherArgs ga{};
+    ga.slots = da.slots; ga.meta = da.meta; ga.nchunks = da.nchunks; ga.n = n; ga.out = d_out; ga.cap = cap;
+    ga.result = reinterpret_cast<unsigned long long *>(p);
+    FNX_TRY(prof_begin(ctx));
+    hipLaunchKernelGGL(deflate_gather_kernel, dim3(da.nchunks), dim3(DF_T), 0, ctx->stream, ga);
+    FNX_HIP(hipGetLastError());
+    FNX_TRY(prof_end(ctx));
+    *d_size = ga.result;
+    return FNX_OK;
+}
+
+}  // namespace fnx

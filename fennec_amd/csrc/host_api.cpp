@@ -557,6 +557,34 @@ int fennec_CompressFilePNGStream(fnx_ctx *ctx, const uint8_t *data, size_t n, co
                              nbytes, color_type, bit_depth);
 }
 
+// The whole branch: the same stages, then deflate.hip on the resident stream and the file's chunks (fnx_png_encode's body).
+int fennec_CompressFilePNG(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_FileOptions *o, uint8_t *out, size_t cap, size_t *nbytes,
+                           int dims[4], int *kind)
+{
+    if (!ctx || !data || !o || !nbytes || !dims || !kind || (!out && cap)) {
+        set_error("invalid argument: CompressFilePNG");
+        return FNX_ERR_INVALID;
+    }
+    *nbytes = 0;
+    *kind = 0;
+    int w = 0, h = 0;
+    FNX_TRY(fnx_jpeg_decode(ctx, data, n, FNX_HOST, nullptr, 0, &w, &h));          // dimensions; refuses what the device decoder does not take
+    const uint8_t *img = nullptr;
+    FNX_TRY(file_stages(ctx, data, n, o, w, h, &img, &w, &h, dims));
+    if (w > 65535 || h > 65535) {
+        set_error("invalid argument: CompressFilePNG takes images of at most 65535 x 65535");
+        return FNX_ERR_INVALID;
+    }
+    void *dp = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_OUT, static_cast<size_t>(w) * h + 16, &dp));
+    uint8_t palette[256 * 4];
+    int ncolors = 0;
+    FNX_TRY(png_reduce_device(ctx, img, w * 4, w, h, 256, static_cast<uint8_t *>(dp), w, kind, palette, &ncolors));
+    const bool nrgba = *kind == FNX_PNG_NRGBA;
+    return png_encode_device(ctx, *kind, nrgba ? img : static_cast<const uint8_t *>(dp), nrgba ? w * 4 : w, w, h, ncolors, -1, palette, out, cap,
+                             nbytes);
+}
+
 }  // extern "C"
 
 // The pool of batch.go:58-128: `workers` threads over ONE closed queue of indices; item(ctx, idx, &result) does the work.

@@ -671,6 +671,40 @@ int fnx_png_filter(fnx_ctx *ctx, int space, int kind, const uint8_t *src, int ss
                    int opaque /* 1, 0, or -1: decide as Opaque() does */, uint8_t *out, size_t cap, size_t *nbytes,
                    int *color_type, int *bit_depth);
 
+/* ---- deflate on the device: zlib streams and whole PNG files (RFC 1950 / 1951) ------------------------------- */
+/* A chunk-parallel deflate (csrc/deflate.hip).  The input is cut into independent chunks of FNX_DEFLATE_CHUNK bytes, one
+ * workgroup and ONE deflate block each (dynamic, fixed or stored, whichever is smallest); no match reaches behind its chunk's
+ * start, and every chunk but the last ends with an empty stored block, so the chunks' outputs are whole bytes and are
+ * concatenated behind the two zlib header bytes, the Adler-32 of the input behind them.  Inside a chunk every lane parses a
+ * sub-chunk of FNX_DEFLATE_SUB bytes greedily: the candidates of a position are the distances 1, 2, 3, 4, 6, 8 and `row`
+ * and one hash candidate, the longest match wins, the smaller distance on ties.  Every pick is deterministic: the bytes are
+ * a function of (src, n, row) alone, never of the launch geometry or of timing.  Any inflate reads the stream back; it is
+ * NOT the stream another encoder (zlib, Go's compress/flate) would write -- expect a size near zlib level 1 over the same
+ * chunks (DESIGN.md section 5.7 has the measured figures). */
+#define FNX_DEFLATE_CHUNK 32768   /* bytes per chunk = per workgroup = per deflate block */
+#define FNX_DEFLATE_SUB   128     /* bytes per lane: tokens are cut at multiples of it */
+/* The largest stream fnx_deflate returns for n bytes: every chunk stored (5 bytes of block header), every chunk's closing
+ * empty stored block (5), header and Adler-32 (6).  Pure; no context.  Monotonic in n, at least n + 6. */
+size_t fnx_deflate_bound(size_t n);
+/* The zlib stream of src[0 .. n), n >= 1.  space: FNX_HOST (src and out in host memory), FNX_DEVICE (both device memory)
+ * or FNX_DEVICE_SRC (device source, host stream).  row: the length of a row of the stream (1 + n of fnx_png_filter) as a
+ * match-distance hint, 0 for none; values outside 1 .. FNX_DEFLATE_CHUNK - 1 are taken as none.  *nbytes is the stream's
+ * size whenever the arguments are good; cap < *nbytes: FNX_ERR_INVALID with *nbytes set (call again; fnx_deflate_bound(n)
+ * always suffices), nothing written.  Bytes of out behind *nbytes are never touched.  Bad arguments are refused before
+ * anything is launched.  One host wait for the size (a second one behind the copy when the stream goes to host memory).
+ * Kernels: deflate_chunk_kernel (the one fnx_ctx_last_kernel(ctx, FNX_PROF_MAIN) names), deflate_gather_kernel. */
+int fnx_deflate(fnx_ctx *ctx, int space, const uint8_t *src, size_t n, int row, uint8_t *out, size_t cap, size_t *nbytes);
+/* fnx_png_filter's row stage and fnx_deflate in one call: the complete PNG file of a resident (or host) image, the filtered
+ * stream never leaving the device.  kind, src, sstride, w, h, ncolors, opaque: as fnx_png_filter's; palette: HOST,
+ * ncolors x 4 bytes r,g,b,a, for FNX_PNG_PALETTED (ignored otherwise).  space: FNX_HOST, FNX_DEVICE or FNX_DEVICE_SRC say
+ * where src lives; out is ALWAYS host memory.  The file: signature, IHDR, for colour type 3 PLTE (3 bytes per entry) and
+ * tRNS (the alphas up to and including the last entry whose alpha != 255; omitted when there is none), one IDAT holding the
+ * zlib stream, IEND -- the chunk layout of the Python binding's png_file.  The chunk CRCs are computed on the host over
+ * bytes that are there anyway.  *nbytes: the file's size; cap < *nbytes: FNX_ERR_INVALID with *nbytes set, nothing
+ * written.  Decodes to the source's pixels; differs from the reference's file in the deflate bytes only. */
+int fnx_png_encode(fnx_ctx *ctx, int space, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors /* paletted: 1..256 */,
+                   int opaque /* 1, 0, or -1: decide as Opaque() does */, const uint8_t *palette, uint8_t *out, size_t cap, size_t *nbytes);
+
 /* ======================================================================= */
 /* fennec_* : the reference's function set (names and argument meaning as in
  * the Go source), mirrored above fnx_*.                                     */
@@ -806,6 +840,14 @@ int fennec_CompressFilePNGReduce(fnx_ctx *ctx, const uint8_t *data, size_t n, co
 int fennec_CompressFilePNGStream(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_FileOptions *opts,
                                  int *kind, uint8_t *palette /* 256 x 4 */, int *ncolors, int *color_type, int *bit_depth,
                                  uint8_t *out, size_t cap, size_t *nbytes, int dims[4]);
+
+/* CompressFile's PNG branch for a JPEG source, whole: fennec_CompressFilePNGStream's stages (decode, ApplyOrientation,
+ * smartResize, compressPNG's reduction, the encoder's row stage, compress.go:94-107), then fnx_deflate on the resident stream
+ * and the file's chunks as fnx_png_encode writes them -- JPEG bytes in, PNG bytes out, no pixel and no scanline on the host.
+ * out: HOST; *nbytes the file's size (cap too small: FNX_ERR_INVALID with *nbytes set); dims as fennec_CompressFileJPEG's;
+ * *kind as fennec_CompressFilePNGReduce's.  Opt-in: the file is larger than png.BestCompression's. */
+int fennec_CompressFilePNG(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_FileOptions *opts,
+                           uint8_t *out, size_t cap, size_t *nbytes, int dims[4], int *kind);
 /* The same pool over JPEG FILES in host memory (what CompressBatch reads for a .jpg item, batch.go:88-101): per item
  * fnx_jpeg_recompress -- decoder, search and encoder on the device, no host codec.  A file the device decoder does not
  * take comes back with failed != 0 and status == FNX_ERR_UNSUPPORTED: the caller decodes it on the host and sends it
