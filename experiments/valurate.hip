@@ -15,9 +15,11 @@ __global__ __launch_bounds__(256) void k(double *out, double seed, unsigned usee
     float f[UNROLL];
     v2f p[UNROLL];
     unsigned u[UNROLL];
+    unsigned long long q[UNROLL];
     for (int i = 0; i < UNROLL; i++) {
         a[i] = seed + i + threadIdx.x; f[i] = static_cast<float>(a[i]); p[i] = (v2f){f[i], f[i] + 1};
         u[i] = useed * (i + 1) + threadIdx.x;
+        q[i] = u[i];
     }
     const double m = 1.0000001, c = 0.25;
     for (int it = 0; it < ITERS; it++) {
@@ -56,10 +58,14 @@ __global__ __launch_bounds__(256) void k(double *out, double seed, unsigned usee
             if (KIND == 31) { unsigned t; asm volatile("v_mad_u32_u16 %0, %1, %2, %1" : "=v"(t) : "v"(u[i]), "v"(useed)); u[i] = t; }
             if (KIND == 32) { unsigned t; asm volatile("v_pk_mad_u16 %0, %1, %2, %1" : "=v"(t) : "v"(u[i]), "v"(useed)); u[i] = t; }
             if (KIND == 33) { unsigned t; asm volatile("v_dot2_u32_u16 %0, %1, %2, %1" : "=v"(t) : "v"(u[i]), "v"(useed)); u[i] = t; }
+            // 64-bit multiply-adds (row * stride + base as the compiler writes a pitched address) and the 64-bit add
+            if (KIND == 34) { unsigned long long t; asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=v"(t) : "v"(u[i]), "v"(useed), "v"(q[i]) : "vcc"); q[i] = t; }
+            if (KIND == 35) { unsigned long long t; asm volatile("v_mad_i64_i32 %0, vcc, %1, %2, %3" : "=v"(t) : "v"(u[i]), "v"(useed), "v"(q[i]) : "vcc"); q[i] = t; }
+            if (KIND == 36) { unsigned long long t; asm volatile("v_lshl_add_u64 %0, %1, 0, %2" : "=v"(t) : "v"(q[i]), "s"(static_cast<unsigned long long>(useed))); q[i] = t; }
         }
     }
     double s = 0;
-    for (int i = 0; i < UNROLL; i++) s += a[i] + f[i] + p[i].x + p[i].y + u[i];
+    for (int i = 0; i < UNROLL; i++) s += a[i] + f[i] + p[i].x + p[i].y + u[i] + static_cast<double>(q[i]);
     out[blockIdx.x * 256 + threadIdx.x] = s;
 }
 
@@ -121,6 +127,9 @@ int main()
     run<31, 16>("v_mad_u32_u16", 1);
     run<32, 16>("v_pk_mad_u16", 1);
     run<33, 16>("v_dot2_u32_u16", 1);
+    run<34, 16>("v_mad_u64_u32", 1);
+    run<35, 16>("v_mad_i64_i32", 1);
+    run<36, 16>("v_lshl_add_u64", 1);
     // dependent chains: 256-thread blocks, 4096 blocks -> 16 waves per SIMD resident; x1 = every
     // instruction of a wave depends on the previous one
     run<3, 1>("v_fma_f32 dependent", 1);

@@ -844,6 +844,63 @@ static int launch_direct_radius(fnx_ctx *ctx, int radius, int n, FusedArgs &fa, 
 // SCORE kernel is built for (the caller then runs the two ops separately).
 // Geometry of a one-pass launch: tile shape, box tables.  Cached on the ctx (batches repeat it).
 constexpr int NHEAD = 260 + 257 * 8;   // uint32 words at the head of the table blob: magic[c] (c <= 256, padded to 260), tiedown[8 c + w]
+
+// blur_mfma_kernel<SCORE, .>'s set-up, which depends on the geometry alone, as two tables at the end of the blob (r7: every
+// workgroup used to work this out from bx / by through LDS, ~300 vector instructions per wave before its first row set):
+//  * per (tile column, wave, lane) one word: coln | cnt << 20 | in[0..3] << 25 | channel << 29 -- the lane's indicator-matrix
+//    column (box column first + slot of the wave's 16 px, channel ch; lane n = 3 slot + ch, n = 15: nothing), how many of the 16
+//    px lie in it (the seed 128 cnt undoes the A operands' - 128) and its byte offset in a table row (spare column: none)
+//  * per segment the byte offset, in a box table, of the box row of each of its seg + 16 staged rows (tile rows -6 ..), then of
+//    its seg output rows; rows outside the segment or the image go to the spare row nby
+// Written as the device code it replaces was, value for value, the corner cases included (a tile or a wave with no boxed column:
+// first = 255 matches every column of slot 0, so cnt = 16 there and the sums land in the spare column).
+static void score_mfma_tables(fnx::ScoreGeom &g, int w, int h)
+{
+    const int seg = g.th, nbx = g.nbx, nby = g.nby;
+    const int tiles_x = (w + 63) / 64, segs = (h + seg - 1) / seg;
+    const size_t ref_words = 4 * (static_cast<size_t>(g.dstW) + g.dstH);
+    const size_t base = (NHEAD + ref_words + static_cast<size_t>(w) + h + 3) & ~size_t(3);   // 16-byte chunks
+    g.coltab = base;
+    g.rowtab = base + 256 * static_cast<size_t>(tiles_x);
+    g.map.resize(g.rowtab + static_cast<size_t>(segs) * (2 * seg + 16), 0);
+    const int32_t *bx = g.map.data() + NHEAD + ref_words, *by = bx + w;
+    uint32_t *col = reinterpret_cast<uint32_t *>(g.map.data()) + g.coltab, *row = reinterpret_cast<uint32_t *>(g.map.data()) + g.rowtab;
+    for (int tx = 0; tx < tiles_x; tx++) {
+        const int x0 = 64 * tx;
+        uint32_t colbox[64];
+        const int b0x = bx[x0];
+        for (int i = 0; i < 64; i++) {
+            const int v = x0 + i < w ? bx[x0 + i] : -1;
+            colbox[i] = (v >= 0 && b0x >= 0) ? static_cast<uint32_t>(v - b0x) : 255u;
+        }
+        for (int wave = 0; wave < 4; wave++) {
+            uint32_t first = 255u;
+            for (int i = 0; i < 16; i++) first = std::min(first, colbox[16 * wave + i]);
+            for (int lane = 0; lane < 64; lane++) {
+                const int r = lane & 15, gq = lane >> 4;
+                const int slot = r / 3, ch = r - 3 * slot;
+                uint32_t cnt = 0, in = 0;
+                for (int i = 0; i < 16; i++) cnt += (r < 15 && colbox[16 * wave + i] == first + slot) ? 1 : 0;
+                for (int e = 0; e < 4; e++)
+                    if (r < 15 && first != 255u && colbox[16 * wave + 4 * gq + e] == first + slot) in |= 1u << e;
+                const uint32_t bc = (r < 15 && first != 255u && cnt > 0) ? first + slot : static_cast<uint32_t>(nbx);
+                const uint32_t coln = 16u * bc + 4u * (r < 15 ? ch : 3);
+                col[(4 * tx + wave) * 64 + lane] = coln | cnt << 20 | in << 25 | static_cast<uint32_t>(ch) << 29;
+            }
+        }
+    }
+    const int rowbytes = 16 * (nbx + 1);
+    for (int ty = 0; ty < segs; ty++) {
+        const int y0 = ty * seg, b0y = by[y0];
+        uint32_t *rh = row + static_cast<size_t>(ty) * (2 * seg + 16), *rv = rh + seg + 16;
+        auto off = [&](int t) {
+            const int v = (t >= 0 && t < seg && y0 + t < h) ? by[y0 + t] : -1;
+            return static_cast<uint32_t>(rowbytes * ((v >= 0 && b0y >= 0) ? v - b0y : nby));
+        };
+        for (int u = 0; u < seg + 16; u++) rh[u] = off(u - 6);
+        for (int t = 0; t < seg; t++) rv[t] = off(t);
+    }
+}
 static bool build_score_geom(fnx::ScoreGeom &g, int w, int h, int radius, int dstW, int dstH, int th_fixed = 0)
 {
     // (th_fixed: the matrix-pipe kernels' tile, whose rows do not depend on the radius -- radii up to 24 since r5)
@@ -953,6 +1010,8 @@ static bool build_score_geom(fnx::ScoreGeom &g, int w, int h, int radius, int ds
     }
 
     g.th = th; g.nbx = nbx; g.nby = nby; g.tall = tall;
+    g.coltab = g.rowtab = 0;
+    if (th_fixed && th_fixed <= 272 && radius <= 6) score_mfma_tables(g, w, h);
     return true;
 }
 
@@ -1009,7 +1068,9 @@ int launch_blur_scored(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstr
     int st;
     if (g.mfma) {
         st = wide ? launch_blur_mfma_wide_scored(ctx, n, srcs, sstride, w, h, kernel, radius, flags, dsts, dstride, fa.bx, fa.by, fa.slabs, nbx, nby, th)
-                  : launch_blur_mfma_scored(ctx, n, srcs, sstride, w, h, kernel, radius, flags, dsts, dstride, fa.bx, fa.by, fa.slabs, nbx, nby, th);
+                  : launch_blur_mfma_scored(ctx, n, srcs, sstride, w, h, kernel, radius, flags, dsts, dstride,
+                                            g.coltab ? static_cast<const uint32_t *>(dmap) + g.coltab : nullptr,
+                                            g.rowtab ? static_cast<const uint32_t *>(dmap) + g.rowtab : nullptr, fa.slabs, nbx, nby, th);
         if (st == FNX_NOOP) return FNX_NOOP;   // (blur_mfma_covers said yes: not reached) the caller runs the two ops back to back
     } else {
         st = exact ? launch_direct_radius<true, true>(ctx, radius, n, fa, tall)

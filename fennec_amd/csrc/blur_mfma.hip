@@ -63,10 +63,13 @@ struct MfmaArgs {
     const uint32_t *tab;              // BH[3][64] x 16 B | BV[3][64] x 8 B | the caller's 13 fp64 weights, centred (GUARD)
     int seed_h, seed_v, thr;          // rounding seeds (+ G in units of 2^-24 with GUARD), 2 G
     // SCORE
-    const int32_t *bx, *by;           // box column / row of each source column / row (-1: none)
+    const int32_t *bx, *by;           // box column / row of each source column / row (-1: none) (blur_mfma_wide_kernel)
+    const uint32_t *coltab, *rowtab;  // blur_mfma_kernel: the set-up of every (tile column, wave, lane) and of every segment's rows, ready-made
     unsigned long long *slabs;        // [image][tile][2][slabn] packed 4 x u16 channel sums (blur.hip: box_from_slabs_kernel)
     int nbx, nby;
     int dbg;                          // development switches (FNX_MFMA_DBG)
+    int narrow;                       // every row offset of source and destination fits 31 bits (launch_mfma_cfg): interior workgroups address
+                                      // rows as scalar base + 32-bit lane offset
 };
 
 // (hi * 256 + mid) * 256 + lo as two v_lshl_add_u32 (left alone the compiler builds two shifts and a v_add3)
@@ -92,6 +95,19 @@ __device__ __forceinline__ const double *mf_scalar_ptr(const double *p)
     const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v)), hi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v >> 32));
     return reinterpret_cast<const double *>((static_cast<unsigned long long>(hi) << 32) | lo);
 }
+// a wave-uniform pointer pinned to a scalar register pair: a 32-bit lane offset added to it IN THE GLOBAL ADDRESS SPACE stays the
+// saddr form of global_load / global_store (left alone the compiler adds the lane's part to the pointer first and carries 64 bits
+// per lane; added to the generic pointer, the sum hides behind the address-space cast)
+typedef __attribute__((address_space(1))) uint8_t mf_g_u8;
+template <typename T> __device__ __forceinline__ T *mf_sgpr_ptr(T *p)
+{
+    unsigned long long v = reinterpret_cast<unsigned long long>(p);
+    asm volatile("" : "+s"(v));
+    return reinterpret_cast<T *>(v);
+}
+// ... and the lane's offset kept 32 bits wide up to the access (widened once before the march it is a 64-bit pair, no saddr offset
+// any more).  In place: the register stays the variable's, no copy.
+__device__ __forceinline__ void mf_lane_off(uint32_t &o) { asm volatile("" : "+v"(o)); }
 typedef int mf_s16i __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ uint32_t mf_exact_u(const double *wd, const uint8_t *base, int step, int ring0, int mask)
 {
@@ -130,7 +146,6 @@ __global__ __launch_bounds__(256, GUARD ? 3 : 1) void blur_mfma_kernel(MfmaArgs 
     // SCORE: byte offset of a staged row's / an output row's box row in the tables (spare row: outside the segment or the image)
     __shared__ __attribute__((aligned(16))) uint32_t s_rowh[SCORE ? MF_SEG_SCORE + 32 : 4];
     __shared__ __attribute__((aligned(16))) uint32_t s_rowv[SCORE ? MF_SEG_SCORE + 16 : 4];
-    __shared__ uint32_t s_colbox[SCORE ? 64 : 1];         // box column (relative to the tile's first) of each tile column, 255: none
     extern __shared__ __attribute__((aligned(16))) uint32_t s_box[];   // SCORE: [source | blurred][(nby+1)(nbx+1)][R, G, B, -]
 
     const int tile = xcd_tile(blockIdx.x, a.tiles);
@@ -181,40 +196,25 @@ __global__ __launch_bounds__(256, GUARD ? 3 : 1) void blur_mfma_kernel(MfmaArgs 
     uint32_t coln = 0;                                              // byte offset of this lane's (box column, channel) in a table row
     const int slabn = SCORE ? (a.nbx + 1) * (a.nby + 1) : 0;
     uint32_t *tbl_s = s_box, *tbl_b = s_box + 4 * slabn;
-    // (called from the march once the first two row sets' loads are in flight: its table look-ups then wait beside them)
+    // (called from the march once the first two row sets' loads are in flight: its table loads then wait beside them)
+    // Everything here depends on the launch's geometry alone, so the host builds it once per geometry (blur.hip:
+    // build_score_geom): one packed word per (tile column, wave, lane) and the two row tables per segment.  No barrier of
+    // its own: step 0's orders the LDS writes before their first readers (H set 0).
     auto score_setup = [&]() {
-        if (!(a.dbg & 4)) for (int e = tid; e < 8 * slabn; e += 256) s_box[e] = 0;
-        const int rowbytes = 16 * (a.nbx + 1);
-        const int b0y = a.by[y0];
-        for (int u = tid; u < 16 * NI; u += 256) {                  // staged row u = tile row u - 6
-            const int t = u - 6;
-            const int v = (t >= 0 && t < a.seg && y0 + t < a.h) ? a.by[y0 + t] : -1;
-            s_rowh[u] = rowbytes * ((v >= 0 && b0y >= 0) ? v - b0y : a.nby);
-        }
-        for (int t = tid; t < 16 * NJ; t += 256) {
-            const int v = (t < a.seg && y0 + t < a.h) ? a.by[y0 + t] : -1;
-            s_rowv[t] = rowbytes * ((v >= 0 && b0y >= 0) ? v - b0y : a.nby);
-        }
-        if (tid < 64) {
-            const int b0x = a.bx[x0], v = x0 + tid < a.w ? a.bx[x0 + tid] : -1;
-            s_colbox[tid] = (v >= 0 && b0x >= 0) ? v - b0x : 255u;
-        }
-        __syncthreads();
-        // the wave's 16 px: first box column present -> slot 0; lane n = 3 slot + channel (n = 15: nothing)
-        uint32_t first = 255u;
-        for (int i = 0; i < 16; i++) first = min(first, s_colbox[16 * wave + i]);
-        const int slot = r / 3, ch = r - 3 * slot;
-        int cnt = 0;
-        for (int i = 0; i < 16; i++) cnt += (r < 15 && s_colbox[16 * wave + i] == first + slot) ? 1 : 0;
-#pragma unroll
-        for (int e = 0; e < 4; e++) {                               // K = byte 16 g + 4 e + ch' of the row's 64 bytes
-            const bool in = r < 15 && first != 255u && s_colbox[16 * wave + 4 * g + e] == first + slot;
-            bbox[e] = in ? (1 << (8 * ch)) : 0;
-        }
-        const int seed = 128 * cnt;                                 // the A operands are (p - 128): the sums come out as sums of p
+        const uint32_t cw = a.coltab[256 * tx + tid];
+        const int nrow = (2 * a.seg + 16) >> 2;                     // 16-byte chunks of the segment's tables: s_rowh's seg + 16 words, then s_rowv's seg
+        const int nrh = (a.seg + 16) >> 2;
+        const u32x4 rw = reinterpret_cast<const u32x4 *>(a.rowtab)[static_cast<size_t>(ty) * nrow + min(tid, nrow - 1)];
+        if (!(a.dbg & 4)) for (int e = tid; e < 2 * slabn; e += 256) reinterpret_cast<u32x4 *>(s_box)[e] = (u32x4){0u, 0u, 0u, 0u};
+        if (tid < nrh) reinterpret_cast<u32x4 *>(s_rowh)[tid] = rw;
+        else if (tid < nrow) reinterpret_cast<u32x4 *>(s_rowv)[tid - nrh] = rw;
+        // cw: coln | cnt << 20 | (this lane's four K columns are in its box column) << 25 | channel << 29
+        coln = cw & 0xfffffu;
+        const int seed = static_cast<int>((cw >> 20) & 31u) << 7;   // 128 cnt: the A operands are (p - 128), the sums come out as sums of p
         sbox = (v4i){seed, seed, seed, seed};
-        const uint32_t bc = (r < 15 && first != 255u && cnt > 0) ? first + slot : static_cast<uint32_t>(a.nbx);
-        coln = 16u * bc + 4u * (r < 15 ? ch : 3);
+        const uint32_t sh = (cw >> 29) << 3;
+#pragma unroll
+        for (int e = 0; e < 4; e++) bbox[e] = static_cast<int>(((cw >> (25 + e)) & 1u) << sh);
     };
 
     // ---- exact recomputation of flagged samples (GUARD), the reference's own arithmetic (effects.go:169-217) ----
@@ -403,16 +403,33 @@ __global__ __launch_bounds__(256, GUARD ? 3 : 1) void blur_mfma_kernel(MfmaArgs 
         }
     };
 
-    // the march itself, in two forms: strips whose source window stays inside the image's columns (16-byte loads, rows
-    // clamped where a set leaves the image) and the first / last strips (clamped px loads, masked stores)
-    auto march = [&](auto xedget) {
-        constexpr bool XEDGE = decltype(xedget)::value;
-        // Interior strips: every lane issues both loads of every set, rows clamped per lane, no branch anywhere -- a load under
+    // the march itself, in three forms: workgroups whose whole source window lies inside the image (form 0: nothing to clamp or
+    // mask, rows addressed from a scalar base), strips whose window stays inside the image's columns (form 1: 16-byte loads, rows
+    // clamped where a set leaves the image) and the first / last strips (form 2: clamped px loads, masked stores)
+    auto march = [&](auto formt) {
+        constexpr int FORM = decltype(formt)::value;
+        constexpr bool XEDGE = FORM == 2, INNER = FORM == 0;
+        // form 0: a row set's address is a wave-uniform 64-bit base, advanced on the scalar unit, plus a 32-bit offset each lane
+        // computes once -- the saddr form of global_load / global_store; the step spends no vector instruction on addresses
+        // (the other forms do not use these)
+        const uint8_t *in_base = INNER ? src + static_cast<ptrdiff_t>(y0 - 6) * a.sstride + 4 * static_cast<ptrdiff_t>(x0 - 6) : src;
+        uint8_t *out_base = INNER ? dst + static_cast<ptrdiff_t>(y0) * a.dstride + 4 * static_cast<ptrdiff_t>(x0) : dst;
+        const uint32_t ss = static_cast<uint32_t>(a.sstride), ds = static_cast<uint32_t>(a.dstride);
+        const uint32_t in_set = 16u * ss, out_set = 16u * ds;
+        uint32_t in_l0 = static_cast<uint32_t>(srow0) * ss + 16u * sch0, in_l1 = static_cast<uint32_t>(srow1) * ss + 16u * sch1;
+        uint32_t out_l = static_cast<uint32_t>(orow) * ds + 16u * och;
+        // Forms 0 and 1: every lane issues both loads of every set (form 1: rows clamped per lane), no branch anywhere -- a load under
         // a branch (the few lanes of the second chunk, a set that touches the image's edge, the last sets of the march)
         // makes the compiler wait for ALL outstanding loads at the joins, and the march then runs one set ahead, not two.
         auto hload = [&](int i, u32x4 (&d)[2]) {
             const int ys = y0 - 6 + 16 * i;
-            if constexpr (!XEDGE) {
+            if constexpr (INNER) {
+                const mf_g_u8 *sb = (const mf_g_u8 *)mf_sgpr_ptr(in_base + static_cast<uint32_t>(i) * in_set);
+                mf_lane_off(in_l0);
+                mf_lane_off(in_l1);
+                d[0] = *(g_u32x4 *)(sb + in_l0);
+                d[1] = *(g_u32x4 *)(sb + in_l1);
+            } else if constexpr (!XEDGE) {
                 const uint8_t *sb = src + 4 * static_cast<ptrdiff_t>(x0 - 6);
                 const int ya = clampi(ys + srow0, 0, a.h - 1), yb = clampi(ys + srow1, 0, a.h - 1);   // clamp-to-edge (effects.go:174-178, 200-204)
                 d[0] = *(g_u32x4 *)(sb + static_cast<ptrdiff_t>(ya) * a.sstride + 16 * sch0);
@@ -431,6 +448,11 @@ __global__ __launch_bounds__(256, GUARD ? 3 : 1) void blur_mfma_kernel(MfmaArgs 
         };
         auto out_store = [&](int j, int buf) {                          // V set j's 16 rows, from the out stage
             const u32x4 o = *reinterpret_cast<const u32x4 *>(s_out + buf * 16 * OP + o_r);
+            if constexpr (INNER) {
+                mf_lane_off(out_l);
+                *(g_u32x4w *)((mf_g_u8 *)mf_sgpr_ptr(out_base + static_cast<uint32_t>(j) * out_set) + out_l) = o;
+                return;
+            }
             const int y = y0 + 16 * j + orow;
             if (y < a.h) {
                 uint8_t *dp = dst + static_cast<size_t>(y) * a.dstride + 4 * static_cast<size_t>(xo);
@@ -464,7 +486,11 @@ __global__ __launch_bounds__(256, GUARD ? 3 : 1) void blur_mfma_kernel(MfmaArgs 
         }
 
     };
-    if (xedge) march(std::true_type{}); else march(std::false_type{});
+    // form 0: no staged row (y0 - 6 .. y0 + 16 NJ + 9) and no column of the window leaves the image
+    const bool inner = !xedge && a.narrow && y0 >= 6 && y0 + 16 * NJ + 10 <= a.h;
+    if (xedge) march(std::integral_constant<int, 2>{});
+    else if (inner) march(std::integral_constant<int, 0>{});
+    else march(std::integral_constant<int, 1>{});
 
     if (SCORE && !(a.dbg & 2)) {   // the tile's slab: [0, slabn) source, [slabn, 2 slabn) blurred, 4 x u16 per entry (a box is <= 256 px)
         __syncthreads();
@@ -1014,6 +1040,12 @@ static int launch_mfma_cfg(fnx_ctx *ctx, int n, MfmaArgs &ma, size_t lds)
     ma.tiles_x = (ma.w + 63) / 64;
     ma.tiles = ma.tiles_x * ((ma.h + ma.seg - 1) / ma.seg);
     dim3 grid(8 * ((ma.tiles + 7) / 8), n);
+    // row offsets as 32-bit lane offsets (the kernel's form 0): a set below the last row included, for both images
+    auto fits = [&](int stride) {
+        return stride > 0 && stride < (1 << 24) &&
+               static_cast<long long>(ma.h - 1) * stride + 4LL * ma.w + 16LL * stride < (1LL << 31);
+    };
+    ma.narrow = fits(ma.sstride) && fits(ma.dstride);
     // the launch's events ride on its own packet (common.hpp: LaunchEvents); SCORE launches always carry a stop event:
     // the step's tail on the ctx's second stream waits for it (blur.hip: launch_blur_scored)
     LaunchEvents ev;
@@ -1152,9 +1184,10 @@ int launch_blur_mfma(fnx_ctx *ctx, int n, const uint8_t *src, const uint8_t *con
 
 // the one-pass form: blur + the tile slabs of both box-sum sides (blur.hip's launch_blur_scored owns the geometry)
 int launch_blur_mfma_scored(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstride, int w, int h, const double *kernel,
-                            int radius, int flags, uint8_t *const *dsts, int dstride, const int32_t *bx, const int32_t *by,
+                            int radius, int flags, uint8_t *const *dsts, int dstride, const uint32_t *coltab, const uint32_t *rowtab,
                             unsigned long long *slabs, int nbx, int nby, int seg)
 {
+    if (!coltab || !rowtab || seg > MF_SEG_SCORE) return FNX_NOOP;
     const bool exact = flags & FNX_BLUR_EXACT;
     MfmaArgs ma{};
     const int st = mfma_prepare(ctx, kernel, radius, exact, &ma);
@@ -1162,7 +1195,7 @@ int launch_blur_mfma_scored(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int
     ma.srcs = srcs; ma.dsts = dsts;
     ma.sstride = sstride; ma.dstride = dstride; ma.w = w; ma.h = h;
     ma.seg = seg;
-    ma.bx = bx; ma.by = by; ma.slabs = slabs; ma.nbx = nbx; ma.nby = nby;
+    ma.coltab = coltab; ma.rowtab = rowtab; ma.slabs = slabs; ma.nbx = nbx; ma.nby = nby;
     const size_t lds = sizeof(uint32_t) * 8 * static_cast<size_t>(nbx + 1) * (nby + 1);
     return exact ? launch_mfma_cfg<true, true>(ctx, n, ma, lds) : launch_mfma_cfg<true, false>(ctx, n, ma, lds);
 }

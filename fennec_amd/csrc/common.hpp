@@ -133,6 +133,9 @@ struct ScoreGeom {
     int seg = 0;
     int th = 0, nbx = 0, nby = 0;
     std::vector<int32_t> map;   // the table blob uploaded to SLOT_BOXMAP
+    // blur_mfma_kernel<SCORE, .>'s set-up tables at the blob's end (word offsets, 0: none): one packed word per
+    // (tile column, wave, lane); per segment the table offsets of its seg + 16 staged rows, then of its seg output rows
+    size_t coltab = 0, rowtab = 0;
 };
 
 // A CSR tap table of one resize pass (precomputeWeights, resize.go:164-197).  id != 0 marks an immutable
@@ -374,8 +377,9 @@ bool blur_mfma_takes(const double *kernel, int radius, int w, int h, bool exact)
 int blur_mfma_segment(const fnx_ctx *ctx, int n, int w, int h, int cap, int occ);
 int launch_blur_mfma(fnx_ctx *ctx, int n, const uint8_t *src, const uint8_t *const *srcs, int sstride, int w, int h,
                      const double *kernel, int radius, int flags, uint8_t *dst, uint8_t *const *dsts, int dstride);
+// (coltab / rowtab: build_score_geom's ready-made set-up of the kernel's column and row look-ups)
 int launch_blur_mfma_scored(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstride, int w, int h, const double *kernel,
-                            int radius, int flags, uint8_t *const *dsts, int dstride, const int32_t *bx, const int32_t *by,
+                            int radius, int flags, uint8_t *const *dsts, int dstride, const uint32_t *coltab, const uint32_t *rowtab,
                             unsigned long long *slabs, int nbx, int nby, int seg);
 bool blur_mfma_wide_scored_covers(const double *kernel, int radius, int w, int h, bool exact);
 int launch_blur_mfma_wide_scored(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstride, int w, int h, const double *kernel,
