@@ -30,7 +30,8 @@ def dev(a):
 
 
 def fibonacci_shuffle():
-    """21 symbols with counts 1, 1, 2, 3, 5, ... (28 656 bytes, one chunk): an unconstrained Huffman code is 20 deep"""
+    """21 symbols with counts 1, 1, 2, 3, 5, ... (28 656 bytes, one chunk): an unconstrained Huffman code of the BYTES is 20
+    deep; the block's own histogram (match lengths, the end-of-block) is not, see test_fibonacci_takes_a_huffman_form"""
     counts = [1, 1]
     while len(counts) < 21:
         counts.append(counts[-1] + counts[-2])
@@ -86,7 +87,10 @@ def test_round_trip(ctx, name):
         round_trip(ctx, gen(n), row)
 
 
-def test_fibonacci_needs_the_length_limit(ctx):
+def test_fibonacci_takes_a_huffman_form(ctx):
+    """a skewed block that takes a Huffman form.  It does NOT reach the 15-bit limit: the shuffle leaves many matches, and the
+    end-of-block's count of 1 beside the chain's two splits the chain, so the literal/length tree is 13 deep and the distance
+    tree 11.  The limit is reached, and certified from the stream, by test_deflate_structure_gpu.py::test_the_15_bit_limit."""
     x = fibonacci_shuffle()
     assert len(x) == 28656 and len(x) <= CH
     out = round_trip(ctx, x)
