@@ -15,8 +15,14 @@
 //    one dword of the TRANSPOSED uint8 intermediate (effects.go:186-188) T[byte column][row].
 //  * V pass, one set = 16 output rows x 16 byte columns: A = T (M = byte column, K = 32 staged rows, 8 contiguous bytes per
 //    lane), B = the weights (K x N = 16 output rows).  C is row-major again: lane (row, chunk) ends up with 4 px = 16 bytes.
+//    blur_mfma_kernel: A's rows are read through per-lane ring addresses, so WHICH 16 columns make a set is free.  A set is
+//    one colour channel of the wave's 16 px (M row (m4, mi) = channel q of px 4 m4 + mi): three sets cover the 48 colour
+//    columns, every accumulator row is a sample that is stored, and C hands lane (row, chunk) channel q of its own four px
+//    -- 9 matrix instructions and 3 ring reads per 16 output rows where four sets over all 64 columns took 12 and 4 and
+//    threw the alpha rows away.  The ring's 16-column groups are skewed for that read (mf_skew).  (blur_mfma_wide_kernel
+//    keeps four sets of 16 consecutive columns.)
 //  * alpha: the H sets' alpha columns carry the centre pixel's alpha through (weight digit 1, byte 0 of the sum), the V
-//    sets fetch it from the intermediate's alpha columns (effects.go:215: alpha comes from the ORIGINAL).
+//    sets fetch it from the intermediate's alpha columns as bytes (effects.go:215: alpha comes from the ORIGINAL).
 //  * SCORE: lane (row, chunk) layouts ARE matrix A operands, so the box sums are two more matrix instructions per 16 x 16
 //    px block (B = 0/1 indicator of up to 5 box columns x RGB over the 64 bytes) and 4 + 4 LDS atomics on what is left.
 //  * GUARD (FNX_BLUR_EXACT): S / 2^24 - exact sum lies in [-255 N, 255 P], N / P the sums of the negative / positive
@@ -46,11 +52,18 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 
 constexpr int MF_RMAX = 6;           // 4 output px + 2 R <= 16 px = the 64-byte K of one H instruction
 constexpr int MF_P = 48;             // bytes per byte column of the ring: 32 rows + 16 (= 16 mod 32: conflict-free 4-row dword writes)
-constexpr int MF_WT = 64 * MF_P + 256;   // ring bytes per wave: 64 byte columns + the 64-byte skew of each 16-column group
+constexpr int MF_WT = 64 * MF_P + 256;   // ring bytes per wave: 64 byte columns + the skew of each 16-column group (64 bytes each; blur_mfma_kernel: 80, mf_skew)
 constexpr int MF_SP = 352;           // pitch of a staged source row (19 chunks of 16 bytes): conflict-free as the A operand (tools/lds_conflicts.py)
 constexpr int MF_OP = 272;           // pitch of an output row in its stage
 constexpr int MF_SEG_SCORE = 272;    // most rows per workgroup with SCORE (row tables and box tables in LDS)
 constexpr int MF_SEG_SCORE_WIDE = 544;   // ... of blur_mfma_wide_kernel<2, ., SCORE>: two workgroups per CU either way (its ring and stages are 43 KB)
+
+// blur_mfma_kernel's ring: byte offset of 16-column group grp (one pixel group: 4 px x RGBA) on top of its columns -- 0, 80, 160,
+// 240 (ascending by less than MF_WT's 256 spare bytes: the groups do not overlap).  A V set reads ONE channel of the wave's 16 px
+// (columns 16 m4 + 4 mi + q), 8 bytes per lane: with the groups 5 x 4 dwords apart, 1 mod 4, the 16 columns of a half wave tile
+// the 64 banks (tools/lds_conflicts.py), and groups 0 / 1 and 2 / 3 lie 20 dwords apart for the alpha byte reads of a half wave.
+__host__ __device__ constexpr int mf_skew(int grp) { return 80 * grp; }
+static_assert(64 * MF_P + mf_skew(3) <= MF_WT, "the ring's last group ends inside the wave's ring");
 
 struct MfmaArgs {
     const uint8_t *src;
@@ -178,14 +191,16 @@ __global__ __launch_bounds__(256, GUARD ? 3 : 1) void blur_mfma_kernel(MfmaArgs 
     const bool two = tid < 48;
     const int st_w0 = srow0 * SP + 16 * sch0, st_w1 = srow1 * SP + 16 * sch1;
     const int st_r = r * SP + 64 * wave + 16 * g;                   // A operand of H set qq: + 16 qq
-    uint8_t *t_w = tw + r * P + 4 * g;                              // + (16 qq) P + 64 qq + 16 slot
+    uint8_t *t_w = tw + r * P + 4 * g;                              // + (16 qq) P + mf_skew(qq) + 16 slot
     const int m4 = r >> 2, mi = r & 3;
-    // A operand of V column set q (+ 4 q P): lane chunk g holds staged rows 8 g .. 8 g + 7 of the set's 32; an odd set's first
-    // 16 staged rows sit in ring rows 16..31, its last 16 in rows 0..15 -- a second lane address, the same weights
-    const uint8_t *t_r = tw + (16 * m4 + mi) * P + 64 * m4 + 8 * g;
-    const uint8_t *t_ro = tw + (16 * m4 + mi) * P + 64 * m4 + ((8 * g + 16) & 31);
-    const uint8_t *t_ae = tw + (16 * g + 3) * P + 64 * g + r + 6;   // centre row's alpha, even / odd V sets: + 4 q P
-    const uint8_t *t_ao = tw + (16 * g + 3) * P + 64 * g + ((r + 22) & 31);
+    // A operand of V set q = colour channel q of the wave's 16 px (+ q P): M row (m4, mi) is px 4 m4 + mi, so C hands lane (row, g)
+    // channel q of ITS four px and no accumulator row goes to an alpha column.  Lane chunk g holds staged rows 8 g .. 8 g + 7
+    // of the set's 32; an odd set's first 16 staged rows sit in ring rows 16..31, its last 16 in rows 0..15 -- a second lane
+    // address, the same weights
+    const uint8_t *t_r = tw + (16 * m4 + 4 * mi) * P + mf_skew(m4) + 8 * g;
+    const uint8_t *t_ro = tw + (16 * m4 + 4 * mi) * P + mf_skew(m4) + ((8 * g + 16) & 31);
+    const uint8_t *t_ae = tw + (16 * g + 3) * P + mf_skew(g) + r + 6;   // centre row's alpha of px 4 g + i, even / odd V sets: + 4 i P
+    const uint8_t *t_ao = tw + (16 * g + 3) * P + mf_skew(g) + ((r + 22) & 31);
     const int o_w = r * OP + 64 * wave + 16 * g;
     const int orow = tid >> 4, och = tid & 15;
     const int o_r = orow * OP + 16 * och;
@@ -252,7 +267,7 @@ __global__ __launch_bounds__(256, GUARD ? 3 : 1) void blur_mfma_kernel(MfmaArgs 
                     for (int k = 0; k < 4; k++) u[k] = mf_comb3(c2[q2][k], c1[q2][k], c0[q2][k]);
                     const uint32_t t01 = __builtin_amdgcn_perm((uint32_t)u[1], (uint32_t)u[0], sel01);
                     const uint32_t t23 = __builtin_amdgcn_perm((uint32_t)u[3], (uint32_t)u[2], sel23);
-                    *reinterpret_cast<uint32_t *>(t_w + (16 * qq) * P + 64 * qq + 16 * slot) = t01 | t23;
+                    *reinterpret_cast<uint32_t *>(t_w + (16 * qq) * P + mf_skew(qq) + 16 * slot) = t01 | t23;
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -282,7 +297,7 @@ __global__ __launch_bounds__(256, GUARD ? 3 : 1) void blur_mfma_kernel(MfmaArgs 
         for (int qq = 0; qq < 4; qq++) {
             const uint32_t t01 = __builtin_amdgcn_perm((uint32_t)u[qq][1], (uint32_t)u[qq][0], sel01);
             const uint32_t t23 = __builtin_amdgcn_perm((uint32_t)u[qq][3], (uint32_t)u[qq][2], sel23);
-            *reinterpret_cast<uint32_t *>(t_w + (16 * qq) * P + 64 * qq + 16 * slot) = t01 | t23;
+            *reinterpret_cast<uint32_t *>(t_w + (16 * qq) * P + mf_skew(qq) + 16 * slot) = t01 | t23;
         }
         if constexpr (GUARD) {
             // one test for the lane's 16 samples: the smallest fraction field (alpha lanes: their seed puts 2^23 + alpha there).
@@ -312,7 +327,7 @@ __global__ __launch_bounds__(256, GUARD ? 3 : 1) void blur_mfma_kernel(MfmaArgs 
                         const int b = __builtin_ctz(flL), qq = b >> 2, k = b & 3;
                         flL &= flL - 1;
                         const uint32_t e = mf_exact_u(wd, sbuf + (4 * gL + k) * SP + 4 * (16 * wave + 4 * qq + (rL >> 2)) + (rL & 3), 4, 0, 0xffff) ^ 0x80u;
-                        if (lane == L) *(t_w + (16 * qq) * P + 64 * qq + 16 * slot + k) = static_cast<uint8_t>(e);
+                        if (lane == L) *(t_w + (16 * qq) * P + mf_skew(qq) + 16 * slot + k) = static_cast<uint8_t>(e);
                     }
                 }
             }
@@ -321,63 +336,65 @@ __global__ __launch_bounds__(256, GUARD ? 3 : 1) void blur_mfma_kernel(MfmaArgs 
     // V set j: 16 output rows into out stage `buf`; odd sets find their first 16 staged rows in ring rows 16..31
     auto vset = [&](int j, int buf, auto oddt) {
         constexpr bool ODD = decltype(oddt)::value;
-        long A[4];
+        long A[3];
         uint32_t al[4];
 #pragma unroll
-        for (int q = 0; q < 4; q++) A[q] = *reinterpret_cast<const long *>((ODD ? t_ro : t_r) + (4 * q) * P);
+        for (int q = 0; q < 3; q++) A[q] = *reinterpret_cast<const long *>((ODD ? t_ro : t_r) + q * P);
 #pragma unroll
-        for (int q = 0; q < 4; q++) al[q] = *((ODD ? t_ao : t_ae) + (4 * q) * P);
-        int u[4][3];
-        if constexpr (!GUARD && !SCORE) {   // plain fast blur: two halves of two column sets (see the H sets)
+        for (int i = 0; i < 4; i++) al[i] = *((ODD ? t_ao : t_ae) + (4 * i) * P);
+        int u[3][4];                        // [channel][px of the lane's four]
+        if constexpr (!GUARD && !SCORE) {   // plain fast blur: two channels, then the third (see the H sets)
 #pragma unroll
             for (int hf = 0; hf < 2; hf++) {
+                const int nq = 2 - hf;
                 v4i c2[2], c1[2], c0[2];
 #pragma unroll
-                for (int q2 = 0; q2 < 2; q2++) {
+                for (int q2 = 0; q2 < nq; q2++) {
                     c2[q2] = __builtin_amdgcn_mfma_i32_16x16x32_i8(A[2 * hf + q2], bv2, zero, 0, 0, 0);
                     c1[q2] = __builtin_amdgcn_mfma_i32_16x16x32_i8(A[2 * hf + q2], bv1, zero, 0, 0, 0);
                     c0[q2] = __builtin_amdgcn_mfma_i32_16x16x32_i8(A[2 * hf + q2], bv0, sv, 0, 0, 0);
                 }
 #pragma unroll
-                for (int q2 = 0; q2 < 2; q2++)
+                for (int q2 = 0; q2 < nq; q2++)
 #pragma unroll
-                    for (int i = 0; i < 3; i++) u[2 * hf + q2][i] = mf_comb3(c2[q2][i], c1[q2][i], c0[q2][i]);
+                    for (int i = 0; i < 4; i++) u[2 * hf + q2][i] = mf_comb3(c2[q2][i], c1[q2][i], c0[q2][i]);
                 __builtin_amdgcn_sched_barrier(0);
             }
         } else {
-            v4i c2[4], c1[4], c0[4];
+            v4i c2[3], c1[3], c0[3];
 #pragma unroll
-            for (int q = 0; q < 4; q++) {
+            for (int q = 0; q < 3; q++) {
                 c2[q] = __builtin_amdgcn_mfma_i32_16x16x32_i8(A[q], bv2, zero, 0, 0, 0);
                 c1[q] = __builtin_amdgcn_mfma_i32_16x16x32_i8(A[q], bv1, zero, 0, 0, 0);
                 c0[q] = __builtin_amdgcn_mfma_i32_16x16x32_i8(A[q], bv0, sv, 0, 0, 0);
             }
 #pragma unroll
-            for (int q = 0; q < 4; q++)
+            for (int q = 0; q < 3; q++)
 #pragma unroll
-                for (int i = 0; i < 3; i++) u[q][i] = mf_comb3(c2[q][i], c1[q][i], c0[q][i]);
+                for (int i = 0; i < 4; i++) u[q][i] = mf_comb3(c2[q][i], c1[q][i], c0[q][i]);
         }
         u32x4 o;
 #pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const uint32_t t01 = __builtin_amdgcn_perm((uint32_t)u[q][1], (uint32_t)u[q][0], 0x0c0c0703u);
-            const uint32_t t23 = __builtin_amdgcn_perm(al[q], (uint32_t)u[q][2], 0x04030c0cu);
-            o[q] = t01 | t23;
+        for (int i = 0; i < 4; i++) {
+            const uint32_t t01 = __builtin_amdgcn_perm((uint32_t)u[1][i], (uint32_t)u[0][i], 0x0c0c0703u);
+            const uint32_t t23 = __builtin_amdgcn_perm(al[i], (uint32_t)u[2][i], 0x04030c0cu);
+            o[i] = t01 | t23;
         }
         uint8_t *op = s_out + buf * 16 * OP + o_w;
         *reinterpret_cast<u32x4 *>(op) = o;
         if constexpr (GUARD) {   // as in the H sets: provisional pixels to the out stage first, flagged bytes patched there
-            uint32_t m[4];
+            uint32_t m[3];
 #pragma unroll
-            for (int q = 0; q < 4; q++)
-                m[q] = min(min(static_cast<uint32_t>(u[q][0]) & 0x00ffffffu, static_cast<uint32_t>(u[q][1]) & 0x00ffffffu), static_cast<uint32_t>(u[q][2]) & 0x00ffffffu);
-            const uint32_t mm = min(min(min(m[0], m[1]), m[2]), m[3]);
+            for (int q = 0; q < 3; q++)
+                m[q] = min(min(min(static_cast<uint32_t>(u[q][0]) & 0x00ffffffu, static_cast<uint32_t>(u[q][1]) & 0x00ffffffu),
+                               static_cast<uint32_t>(u[q][2]) & 0x00ffffffu), static_cast<uint32_t>(u[q][3]) & 0x00ffffffu);
+            const uint32_t mm = min(min(m[0], m[1]), m[2]);
             if (__builtin_amdgcn_ballot_w64(mm < static_cast<uint32_t>(a.thr))) {
-                uint32_t fl = 0;                                                     // bit 4 q + i
+                uint32_t fl = 0;                                                     // bit 4 q + i: channel q of px i
 #pragma unroll
-                for (int q = 0; q < 4; q++)
+                for (int q = 0; q < 3; q++)
 #pragma unroll
-                    for (int i = 0; i < 3; i++) fl |= ((static_cast<uint32_t>(u[q][i]) & 0x00ffffffu) < static_cast<uint32_t>(a.thr) ? 1u : 0u) << (4 * q + i);
+                    for (int i = 0; i < 4; i++) fl |= ((static_cast<uint32_t>(u[q][i]) & 0x00ffffffu) < static_cast<uint32_t>(a.thr) ? 1u : 0u) << (4 * q + i);
                 unsigned long long todo = __builtin_amdgcn_ballot_w64(fl != 0);
                 while (todo) {
                     const int L = __builtin_ctzll(todo);
@@ -387,8 +404,8 @@ __global__ __launch_bounds__(256, GUARD ? 3 : 1) void blur_mfma_kernel(MfmaArgs 
                     while (flL) {
                         const int b = __builtin_ctz(flL), q = b >> 2, i = b & 3;
                         flL &= flL - 1;
-                        const uint32_t e = mf_exact_u(wd, tw + (16 * gL + 4 * q + i) * P + 64 * gL, 1, (ODD ? 16 : 0) + rL, 31);
-                        if (lane == L) op[4 * q + i] = static_cast<uint8_t>(e);
+                        const uint32_t e = mf_exact_u(wd, tw + (16 * gL + 4 * i + q) * P + mf_skew(gL), 1, (ODD ? 16 : 0) + rL, 31);
+                        if (lane == L) op[4 * i + q] = static_cast<uint8_t>(e);
                     }
                 }
                 if constexpr (SCORE) o = *reinterpret_cast<const u32x4 *>(op);       // the box sums are those of the exact image

@@ -43,6 +43,27 @@ if __name__ == '__main__':
         wr = max(cycles('write_b128', lambda l, w=w: waddr(l, w))[0] for w in range(4))
         rb = max(cycles('read_b64', lambda l, w=w, h=h: (l & 15) * SP + 24 + 64 * w + 16 * (l >> 4) + 8 * h)[0] for w in range(4) for h in range(2))
         print(f'stage pitch {SP}: A read {rd} (4), write {wr} (8), box operand read_b64 {rb} (2)')
+    # ring of blur_mfma_kernel: byte column c of a wave at c * P + skew(c // 16), 32 rows; a V set's A operand is 8 rows of 16
+    # columns (lane (m4, mi) = lane & 15, rows 8 g ..).  Three ways to pick the 16 columns: the four-set form (every fourth
+    # column of a pixel group: RGBA of px q), the 48 colour columns in order (colour 4 q + mi of group m4), one channel per set
+    P = 48
+    old_skew = lambda grp: 64 * grp
+    new_skew = lambda grp: 80 * grp
+    maps = {
+        'four sets, px q of each group, skew 64 grp': (4, old_skew, lambda m4, mi, q: 16 * m4 + mi + 4 * q),
+        'three sets, colours in order, skew 64 grp': (3, old_skew, lambda m4, mi, q: 16 * m4 + (4 * q + mi) + (4 * q + mi) // 3),
+        'three sets, channel q, skew 64 grp': (3, old_skew, lambda m4, mi, q: 16 * m4 + 4 * mi + q),
+        'three sets, channel q, skew 80 grp': (3, new_skew, lambda m4, mi, q: 16 * m4 + 4 * mi + q),
+    }
+    for name, (nq, skew, col) in maps.items():
+        rd = [cycles('read_b64', lambda l, q=q, odd=odd: col((l & 15) >> 2, l & 3, q) * P + skew((l & 15) >> 2) + ((8 * (l >> 4) + 16 * odd) & 31))[0]
+              for odd in range(2) for q in range(nq)]
+        al = [cycles('read_b32', lambda l, q=q, odd=odd: ((16 * (l >> 4) + 3 + 4 * q) * P + skew(l >> 4) + (((l & 15) + 6 + 16 * odd) & 31)) & ~3)[0]
+              for odd in range(2) for q in range(4)]
+        wr = [cycles('write_b32', lambda l, q=q, slot=slot: ((l & 15) + 16 * q) * P + skew(q) + 4 * (l >> 4) + 16 * slot)[0]
+              for slot in range(2) for q in range(4)]
+        print(f'ring, {name}: V operand read_b64 {sum(rd) // 2} per V group ({2 * nq}), alpha byte reads {sum(al) // 2} (8), '
+              f'H writes {sum(wr) // 2} per H group (8), at most {max(wr)} (2) each')
     for OP in range(256, 401, 16):
         wr = max(cycles('write_b128', lambda l, w=w: (l & 15) * OP + 64 * w + 16 * (l >> 4))[0] for w in range(4))
         rd = max(cycles('read_b128', lambda l, w=w: (4 * w + (l >> 4)) * OP + 16 * (l & 15))[0] for w in range(4))
