@@ -41,6 +41,7 @@ FNX_OK, FNX_NOOP, FNX_EMPTY = 0, 1, 2
 FNX_HOST, FNX_DEVICE, FNX_DEVICE_SRC = 0, 1, 2
 FNX_BLUR_FAST, FNX_BLUR_EXACT, FNX_BLUR_KEEP_BOX_SUMS = 0, 1, 2
 FNX_PNG_PALETTED, FNX_PNG_GRAY, FNX_PNG_NRGBA = 1, 2, 3      # fnx_png_reduce's kinds (compress.go:90-108)
+FNX_PNG_DECODE_ROWS = 1024                                    # png_decode.hip: rows a workgroup of png_unfilter_kernel keeps in flight
 FNX_DEFLATE_CHUNK, FNX_DEFLATE_SUB = 32768, 128               # deflate.hip: bytes per chunk (= per workgroup, per block) and per lane
 PROF_MAIN, PROF_SSIM, PROF_RESIZE, PROF_FX, PROF_JPEG = 1, 2, 4, 8, 16
 
@@ -100,7 +101,7 @@ class FennecError(RuntimeError):
 
 
 class FennecUnsupported(FennecError):
-    """fnx_jpeg_decode / fnx_jpeg_recompress: a file the device decoder does not take (FNX_ERR_UNSUPPORTED) -- decode it
+    """fnx_jpeg_decode / fnx_jpeg_recompress / fnx_png_decode: a file the device decoder does not take (FNX_ERR_UNSUPPORTED) -- decode it
     on the host."""
 
 
@@ -260,6 +261,9 @@ def load_library() -> C.CDLL:
         _sig(L, "fnx_deflate_bound", C.c_size_t, [C.c_size_t])
         _sig(L, "fnx_deflate", i, [ctx, i, _u8p, C.c_size_t, i, _u8p, C.c_size_t, C.POINTER(C.c_size_t)])
         _sig(L, "fnx_png_encode", i, [ctx, i, i, _u8p, i, i, i, i, i, _u8p, _u8p, C.c_size_t, C.POINTER(C.c_size_t)])
+        _sig(L, "fnx_inflate", i, [_u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(C.c_size_t)])
+        _sig(L, "fnx_png_info", i, [_u8p, C.c_size_t, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)])
+        _sig(L, "fnx_png_decode", i, [ctx, _u8p, C.c_size_t, i, C.c_void_p, i, C.POINTER(i), C.POINTER(i)])
         _sig(L, "fennec_CompressFilePNG", i, [ctx, _u8p, C.c_size_t, C.POINTER(FileOptions), _u8p, C.c_size_t, C.POINTER(C.c_size_t),
                                                C.POINTER(i), C.POINTER(i)])
         _sig(L, "fennec_gaussianKernel", None, [i, d, _f64p])
@@ -1072,7 +1076,7 @@ class Context:
         return res
 
     def compress_file_jpeg(self, data: bytes, target_ssim: float, orient: int = 1, max_w: int = 0, max_h: int = 0, auto_format: bool = False):
-        """CompressFile for a JPEG source in standard mode, every pixel stage on the device (fennec_CompressFileJPEG): decode,
+        """CompressFile for a JPEG or PNG source (the signature decides) in standard mode, every pixel stage on the device (fennec_CompressFileJPEG): decode,
         ApplyOrientation(orient), smartResize(max_w, max_h), analyzeFormat (auto_format), compressJPEGOptimal ->
         (bytes, quality, ssim, steps, original (w, h), final (w, h)); bytes is None when analyzeFormat chose PNG."""
         src = np.frombuffer(data, dtype=np.uint8)
@@ -1608,6 +1612,40 @@ class Context:
             self._chk(rc, "fnx_png_encode")
         return buf[:n.value].tobytes()
 
+    def png_decode_config(self, data: bytes):
+        """png.DecodeConfig as far as the device decoder goes: (w, h); FennecUnsupported for files it does not take (Adam7,
+        a dimension above 65535), FennecError for damaged ones.  Host work only."""
+        buf = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, dtype=np.uint8)
+        w, h = C.c_int(), C.c_int()
+        self._chk(self._lib.fnx_png_decode(self._h, buf.ctypes.data_as(_u8p), len(data), FNX_HOST, None, 0, C.byref(w), C.byref(h)),
+                  "fnx_png_decode")
+        return w.value, h.value
+
+    def png_decode(self, data: bytes, space: str = "device", out=None):
+        """toNRGBA(image.Decode(data)) for a PNG file (fnx_png_decode): chunk walk and inflate on the host, the row filters'
+        inverse and the pixel conversion on the device.  space="device": a torch tensor on the ctx's device; "host": an
+        (h, w, 4) uint8 array.  out: the destination instead of a fresh one (an (h, w, 4) view, rows may be strided)."""
+        if space not in ("device", "host"):
+            raise FennecError('space is "device" or "host"')
+        w, h, _, _, interlace = png_info(data)             # IHDR alone: the call below walks the file, once
+        if interlace or w > 65535 or h > 65535:
+            raise FennecUnsupported("fnx_png_decode: Adam7 interlace or a dimension above 65535 -- decode it on the host")
+        buf = np.frombuffer(data, dtype=np.uint8)
+        if out is not None:
+            dst = out
+        elif space == "device":
+            import torch
+            dst = torch.empty((h, w, 4), dtype=torch.uint8, device=f"cuda:{self.device}")
+        else:
+            dst = np.empty((h, w, 4), dtype=np.uint8)
+        d = _Img(dst)
+        if (d.w, d.h) != (w, h):
+            raise FennecError(f"out is {d.w} x {d.h}, the file {w} x {h}")
+        with self._ordered(dst):
+            self._chk(self._lib.fnx_png_decode(self._h, buf.ctypes.data_as(_u8p), len(data), d.space, d.ptr, d.stride, C.byref(C.c_int()),
+                                               C.byref(C.c_int())), "fnx_png_decode")
+        return dst
+
     def compress_file_png(self, data: bytes, orient: int = 1, max_w: int = 0, max_h: int = 0, cap: int | None = None):
         """CompressFile's PNG branch for a JPEG source in one call (fennec_CompressFilePNG): decode, ApplyOrientation(orient),
         smartResize(max_w, max_h), compressPNG's reduction, the encoder's row stage and the deflate on the device ->
@@ -1895,6 +1933,39 @@ def compress_png(img, level=9, device_deflate=False): return default_context(_de
 def deflate(buf, row=0): return default_context(_dev_of(buf)).deflate(buf, row)
 def png_encode(src, kind=None, ncolors=0, opaque=-1, palette=None): return default_context(_dev_of(src)).png_encode(src, kind, ncolors, opaque, palette)
 def deflate_bound(n): return int(load_library().fnx_deflate_bound(int(n)))
+
+
+def inflate(data: bytes, cap: int | None = None) -> bytes:
+    """The bytes of a zlib stream (fnx_inflate: host code, no device, no zlib).  cap: the most the stream may hold; by default
+    the buffer grows, up to the 1032 x len(data) a deflate stream can reach, until the stream fits.  FennecError for a damaged
+    stream, or one that holds more than cap bytes."""
+    L = load_library()
+    src = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, dtype=np.uint8)
+    bound = 1032 * len(data)
+    size = min(bound, max(64, 4 * len(data))) if cap is None else int(cap)
+    while True:
+        out = np.empty(max(size, 1), dtype=np.uint8)
+        n = C.c_size_t(0)
+        rc = L.fnx_inflate(src.ctypes.data, len(data), out.ctypes.data, size, C.byref(n))
+        if rc == FNX_OK:
+            return out[:n.value].tobytes()
+        if cap is None and n.value == size + 1 and size < bound:          # cap + 1: the buffer was small, nothing else is wrong so far
+            size = min(bound, 8 * size)
+            continue
+        raise FennecError(f"fnx_inflate failed ({rc}): {L.fnx_last_error().decode()}")
+
+
+def png_info(data: bytes):
+    """(w, h, colour type, bit depth, interlace) of a PNG file's IHDR (fnx_png_info: host code); FennecError when the
+    signature or the header is damaged."""
+    L = load_library()
+    src = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, dtype=np.uint8)
+    v = [C.c_int() for _ in range(5)]
+    rc = L.fnx_png_info(src.ctypes.data, len(data), *[C.byref(x) for x in v])
+    if rc < 0:
+        raise FennecError(f"fnx_png_info failed ({rc}): {L.fnx_last_error().decode()}")
+    return tuple(x.value for x in v)
+
 def png_reduce(img, max_colors=256, want_plane=True): return default_context(_dev_of(img)).png_reduce(img, max_colors, want_plane)
 def tryPalettize(img, max_colors=256): return default_context(_dev_of(img)).tryPalettize(img, max_colors)
 

@@ -109,6 +109,7 @@ enum Slot {
     SLOT_PNG,        // png_reduce.hip: the colour set's result (over, count, palette) and the colour -> index table of the plane pass
     SLOT_PNG_STREAM, // png_filter.hip: the filtered scanlines on their way to a host buffer
     SLOT_DEFLATE_TOK, SLOT_DEFLATE_SLOTS, SLOT_DEFLATE_OUT,   // deflate.hip: the chunks' tokens; the result word, the chunks' sizes and output slots; the stream on its way to a host buffer
+    SLOT_PNG_DEC_STREAM, SLOT_PNG_DEC_ROWS, SLOT_PNG_DEC_TAB,   // png_decode.hip: the inflated stream, the reconstructed rows, the unit table + the palette's pixel values
     SLOT_DONE,       // workgroup counters of the kernels that finish their own reduction (ssim.hip), zero between launches
     SLOT_COUNT
 };
@@ -679,6 +680,45 @@ struct JpegBatchItem {
 };
 size_t jpeg_decode_chunk_bytes(const JpegFile &f, size_t n);      // device scratch the file adds to a chunk (an upper estimate, from its bytes)
 int jpeg_decode_planes_chunk(fnx_ctx *ctx, int m, JpegBatchItem *items);
+// ---- PNG sources (png_parse.cpp: host only; png_decode.hip) ----
+struct PngFile {
+    int w = 0, h = 0, color_type = 0, depth = 0, interlace = 0;
+    int channels = 1;
+    int bpp = 1;                 // the filters' pixel distance: max(1, channels * depth / 8)
+    size_t rowbytes = 0;         // ceil(w * channels * depth / 8): a row of the inflated stream is 1 + rowbytes
+    int npal = 0, ntrns = 0;     // PLTE entries; tRNS alphas of a paletted file
+    bool has_trns = false;
+    uint8_t plte[768], trns[256];
+    uint16_t trns16[3] = {0, 0, 0};   // the tRNS sample(s) of colour types 0 and 2
+    std::vector<uint8_t> idat;   // the IDAT bodies back to back: one zlib stream
+};
+int png_corrupt(const char *what);          // set_error + FNX_ERR_INVALID
+int png_unsupported(const char *what);      // set_error + FNX_ERR_UNSUPPORTED
+// the signature and IHDR alone (CRC checked): the dimensions, and FNX_ERR_UNSUPPORTED for what the device does not take -- the
+// file-level probe of host_api.cpp, which decodes next and so leaves the walk of the other chunks to that call
+int png_probe(const uint8_t *data, size_t n, PngFile *f);
+int png_parse(const uint8_t *data, size_t n, PngFile *f);
+// the zlib stream src[0 .. n) into out[0 .. cap); *nbytes: the bytes written.  A stream with more than cap bytes is refused
+// with *nbytes = cap + 1
+int png_inflate(const uint8_t *src, size_t n, uint8_t *out, size_t cap, size_t *nbytes);
+// h * (1 + rowbytes), the size the inflated stream must have -- refused when the file's IDAT bytes cannot hold that much
+int png_stream_size(const PngFile &f, size_t *want);
+// png_unfilter_kernel's work: a workgroup keeps PNG_DEC_ROWS rows in flight, one per lane.  The chain-segment table (a row of
+// type None or Sub, and row 0, starts a segment; segments are independent) is cut into UNITS of whole segments, one workgroup
+// each: a unit ends at the first segment boundary at which it holds PNG_UNIT_MIN_ROWS rows, so a long chain is one unit however
+// long, and short segments share a workgroup instead of taking one each.  units: [first row, end row) pairs.  Refuses a
+// filter type above 4.
+constexpr int PNG_DEC_ROWS = FNX_PNG_DECODE_ROWS;
+constexpr int PNG_UNIT_MIN_ROWS = 64;
+int png_row_plan(const uint8_t *stream, const PngFile &f, std::vector<uint32_t> *units);
+void png_palette_table(const PngFile &f, uint32_t table[256]);   // r | g << 8 | b << 16 | a << 24 of every index, toNRGBA applied
+struct PngExpand {                          // what png_expand_kernel needs of the file
+    int w, h, color_type, depth, has_trns;
+    uint32_t key[3];                        // the tRNS sample(s)
+};
+size_t png_plane_pitch(const PngFile &f);   // bytes between the reconstructed rows: rowbytes rounded up to 16
+int launch_png_unfilter(fnx_ctx *ctx, const uint8_t *d_stream, const PngFile &f, const uint32_t *d_units, int nunits, uint8_t *d_rows);
+int launch_png_expand(fnx_ctx *ctx, const uint8_t *d_rows, const PngFile &f, const uint32_t *d_table, uint8_t *dst, int dstride);
 int launch_scan(fnx_ctx *ctx, const uint32_t *in, unsigned long long *out, unsigned long long *totals, int n, unsigned long long *grand);
 
 }  // namespace fnx

@@ -413,7 +413,27 @@ void fennec_pool_release(void)
     for (auto &e : all) fnx_ctx_destroy(e.second);
 }
 
-// What CompressFile does to a decoded JPEG before it looks at the format (fennec.go:107-129), on the device: image.Decode +
+// image.Decode's choice of decoder (io.go:65-88): a file that opens with the PNG signature is a PNG source, everything else goes
+// to the JPEG decoder (which refuses what is no JPEG).  Arguments and answers: fnx_jpeg_decode's.
+static bool is_png(const uint8_t *data, size_t n)
+{
+    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+    return n >= 8 && std::memcmp(data, sig, 8) == 0;
+}
+
+static int decode_file(fnx_ctx *ctx, const uint8_t *data, size_t n, int space, uint8_t *dst, int dstride, int *w, int *h)
+{
+    if (!is_png(data, n)) return fnx_jpeg_decode(ctx, data, n, space, dst, dstride, w, h);
+    if (dst == nullptr) {                       // the dimension probe: IHDR alone -- the decode that follows walks every chunk, once
+        PngFile f;
+        FNX_TRY(png_probe(data, n, &f));
+        *w = f.w; *h = f.h;
+        return FNX_OK;
+    }
+    return fnx_png_decode(ctx, data, n, space, dst, dstride, w, h);
+}
+
+// What CompressFile does to a decoded JPEG or PNG before it looks at the format (fennec.go:107-129), on the device: image.Decode +
 // toNRGBA of a file whose dimensions (w x h) the caller has read, ApplyOrientation (AutoOrient; the caller read the tag,
 // exif.go), smartResize (MaxWidth / MaxHeight).  *img: the resident tight *pw x *ph image (SLOT_FILE0 or SLOT_FILE1).
 static int file_stages(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_FileOptions *o, int w, int h, const uint8_t **pimg,
@@ -421,7 +441,7 @@ static int file_stages(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec
 {
     void *b0 = nullptr;
     FNX_TRY(scratch(ctx, SLOT_FILE0, static_cast<size_t>(w) * h * 4 + 16, &b0));
-    FNX_TRY(fnx_jpeg_decode(ctx, data, n, FNX_DEVICE, static_cast<uint8_t *>(b0), w * 4, &w, &h));
+    FNX_TRY(decode_file(ctx, data, n, FNX_DEVICE, static_cast<uint8_t *>(b0), w * 4, &w, &h));
     const uint8_t *img = static_cast<const uint8_t *>(b0);
     bool in0 = true;
     if (o->orient > 1 && o->orient <= 8) {                                         // fennec.go:119-122 (OrientNormal == 1)
@@ -459,8 +479,8 @@ int fennec_CompressFileJPEG(fnx_ctx *ctx, const uint8_t *data, size_t n, const f
     }
     *nbytes = 0;
     int w = 0, h = 0;
-    FNX_TRY(fnx_jpeg_decode(ctx, data, n, FNX_HOST, nullptr, 0, &w, &h));          // dimensions; refuses what the device decoder does not take
-    if (!(o->orient > 1 && o->orient <= 8) && o->max_w <= 0 && o->max_h <= 0 && !o->auto_format) {
+    FNX_TRY(decode_file(ctx, data, n, FNX_HOST, nullptr, 0, &w, &h));          // dimensions; refuses what the device decoder does not take
+    if (!is_png(data, n) && !(o->orient > 1 && o->orient <= 8) && o->max_w <= 0 && o->max_h <= 0 && !o->auto_format) {
         // nothing between the decode and the search: the item body without the decoded image (fnx_jpeg_recompress, r3)
         dims[0] = dims[2] = w; dims[1] = dims[3] = h;
         return fnx_jpeg_recompress(ctx, data, n, o->target_ssim, ssim_window(), out, cap, nbytes, quality, ssim, steps, &w, &h);
@@ -468,8 +488,8 @@ int fennec_CompressFileJPEG(fnx_ctx *ctx, const uint8_t *data, size_t n, const f
     const uint8_t *img = nullptr;
     FNX_TRY(file_stages(ctx, data, n, o, w, h, &img, &w, &h, dims));
     if (o->auto_format) {
-        // analyzeFormat (convert.go:105-146) on what a JPEG decodes to (opaque): PNG when fewer than 256 distinct colours
-        // among the sampled pixels.  The samples come to the host (<= 80 KB); the set is the reference's, early stop included.
+        // analyzeFormat (convert.go:105-146): PNG when a sampled pixel is translucent (a PNG source can be; what a JPEG decodes
+        // to is opaque) or fewer than 256 distinct colours are among the sampled pixels.  The samples come to the host (<= 80 KB); the set is the reference's, early stop included.
         const long long total = static_cast<long long>(w) * h;
         const long long step = total > 10000 ? total / 10000 : 1;
         const int ns = static_cast<int>((total + step - 1) / step);
@@ -506,7 +526,7 @@ int fennec_CompressFilePNGReduce(fnx_ctx *ctx, const uint8_t *data, size_t n, co
     *kind = 0;
     *ncolors = 0;
     int w = 0, h = 0;
-    FNX_TRY(fnx_jpeg_decode(ctx, data, n, FNX_HOST, nullptr, 0, &w, &h));          // dimensions; refuses what the device decoder does not take
+    FNX_TRY(decode_file(ctx, data, n, FNX_HOST, nullptr, 0, &w, &h));          // dimensions; refuses what the device decoder does not take
     const uint8_t *img = nullptr;
     FNX_TRY(file_stages(ctx, data, n, o, w, h, &img, &w, &h, dims));
     if (w > 65535 || h > 65535) {
@@ -542,7 +562,7 @@ int fennec_CompressFilePNGStream(fnx_ctx *ctx, const uint8_t *data, size_t n, co
     *color_type = 0;
     *bit_depth = 0;
     int w = 0, h = 0;
-    FNX_TRY(fnx_jpeg_decode(ctx, data, n, FNX_HOST, nullptr, 0, &w, &h));          // dimensions; refuses what the device decoder does not take
+    FNX_TRY(decode_file(ctx, data, n, FNX_HOST, nullptr, 0, &w, &h));          // dimensions; refuses what the device decoder does not take
     const uint8_t *img = nullptr;
     FNX_TRY(file_stages(ctx, data, n, o, w, h, &img, &w, &h, dims));
     if (w > 65535 || h > 65535) {
@@ -568,7 +588,7 @@ int fennec_CompressFilePNG(fnx_ctx *ctx, const uint8_t *data, size_t n, const fe
     *nbytes = 0;
     *kind = 0;
     int w = 0, h = 0;
-    FNX_TRY(fnx_jpeg_decode(ctx, data, n, FNX_HOST, nullptr, 0, &w, &h));          // dimensions; refuses what the device decoder does not take
+    FNX_TRY(decode_file(ctx, data, n, FNX_HOST, nullptr, 0, &w, &h));          // dimensions; refuses what the device decoder does not take
     const uint8_t *img = nullptr;
     FNX_TRY(file_stages(ctx, data, n, o, w, h, &img, &w, &h, dims));
     if (w > 65535 || h > 65535) {

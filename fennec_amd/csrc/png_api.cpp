@@ -1,6 +1,7 @@
 // The deflate entry points: fnx_deflate_bound, fnx_deflate (deflate.hip's two kernels behind the argument checks and the
 // staging of the three spaces) and fnx_png_encode (png_filter.hip's row stage, then the deflate, on the device; the file's
-// chunks and their CRCs on the host).
+// chunks and their CRCs on the host); and fnx_png_decode, the other direction: png_parse.cpp's host side (chunk walk, inflate,
+// the filter bytes), then png_decode.hip's two kernels.
 #include "common.hpp"
 
 #include <algorithm>
@@ -199,6 +200,51 @@ int fnx_png_encode(fnx_ctx *ctx, int space, int kind, const uint8_t *src, int ss
         dsrc = static_cast<const uint8_t *>(d);
     }
     return png_encode_device(ctx, kind, dsrc, sstride, w, h, ncolors, opaque, palette, out, cap, nbytes);
+}
+
+int fnx_png_decode(fnx_ctx *ctx, const uint8_t *data, size_t n, int space, uint8_t *dst, int dstride, int *w, int *h)
+{
+    FNX_REQUIRE(data != nullptr && w != nullptr && h != nullptr, "decode arguments");
+    FNX_REQUIRE(space == FNX_HOST || space == FNX_DEVICE, "space: FNX_HOST or FNX_DEVICE (also where only the dimensions are asked for)");
+    PngFile f;
+    if (dst == nullptr) {                        // png.DecodeConfig: the dimensions only (and whether the device takes the file);
+        FNX_TRY(png_parse(data, n, &f));         // host work, no ctx needed
+        *w = f.w; *h = f.h;
+        return FNX_OK;
+    }
+    FNX_ENTER(ctx);
+    FNX_TRY(png_parse(data, n, &f));
+    *w = f.w; *h = f.h;
+    FNX_TRY(check_img(dst, dstride, f.w, f.h, "dst"));
+    FNX_REQUIRE(space != FNX_DEVICE || (reinterpret_cast<uintptr_t>(dst) & 3u) == 0, "a device image is 4-byte aligned");
+    // the stream's size is known beforehand; fewer or more bytes are image/png's "not enough" / "too much pixel data"
+    size_t want = 0;
+    FNX_TRY(png_stream_size(f, &want));
+    void *pin = nullptr;
+    FNX_TRY(pinned_alloc(ctx, want + 64, &pin));
+    uint8_t *stream = static_cast<uint8_t *>(pin);
+    size_t got = 0;
+    FNX_TRY(png_inflate(f.idat.data(), f.idat.size(), stream, want, &got));
+    if (got != want) return png_corrupt("not enough pixel data");
+    std::vector<uint32_t> units;
+    FNX_TRY(png_row_plan(stream, f, &units));    // a filter type above 4 is refused here: nothing has been launched
+    DevOut d;
+    FNX_TRY(stage_out(ctx, space, dst, dstride, f.w, f.h, SLOT_OUT, &d));
+    void *ds = nullptr, *dr = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_PNG_DEC_STREAM, want + 64, &ds));            // the kernel's 16-byte loads reach up to 15 bytes past a row
+    FNX_TRY(scratch(ctx, SLOT_PNG_DEC_ROWS, png_plane_pitch(f) * f.h + 16, &dr));
+    FNX_HIP(hipMemcpyAsync(ds, stream, want, hipMemcpyHostToDevice, ctx->stream));
+    uint32_t table[256];
+    std::memset(table, 0, sizeof table);
+    if (f.color_type == 3) png_palette_table(f, table);
+    const void *hosts[2] = {units.data(), table};
+    const size_t sizes[2] = {sizeof(uint32_t) * units.size(), sizeof table};
+    void *dp[2];
+    FNX_TRY(upload_tables(ctx, SLOT_PNG_DEC_TAB, hosts, sizes, 2, dp));
+    FNX_TRY(launch_png_unfilter(ctx, static_cast<const uint8_t *>(ds), f, static_cast<const uint32_t *>(dp[0]), static_cast<int>(units.size() / 2),
+                                static_cast<uint8_t *>(dr)));
+    FNX_TRY(launch_png_expand(ctx, static_cast<const uint8_t *>(dr), f, static_cast<const uint32_t *>(dp[1]), d.p, d.stride));
+    return finish(ctx, space, &d);
 }
 
 }  // extern "C"

@@ -37,6 +37,7 @@ import "C"
 
 import (
 	"bufio"
+	"bytes"
 	"compress/zlib"
 	"context"
 	"encoding/binary"
@@ -1054,6 +1055,47 @@ func jpegDecodeHIP(data []byte) (img *image.NRGBA, ok bool) {
 	}
 	img = image.NewNRGBA(image.Rect(0, 0, int(w), int(h)))
 	st := C.fnx_jpeg_decode(c, (*C.uint8_t)(unsafe.Pointer(&data[0])), C.size_t(len(data)), C.FNX_HOST, pix(img), C.int(img.Stride), &w, &h)
+	runtime.KeepAlive(data)
+	if st != C.FNX_OK {
+		return nil, false
+	}
+	return img, true
+}
+
+// decodePNG is image.Decode + toNRGBA for a PNG file (io.go:65-88 -> convert.go:12-64): chunk walk and inflate on the host
+// inside the library, the row filters' inverse and the pixel conversion on the device.  The device does not take every
+// file -- Adam7 interlace, a dimension above 65535: FNX_ERR_UNSUPPORTED -- and may find one damaged (FNX_ERR_INVALID) or
+// not be there at all; in each case the reference's own decoder runs and the call is counted (HIPFallbacks()["decodePNG"]),
+// so what Go says about a damaged file stays Go's own answer.
+func decodePNG(data []byte) (*image.NRGBA, error) {
+	if img, ok := pngDecodeHIP(data); ok {
+		return img, nil
+	}
+	fellBack("decodePNG")
+	return decodePNGGo(data)
+}
+
+// decodePNGGo is the reference's path: png.Decode, then toNRGBA.
+func decodePNGGo(data []byte) (*image.NRGBA, error) {
+	img, err := png.Decode(bytes.NewReader(data))
+	if err != nil {
+		return nil, err
+	}
+	return toNRGBA(img), nil
+}
+
+func pngDecodeHIP(data []byte) (img *image.NRGBA, ok bool) {
+	c := poolGetIf(useDeviceSearch && len(data) > 8)
+	if c == nil {
+		return nil, false
+	}
+	defer pool.put(c)
+	var w, h C.int
+	if C.fnx_png_decode(c, (*C.uint8_t)(unsafe.Pointer(&data[0])), C.size_t(len(data)), C.FNX_HOST, nil, 0, &w, &h) != C.FNX_OK {
+		return nil, false
+	}
+	img = image.NewNRGBA(image.Rect(0, 0, int(w), int(h)))
+	st := C.fnx_png_decode(c, (*C.uint8_t)(unsafe.Pointer(&data[0])), C.size_t(len(data)), C.FNX_HOST, pix(img), C.int(img.Stride), &w, &h)
 	runtime.KeepAlive(data)
 	if st != C.FNX_OK {
 		return nil, false

@@ -69,7 +69,7 @@ extern "C" {
 #define FNX_ERR_NO_DEVICE (-2)
 #define FNX_ERR_HIP (-3)
 #define FNX_ERR_OOM (-4)
-#define FNX_ERR_UNSUPPORTED (-5) /* fnx_jpeg_decode / fnx_jpeg_recompress: a file the device decoder does not handle; decode it on the host */
+#define FNX_ERR_UNSUPPORTED (-5) /* fnx_jpeg_decode / fnx_jpeg_recompress / fnx_png_decode: a file the device decoder does not handle; decode it on the host */
 
 /* most images one *_batch / *_batch_enqueue call of round 6 takes (the image is a grid dimension of the launch) */
 #define FNX_BATCH_MAX 65535
@@ -705,6 +705,64 @@ int fnx_deflate(fnx_ctx *ctx, int space, const uint8_t *src, size_t n, int row, 
 int fnx_png_encode(fnx_ctx *ctx, int space, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors /* paletted: 1..256 */,
                    int opaque /* 1, 0, or -1: decide as Opaque() does */, const uint8_t *palette, uint8_t *out, size_t cap, size_t *nbytes);
 
+/* ---- PNG sources: loadImage's image.Decode + toNRGBA for a .png (io.go:65-88 -> convert.go:12-64) --------------------- */
+/* The zlib stream src[0 .. n) (RFC 1950: CM 8, CINFO <= 7, FCHECK; a preset dictionary is refused) of stored, fixed and dynamic
+ * deflate blocks (RFC 1951) into out[0 .. cap).  Pure host code: no context, no device, no zlib.  Refused (FNX_ERR_INVALID):
+ * a bad header, block type 3, LEN != ~NLEN, an over-subscribed code, an incomplete code (except, as zlib's and Go's
+ * inflaters allow, a literal/length or distance code with no code at all or a single one-bit code), a bit pattern outside a
+ * code, a distance that reaches before the start of the output, a stream that ends early, a wrong Adler-32 -- and a stream
+ * of more than cap bytes: that one alone leaves *nbytes = cap + 1 (call again with more room; a deflate stream grows at most
+ * 1032-fold, so 1032 * n always suffices), every other refusal *nbytes <= cap.  Bytes behind the Adler-32 are not looked at.
+ * *nbytes: the output's size. */
+int fnx_inflate(const uint8_t *src, size_t n, uint8_t *out, size_t cap, size_t *nbytes);
+/* What a PNG file's signature and IHDR say (CRC checked): FNX_OK for every well-formed header -- also the interlaced and
+ * oversized ones fnx_png_decode answers FNX_ERR_UNSUPPORTED to -- else FNX_ERR_INVALID.  Pure host code, no context. */
+int fnx_png_info(const uint8_t *data, size_t n, int *w, int *h, int *color_type, int *bit_depth, int *interlace);
+/* dst = toNRGBA(image.Decode(data)) for a PNG file, *w x *h.  The contract is fnx_jpeg_decode's: `data` is HOST memory, dst is
+ * in `space` (FNX_HOST or FNX_DEVICE; a device dst is 4-byte aligned); dst == NULL: the dimensions only and whether the device
+ * takes the file (host work: ctx may be NULL; `space` is checked there too).  Bad arguments and damaged files are refused
+ * before anything is launched.
+ * Go's image/png is not part of the reference tree, so the rule is restated here and parity with Go is unpinned in the sense
+ * of DESIGN.md section 1; tests/png_decode_ref.py restates exactly this text.
+ * Host (csrc/png_parse.cpp): the signature and every chunk's CRC-32; IHDR first (w, h >= 1, one of the 15 colour type / bit
+ * depth pairs, compression 0, filter 0); PLTE once, before tRNS and IDAT, 1..256 entries (at most 2^depth for colour type 3,
+ * none for types 0 and 4), mandatory for type 3; tRNS once, before IDAT, after PLTE: <= 256 alphas for type 3, one 16-bit sample for
+ * type 0, three for type 2, illegal for 4 and 6; consecutive IDATs concatenated; IEND ends the file; every other chunk is
+ * skipped after its CRC.  A violation is FNX_ERR_INVALID.  The IDAT stream goes through fnx_inflate's code and must yield
+ * exactly h * (1 + rowbytes) bytes, rowbytes = ceil(w * channels * depth / 8); each row's first byte is its filter type, above
+ * 4: FNX_ERR_INVALID.  FNX_ERR_UNSUPPORTED (decode it on the host): Adam7-interlaced files, w or h above 65535.
+ * Reconstruction (png_unfilter_kernel), the inverse of fnx_png_filter's table: with bpp = max(1, channels * depth / 8),
+ * a = the reconstructed byte bpp to the left (0 for i < bpp), b = the byte above (0 for row 0), c = the byte above-left (0
+ * for i < bpp or row 0), f the stream's byte, mod 256:
+ *   0 None f    1 Sub f + a    2 Up f + b    3 Average f + ((a + b) >> 1), the sum in 9 bits    4 Paeth f + paeth(a, b, c),
+ *   p = a + b - c, pa = |p-a|, pb = |p-b|, pc = |p-c|: a if pa <= pb && pa <= pc, else b if pb <= pc, else c.
+ * Rows of type None and Sub, and row 0, do not read the row above: they cut the image into independent chain segments.  A
+ * workgroup keeps FNX_PNG_DECODE_ROWS rows of a chain in flight, one lane a row, each one pixel behind the row above, and
+ * marches a longer chain band by band itself; no workgroup waits for another.  Bit-exact, independent of launch geometry.
+ * Pixels (png_expand_kernel).  Samples of depth 1, 2, 4 are unpacked MSB first, grey values scaled by 0xff, 0x55, 0x11; 16-bit
+ * samples are big-endian.  A tRNS match compares, at depth <= 8, the raw sample(s) with the LOW BYTE of the tRNS sample(s), at
+ * depth 16 the full samples.
+ *   source                                Go's type            toNRGBA's pixel
+ *   type 6 / 8                            *image.NRGBA         the stored bytes (convert.go:13-17 copies)
+ *   type 4 / 8                            *image.NRGBA         (y, y, y, a)
+ *   type 0, depth <= 8, tRNS              *image.NRGBA         (y, y, y, 0) for a match, else (y, y, y, 255): the colour is KEPT
+ *   type 2 / 8, tRNS                      *image.NRGBA         (r, g, b, 0) for a match, else (r, g, b, 255): the colour is KEPT
+ *   type 0, depth <= 8                    *image.Gray          (y, y, y, 255)
+ *   type 2 / 8                            *image.RGBA          (r, g, b, 255)
+ *   type 0 / 16                           *image.Gray16        (hi, hi, hi, 255), hi = the sample's high byte
+ *   type 2 / 16                           *image.RGBA64        the high bytes, 255
+ *   types 0 / 16 and 2 / 16 with tRNS (A = 0 for a match, else 0xffff), 4 / 16, 6 / 16: *image.NRGBA64 through convertToNRGBA
+ *     (convert.go:34-64), in exact uint32 on the 16-bit R, G, B, A: A == 0 -> (0, 0, 0, 0), the colour ZEROED; A == 0xffff ->
+ *     (R >> 8, G >> 8, B >> 8, 255); else r' = R * A / 0xffff and the pixel is ((r' * 0xffff / A) >> 8, ..., A >> 8)
+ *   type 3                                *image.Paletted      entry i is (r, g, b, t), t = tRNS[i] or 255, as a color.NRGBA; with
+ *     A16 = t * 0x101: t == 255 -> (r, g, b, 255); t == 0 -> (0, 0, 0, 0); else r' = (r * 0x101) * t / 0xff and the pixel is
+ *     ((r' * 0xffff / A16) >> 8, ..., t) -- lossy on purpose, it is the reference's round trip.  An index behind the palette's
+ *     end reads as opaque black (under tRNS[i] where tRNS is longer than PLTE).  The 256 pixel values are made on the host.
+ * Inflate is one serial bit stream and stays on the host; the stream goes up as it is, 1/8 to 8 bytes a pixel.
+ * Kernels: csrc/png_decode.hip; fnx_ctx_last_kernel(ctx, FNX_PROF_MAIN) answers "png_unfilter_kernel, png_expand_kernel". */
+#define FNX_PNG_DECODE_ROWS 1024   /* rows a workgroup of png_unfilter_kernel keeps in flight */
+int fnx_png_decode(fnx_ctx *ctx, const uint8_t *data, size_t n, int space, uint8_t *dst, int dstride, int *w, int *h);
+
 /* ======================================================================= */
 /* fennec_* : the reference's function set (names and argument meaning as in
  * the Go source), mirrored above fnx_*.                                     */
@@ -803,13 +861,15 @@ int fennec_CompressBatchNRGBADevices(const int *devices, int ndev, int workers, 
                                      const int *strides, const int *widths, const int *heights, const int64_t *original_sizes,
                                      double target_ssim, uint8_t *const *outs, const size_t *caps, fennec_BatchResult *results,
                                      const volatile int *cancel /* may be NULL */, fennec_on_item on_item /* may be NULL */, void *user);
-/* CompressFile for a JPEG source in standard mode (fennec.go:30-76 -> compressImageInternal :107-141 -> handleStandardMode
- * :162-205) from the file's bytes with every pixel stage on the device: image.Decode + toNRGBA (fnx_jpeg_decode),
+/* CompressFile for a JPEG or PNG source in standard mode (fennec.go:30-76 -> compressImageInternal :107-141 -> handleStandardMode
+ * :162-205) from the file's bytes with every pixel stage on the device: image.Decode + toNRGBA (a file that opens with the
+ * eight PNG signature bytes goes to fnx_png_decode, every other one to fnx_jpeg_decode; the same holds for the three
+ * fennec_CompressFilePNG* entries below and for the items of fennec_CompressBatchJPEGOpts),
  * ApplyOrientation when opts->orient is 2..8 (Options.AutoOrient; the caller reads the tag as exif.go does),
  * smartResize when max_w or max_h > 0 (Options.MaxWidth / MaxHeight), analyzeFormat when auto_format (Format: Auto),
  * compressJPEGOptimal at target_ssim.  dims = {OriginalDimensions (after orientation), FinalDimensions}.
- * FNX_NOOP: analyzeFormat chose PNG (fewer than 256 sampled colours) -- the caller's compressPNG takes the item, dims are
- * set.  FNX_ERR_UNSUPPORTED as fnx_jpeg_decode.  Target-size mode is a call of its own: hitTargetSize's JPEG
+ * FNX_NOOP: analyzeFormat chose PNG (a translucent sampled pixel, which only a PNG source can have, or fewer than 256 sampled
+ * colours) -- the caller's compressPNG takes the item, dims are set.  FNX_ERR_UNSUPPORTED as fnx_jpeg_decode / fnx_png_decode.  Target-size mode is a call of its own: hitTargetSize's JPEG
  * strategies run on the device in fnx_jpeg_target_size (the PNG strategy stays the caller's). */
 typedef struct fennec_FileOptions {
     int32_t orient;      /* EXIF orientation 1..8; <= 1: none */
