@@ -42,6 +42,7 @@ FNX_HOST, FNX_DEVICE, FNX_DEVICE_SRC = 0, 1, 2
 FNX_BLUR_FAST, FNX_BLUR_EXACT, FNX_BLUR_KEEP_BOX_SUMS = 0, 1, 2
 FNX_PNG_PALETTED, FNX_PNG_GRAY, FNX_PNG_NRGBA = 1, 2, 3      # fnx_png_reduce's kinds (compress.go:90-108)
 FNX_PNG_DECODE_ROWS = 1024                                    # png_decode.hip: rows a workgroup of png_unfilter_kernel keeps in flight
+FNX_PNG_DECODE_CHUNK = 32                                     # fnx_png_decode_batch: files per set of launches, at most
 FNX_DEFLATE_CHUNK, FNX_DEFLATE_SUB = 32768, 128               # deflate.hip: bytes per chunk (= per workgroup, per block) and per lane
 PROF_MAIN, PROF_SSIM, PROF_RESIZE, PROF_FX, PROF_JPEG = 1, 2, 4, 8, 16
 
@@ -264,6 +265,8 @@ def load_library() -> C.CDLL:
         _sig(L, "fnx_inflate", i, [_u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(C.c_size_t)])
         _sig(L, "fnx_png_info", i, [_u8p, C.c_size_t, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)])
         _sig(L, "fnx_png_decode", i, [ctx, _u8p, C.c_size_t, i, C.c_void_p, i, C.POINTER(i), C.POINTER(i)])
+        _sig(L, "fnx_png_decode_batch", i, [ctx, i, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(i), i,
+                                            C.POINTER(i), C.POINTER(i), C.POINTER(i)])
         _sig(L, "fennec_CompressFilePNG", i, [ctx, _u8p, C.c_size_t, C.POINTER(FileOptions), _u8p, C.c_size_t, C.POINTER(C.c_size_t),
                                                C.POINTER(i), C.POINTER(i)])
         _sig(L, "fennec_gaussianKernel", None, [i, d, _f64p])
@@ -1645,6 +1648,40 @@ class Context:
             self._chk(self._lib.fnx_png_decode(self._h, buf.ctypes.data_as(_u8p), len(data), d.space, d.ptr, d.stride, C.byref(C.c_int()),
                                                C.byref(C.c_int())), "fnx_png_decode")
         return dst
+
+    def png_decode_batch(self, files, device: bool = False, workers: int = 0):
+        """toNRGBA(image.Decode(f)) of every PNG file of a list in one call (fnx_png_decode_batch: the files' host side on
+        `workers` threads -- 0: min(8, files in a chunk) --, then one set of launches per chunk) -> (images, statuses).
+        images[i] is an (h, w, 4) uint8 array -- with device=True a torch tensor on the ctx's device -- and what
+        png_decode(files[i]) returns, or None where statuses[i] != FNX_OK."""
+        import torch
+        files = [bytes(f) for f in files]
+        n = len(files)
+        if n == 0:
+            raise FennecError("png_decode_batch takes a non-empty list of files")
+        bufs = [np.frombuffer(f, dtype=np.uint8) if len(f) else np.zeros(1, dtype=np.uint8) for f in files]
+        dsts = []
+        for f in files:                                   # a file whose header does not parse goes in with no destination
+            try:
+                w, h, _, _, interlace = png_info(f)
+                if interlace or w > 65535 or h > 65535:   # refused by the call; no memory is sized by such a header
+                    dsts.append(None)
+                else:
+                    dsts.append(torch.empty((h, w, 4), dtype=torch.uint8, device=f"cuda:{self.device}"))
+            except FennecError:
+                dsts.append(None)
+        views = [None if t is None else _Img(t) for t in dsts]
+        pf = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+        ps = (C.c_size_t * n)(*[len(f) for f in files])
+        pd = (C.c_void_p * n)(*[None if v is None else v.ptr for v in views])
+        pst = (C.c_int * n)(*[0 if v is None else v.stride for v in views])
+        ws, hs, status = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        with self._ordered(*[t for t in dsts if t is not None]):
+            self._chk(self._lib.fnx_png_decode_batch(self._h, n, pf, ps, pd, pst, int(workers), ws, hs, status), "fnx_png_decode_batch")
+            images = [dsts[i] if status[i] == FNX_OK else None for i in range(n)]
+            if not device:
+                images = [None if t is None else t.cpu().numpy() for t in images]
+        return images, list(status)
 
     def compress_file_png(self, data: bytes, orient: int = 1, max_w: int = 0, max_h: int = 0, cap: int | None = None):
         """CompressFile's PNG branch for a JPEG source in one call (fennec_CompressFilePNG): decode, ApplyOrientation(orient),

@@ -188,6 +188,12 @@ struct fnx_ctx {
     // pinned host ring: tables going up, scalars coming down
     unsigned char *pinned = nullptr;
     size_t pinned_cap = 0, pinned_off = 0;
+    // fnx_png_decode_batch: the pinned home of a chunk's inflated streams, and the event behind the chunk's uploads -- the next
+    // chunk (of this call or a later one) is inflated into the same bytes once that event has passed
+    unsigned char *png_stage = nullptr;
+    size_t png_stage_cap = 0;
+    hipEvent_t png_stage_ev = nullptr;
+    bool png_stage_busy = false;
     int num_cus = 256;
     // results of the *_enqueue calls not fetched yet, oldest first: each batch has its own pinned slots and
     // an event right behind its result kernels, so a fetch waits for THAT batch only and a caller may queue
@@ -717,6 +723,45 @@ struct PngExpand {                          // what png_expand_kernel needs of t
     uint32_t key[3];                        // the tRNS sample(s)
 };
 size_t png_plane_pitch(const PngFile &f);   // bytes between the reconstructed rows: rowbytes rounded up to 16
+// fnx_png_decode_batch's host side: everything fnx_png_decode does to a file before its first launch, for m files on up to
+// `workers` threads (1: the calling thread alone, no thread started; more: the calling thread is one of them), handed out by
+// an atomic index.  No HIP call, no ctx.  In: stream / cap, where the file's inflated stream goes (the batch's pinned staging;
+// cap 0 for a file whose header promises more than its bytes can hold -- png_stream_size refuses it before the inflate).  Out:
+// status, and for a refused file `what`, the static text png_corrupt / png_unsupported was called with (set_error is
+// thread_local, so the caller re-issues the message: png_reissue).  Nothing depends on which thread took which file.
+struct PngPrepared {
+    uint8_t *stream = nullptr;
+    size_t cap = 0;
+    PngFile f;
+    size_t want = 0;                        // the stream's bytes
+    std::vector<uint32_t> units;            // png_row_plan
+    uint32_t table[256] = {};               // png_palette_table (colour type 3; zeros otherwise)
+    int status = FNX_OK;
+    const char *what = nullptr;
+};
+int png_workers(int workers, int m);        // the threads png_prepare_many runs m files on: 0 -> min(8, m), never above m
+void png_prepare_many(const uint8_t *const *files, const size_t *sizes, int m, int workers, PngPrepared *items);
+int png_reissue(const PngPrepared &it);     // the item's set_error again, on this thread; returns its status
+// a chunk of prepared files through one set of launches (png_decode.hip): per file what the two batched kernels read
+struct PngBatchFile {
+    const uint8_t *stream;                  // h rows of spitch = 1 + rowbytes bytes, 16 readable bytes on both sides
+    size_t spitch;
+    uint8_t *rows;                          // the reconstructed rows, ppitch (a multiple of 16) apart
+    size_t ppitch;
+    int rowbytes, npix;
+    PngExpand e;
+    const uint32_t *table;                  // colour type 3: the file's 256 pixel values
+    uint8_t *dst;
+    int dstride;
+    uint32_t tile0;                         // png_expand_batch_kernel: the file's first workgroup (256 pixels of a row each)
+};
+struct PngBatchUnit {
+    uint32_t file, r0, r1;                  // rows [r0, r1) of file `file` of the chunk
+};
+// d_units: the chunk's units sorted by bpp, nunits[k] of them with bpp PNG_BPPS[k]; d_files: m descriptors; tiles: the sum of
+// the files' workgroups of the expand kernel
+constexpr int PNG_BPPS[6] = {1, 2, 3, 4, 6, 8};
+int launch_png_decode_chunk(fnx_ctx *ctx, const PngBatchUnit *d_units, const int nunits[6], const PngBatchFile *d_files, int m, uint32_t tiles);
 int launch_png_unfilter(fnx_ctx *ctx, const uint8_t *d_stream, const PngFile &f, const uint32_t *d_units, int nunits, uint8_t *d_rows);
 int launch_png_expand(fnx_ctx *ctx, const uint8_t *d_rows, const PngFile &f, const uint32_t *d_table, uint8_t *dst, int dstride);
 int launch_scan(fnx_ctx *ctx, const uint32_t *in, unsigned long long *out, unsigned long long *totals, int n, unsigned long long *grand);

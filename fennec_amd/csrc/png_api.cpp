@@ -1,7 +1,8 @@
 // The deflate entry points: fnx_deflate_bound, fnx_deflate (deflate.hip's two kernels behind the argument checks and the
 // staging of the three spaces) and fnx_png_encode (png_filter.hip's row stage, then the deflate, on the device; the file's
 // chunks and their CRCs on the host); and fnx_png_decode, the other direction: png_parse.cpp's host side (chunk walk, inflate,
-// the filter bytes), then png_decode.hip's two kernels.
+// the filter bytes), then png_decode.hip's two kernels; and fnx_png_decode_batch, which does the host side of a chunk of files
+// on several threads and sends the chunk through one set of launches.
 #include "common.hpp"
 
 #include <algorithm>
@@ -55,6 +56,159 @@ uint8_t *close_chunk(uint8_t *at, const char *tag, size_t len)
     std::memcpy(at + 4, tag, 4);
     put_be32(at + 8 + len, ~crc32_update(0xffffffffu, at + 4, 4 + len));
     return at + 12 + len;
+}
+
+// ---- fnx_png_decode_batch ---------------------------------------------------------------------------------------------------
+// the device scratch (inflated streams + reconstructed planes) a chunk may ask for; a file that alone needs more is a chunk of one
+constexpr size_t PNG_BATCH_SCRATCH = FNX_PNG_DECODE_CHUNK_BYTES;
+
+size_t align16(size_t v) { return (v + 15) & ~size_t(15); }
+
+struct BatchEntry {              // a file of the chunk in hand
+    int index = 0;               // in the caller's arrays
+    size_t stream_off = 0;       // in the staging area and in SLOT_PNG_DEC_STREAM alike: 16-byte aligned, want + 64 bytes
+    size_t rows_off = 0;         // in SLOT_PNG_DEC_ROWS
+};
+
+// the batch's answer for its error text: the message of the lowest-indexed refused item
+struct FirstRefusal {
+    int index = -1;
+    char text[512] = "";
+    void note(int i)             // item i was refused just now: its message is this thread's last error
+    {
+        if (index >= 0 && index < i) return;
+        index = i;
+        std::snprintf(text, sizeof text, "%s", fnx_last_error());
+    }
+};
+
+// the chunk's pinned staging area, free to be written: the uploads of the chunk before it have completed
+int png_stage(fnx_ctx *ctx, size_t bytes, uint8_t **out)
+{
+    if (!ctx->png_stage_ev) FNX_HIP(hipEventCreateWithFlags(&ctx->png_stage_ev, hipEventDisableTiming));
+    if (ctx->png_stage_busy) {
+        FNX_HIP(hipEventSynchronize(ctx->png_stage_ev));
+        ctx->png_stage_busy = false;
+    }
+    if (bytes > ctx->png_stage_cap) {
+        if (ctx->png_stage) FNX_HIP(hipHostFree(ctx->png_stage));
+        ctx->png_stage = nullptr;
+        ctx->png_stage_cap = 0;
+        const size_t cap = (bytes + bytes / 4 + 4095) & ~size_t(4095);
+        FNX_HIP(hipHostMalloc(reinterpret_cast<void **>(&ctx->png_stage), cap, hipHostMallocDefault));
+        ctx->png_stage_cap = cap;
+    }
+    *out = ctx->png_stage;
+    return FNX_OK;
+}
+
+// One chunk: the host side of its files on `workers` threads, then -- on this thread, which owns the stream -- the uploads of
+// the files that passed, the tables, and one set of launches.  Below 0 only where the chunk could not run at all.
+int png_decode_chunk(fnx_ctx *ctx, const std::vector<BatchEntry> &chunk, const std::vector<PngFile> &heads, size_t stage_bytes, size_t rows_bytes,
+                     const uint8_t *const *files, const size_t *sizes, uint8_t *const *dsts, const int *dstrides, int workers, int *status,
+                     FirstRefusal *first)
+{
+    const int m = static_cast<int>(chunk.size());
+    uint8_t *stage = nullptr;
+    FNX_TRY(png_stage(ctx, stage_bytes ? stage_bytes : 16, &stage));
+    std::vector<PngPrepared> items(m);
+    std::vector<const uint8_t *> cf(m);
+    std::vector<size_t> cs(m);
+    for (int j = 0; j < m; j++) {
+        const PngFile &h = heads[j];
+        const size_t want = static_cast<size_t>(h.h) * (1 + h.rowbytes);
+        cf[j] = files[chunk[j].index];
+        cs[j] = sizes[chunk[j].index];
+        if (want / 1032 <= cs[j]) {                      // else png_stream_size refuses the file: it gets no room
+            items[j].stream = stage + chunk[j].stream_off;
+            items[j].cap = want;
+        }
+    }
+    png_prepare_many(cf.data(), cs.data(), m, workers, items.data());
+
+    // verdicts in index order; the files that passed get a descriptor each, and their units are sorted by bpp
+    std::vector<PngBatchFile> desc;
+    std::vector<int> ok;
+    std::vector<PngBatchUnit> units[6];
+    size_t npal = 0;
+    for (int j = 0; j < m; j++) {
+        const int i = chunk[j].index;
+        status[i] = items[j].status;
+        if (items[j].status != FNX_OK) {
+            png_reissue(items[j]);
+            first->note(i);
+            continue;
+        }
+        int k = 0;
+        while (k < 5 && PNG_BPPS[k] != items[j].f.bpp) k++;
+        for (size_t u = 0; u + 1 < items[j].units.size(); u += 2)
+            units[k].push_back(PngBatchUnit{static_cast<uint32_t>(ok.size()), items[j].units[u], items[j].units[u + 1]});
+        if (items[j].f.color_type == 3) npal++;
+        ok.push_back(j);
+    }
+    if (ok.empty()) return FNX_OK;
+    void *ds = nullptr, *dr = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_PNG_DEC_STREAM, stage_bytes + 16, &ds));
+    FNX_TRY(scratch(ctx, SLOT_PNG_DEC_ROWS, rows_bytes + 16, &dr));
+    for (int j : ok)
+        FNX_HIP(hipMemcpyAsync(static_cast<uint8_t *>(ds) + chunk[j].stream_off, items[j].stream, items[j].want, hipMemcpyHostToDevice, ctx->stream));
+    FNX_HIP(hipEventRecord(ctx->png_stage_ev, ctx->stream));
+    ctx->png_stage_busy = true;
+
+    // the tables: the sorted units, the descriptors, a palette's 256 pixel values per paletted file.  The descriptors hold
+    // pointers into the table slot itself, so its address is asked for first (same size: the same buffer)
+    std::vector<PngBatchUnit> sorted;
+    int nunits[6];
+    for (int k = 0; k < 6; k++) {
+        nunits[k] = static_cast<int>(units[k].size());
+        sorted.insert(sorted.end(), units[k].begin(), units[k].end());
+    }
+    std::vector<uint32_t> pals(256 * (npal ? npal : 1), 0);
+    const size_t tsizes[3] = {sizeof(PngBatchUnit) * sorted.size(), sizeof(PngBatchFile) * ok.size(), sizeof(uint32_t) * pals.size()};
+    void *tab = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_PNG_DEC_TAB, align16(tsizes[0]) + align16(tsizes[1]) + align16(tsizes[2]), &tab));
+    const uint32_t *d_pals = reinterpret_cast<const uint32_t *>(static_cast<uint8_t *>(tab) + align16(tsizes[0]) + align16(tsizes[1]));
+    unsigned long long tiles = 0;
+    size_t pal = 0;
+    desc.reserve(ok.size());
+    for (int j : ok) {
+        const PngFile &f = items[j].f;
+        const int i = chunk[j].index;
+        PngBatchFile d;
+        std::memset(&d, 0, sizeof d);
+        d.stream = static_cast<const uint8_t *>(ds) + chunk[j].stream_off;
+        d.spitch = 1 + f.rowbytes;
+        d.rows = static_cast<uint8_t *>(dr) + chunk[j].rows_off;
+        d.ppitch = png_plane_pitch(f);
+        d.rowbytes = static_cast<int>(f.rowbytes);
+        d.npix = static_cast<int>(f.rowbytes / f.bpp);
+        d.e.w = f.w; d.e.h = f.h; d.e.color_type = f.color_type; d.e.depth = f.depth;
+        d.e.has_trns = f.has_trns ? 1 : 0;
+        for (int k = 0; k < 3; k++) d.e.key[k] = f.trns16[k];
+        d.table = d_pals;
+        if (f.color_type == 3) {
+            std::memcpy(pals.data() + 256 * pal, items[j].table, sizeof items[j].table);
+            d.table = d_pals + 256 * pal++;
+        }
+        d.dst = dsts[i];
+        d.dstride = dstrides[i];
+        d.tile0 = static_cast<uint32_t>(tiles);
+        tiles += static_cast<unsigned long long>((f.w + 255) / 256) * f.h;
+        desc.push_back(d);
+    }
+    if (tiles > 0x7fffffffull) {
+        set_error("internal: a chunk of %llu workgroups of png_expand_batch_kernel", tiles);
+        return FNX_ERR_INVALID;
+    }
+    const void *hosts[3] = {sorted.data(), desc.data(), pals.data()};
+    void *dp[3];
+    FNX_TRY(upload_tables(ctx, SLOT_PNG_DEC_TAB, hosts, tsizes, 3, dp));
+    if (dp[2] != static_cast<const void *>(d_pals)) {
+        set_error("internal: the table slot moved between two requests of one size");
+        return FNX_ERR_INVALID;
+    }
+    return launch_png_decode_chunk(ctx, static_cast<const PngBatchUnit *>(dp[0]), nunits, static_cast<const PngBatchFile *>(dp[1]),
+                                   static_cast<int>(ok.size()), static_cast<uint32_t>(tiles));
 }
 
 }  // namespace
@@ -245,6 +399,78 @@ int fnx_png_decode(fnx_ctx *ctx, const uint8_t *data, size_t n, int space, uint8
                                 static_cast<uint8_t *>(dr)));
     FNX_TRY(launch_png_expand(ctx, static_cast<const uint8_t *>(dr), f, static_cast<const uint32_t *>(dp[1]), d.p, d.stride));
     return finish(ctx, space, &d);
+}
+
+int fnx_png_decode_batch(fnx_ctx *ctx, int n, const uint8_t *const *files, const size_t *sizes, uint8_t *const *dsts, const int *dstrides,
+                         int workers, int *ws, int *hs, int *status)
+{
+    FNX_ENTER(ctx);
+    FNX_REQUIRE(n >= 1 && n <= FNX_BATCH_MAX, "decode batch: n must be 1..FNX_BATCH_MAX (65535)");
+    FNX_REQUIRE(files && sizes && dsts && dstrides && ws && hs && status, "decode batch: NULL array");
+    FNX_REQUIRE(workers >= 0 && workers <= 64, "decode batch: workers must be 0..64 (0: min(8, files in the chunk))");
+    FirstRefusal first;
+    std::vector<BatchEntry> chunk;
+    std::vector<PngFile> heads;
+    size_t stage_bytes = 0, rows_bytes = 0;
+    auto flush = [&]() -> int {
+        if (chunk.empty()) return FNX_OK;
+        const int rc = png_decode_chunk(ctx, chunk, heads, stage_bytes, rows_bytes, files, sizes, dsts, dstrides, workers, status, &first);
+        chunk.clear();
+        heads.clear();
+        stage_bytes = rows_bytes = 0;
+        return rc;
+    };
+    for (int i = 0; i < n; i++) {
+        ws[i] = hs[i] = 0;
+        status[i] = FNX_ERR_INVALID;
+        if (!files[i]) {
+            set_error("invalid argument: decode batch: files[%d] is NULL", i);
+            first.note(i);
+            continue;
+        }
+        // the signature and IHDR on this thread: the dimensions, what the device does not take, and the item's own arguments --
+        // the order of fnx_png_decode's refusals.  The rest of the file is the workers' business
+        PngFile head;
+        const int rc = png_probe(files[i], sizes[i], &head);
+        if (rc == FNX_OK || rc == FNX_ERR_UNSUPPORTED) { ws[i] = head.w; hs[i] = head.h; }
+        if (rc < 0) {
+            status[i] = rc;
+            first.note(i);
+            continue;
+        }
+        if (!dsts[i]) {
+            set_error("invalid argument: decode batch: dsts[%d] is NULL", i);
+            first.note(i);
+            continue;
+        }
+        if (check_img(dsts[i], dstrides[i], head.w, head.h, "dst") < 0) {
+            first.note(i);
+            continue;
+        }
+        if (reinterpret_cast<uintptr_t>(dsts[i]) & 3u) {
+            set_error("invalid argument: a device image is 4-byte aligned");
+            first.note(i);
+            continue;
+        }
+        const size_t want = static_cast<size_t>(head.h) * (1 + head.rowbytes);
+        const bool room = want / 1032 <= sizes[i];       // else the file cannot hold its rows: refused before its inflate, no room needed
+        const size_t sbytes = room ? align16(want + 64) : 0, rbytes = room ? align16(png_plane_pitch(head) * head.h + 16) : 0;
+        if (!chunk.empty() && (static_cast<int>(chunk.size()) >= FNX_PNG_DECODE_CHUNK || stage_bytes + rows_bytes + sbytes + rbytes > PNG_BATCH_SCRATCH)) {
+            const int frc = flush();
+            if (frc < 0) return frc;
+        }
+        BatchEntry e;
+        e.index = i;
+        e.stream_off = stage_bytes;
+        e.rows_off = rows_bytes;
+        stage_bytes += sbytes;
+        rows_bytes += rbytes;
+        chunk.push_back(e);
+        heads.push_back(head);
+    }
+    FNX_TRY(flush());
+    if (first.index >= 0) set_error("%s", first.text);
+    return FNX_OK;
 }
 
 }  // extern "C"

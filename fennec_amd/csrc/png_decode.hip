@@ -1,6 +1,8 @@
 // fnx_png_decode's device side: the inflated stream of a PNG file (h rows of 1 + rowbytes bytes: the filter type, the
 // filtered row) -> the reconstructed rows (png_unfilter_kernel) -> image.Decode's pixels through toNRGBA (png_expand_kernel).
-// The rule both kernels follow is restated above fnx_png_decode in include/fennec_hip.h.
+// The rule both kernels follow is restated above fnx_png_decode in include/fennec_hip.h.  fnx_png_decode_batch runs the same
+// two bodies over a chunk of files at once: png_unfilter_batch_kernel, png_expand_batch_kernel (per-file descriptors in device
+// memory instead of kernel arguments; one workgroup per unit of any file, 256 pixels of a row of any file).
 //
 // png_unfilter_kernel.  Average and Paeth need the pixel to the left and the row above, so a chain of dependent rows is
 // walked as a skewed wavefront: a lane owns a row and trails the lane that owns the row above by one pixel (one step), so at
@@ -162,12 +164,11 @@ struct UnfilterArgs {
     size_t ppitch;
 };
 
+// the rows [r0, r1) of one unit, band by band: the body of both unfilter kernels.  A, r0 and r1 are the same in every lane
 template <int BPP>
-__global__ __launch_bounds__(UF_T) void png_unfilter_kernel(UnfilterArgs A)
+__device__ __forceinline__ void unfilter_unit(const UnfilterArgs &A, const uint32_t r0, const uint32_t r1, u64 (*ring)[UF_RING])
 {
-    __shared__ u64 ring[UF_WAVES - 1][UF_RING];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const uint32_t r0 = A.units[2 * blockIdx.x], r1 = A.units[2 * blockIdx.x + 1];
     const int lag = t + wv * UF_C;
     for (uint32_t band = r0; band < r1; band += UF_T) {
         // the band's last row finishes its last pixel at step npix - 1 + its lane's lag: a short unit does not pay for idle lanes
@@ -216,6 +217,33 @@ __global__ __launch_bounds__(UF_T) void png_unfilter_kernel(UnfilterArgs A)
     }
 }
 
+template <int BPP>
+__global__ __launch_bounds__(UF_T) void png_unfilter_kernel(UnfilterArgs A)
+{
+    __shared__ u64 ring[UF_WAVES - 1][UF_RING];
+    unfilter_unit<BPP>(A, A.units[2 * blockIdx.x], A.units[2 * blockIdx.x + 1], ring);
+}
+
+// fnx_png_decode_batch: the units of all files of a chunk whose pixels are BPP bytes, one workgroup each.  The unit and its
+// file's descriptor are indexed by blockIdx.x alone -- uniform, so they are read once through the scalar cache and stay in
+// scalar registers --, and from there the workgroup is png_unfilter_kernel's
+template <int BPP>
+__global__ __launch_bounds__(UF_T) void png_unfilter_batch_kernel(const PngBatchUnit *__restrict__ units, const PngBatchFile *__restrict__ files)
+{
+    __shared__ u64 ring[UF_WAVES - 1][UF_RING];
+    const PngBatchUnit u = units[blockIdx.x];
+    const PngBatchFile &f = files[u.file];
+    UnfilterArgs A;
+    A.stream = f.stream;
+    A.spitch = f.spitch;
+    A.rowbytes = f.rowbytes;
+    A.npix = f.npix;
+    A.units = nullptr;
+    A.rows = f.rows;
+    A.ppitch = f.ppitch;
+    unfilter_unit<BPP>(A, u.r0, u.r1, ring);
+}
+
 // ---- png_expand_kernel: one thread per pixel ------------------------------------------------------------------------------
 struct ExpandArgs {
     const uint8_t *rows;
@@ -237,18 +265,15 @@ __device__ inline uint32_t nrgba64_pixel(uint32_t R, uint32_t G, uint32_t B, uin
     return pack(r >> 8, g >> 8, b >> 8, A >> 8);
 }
 
-__global__ __launch_bounds__(256) void png_expand_kernel(ExpandArgs A)
+// pixel x of the reconstructed row r
+__device__ __forceinline__ uint32_t expand_pixel(const PngExpand &e, const uint32_t *table, const uint8_t *r, const int x)
 {
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-    const PngExpand &e = A.e;
-    if (x >= e.w) return;
-    const uint8_t *r = A.rows + static_cast<size_t>(y) * A.ppitch;
     uint32_t out = 0;
     if (e.depth < 8) {                                   // colour types 0 and 3: samples packed MSB first
         const int bit = x * e.depth;
         const uint32_t v = (static_cast<uint32_t>(r[bit >> 3]) >> (8 - e.depth - (bit & 7))) & ((1u << e.depth) - 1u);
         if (e.color_type == 3) {
-            out = A.table[v];
+            out = table[v];
         } else {
             const uint32_t g = v * (e.depth == 1 ? 0xffu : e.depth == 2 ? 0x55u : 0x11u);
             out = pack(g, g, g, (e.has_trns && v == (e.key[0] & 0xffu)) ? 0 : 255);
@@ -266,7 +291,7 @@ __global__ __launch_bounds__(256) void png_expand_kernel(ExpandArgs A)
             out = pack(cr, cg, cb, hit ? 0 : 255);
             break;
         }
-        case 3: out = A.table[r[x]]; break;
+        case 3: out = table[r[x]]; break;
         case 4: out = pack(r[2 * x], r[2 * x], r[2 * x], r[2 * x + 1]); break;
         default: out = pack(r[4 * x], r[4 * x + 1], r[4 * x + 2], r[4 * x + 3]); break;
         }
@@ -294,7 +319,36 @@ __global__ __launch_bounds__(256) void png_expand_kernel(ExpandArgs A)
         }
         out = alpha ? nrgba64_pixel(R, G, B, Al) : pack(R >> 8, G >> 8, B >> 8, 255);     // Gray16 / RGBA64: the high bytes
     }
+    return out;
+}
+
+__global__ __launch_bounds__(256) void png_expand_kernel(ExpandArgs A)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= A.e.w) return;
+    const uint32_t out = expand_pixel(A.e, A.table, A.rows + static_cast<size_t>(y) * A.ppitch, x);
     *reinterpret_cast<uint32_t *>(A.dst + static_cast<size_t>(y) * A.dstride + 4 * static_cast<size_t>(x)) = out;
+}
+
+// fnx_png_decode_batch: the pixels of all files of a chunk in one launch.  A workgroup is 256 pixels of one row of one file;
+// the files' workgroups lie back to back (tile0: a file's first one, files[m].tile0 would be the grid), so the file is found
+// by a search over at most FNX_PNG_DECODE_CHUNK descriptors that is the same in every lane.  A chunk's rows do not fit a grid
+// dimension the way one file's h <= 65535 does.
+__global__ __launch_bounds__(256) void png_expand_batch_kernel(const PngBatchFile *__restrict__ files, const int m)
+{
+    int lo = 0, hi = m - 1;                              // the last file whose tile0 <= blockIdx.x
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (files[mid].tile0 <= blockIdx.x) lo = mid;
+        else hi = mid - 1;
+    }
+    const PngBatchFile &f = files[lo];
+    const uint32_t tile = blockIdx.x - f.tile0, tiles_x = (static_cast<uint32_t>(f.e.w) + 255u) / 256u;
+    const uint32_t y = tile / tiles_x;
+    const int x = static_cast<int>((tile - y * tiles_x) * 256u + threadIdx.x);
+    if (x >= f.e.w || y >= static_cast<uint32_t>(f.e.h)) return;
+    const uint32_t out = expand_pixel(f.e, f.table, f.rows + static_cast<size_t>(y) * f.ppitch, x);
+    *reinterpret_cast<uint32_t *>(f.dst + static_cast<size_t>(y) * f.dstride + 4 * static_cast<size_t>(x)) = out;
 }
 
 }  // namespace
@@ -340,6 +394,33 @@ int launch_png_expand(fnx_ctx *ctx, const uint8_t *d_rows, const PngFile &f, con
     note_route(ctx, FNX_PROF_MAIN, "png_unfilter_kernel, png_expand_kernel");
     FNX_TRY(prof_begin(ctx));
     hipLaunchKernelGGL(png_expand_kernel, dim3((f.w + 255) / 256, f.h), dim3(256), 0, ctx->stream, a);
+    FNX_HIP(hipGetLastError());
+    return prof_end(ctx);
+}
+
+int launch_png_decode_chunk(fnx_ctx *ctx, const PngBatchUnit *d_units, const int nunits[6], const PngBatchFile *d_files, int m, uint32_t tiles)
+{
+    note_route(ctx, FNX_PROF_MAIN, "png_unfilter_batch_kernel, png_expand_batch_kernel");
+    const dim3 block(UF_T);
+    const PngBatchUnit *u = d_units;
+    for (int k = 0; k < 6; k++) {
+        if (nunits[k] == 0) continue;
+        const dim3 grid(nunits[k]);
+        FNX_TRY(prof_begin(ctx));
+        switch (PNG_BPPS[k]) {
+        case 1: hipLaunchKernelGGL(png_unfilter_batch_kernel<1>, grid, block, 0, ctx->stream, u, d_files); break;
+        case 2: hipLaunchKernelGGL(png_unfilter_batch_kernel<2>, grid, block, 0, ctx->stream, u, d_files); break;
+        case 3: hipLaunchKernelGGL(png_unfilter_batch_kernel<3>, grid, block, 0, ctx->stream, u, d_files); break;
+        case 4: hipLaunchKernelGGL(png_unfilter_batch_kernel<4>, grid, block, 0, ctx->stream, u, d_files); break;
+        case 6: hipLaunchKernelGGL(png_unfilter_batch_kernel<6>, grid, block, 0, ctx->stream, u, d_files); break;
+        default: hipLaunchKernelGGL(png_unfilter_batch_kernel<8>, grid, block, 0, ctx->stream, u, d_files); break;
+        }
+        FNX_HIP(hipGetLastError());
+        FNX_TRY(prof_end(ctx));
+        u += nunits[k];
+    }
+    FNX_TRY(prof_begin(ctx));
+    hipLaunchKernelGGL(png_expand_batch_kernel, dim3(tiles), dim3(256), 0, ctx->stream, d_files, m);
     FNX_HIP(hipGetLastError());
     return prof_end(ctx);
 }

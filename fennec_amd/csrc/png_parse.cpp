@@ -4,18 +4,30 @@
 //   png_inflate      RFC 1950 / 1951 inflate (the library links no zlib)
 //   png_row_plan     the h filter-type bytes of the inflated stream -> the work units of png_unfilter_kernel
 //   png_palette_table  a colour-type-3 file's 256 pixel values, toNRGBA already applied
+//   png_prepare_many those four for a list of files on several threads (fnx_png_decode_batch; tools/png_batch_host.cpp runs it
+//                    under the address and the thread sanitizer)
 #include "common.hpp"
+
+#include <atomic>
+#include <system_error>
+#include <thread>
 
 namespace fnx {
 
+namespace {
+thread_local const char *t_what = nullptr;   // the text of this thread's last refusal: png_prepare_many carries it in the item
+}
+
 int png_corrupt(const char *what)
 {
+    t_what = what;
     set_error("invalid PNG: %s", what);
     return FNX_ERR_INVALID;
 }
 
 int png_unsupported(const char *what)
 {
+    t_what = what;
     set_error("unsupported PNG (decode it on the host): %s", what);
     return FNX_ERR_UNSUPPORTED;
 }
@@ -497,6 +509,60 @@ void png_palette_table(const PngFile &f, uint32_t table[256])
         }
         table[i] = o[0] | (o[1] << 8) | (o[2] << 16) | (t << 24);
     }
+}
+
+// ---- a list of files on several threads (fnx_png_decode_batch) ------------------------------------------------------------
+namespace {
+
+int prepare_one(const uint8_t *data, size_t n, PngPrepared *it)
+{
+    FNX_TRY(png_parse(data, n, &it->f));
+    FNX_TRY(png_stream_size(it->f, &it->want));
+    if (it->stream == nullptr || it->want > it->cap) return png_corrupt("internal: no staging for a file's stream");
+    size_t got = 0;
+    FNX_TRY(png_inflate(it->f.idat.data(), it->f.idat.size(), it->stream, it->want, &got));
+    if (got != it->want) return png_corrupt("not enough pixel data");
+    FNX_TRY(png_row_plan(it->stream, it->f, &it->units));
+    if (it->f.color_type == 3) png_palette_table(it->f, it->table);
+    return FNX_OK;
+}
+
+}  // namespace
+
+int png_workers(int workers, int m)
+{
+    if (workers == 0) workers = 8;
+    return workers < m ? workers : m;
+}
+
+void png_prepare_many(const uint8_t *const *files, const size_t *sizes, int m, int workers, PngPrepared *items)
+{
+    std::atomic<int> next(0);
+    auto run = [&]() {
+        for (int i = next.fetch_add(1); i < m; i = next.fetch_add(1)) {
+            PngPrepared &it = items[i];
+            std::memset(it.table, 0, sizeof it.table);
+            it.what = nullptr;
+            it.status = prepare_one(files[i], sizes[i], &it);
+            if (it.status != FNX_OK) it.what = t_what;
+            it.f.idat = std::vector<uint8_t>();          // the compressed bytes are not needed again
+        }
+    };
+    const int nthreads = png_workers(workers, m);
+    std::vector<std::thread> pool;
+    try {
+        for (int t = 1; t < nthreads; t++) pool.emplace_back(run);
+    } catch (const std::system_error &) {
+        // no (further) thread to be had: the ones that started and this one share the files
+    }
+    run();
+    for (std::thread &t : pool) t.join();
+}
+
+int png_reissue(const PngPrepared &it)
+{
+    if (it.status == FNX_OK) return FNX_OK;
+    return it.status == FNX_ERR_UNSUPPORTED ? png_unsupported(it.what ? it.what : "") : png_corrupt(it.what ? it.what : "");
 }
 
 }  // namespace fnx

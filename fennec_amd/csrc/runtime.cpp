@@ -499,6 +499,8 @@ void fnx_ctx_destroy(fnx_ctx *ctx)
         for (auto &s : ctx->slot)
             if (s.p) (void)hipFree(s.p);
         if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+        if (ctx->png_stage) (void)hipHostFree(ctx->png_stage);
+        if (ctx->png_stage_ev) (void)hipEventDestroy(ctx->png_stage_ev);
         for (auto &q : ctx->res_q)
             if (q.ev) (void)hipEventDestroy(q.ev);
         for (auto &rb : ctx->res_buf)

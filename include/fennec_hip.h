@@ -762,6 +762,32 @@ int fnx_png_info(const uint8_t *data, size_t n, int *w, int *h, int *color_type,
  * Kernels: csrc/png_decode.hip; fnx_ctx_last_kernel(ctx, FNX_PROF_MAIN) answers "png_unfilter_kernel, png_expand_kernel". */
 #define FNX_PNG_DECODE_ROWS 1024   /* rows a workgroup of png_unfilter_kernel keeps in flight */
 int fnx_png_decode(fnx_ctx *ctx, const uint8_t *data, size_t n, int space, uint8_t *dst, int dstride, int *w, int *h);
+/* image.Decode + toNRGBA of n PNG files in host memory (the loadImage of CompressBatch's items, batch.go:88-122 ->
+ * io.go:65-88 -> convert.go:12-64) in one call.  The contract is fnx_jpeg_decode_batch's: files[i] is HOST memory, dsts[i]
+ * DEVICE memory (4-byte aligned, stride dstrides[i]); dsts[i] and status[i] are what fnx_png_decode(ctx, files[i], sizes[i],
+ * FNX_DEVICE, dsts[i], dstrides[i], ..) gives, byte for byte, FNX_ERR_INVALID (a damaged file) and FNX_ERR_UNSUPPORTED (Adam7,
+ * a dimension above 65535) included; a refused item leaves its destination untouched.  ws[i] / hs[i] are set whenever the
+ * IHDR parses -- also for the unsupported files, as fnx_png_info would -- else 0.  files[i] == NULL, dsts[i] == NULL, or a
+ * stride or alignment fnx_png_decode refuses: FNX_ERR_INVALID for that item only.  The files may differ in every respect
+ * (size, colour type, depth, number of chains).
+ * A chunk is at most FNX_PNG_DECODE_CHUNK files, fewer where their inflated streams and reconstructed planes would pass
+ * FNX_PNG_DECODE_CHUNK_BYTES of device scratch (a file that alone needs more is a chunk of its own).  Per chunk, the host
+ * side of fnx_png_decode -- chunk walk, inflate, row plan, palette table -- runs on `workers` host threads, handed out file
+ * by file; the threads make no HIP call.  workers == 1: the calling thread alone, no thread is started; more: the calling
+ * thread is one of them; 0: min(8, files in the chunk).  Then the chunk's streams go up from a pinned staging area and ALL
+ * its chains go through one set of launches: png_unfilter_batch_kernel once per pixel size (bpp) present, one workgroup per
+ * unit of any file, and png_expand_batch_kernel once -- where a loop of fnx_png_decode runs a single-chain file on one compute
+ * unit, n times in a row.  The staging area is written again only after an event behind the chunk's uploads; the device is
+ * never synchronised as a whole.
+ * Neither the bytes, nor the statuses, nor fnx_last_error's text -- the message of the LOWEST-indexed refused item -- depend
+ * on `workers` or on which thread finished first.  Returns FNX_OK when the batch ran; an error for bad arguments (n outside
+ * 1..FNX_BATCH_MAX, a NULL array, workers outside 0..64) before anything is launched or any thread is started.  When it
+ * returns, the images are enqueued on the ctx's stream (as fnx_png_decode with FNX_DEVICE).
+ * fnx_ctx_last_kernel(ctx, FNX_PROF_MAIN) answers "png_unfilter_batch_kernel, png_expand_batch_kernel". */
+#define FNX_PNG_DECODE_CHUNK 32   /* files per set of launches, at most */
+#define FNX_PNG_DECODE_CHUNK_BYTES ((size_t)1 << 30)   /* device scratch of a chunk's streams + planes, at most (as the JPEG batch's) */
+int fnx_png_decode_batch(fnx_ctx *ctx, int n, const uint8_t *const *files, const size_t *sizes, uint8_t *const *dsts,
+                         const int *dstrides, int workers, int *ws /* n */, int *hs /* n */, int *status /* n */);
 
 /* ======================================================================= */
 /* fennec_* : the reference's function set (names and argument meaning as in
