@@ -43,6 +43,7 @@ FNX_BLUR_FAST, FNX_BLUR_EXACT, FNX_BLUR_KEEP_BOX_SUMS = 0, 1, 2
 FNX_PNG_PALETTED, FNX_PNG_GRAY, FNX_PNG_NRGBA = 1, 2, 3      # fnx_png_reduce's kinds (compress.go:90-108)
 FNX_PNG_DECODE_ROWS = 1024                                    # png_decode.hip: rows a workgroup of png_unfilter_kernel keeps in flight
 FNX_PNG_DECODE_CHUNK = 32                                     # fnx_png_decode_batch: files per set of launches, at most
+FNX_PNG_COMPRESS_CHUNK = 32                                   # fnx_png_compress_batch: images per set of launches, at most
 FNX_DEFLATE_CHUNK, FNX_DEFLATE_SUB = 32768, 128               # deflate.hip: bytes per chunk (= per workgroup, per block) and per lane
 PROF_MAIN, PROF_SSIM, PROF_RESIZE, PROF_FX, PROF_JPEG = 1, 2, 4, 8, 16
 
@@ -269,6 +270,12 @@ def load_library() -> C.CDLL:
                                             C.POINTER(i), C.POINTER(i), C.POINTER(i)])
         _sig(L, "fennec_CompressFilePNG", i, [ctx, _u8p, C.c_size_t, C.POINTER(FileOptions), _u8p, C.c_size_t, C.POINTER(C.c_size_t),
                                                C.POINTER(i), C.POINTER(i)])
+        _sig(L, "fnx_png_file_bound", C.c_size_t, [i, i])
+        _sig(L, "fnx_png_compress_batch", i, [ctx, i, C.POINTER(C.c_void_p), C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(C.c_void_p),
+                                              C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(i), C.POINTER(i)])
+        _sig(L, "fnx_png_recompress_batch", i, [ctx, i, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), i, C.POINTER(C.c_void_p),
+                                                C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(i), C.POINTER(i), C.POINTER(i),
+                                                C.POINTER(i)])
         _sig(L, "fennec_gaussianKernel", None, [i, d, _f64p])
         _sig(L, "fennec_blurKernel", i, [d, _f64p])
         _sig(L, "fennec_lanczosKernel", d, [d])
@@ -1683,6 +1690,65 @@ class Context:
                 images = [None if t is None else t.cpu().numpy() for t in images]
         return images, list(status)
 
+    def png_compress_batch(self, imgs):
+        """compressPNG of a list of device images in one call (fnx_png_compress_batch: one set of launches and three host waits
+        per chunk of up to FNX_PNG_COMPRESS_CHUNK images) -> (files, kinds).  files[i] is, byte for byte, what
+        compress_png(imgs[i], device_deflate=True) returns; kinds[i] its FNX_PNG_* kind.  The images are (h, w, 4) uint8 device
+        tensors and may differ in size, stride and content."""
+        imgs = list(imgs)
+        n = len(imgs)
+        if n == 0:
+            raise FennecError("png_compress_batch takes a non-empty list of images")
+        views = [_Img(t) for t in imgs]
+        if any(v.space != FNX_DEVICE for v in views):
+            raise FennecError("png_compress_batch takes device images")
+        bufs = [np.empty(int(self._lib.fnx_png_file_bound(v.w, v.h)), dtype=np.uint8) for v in views]
+        ps = (C.c_void_p * n)(*[v.ptr for v in views])
+        pst = (C.c_int * n)(*[v.stride for v in views])
+        pw = (C.c_int * n)(*[v.w for v in views])
+        ph = (C.c_int * n)(*[v.h for v in views])
+        po = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+        pc = (C.c_size_t * n)(*[len(b) for b in bufs])
+        nb, kinds, status = (C.c_size_t * n)(), (C.c_int * n)(), (C.c_int * n)()
+        with self._ordered(*imgs):
+            self._chk(self._lib.fnx_png_compress_batch(self._h, n, ps, pst, pw, ph, po, pc, nb, kinds, status), "fnx_png_compress_batch")
+        for i in range(n):
+            if status[i] != FNX_OK:
+                self._chk(status[i], f"fnx_png_compress_batch: image {i}")
+        return [bufs[i][:nb[i]].tobytes() for i in range(n)], list(kinds)
+
+    def png_recompress_batch(self, files, workers: int = 0):
+        """CompressBatch's item body for files that end as PNG (fnx_png_recompress_batch): PNG and JPEG files decoded by the
+        batched decoders into device images, then png_compress_batch's launches -> (files, kinds, statuses).  files[i] is what
+        compress_png(png_decode(f) or jpeg_decode(f), device_deflate=True) returns, or None where statuses[i] != FNX_OK (the
+        decoder's answer for a file it refused)."""
+        files = [bytes(f) for f in files]
+        n = len(files)
+        if n == 0:
+            raise FennecError("png_recompress_batch takes a non-empty list of files")
+        srcs = [np.frombuffer(f, dtype=np.uint8) if len(f) else np.zeros(1, dtype=np.uint8) for f in files]
+        caps = []
+        for f in files:                                   # a file whose header does not parse is refused by the call: no room
+            w = h = 0
+            try:
+                if f[:8] == b"\x89PNG\r\n\x1a\n":
+                    w, h = png_info(f)[:2]
+                else:
+                    w, h = self.jpeg_decode_config(f)
+            except FennecError:
+                pass
+            caps.append(int(self._lib.fnx_png_file_bound(w, h)) if 1 <= w <= 65535 and 1 <= h <= 65535 else 0)
+        bufs = [np.empty(max(c, 1), dtype=np.uint8) for c in caps]
+        pf = (C.c_void_p * n)(*[b.ctypes.data for b in srcs])
+        ps = (C.c_size_t * n)(*[len(f) for f in files])
+        po = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+        pc = (C.c_size_t * n)(*caps)
+        nb, kinds, ws, hs, status = (C.c_size_t * n)(), (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        self._chk(self._lib.fnx_png_recompress_batch(self._h, n, pf, ps, int(workers), po, pc, nb, kinds, ws, hs, status),
+                  "fnx_png_recompress_batch")
+        out = [bufs[i][:nb[i]].tobytes() if status[i] == FNX_OK else None for i in range(n)]
+        return out, list(kinds), list(status)
+
     def compress_file_png(self, data: bytes, orient: int = 1, max_w: int = 0, max_h: int = 0, cap: int | None = None):
         """CompressFile's PNG branch for a JPEG source in one call (fennec_CompressFilePNG): decode, ApplyOrientation(orient),
         smartResize(max_w, max_h), compressPNG's reduction, the encoder's row stage and the deflate on the device ->
@@ -1970,6 +2036,7 @@ def compress_png(img, level=9, device_deflate=False): return default_context(_de
 def deflate(buf, row=0): return default_context(_dev_of(buf)).deflate(buf, row)
 def png_encode(src, kind=None, ncolors=0, opaque=-1, palette=None): return default_context(_dev_of(src)).png_encode(src, kind, ncolors, opaque, palette)
 def deflate_bound(n): return int(load_library().fnx_deflate_bound(int(n)))
+def png_file_bound(w, h): return int(load_library().fnx_png_file_bound(int(w), int(h)))
 
 
 def inflate(data: bytes, cap: int | None = None) -> bytes:

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/fennec_hip.h"
+#include "png_compress_plan.hpp"
 
 namespace fnx {
 
@@ -110,6 +111,9 @@ enum Slot {
     SLOT_PNG_STREAM, // png_filter.hip: the filtered scanlines on their way to a host buffer
     SLOT_DEFLATE_TOK, SLOT_DEFLATE_SLOTS, SLOT_DEFLATE_OUT,   // deflate.hip: the chunks' tokens; the result word, the chunks' sizes and output slots; the stream on its way to a host buffer
     SLOT_PNG_DEC_STREAM, SLOT_PNG_DEC_ROWS, SLOT_PNG_DEC_TAB,   // png_decode.hip: the inflated stream, the reconstructed rows, the unit table + the palette's pixel values
+    // fnx_png_compress_batch: the colours pass's work area (results, tables, lists), the chunk's planes, its filtered streams, the
+    // unit and image tables of its four stages; fnx_png_recompress_batch: the decoded images of a span
+    SLOT_PNG_CB_WORK, SLOT_PNG_CB_PLANES, SLOT_PNG_CB_STREAMS, SLOT_PNG_CB_TAB0, SLOT_PNG_CB_TAB1, SLOT_PNG_CB_TAB2, SLOT_PNG_CB_TAB3, SLOT_PNG_CB_IMG,
     SLOT_DONE,       // workgroup counters of the kernels that finish their own reduction (ssim.hip), zero between launches
     SLOT_COUNT
 };
@@ -560,14 +564,42 @@ int png_filter_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, i
                       uint8_t *out, size_t cap, size_t *nbytes, int *color_type, int *bit_depth);
 // deflate.hip: the zlib stream of n >= 1 device bytes into d_out (device, cap bytes; a larger stream writes nothing);
 // *d_size: the device word that holds the stream's size once both kernels have run.  row: a match-distance hint, 0 for none.
-size_t deflate_chunks(size_t n);
-size_t deflate_bound(size_t n);
+// (deflate_chunks, deflate_bound: deflate_batch.hpp)
 int launch_deflate(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, uint8_t *d_out, size_t cap, const unsigned long long **d_size);
 // png_api.cpp: the body of fnx_deflate for device bytes (out: device or host memory), and of fnx_png_encode for a DEVICE image or
 // plane (out: host memory; palette: host)
 int deflate_device(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, bool out_on_device, uint8_t *out, size_t cap, size_t *nbytes);
 int png_encode_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors, int opaque, const uint8_t *palette,
                       uint8_t *out, size_t cap, size_t *nbytes);
+// ---- fnx_png_compress_batch: a chunk of images through one set of launches (png_compress_plan.hpp has the host plan) ----
+struct PngCbSrc {                        // an image of the chunk: DEVICE, NRGBA, 4-byte aligned, the flat Pix readable
+    const uint8_t *src;
+    int sstride, w, h;
+};
+// png_reduce.hip: png_colors_batch_kernel, png_finish_batch_kernel, png_flags_batch_kernel -> *d_results, m records of
+// png_result_bytes(): words 0 over, 2 ncolors, 3 flags (bit 0: a visible pixel is translucent, bit 1: the flat walk met a
+// non-grey pixel), then the palette.  Nothing is waited for.  launch_png_planes_batch: png_plane_batch_kernel over the images
+// with which[i] != 0 (1: the index plane from those results, 2: toGray's plane).
+int launch_png_classify_batch(fnx_ctx *ctx, int m, const PngCbSrc *imgs, const void **d_results);
+int launch_png_planes_batch(fnx_ctx *ctx, int m, const PngCbSrc *imgs, const int *which, uint8_t *const *planes, const int *pstrides);
+// png_filter.hip: the row stage.  A record is what both single kernels take as their argument; d_units: the units of forms 0, 1,
+// ... back to back, nunits[k] of form k
+struct PngCbRows {
+    const uint8_t *src;                  // the image, or its plane
+    int sstride, w, h;
+    int n;                               // raw bytes per row
+    int al4;                             // png_cb_al4(src, sstride)
+    uint8_t *out;                        // h rows of 1 + n bytes
+};
+int png_cb_al4(const uint8_t *src, int sstride);
+int launch_png_rows_batch(fnx_ctx *ctx, const PngCbUnit *d_units, const int nunits[PNG_CB_FORMS], const PngCbRows *d_rows);
+// deflate.hip: deflate_chunk_batch_kernel, deflate_gather_batch_kernel over DEVICE tables of nunits units and m streams;
+// out_bytes: the sum of the streams' bounds.  *d_out: the zlib streams back to back at their true sizes, *d_sizes: the m sizes
+int launch_deflate_batch(fnx_ctx *ctx, const DeflateBatchUnit *d_units, const DeflateBatchImage *d_images, uint32_t nunits, uint32_t m,
+                         size_t out_bytes, const uint8_t **d_out, const unsigned long long **d_sizes);
+// jpeg_api.cpp: fnx_jpeg_decode_batch's body (the files' images into DEVICE dsts; per item fnx_jpeg_decode's answer)
+int jpeg_decode_batch_device(fnx_ctx *ctx, int n, const uint8_t *const *files, const size_t *sizes, uint8_t *const *dsts, const int *dstrides,
+                             int *ws, int *hs, int *status);
 // applyPalette (+ palettedToNRGBA): palette = n x 4 host bytes (opaque); idx and/or quant may be null
 int launch_apply_palette(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, const uint8_t *palette, int n,
                          uint8_t *idx, int istride, uint8_t *quant, int qstride);

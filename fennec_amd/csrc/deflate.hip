@@ -44,10 +44,17 @@
 // workgroup for itself), the two header bytes, the byte copy into the caller's buffer (aligned dwords by v_alignbyte), the
 // combined Adler-32 behind the last chunk, the total size in a result word.  A total above `cap` writes nothing.
 //
-// Resources (hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage): no scratch in either kernel;
-// VGPRs: see DESIGN.md section 5.7 (the figures are the compiler's and are restated there with the LDS sizes).
+// deflate_chunk_batch_kernel, deflate_gather_batch_kernel (fnx_png_compress_batch): the same two bodies over the streams of a
+// batch -- a workgroup per 32 KiB of ANY stream, the unit {source, length, row, last-of-stream, stream} read through the scalar
+// cache; the gather places a chunk by the prefix over its own stream's units and the stream by the sum over the units in front,
+// so the streams lie back to back at their true sizes.  The chunk body is deflate_chunk.inc, included into both chunk kernels.
+//
+// Resources (hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage): no scratch in any kernel;
+// VGPRs: see DESIGN.md section 5.7 (the figures are the compiler's and are restated there with the LDS sizes); the batched
+// kernels have their twins' figures: 60 VGPRs / 53296 bytes of LDS (chunk), 34 / 32 (gather) -- DESIGN.md section 5.10.
 #include "common.hpp"
 #include "devutil.hpp"
+#include "deflate_batch.hpp"
 
 #include <algorithm>
 
@@ -57,7 +64,7 @@ constexpr int DF_T = 256;                          // lanes per workgroup
 constexpr int DF_C = FNX_DEFLATE_CHUNK;
 constexpr int DF_S = FNX_DEFLATE_SUB;              // a lane's sub-chunk
 constexpr int DF_HBITS = 12;
-constexpr int DF_SLOT = DF_C + 32;                 // a chunk's output slot: stored bound C + 10, dword reads one past the end
+constexpr int DF_SLOT = DEFLATE_SLOT_BYTES;        // a chunk's output slot: stored bound C + 10, dword reads one past the end
 constexpr uint32_t DF_ADLER = 65521u;
 constexpr int DF_STORED = 0, DF_FIXED = 1, DF_DYNAMIC = 2;   // BTYPE
 static_assert(DF_S * DF_T == DF_C && DF_S >= 64, "equal sub-chunks of at least 64 bytes");
@@ -211,296 +218,35 @@ struct DfBits {
 
 __global__ __launch_bounds__(DF_T) void deflate_chunk_kernel(DeflateArgs a)
 {
-    __shared__ uint32_t s_w[(DF_C + 64) / 4];                        // the chunk's bytes, later its output bits
-    __shared__ uint32_t s_hash[1 << DF_HBITS];                       // position + 1; later three HuffWork
-    __shared__ uint32_t s_llf[288], s_df[32], s_clf[20];
-    __shared__ uint8_t s_lll[288], s_dl[32], s_cll[20];
-    __shared__ uint16_t s_llc[288], s_dc[32], s_clc[20];
-    __shared__ uint16_t s_cltok[320];                                // symbol | extra value << 8
-    __shared__ uint32_t s_scan[DF_T];
-    __shared__ uint32_t s_adler[2];
-    __shared__ uint32_t s_form, s_hlit, s_hdist, s_hclen, s_ncl, s_hdr_bits, s_nbytes;
-    static_assert(3 * sizeof(HuffWork) <= sizeof(uint32_t) << DF_HBITS, "the Huffman work arrays take the hash table's words");
+#define DF_CHUNK_INDEX blockIdx.x
+#include "deflate_chunk.inc"
+#undef DF_CHUNK_INDEX
+}
 
-    const int tid = threadIdx.x;
-    const uint32_t c = blockIdx.x;
-    const size_t base = static_cast<size_t>(c) * DF_C;
-    const int len = static_cast<int>(std::min<size_t>(DF_C, a.n - base));
-    const bool last = c + 1 == a.nchunks;
-    const uint8_t *src = a.src + base;
-    uint8_t *s_b = reinterpret_cast<uint8_t *>(s_w);
-    uint32_t *tok = a.tok + static_cast<size_t>(c) * DF_C;
-    HuffWork *hw = reinterpret_cast<HuffWork *>(s_hash);
+// The streams of a batch in one launch each (the PNG compress batch): unit c -- a chunk of any stream -- has token words, slot
+// and meta words c; the unit and, in the gather, its stream's record come through the scalar cache.
+struct DeflateBatchArgs {
+    const DeflateBatchUnit *units;
+    const DeflateBatchImage *images;
+    uint32_t *tok;                       // DF_C words per unit
+    uint8_t *slots;                      // DF_SLOT bytes per unit, 16-byte aligned
+    uint32_t *meta;                      // per unit: bytes, adler a, adler b, len
+    uint8_t *out;                        // the zlib streams one behind another, stream i at 6 i + the block bytes of the units in front of its first
+    unsigned long long *sizes;           // per stream
+};
 
-    // ---- the chunk into LDS
-    if ((reinterpret_cast<uintptr_t>(src) & 3u) == 0) {
-        const int nd = len >> 2;
-        for (int i = tid; i < nd; i += DF_T) s_w[i] = *(g_u32 *)(src + 4 * i);
-        for (int i = 4 * nd + tid; i < len; i += DF_T) s_b[i] = src[i];
-    } else {
-        for (int i = tid; i < len; i += DF_T) s_b[i] = src[i];
-    }
-    for (int i = tid; i < (1 << DF_HBITS); i += DF_T) s_hash[i] = 0;
-    for (int i = tid; i < 288; i += DF_T) s_llf[i] = i == 256 ? 1u : 0u;   // one end-of-block
-    if (tid < 32) s_df[tid] = 0;
-    if (tid < 20) s_clf[tid] = 0;
-    if (tid < 2) s_adler[tid] = 0;
-    __syncthreads();
-
-    // ---- the hash candidate of every position, segment by segment: tok[p] = its distance, 0 for none
-    for (int seg = 0; seg < len; seg += DF_T) {
-        const int p = seg + tid;
-        const bool hashed = p + 2 < len;
-        uint32_t h = 0;
-        if (hashed) {
-            const uint32_t v = s_b[p] | (static_cast<uint32_t>(s_b[p + 1]) << 8) | (static_cast<uint32_t>(s_b[p + 2]) << 16);
-            h = (v * 0x9e3779b1u) >> (32 - DF_HBITS);
-            const uint32_t seen = s_hash[h];
-            tok[p] = seen ? static_cast<uint32_t>(p) + 1u - seen : 0u;
-        } else if (p < len) {
-            tok[p] = 0;
-        }
-        __syncthreads();
-        if (hashed) atomicMax(&s_hash[h], static_cast<uint32_t>(p) + 1u);
-        __syncthreads();
-    }
-
-    // ---- the greedy parse of this lane's sub-chunk
-    const int s0 = tid * DF_S, e0 = min(s0 + DF_S, len);
-    int ntok = 0;
-    {
-        uint32_t asum = 0, bsum = 0;
-        for (int p = s0; p < e0;) {
-            const int maxl = min(258, e0 - p);
-            int best = 0, bestd = 0;
-            if (maxl >= 3) {
-                const int hd = static_cast<int>(tok[p]);
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const int d = k == 0 ? 1 : k == 1 ? 2 : k == 2 ? 3 : k == 3 ? 4 : k == 4 ? 6 : k == 5 ? 8 : k == 6 ? a.row : hd;
-                    if (d <= 0 || d > p) continue;
-                    int l = 0;
-                    while (l < maxl && s_b[p + l] == s_b[p - d + l]) l++;
-                    if (l == 3 && d > 4096) continue;
-                    if (l > best || (l == best && d < bestd)) { best = l; bestd = d; }
-                }
-            }
-            if (best >= 3) {
-                int sym, eb, ev;
-                df_len_sym(best, sym, eb, ev);
-                atomicAdd(&s_llf[sym], 1u);
-                df_dist_sym(bestd, sym, eb, ev);
-                atomicAdd(&s_df[sym], 1u);
-                tok[s0 + ntok++] = df_match_tok(best, bestd);
-                p += best;
-            } else {
-                const uint32_t b = s_b[p];
-                atomicAdd(&s_llf[b], 1u);
-                tok[s0 + ntok++] = b;
-                p++;
-            }
-        }
-        // Adler-32's sums of the sub-chunk, b against the CHUNK's end: at most 128 * 255 * 32768 < 2^32
-        for (int i = s0; i < e0; i++) {
-            const uint32_t x = s_b[i];
-            asum += x;
-            bsum += x * static_cast<uint32_t>(len - i);
-        }
-        if (s0 < e0) {
-            atomicAdd(&s_adler[0], asum);                            // at most 32768 * 255
-            atomicAdd(&s_adler[1], bsum % DF_ADLER);                 // at most 256 * 65520
-        }
-    }
-    __syncthreads();
-
-    // ---- the codes
-    df_rank(s_llf, 286, hw[0].order, tid);
-    df_rank(s_df, 30, hw[1].order, tid);
-    __syncthreads();
-    if (tid == 0) df_build_lengths(s_llf, 286, 15, s_lll, hw[0]);
-    if (tid == 64) {
-        df_build_lengths(s_df, 30, 15, s_dl, hw[1]);
-        bool any = false;
-        for (int j = 0; j < 30; j++) any = any || s_dl[j] != 0;
-        if (!any) s_dl[0] = 1;                                       // no match in the block: one distance code all the same
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int hlit = 286, hdist = 30;
-        while (hlit > 257 && s_lll[hlit - 1] == 0) hlit--;
-        while (hdist > 1 && s_dl[hdist - 1] == 0) hdist--;
-        // the HLIT + HDIST lengths as one sequence in the code-length code
-        int ncl = 0;
-        const int nseq = hlit + hdist;
-        for (int i = 0; i < nseq;) {
-            const int v = i < hlit ? s_lll[i] : s_dl[i - hlit];
-            int r = 1;
-            while (i + r < nseq && (i + r < hlit ? s_lll[i + r] : s_dl[i + r - hlit]) == v) r++;
-            i += r;
-            if (v == 0) {
-                while (r >= 11) { const int t = min(r, 138); s_cltok[ncl++] = static_cast<uint16_t>(18 | ((t - 11) << 8)); s_clf[18]++; r -= t; }
-                if (r >= 3) { s_cltok[ncl++] = static_cast<uint16_t>(17 | ((r - 3) << 8)); s_clf[17]++; r = 0; }
-            } else {
-                s_cltok[ncl++] = static_cast<uint16_t>(v); s_clf[v]++; r--;
-                while (r >= 3) { const int t = min(r, 6); s_cltok[ncl++] = static_cast<uint16_t>(16 | ((t - 3) << 8)); s_clf[16]++; r -= t; }
-            }
-            for (; r > 0; r--) { s_cltok[ncl++] = static_cast<uint16_t>(v); s_clf[v]++; }
-        }
-        int m = 0;
-        for (int s = 0; s < 19; s++) {
-            const uint32_t f = s_clf[s];
-            if (!f) continue;
-            int r = 0;
-            for (int j = 0; j < 19; j++) {
-                const uint32_t g = s_clf[j];
-                r += (g != 0 && (g < f || (g == f && j < s))) ? 1 : 0;
-            }
-            hw[2].order[r] = static_cast<uint16_t>(s);
-            m++;
-        }
-        df_build_lengths(s_clf, 19, 7, s_cll, hw[2]);
-        if (m == 1) s_cll[hw[2].order[0] == 0 ? 1 : 0] = 1;         // inflate refuses an incomplete code-length code
-        int hclen = 19;
-        while (hclen > 4 && s_cll[DF_CLORD[hclen - 1]] == 0) hclen--;
-        uint32_t hdr = 3 + 5 + 5 + 4 + 3 * static_cast<uint32_t>(hclen);
-        for (int i = 0; i < ncl; i++) {
-            const int s = s_cltok[i] & 0xff;
-            hdr += s_cll[s] + (s == 16 ? 2 : (s == 17 ? 3 : (s == 18 ? 7 : 0)));
-        }
-        uint32_t dyn = hdr, fix = 3;
-        for (int s = 0; s < 286; s++) {
-            const uint32_t f = s_llf[s];
-            dyn += f * (s_lll[s] + df_len_ebits(s));
-            fix += f * (df_fixed_len(s) + df_len_ebits(s));
-        }
-        for (int s = 0; s < 30; s++) {
-            const uint32_t f = s_df[s];
-            dyn += f * (s_dl[s] + df_dist_ebits(s));
-            fix += f * (5 + df_dist_ebits(s));
-        }
-        int form = DF_DYNAMIC;
-        uint32_t bits = dyn;
-        if (fix < bits) { form = DF_FIXED; bits = fix; }
-        if (8u * (5u + static_cast<uint32_t>(len)) <= bits) form = DF_STORED;
-        s_form = form; s_hlit = hlit; s_hdist = hdist; s_hclen = hclen; s_ncl = ncl;
-        s_hdr_bits = form == DF_DYNAMIC ? hdr : 3;
-    }
-    __syncthreads();
-    const int form = static_cast<int>(s_form);
-    uint32_t *slot = reinterpret_cast<uint32_t *>(a.slots + static_cast<size_t>(c) * DF_SLOT);
-
-    if (form == DF_STORED) {
-        // header, LEN, ~LEN, the bytes, and behind every chunk but the last the empty stored block (whose header byte is zero too)
-        const int nb = 5 + len + (last ? 0 : 5);
-        for (int j = tid; 4 * j < nb; j += DF_T) {
-            uint32_t v = 0;
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const int k = 4 * j + e;
-                uint32_t b = 0;
-                if (k == 0) b = last ? 1u : 0u;
-                else if (k < 3) b = (static_cast<uint32_t>(len) >> (8 * (k - 1))) & 0xffu;
-                else if (k < 5) b = (~static_cast<uint32_t>(len) >> (8 * (k - 3))) & 0xffu;
-                else if (k < 5 + len) b = s_b[k - 5];
-                else if (k < nb) b = k >= 5 + len + 3 ? 0xffu : 0u;
-                v |= b << (8 * e);
-            }
-            *(g_u32w *)(slot + j) = v;
-        }
-        if (tid == 0) s_nbytes = nb;
-    } else {
-        if (form == DF_DYNAMIC) {
-            df_assign_codes(s_lll, 286, s_llc, tid);
-            df_assign_codes(s_dl, 30, s_dc, tid);
-            df_assign_codes(s_cll, 19, s_clc, tid);
-        } else {
-            for (int s = tid; s < 288; s += DF_T) {
-                const int L = df_fixed_len(s);
-                const uint32_t code = s < 144 ? 0x30u + s : (s < 256 ? 0x190u + (s - 144) : (s < 280 ? s - 256u : 0xc0u + (s - 280)));
-                s_lll[s] = static_cast<uint8_t>(L);
-                s_llc[s] = static_cast<uint16_t>(__brev(code) >> (32 - L));
-            }
-            if (tid < 32) {
-                s_dl[tid] = 5;
-                s_dc[tid] = static_cast<uint16_t>(__brev(static_cast<uint32_t>(tid)) >> 27);
-            }
-        }
-        for (int i = tid; i < (DF_C + 64) / 4; i += DF_T) s_w[i] = 0;    // the chunk's bytes are not read again
-        __syncthreads();
-        uint32_t mybits = 0;
-        for (int k = 0; k < ntok; k++) {
-            const uint32_t t = tok[s0 + k];
-            if (t & 0x80000000u) {
-                int sym, eb, ev;
-                df_len_sym(static_cast<int>((t >> 16) & 0xffu) + 3, sym, eb, ev);
-                mybits += s_lll[sym] + eb;
-                df_dist_sym(static_cast<int>(t & 0xffffu) + 1, sym, eb, ev);
-                mybits += s_dl[sym] + eb;
-            } else {
-                mybits += s_lll[t];
-            }
-        }
-        s_scan[tid] = mybits;
-        __syncthreads();
-        uint32_t off = s_hdr_bits;
-        for (int j = 0; j < tid; j++) off += s_scan[j];
-        if (tid == 0) {
-            DfBits hb(s_w, 0);
-            hb.put(last ? 1u : 0u, 1);
-            hb.put(static_cast<uint32_t>(form), 2);
-            if (form == DF_DYNAMIC) {
-                hb.put(s_hlit - 257, 5);
-                hb.put(s_hdist - 1, 5);
-                hb.put(s_hclen - 4, 4);
-                for (uint32_t i = 0; i < s_hclen; i++) hb.put(s_cll[DF_CLORD[i]], 3);
-                for (uint32_t i = 0; i < s_ncl; i++) {
-                    const int s = s_cltok[i] & 0xff;
-                    hb.put(s_clc[s], s_cll[s]);
-                    if (s >= 16) hb.put(s_cltok[i] >> 8, s == 16 ? 2 : (s == 17 ? 3 : 7));
-                }
-            }
-            hb.flush();
-        }
-        DfBits bw(s_w, off);
-        for (int k = 0; k < ntok; k++) {
-            const uint32_t t = tok[s0 + k];
-            if (t & 0x80000000u) {
-                int sym, eb, ev;
-                df_len_sym(static_cast<int>((t >> 16) & 0xffu) + 3, sym, eb, ev);
-                bw.put(s_llc[sym], s_lll[sym]);
-                if (eb) bw.put(static_cast<uint32_t>(ev), eb);
-                df_dist_sym(static_cast<int>(t & 0xffffu) + 1, sym, eb, ev);
-                bw.put(s_dc[sym], s_dl[sym]);
-                if (eb) bw.put(static_cast<uint32_t>(ev), eb);
-            } else {
-                bw.put(s_llc[t], s_lll[t]);
-            }
-        }
-        if (tid == DF_T - 1) {                                       // behind the last lane's tokens: the block's end
-            bw.put(s_llc[256], s_lll[256]);
-            if (!last) {
-                bw.put(0u, 3);
-                bw.align8();
-                bw.put(0u, 16);
-                bw.put(0xffffu, 16);
-            } else {
-                bw.align8();
-            }
-            s_nbytes = bw.pos() >> 3;
-        }
-        bw.flush();
-        __syncthreads();
-        const int nb = static_cast<int>(s_nbytes);
-        for (int j = tid; 4 * j < nb; j += DF_T) *(g_u32w *)(slot + j) = s_w[j];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t *m = a.meta + 4 * static_cast<size_t>(c);
-        m[0] = s_nbytes;
-        m[1] = s_adler[0] % DF_ADLER;
-        m[2] = s_adler[1] % DF_ADLER;
-        m[3] = static_cast<uint32_t>(len);
-    }
+__global__ __launch_bounds__(DF_T) void deflate_chunk_batch_kernel(DeflateBatchArgs b)
+{
+    const DeflateBatchUnit u = b.units[blockIdx.x];
+    DeflateArgs a;                                                   // the unit as chunk 0 of a stream of its own bytes
+    a.src = u.src; a.n = u.len; a.row = u.row;
+    a.nchunks = u.last ? 1u : 2u;                                    // (a chunk is the last one when none follows)
+    a.tok = b.tok + static_cast<size_t>(blockIdx.x) * DF_C;
+    a.slots = b.slots + static_cast<size_t>(blockIdx.x) * DF_SLOT;
+    a.meta = b.meta + 4 * static_cast<size_t>(blockIdx.x);
+#define DF_CHUNK_INDEX 0u
+#include "deflate_chunk.inc"
+#undef DF_CHUNK_INDEX
 }
 
 struct GatherArgs {
@@ -524,19 +270,12 @@ __device__ __forceinline__ unsigned long long df_block_sum(unsigned long long v,
     return s_red[0] + s_red[1] + s_red[2] + s_red[3];
 }
 
-__global__ __launch_bounds__(DF_T) void deflate_gather_kernel(GatherArgs a)
+// Chunk c of the stream `a` describes, every lane of the workgroup: `before` block bytes of the stream lie in front of the
+// chunk's, `all` is the stream's sum.  Both gather kernels are this body behind their own prefix sums.
+__device__ __forceinline__ void df_gather(const GatherArgs &a, const uint32_t c, const unsigned long long before, const unsigned long long all,
+                                          unsigned long long *s_red)
 {
-    __shared__ unsigned long long s_red[4];
     const int tid = threadIdx.x;
-    const uint32_t c = blockIdx.x;
-    unsigned long long before = 0, all = 0;
-    for (uint32_t j = tid; j < a.nchunks; j += DF_T) {
-        const unsigned long long nb = a.meta[4 * static_cast<size_t>(j)];
-        all += nb;
-        if (j < c) before += nb;
-    }
-    before = df_block_sum(before, s_red);
-    all = df_block_sum(all, s_red);
     const unsigned long long size = 2 + all + 4;
     if (c == 0 && tid == 0) *a.result = size;
     if (size > a.cap) return;                                        // the caller is told the size and nothing is written
@@ -576,10 +315,54 @@ __global__ __launch_bounds__(DF_T) void deflate_gather_kernel(GatherArgs a)
     }
 }
 
-size_t deflate_chunks(size_t n) { return n ? (n + DF_C - 1) / DF_C : 1; }
+__global__ __launch_bounds__(DF_T) void deflate_gather_kernel(GatherArgs a)
+{
+    __shared__ unsigned long long s_red[4];
+    const int tid = threadIdx.x;
+    const uint32_t c = blockIdx.x;
+    unsigned long long before = 0, all = 0;
+    for (uint32_t j = tid; j < a.nchunks; j += DF_T) {
+        const unsigned long long nb = a.meta[4 * static_cast<size_t>(j)];
+        all += nb;
+        if (j < c) before += nb;
+    }
+    before = df_block_sum(before, s_red);
+    all = df_block_sum(all, s_red);
+    df_gather(a, c, before, all, s_red);
+}
 
-// every chunk stored (5 bytes of block header) and closed by the empty stored block (5), the zlib header and the Adler-32
-size_t deflate_bound(size_t n) { return n + 10 * deflate_chunks(n) + 6; }
+// A workgroup per unit: the prefix over its OWN stream's units places the chunk inside the stream, the sum over the units of
+// the streams in front places the stream -- stream i starts at out + 6 i + that sum, so the streams lie back to back at their
+// true sizes and one copy of sum(sizes) bytes brings them all down.  Nothing depends on the order the workgroups run in.
+__global__ __launch_bounds__(DF_T) void deflate_gather_batch_kernel(DeflateBatchArgs a)
+{
+    __shared__ unsigned long long s_red[4];
+    const int tid = threadIdx.x;
+    const uint32_t c = blockIdx.x;
+    const uint32_t image = a.units[c].image;
+    const DeflateBatchImage im = a.images[image];
+    unsigned long long front = 0, before = 0, all = 0;
+    for (uint32_t j = tid; j < im.chunk0 + im.nchunks; j += DF_T) {
+        const unsigned long long nb = a.meta[4 * static_cast<size_t>(j)];
+        if (j < im.chunk0) front += nb;
+        else {
+            all += nb;
+            if (j < c) before += nb;
+        }
+    }
+    front = df_block_sum(front, s_red);
+    before = df_block_sum(before, s_red);
+    all = df_block_sum(all, s_red);
+    GatherArgs g;
+    g.slots = a.slots + static_cast<size_t>(im.chunk0) * DF_SLOT;
+    g.meta = a.meta + 4 * static_cast<size_t>(im.chunk0);
+    g.nchunks = im.nchunks;
+    g.n = static_cast<size_t>(im.n);
+    g.out = a.out + 6 * static_cast<size_t>(image) + front;
+    g.cap = ~size_t(0);                                              // the area holds every stream's bound
+    g.result = a.sizes + image;
+    df_gather(g, c - im.chunk0, before, all, s_red);
+}
 
 int launch_deflate(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, uint8_t *d_out, size_t cap, const unsigned long long **d_size)
 {
@@ -591,7 +374,7 @@ int launch_deflate(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, uint8_
     FNX_TRY(scratch(ctx, SLOT_DEFLATE_SLOTS, meta_bytes + nchunks * DF_SLOT + 16, &ds));
     uint8_t *p = static_cast<uint8_t *>(ds);
     DeflateArgs da{};
-    da.src = d_src; da.n = n; da.row = row > 0 && row < DF_C ? row : 0; da.nchunks = static_cast<uint32_t>(nchunks);
+    da.src = d_src; da.n = n; da.row = deflate_row_hint(row); da.nchunks = static_cast<uint32_t>(nchunks);
     da.tok = static_cast<uint32_t *>(dt);
     da.meta = reinterpret_cast<uint32_t *>(p + 16);
     da.slots = p + meta_bytes;
@@ -608,6 +391,39 @@ int launch_deflate(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, uint8_
     FNX_HIP(hipGetLastError());
     FNX_TRY(prof_end(ctx));
     *d_size = ga.result;
+    return FNX_OK;
+}
+
+// d_units / d_images: DEVICE tables of the batch's nunits units (sorted by stream, a stream's units in order) and m streams;
+// out_bytes: the sum of the streams' bounds.  *d_out: the streams back to back (see the gather), *d_sizes: their m sizes.
+int launch_deflate_batch(fnx_ctx *ctx, const DeflateBatchUnit *d_units, const DeflateBatchImage *d_images, uint32_t nunits, uint32_t m,
+                         size_t out_bytes, const uint8_t **d_out, const unsigned long long **d_sizes)
+{
+    void *dt = nullptr, *ds = nullptr, *dz = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_DEFLATE_TOK, static_cast<size_t>(nunits) * DF_C * sizeof(uint32_t) + 16, &dt));
+    // the streams' sizes, the units' (bytes, a, b, len), the units' slots
+    const size_t sizes_bytes = (8 * static_cast<size_t>(m) + 15) & ~size_t(15);
+    const size_t meta_bytes = 16 * static_cast<size_t>(nunits);
+    FNX_TRY(scratch(ctx, SLOT_DEFLATE_SLOTS, sizes_bytes + meta_bytes + static_cast<size_t>(nunits) * DF_SLOT + 16, &ds));
+    FNX_TRY(scratch(ctx, SLOT_DEFLATE_OUT, out_bytes + 16, &dz));
+    uint8_t *p = static_cast<uint8_t *>(ds);
+    DeflateBatchArgs a{};
+    a.units = d_units; a.images = d_images;
+    a.tok = static_cast<uint32_t *>(dt);
+    a.sizes = reinterpret_cast<unsigned long long *>(p);
+    a.meta = reinterpret_cast<uint32_t *>(p + sizes_bytes);
+    a.slots = p + sizes_bytes + meta_bytes;
+    a.out = static_cast<uint8_t *>(dz);
+    FNX_TRY(prof_begin(ctx));
+    hipLaunchKernelGGL(deflate_chunk_batch_kernel, dim3(nunits), dim3(DF_T), 0, ctx->stream, a);
+    FNX_HIP(hipGetLastError());
+    FNX_TRY(prof_end(ctx));
+    FNX_TRY(prof_begin(ctx));
+    hipLaunchKernelGGL(deflate_gather_batch_kernel, dim3(nunits), dim3(DF_T), 0, ctx->stream, a);
+    FNX_HIP(hipGetLastError());
+    FNX_TRY(prof_end(ctx));
+    *d_out = a.out;
+    *d_sizes = a.sizes;
     return FNX_OK;
 }
 

@@ -833,7 +833,9 @@ int fnx_jpeg_decode(fnx_ctx *ctx, const uint8_t *data, size_t n, int space, uint
 }
 
 // ---- the same for a batch of files (fnx_jpeg_decode_batch; jpeg_dec.hip: jpeg_decode_planes_chunk) ------------------------
-namespace {
+}  // extern "C"
+
+namespace fnx {
 
 // The files' images into dsts (DEVICE), per item what fnx_jpeg_decode(files[i], FNX_DEVICE, dsts[i]) gives.  Baseline files go
 // through the decoder in chunks -- at most FNX_JPEG_DECODE_CHUNK files and JPEG_BATCH_SCRATCH of device scratch each (a file
@@ -903,7 +905,9 @@ int jpeg_decode_batch_device(fnx_ctx *ctx, int n, const uint8_t *const *files, c
     return FNX_OK;
 }
 
-}  // namespace
+}  // namespace fnx
+
+extern "C" {
 
 int fnx_jpeg_decode_batch(fnx_ctx *ctx, int n, const uint8_t *const *files, const size_t *sizes, uint8_t *const *dsts, const int *dstrides,
                           int *ws, int *hs, int *status)

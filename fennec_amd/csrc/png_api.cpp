@@ -2,7 +2,8 @@
 // staging of the three spaces) and fnx_png_encode (png_filter.hip's row stage, then the deflate, on the device; the file's
 // chunks and their CRCs on the host); and fnx_png_decode, the other direction: png_parse.cpp's host side (chunk walk, inflate,
 // the filter bytes), then png_decode.hip's two kernels; and fnx_png_decode_batch, which does the host side of a chunk of files
-// on several threads and sends the chunk through one set of launches.
+// on several threads and sends the chunk through one set of launches; and fnx_png_compress_batch / fnx_png_recompress_batch,
+// compressPNG for a list of resident images (or of files) with one set of launches and three host waits per chunk.
 #include "common.hpp"
 
 #include <algorithm>
@@ -56,6 +57,52 @@ uint8_t *close_chunk(uint8_t *at, const char *tag, size_t len)
     std::memcpy(at + 4, tag, 4);
     put_be32(at + 8 + len, ~crc32_update(0xffffffffu, at + 4, 4 + len));
     return at + 12 + len;
+}
+
+// ---- the file around a zlib stream: signature, IHDR, PLTE + tRNS for colour type 3, one IDAT, IEND ---------------------------
+struct PngFrame {
+    int w, h, color_type, bit_depth;
+    int ncolors;                         // colour type 3: the palette's entries
+    const uint8_t *palette;              // HOST, ncolors x 4 bytes r, g, b, a
+    int ntrns() const                    // the alphas tRNS holds: up to and including the last one that is not 255
+    {
+        int n = 0;
+        if (color_type == 3) {
+            for (int i = 0; i < ncolors; i++) {
+                if (palette[4 * i + 3] != 255) n = i + 1;
+            }
+        }
+        return n;
+    }
+    size_t file_bytes(size_t zsize) const { return 8 + 25 + (color_type == 3 ? png_palette_chunks(ncolors, ntrns()) : 0) + 12 + zsize + 12; }
+};
+
+// everything in front of the stream; returns where the IDAT chunk starts (its body, the stream, goes to that + 8)
+uint8_t *png_frame_head(const PngFrame &f, uint8_t *out)
+{
+    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+    std::memcpy(out, sig, 8);
+    uint8_t *at = out + 8;
+    put_be32(at + 8, static_cast<uint32_t>(f.w));
+    put_be32(at + 12, static_cast<uint32_t>(f.h));
+    at[16] = static_cast<uint8_t>(f.bit_depth); at[17] = static_cast<uint8_t>(f.color_type); at[18] = 0; at[19] = 0; at[20] = 0;
+    at = close_chunk(at, "IHDR", 13);
+    if (f.color_type == 3) {
+        const int ntrns = f.ntrns();
+        for (int i = 0; i < f.ncolors; i++) std::memcpy(at + 8 + 3 * i, f.palette + 4 * i, 3);
+        at = close_chunk(at, "PLTE", 3 * static_cast<size_t>(f.ncolors));
+        if (ntrns) {
+            for (int i = 0; i < ntrns; i++) at[8 + i] = f.palette[4 * i + 3];
+            at = close_chunk(at, "tRNS", static_cast<size_t>(ntrns));
+        }
+    }
+    return at;
+}
+
+// the IDAT chunk whose zsize body bytes are in place, and IEND
+void png_frame_tail(uint8_t *idat, size_t zsize)
+{
+    close_chunk(close_chunk(idat, "IDAT", zsize), "IEND", 0);
 }
 
 // ---- fnx_png_decode_batch ---------------------------------------------------------------------------------------------------
@@ -211,6 +258,9 @@ int png_decode_chunk(fnx_ctx *ctx, const std::vector<BatchEntry> &chunk, const s
                                    static_cast<int>(ok.size()), static_cast<uint32_t>(tiles));
 }
 
+int png_decode_batch_device(fnx_ctx *ctx, int n, const uint8_t *const *files, const size_t *sizes, uint8_t *const *dsts, const int *dstrides,
+                            int workers, int *ws, int *hs, int *status, FirstRefusal *firstp);
+
 }  // namespace
 
 namespace fnx {
@@ -263,15 +313,8 @@ int png_encode_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, i
     unsigned long long zsize = 0;
     FNX_TRY(fetch_bytes(ctx, d_size, &zsize, sizeof(zsize)));
 
-    // the file: signature, IHDR, PLTE + tRNS for colour type 3, one IDAT, IEND
-    int ntrns = 0;
-    if (color_type == 3) {
-        for (int i = 0; i < ncolors; i++) {
-            if (palette[4 * i + 3] != 255) ntrns = i + 1;
-        }
-    }
-    const size_t plte = color_type == 3 ? 12 + 3 * static_cast<size_t>(ncolors) + (ntrns ? 12 + static_cast<size_t>(ntrns) : 0) : 0;
-    *nbytes = 8 + 25 + plte + 12 + static_cast<size_t>(zsize) + 12;
+    const PngFrame frame{w, h, color_type, bit_depth, ncolors, palette};
+    *nbytes = frame.file_bytes(static_cast<size_t>(zsize));
     if (cap < *nbytes || !out) {
         set_error("invalid argument: the PNG file needs %zu bytes of output, cap is %zu", *nbytes, cap);
         return FNX_ERR_INVALID;
@@ -280,25 +323,10 @@ int png_encode_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, i
         set_error("invalid argument: a PNG chunk holds at most 2^31 - 1 bytes");
         return FNX_ERR_INVALID;
     }
-    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
-    std::memcpy(out, sig, 8);
-    uint8_t *at = out + 8;
-    put_be32(at + 8, static_cast<uint32_t>(w));
-    put_be32(at + 12, static_cast<uint32_t>(h));
-    at[16] = static_cast<uint8_t>(bit_depth); at[17] = static_cast<uint8_t>(color_type); at[18] = 0; at[19] = 0; at[20] = 0;
-    at = close_chunk(at, "IHDR", 13);
-    if (color_type == 3) {
-        for (int i = 0; i < ncolors; i++) std::memcpy(at + 8 + 3 * i, palette + 4 * i, 3);
-        at = close_chunk(at, "PLTE", 3 * static_cast<size_t>(ncolors));
-        if (ntrns) {
-            for (int i = 0; i < ntrns; i++) at[8 + i] = palette[4 * i + 3];
-            at = close_chunk(at, "tRNS", static_cast<size_t>(ntrns));
-        }
-    }
+    uint8_t *at = png_frame_head(frame, out);
     FNX_HIP(hipMemcpyAsync(at + 8, dz, static_cast<size_t>(zsize), hipMemcpyDeviceToHost, ctx->stream));
     FNX_HIP(hipStreamSynchronize(ctx->stream));
-    at = close_chunk(at, "IDAT", static_cast<size_t>(zsize));
-    close_chunk(at, "IEND", 0);
+    png_frame_tail(at, static_cast<size_t>(zsize));
     return FNX_OK;
 }
 
@@ -409,6 +437,20 @@ int fnx_png_decode_batch(fnx_ctx *ctx, int n, const uint8_t *const *files, const
     FNX_REQUIRE(files && sizes && dsts && dstrides && ws && hs && status, "decode batch: NULL array");
     FNX_REQUIRE(workers >= 0 && workers <= 64, "decode batch: workers must be 0..64 (0: min(8, files in the chunk))");
     FirstRefusal first;
+    FNX_TRY(png_decode_batch_device(ctx, n, files, sizes, dsts, dstrides, workers, ws, hs, status, &first));
+    if (first.index >= 0) set_error("%s", first.text);
+    return FNX_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// fnx_png_decode_batch behind its argument checks; first: the lowest-indexed refused item's message so far
+int png_decode_batch_device(fnx_ctx *ctx, int n, const uint8_t *const *files, const size_t *sizes, uint8_t *const *dsts, const int *dstrides,
+                            int workers, int *ws, int *hs, int *status, FirstRefusal *firstp)
+{
+    FirstRefusal &first = *firstp;
     std::vector<BatchEntry> chunk;
     std::vector<PngFile> heads;
     size_t stage_bytes = 0, rows_bytes = 0;
@@ -468,7 +510,310 @@ int fnx_png_decode_batch(fnx_ctx *ctx, int n, const uint8_t *const *files, const
         chunk.push_back(e);
         heads.push_back(head);
     }
-    FNX_TRY(flush());
+    return flush();
+}
+
+// ---- fnx_png_compress_batch ---------------------------------------------------------------------------------------------------
+constexpr const char *PNG_CB_ROUTE =
+    "png_colors_batch_kernel, png_finish_batch_kernel, png_flags_batch_kernel, png_plane_batch_kernel, png_filter_batch_kernel, "
+    "png_pack_batch_kernel, deflate_chunk_batch_kernel, deflate_gather_batch_kernel";
+
+// `bytes` device bytes into pinned host memory, waited for: one of a chunk's three host waits
+int png_cb_fetch(fnx_ctx *ctx, const void *d, size_t bytes, const uint8_t **host)
+{
+    void *pin = nullptr;
+    FNX_TRY(pinned_alloc(ctx, bytes ? bytes : 16, &pin));
+    if (bytes) FNX_HIP(hipMemcpyAsync(pin, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    FNX_HIP(hipStreamSynchronize(ctx->stream));
+    *host = static_cast<const uint8_t *>(pin);
+    return FNX_OK;
+}
+
+// One chunk: m images that passed their argument checks (at[j]: image j's place in the caller's arrays) through one set of
+// launches and three host waits -- the classification words, the streams' sizes, the streams' bytes.  (The three fetches and
+// the table uploads take their pinned bytes from the ctx's ring: where the ring grows or wraps, pinned_alloc waits for the
+// stream once more -- by then the stream is idle or nearly so, but it is a wait.)
+int png_compress_chunk(fnx_ctx *ctx, int m, const PngCbSrc *imgs, const int *at, int base, uint8_t *const *outs, const size_t *caps, size_t *nbytes,
+                       int *kinds, int *status, FirstRefusal *first)
+{
+    note_route(ctx, FNX_PROF_MAIN, PNG_CB_ROUTE);
+    const void *d_results = nullptr;
+    FNX_TRY(launch_png_classify_batch(ctx, m, imgs, &d_results));
+    const size_t rb = png_result_bytes();
+    const uint8_t *pin = nullptr;
+    FNX_TRY(png_cb_fetch(ctx, d_results, rb * m, &pin));                       // wait 1
+    std::vector<uint8_t> results(pin, pin + rb * m);                         // (the pinned ring is used again below)
+
+    // compress.go:92-107 per image: tryPalettize, else isGrayscale + toGray, else the image as it is (RGB rows when Opaque())
+    std::vector<PngCbClass> cls(m);
+    std::vector<int> ws(m), hs(m), which(m);
+    for (int j = 0; j < m; j++) {
+        uint32_t r[4];
+        std::memcpy(r, results.data() + rb * j, sizeof r);
+        ws[j] = imgs[j].w; hs[j] = imgs[j].h;
+        if (!r[0]) cls[j] = PngCbClass{FNX_PNG_PALETTED, static_cast<int>(r[2]), 0};
+        else if (!(r[3] & 2u)) cls[j] = PngCbClass{FNX_PNG_GRAY, 0, 0};
+        else cls[j] = PngCbClass{FNX_PNG_NRGBA, 0, (r[3] & 1u) ? 0 : 1};
+        which[j] = cls[j].kind == FNX_PNG_PALETTED ? 1 : (cls[j].kind == FNX_PNG_GRAY ? 2 : 0);
+    }
+    PngCbPlan plan;
+    png_cb_plan(ws.data(), hs.data(), cls.data(), m, &plan);
+
+    void *dpl = nullptr, *dst = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_PNG_CB_PLANES, plan.plane_bytes + 16, &dpl));
+    FNX_TRY(scratch(ctx, SLOT_PNG_CB_STREAMS, plan.stream_bytes + 16, &dst));
+    uint8_t *planes = static_cast<uint8_t *>(dpl), *streams = static_cast<uint8_t *>(dst);
+    std::vector<uint8_t *> pp(m);
+    std::vector<int> ps(m);
+    for (int j = 0; j < m; j++) {
+        pp[j] = which[j] ? planes + plan.images[j].plane_off : nullptr;
+        ps[j] = static_cast<int>(plan.images[j].plane_pitch);
+    }
+    FNX_TRY(launch_png_planes_batch(ctx, m, imgs, which.data(), pp.data(), ps.data()));
+
+    // the row stage: a record per image, the units of the forms back to back
+    std::vector<PngCbRows> rows(m);
+    std::vector<PngCbUnit> units;
+    int nunits[PNG_CB_FORMS];
+    for (int j = 0; j < m; j++) {
+        PngCbRows &r = rows[j];
+        r.src = which[j] ? pp[j] : imgs[j].src;
+        r.sstride = which[j] ? ps[j] : imgs[j].sstride;
+        r.w = imgs[j].w; r.h = imgs[j].h;
+        r.n = static_cast<int>(plan.images[j].rowbytes);
+        r.al4 = png_cb_al4(r.src, r.sstride);
+        r.out = streams + plan.images[j].stream_off;
+    }
+    for (int k = 0; k < PNG_CB_FORMS; k++) {
+        nunits[k] = static_cast<int>(plan.rows[k].size());
+        units.insert(units.end(), plan.rows[k].begin(), plan.rows[k].end());
+    }
+    {
+        const void *hosts[2] = {rows.data(), units.data()};
+        const size_t sizes[2] = {sizeof(PngCbRows) * rows.size(), sizeof(PngCbUnit) * units.size()};
+        void *dp[2];
+        FNX_TRY(upload_tables(ctx, SLOT_PNG_CB_TAB2, hosts, sizes, 2, dp));
+        FNX_TRY(launch_png_rows_batch(ctx, static_cast<const PngCbUnit *>(dp[1]), nunits, static_cast<const PngCbRows *>(dp[0])));
+    }
+
+    // the deflate: a workgroup per 32 KiB of any stream
+    std::vector<DeflateBatchUnit> du(plan.deflate.size());
+    std::vector<DeflateBatchImage> di(m);
+    for (size_t k = 0; k < du.size(); k++) {
+        const PngCbDeflateUnit &u = plan.deflate[k];
+        du[k] = DeflateBatchUnit{streams + u.src_off, u.len, u.row, u.last, u.image};
+    }
+    for (int j = 0; j < m; j++) di[j] = DeflateBatchImage{plan.images[j].stream_bytes, plan.images[j].chunk0, plan.images[j].nchunks};
+    const uint8_t *d_out = nullptr;
+    const unsigned long long *d_sizes = nullptr;
+    {
+        const void *hosts[2] = {du.data(), di.data()};
+        const size_t sizes[2] = {sizeof(DeflateBatchUnit) * du.size(), sizeof(DeflateBatchImage) * di.size()};
+        void *dp[2];
+        FNX_TRY(upload_tables(ctx, SLOT_PNG_CB_TAB3, hosts, sizes, 2, dp));
+        FNX_TRY(launch_deflate_batch(ctx, static_cast<const DeflateBatchUnit *>(dp[0]), static_cast<const DeflateBatchImage *>(dp[1]),
+                                     static_cast<uint32_t>(du.size()), static_cast<uint32_t>(m), plan.out_bytes, &d_out, &d_sizes));
+    }
+    FNX_TRY(png_cb_fetch(ctx, d_sizes, sizeof(unsigned long long) * m, &pin));  // wait 2
+    std::vector<unsigned long long> zsizes(m);
+    std::memcpy(zsizes.data(), pin, sizeof(unsigned long long) * m);
+    size_t total = 0;
+    for (int j = 0; j < m; j++) {
+        if (zsizes[j] > deflate_bound(plan.images[j].stream_bytes)) {
+            set_error("internal: a stream of the compress batch is longer than its bound");
+            return FNX_ERR_INVALID;
+        }
+        total += static_cast<size_t>(zsizes[j]);
+    }
+    FNX_TRY(png_cb_fetch(ctx, d_out, total, &pin));                           // wait 3: the streams' own bytes, back to back
+
+    // the files: the chunks around each stream and their CRCs, on this thread
+    size_t off = 0;
+    for (int j = 0; j < m; j++) {
+        const int i = at[j];
+        const PngCbImage &im = plan.images[j];
+        const size_t zsize = static_cast<size_t>(zsizes[j]);
+        const PngFrame frame{im.w, im.h, im.color_type, im.depth, cls[j].ncolors, results.data() + rb * j + 16};
+        nbytes[i] = frame.file_bytes(zsize);
+        kinds[i] = im.kind;
+        if (caps[i] < nbytes[i] || !outs[i]) {
+            set_error("invalid argument: compress batch: the PNG file of image %d needs %zu bytes of output, cap is %zu", base + i, nbytes[i], caps[i]);
+            status[i] = FNX_ERR_INVALID;
+            first->note(base + i);
+        } else if (zsize > 0x7fffffffull) {
+            set_error("invalid argument: a PNG chunk holds at most 2^31 - 1 bytes");
+            status[i] = FNX_ERR_INVALID;
+            first->note(base + i);
+        } else {
+            uint8_t *idat = png_frame_head(frame, outs[i]);
+            std::memcpy(idat + 8, pin + off, zsize);
+            png_frame_tail(idat, zsize);
+            status[i] = FNX_OK;
+        }
+        off += zsize;
+    }
+    return FNX_OK;
+}
+
+// The batch behind its argument checks: every item's own checks, then the items that passed, chunk by chunk.  skip[i] != 0
+// (may be NULL): item i is not this call's business (fnx_png_recompress_batch: its file was refused), nothing of it is touched.
+// base: item 0's index in the caller's batch, for the messages.
+int png_compress_items(fnx_ctx *ctx, int base, int n, const uint8_t *const *srcs, const int *sstrides, const int *ws, const int *hs, uint8_t *const *outs,
+                       const size_t *caps, size_t *nbytes, int *kinds, int *status, const char *skip, FirstRefusal *first)
+{
+    std::vector<PngCbSrc> imgs;
+    std::vector<int> at, vw, vh;
+    for (int i = 0; i < n; i++) {
+        if (skip && skip[i]) continue;
+        nbytes[i] = 0;
+        kinds[i] = 0;
+        status[i] = FNX_ERR_INVALID;
+        const char *why = nullptr;
+        if (!srcs[i]) why = "srcs[%d] is NULL";
+        else if (!outs[i] && caps[i] != 0) why = "outs[%d] is NULL and its cap is not 0";
+        else if (ws[i] < 1 || hs[i] < 1 || ws[i] > 65535 || hs[i] > 65535) why = "image %d: dims are 1..65535";
+        else if (sstrides[i] < 4 * ws[i] || (sstrides[i] & 3)) why = "image %d: the stride is at least 4w and a multiple of 4";
+        else if (reinterpret_cast<uintptr_t>(srcs[i]) & 3u) why = "image %d: a device image is 4-byte aligned";
+        if (why) {
+            char fmt[160];
+            std::snprintf(fmt, sizeof fmt, "invalid argument: compress batch: %s", why);
+            set_error(fmt, base + i);
+            first->note(base + i);
+            continue;
+        }
+        imgs.push_back(PngCbSrc{srcs[i], sstrides[i], ws[i], hs[i]});
+        at.push_back(i);
+        vw.push_back(ws[i]);
+        vh.push_back(hs[i]);
+    }
+    if (imgs.empty()) return FNX_OK;
+    std::vector<int> firsts;
+    png_cb_split(vw.data(), vh.data(), static_cast<int>(imgs.size()), &firsts);
+    for (size_t c = 0; c + 1 < firsts.size(); c++) {
+        const int j0 = firsts[c], m = firsts[c + 1] - j0;
+        FNX_TRY(png_compress_chunk(ctx, m, imgs.data() + j0, at.data() + j0, base, outs, caps, nbytes, kinds, status, first));
+    }
+    return FNX_OK;
+}
+
+bool is_png_file(const uint8_t *data, size_t n)
+{
+    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+    return n >= 8 && std::memcmp(data, sig, 8) == 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fnx_png_compress_batch(fnx_ctx *ctx, int n, const uint8_t *const *srcs, const int *sstrides, const int *ws, const int *hs, uint8_t *const *outs,
+                           const size_t *caps, size_t *nbytes, int *kinds, int *status)
+{
+    FNX_REQUIRE(n >= 1 && n <= FNX_BATCH_MAX, "compress batch: n must be 1..FNX_BATCH_MAX (65535)");
+    FNX_REQUIRE(srcs && sstrides && ws && hs && outs && caps && nbytes && kinds && status, "compress batch: NULL array");
+    FNX_ENTER(ctx);
+    FNX_REQUIRE(ctx->res_count == 0, "enqueued batches are waiting for fnx_results_fetch: fetch them before a blocking batch call");
+    FirstRefusal first;
+    FNX_TRY(png_compress_items(ctx, 0, n, srcs, sstrides, ws, hs, outs, caps, nbytes, kinds, status, nullptr, &first));
+    if (first.index >= 0) set_error("%s", first.text);
+    return FNX_OK;
+}
+
+// CompressBatch's item body for n files that end as PNG: the files of a span -- as many as decode into
+// FNX_PNG_COMPRESS_CHUNK_BYTES of tight images in SLOT_PNG_CB_IMG, at least one -- go through fnx_png_decode_batch's chunk path
+// (the PNG ones) and fnx_jpeg_decode_batch's (the others), then the images that decoded through the compress batch.
+int fnx_png_recompress_batch(fnx_ctx *ctx, int n, const uint8_t *const *files, const size_t *sizes, int workers, uint8_t *const *outs,
+                             const size_t *caps, size_t *nbytes, int *kinds, int *ws, int *hs, int *status)
+{
+    FNX_REQUIRE(n >= 1 && n <= FNX_BATCH_MAX, "recompress batch: n must be 1..FNX_BATCH_MAX (65535)");
+    FNX_REQUIRE(files && sizes && outs && caps && nbytes && kinds && ws && hs && status, "recompress batch: NULL array");
+    FNX_REQUIRE(workers >= 0 && workers <= 64, "recompress batch: workers must be 0..64 (0: min(8, files in the chunk))");
+    FNX_ENTER(ctx);
+    FNX_REQUIRE(ctx->res_count == 0, "enqueued batches are waiting for fnx_results_fetch: fetch them before a blocking batch call");
+    FirstRefusal first;
+    std::vector<size_t> off;
+    std::vector<char> png;
+    for (int s0 = 0; s0 < n;) {
+        // the span: the dimensions from the headers alone (a file whose header does not parse gets no room; its decoder answers)
+        int s1 = s0;
+        size_t total = 0;
+        off.clear();
+        png.clear();
+        for (; s1 < n; s1++) {
+            int w = 0, h = 0;
+            const bool isp = files[s1] && is_png_file(files[s1], sizes[s1]);
+            if (isp) {
+                PngFile head;
+                if (png_probe(files[s1], sizes[s1], &head) == FNX_OK) { w = head.w; h = head.h; }
+            } else if (files[s1]) {
+                JpegFile f;
+                if (jpeg_parse(files[s1], sizes[s1], &f) >= 0) { w = f.w; h = f.h; }
+            }
+            const size_t b = (static_cast<size_t>(w) * h * 4 + 16 + 255) & ~size_t(255);
+            if (s1 > s0 && total + b > FNX_PNG_COMPRESS_CHUNK_BYTES) break;
+            off.push_back(total);
+            png.push_back(isp ? 1 : 0);
+            total += b;
+            ws[s1] = w; hs[s1] = h;
+        }
+        const int m = s1 - s0;
+        void *t = nullptr;
+        const int src = scratch(ctx, SLOT_PNG_CB_IMG, total, &t);
+        if (src == FNX_ERR_OOM && m == 1) {
+            // one file whose header asks for more than the device has (the span's first file is exempt from the byte cap): that
+            // item's refusal, not the call's -- the other spans go on
+            status[s0] = FNX_ERR_OOM;
+            nbytes[s0] = 0;
+            kinds[s0] = 0;
+            first.note(s0);
+            s0 = s1;
+            continue;
+        }
+        FNX_TRY(src);
+        // the two decoders, each over its own files of the span in the span's order
+        std::vector<uint8_t *> dst(m, nullptr);
+        std::vector<int> dstride(m, 0);
+        for (int j = 0; j < m; j++) {
+            nbytes[s0 + j] = 0;
+            kinds[s0 + j] = 0;
+            if (ws[s0 + j] <= 0) continue;
+            dst[j] = static_cast<uint8_t *>(t) + off[j];
+            dstride[j] = ws[s0 + j] * 4;
+        }
+        for (int pass = 0; pass < 2; pass++) {
+            std::vector<int> idx;
+            for (int j = 0; j < m; j++) {
+                if ((png[j] != 0) == (pass == 0)) idx.push_back(j);
+            }
+            if (idx.empty()) continue;
+            const int k = static_cast<int>(idx.size());
+            std::vector<const uint8_t *> f(k);
+            std::vector<size_t> fs(k);
+            std::vector<uint8_t *> d(k);
+            std::vector<int> dstr(k), w(k), h(k), st(k);
+            for (int q = 0; q < k; q++) { f[q] = files[s0 + idx[q]]; fs[q] = sizes[s0 + idx[q]]; d[q] = dst[idx[q]]; dstr[q] = dstride[idx[q]]; }
+            if (pass == 0) {
+                FirstRefusal sub;
+                FNX_TRY(png_decode_batch_device(ctx, k, f.data(), fs.data(), d.data(), dstr.data(), workers, w.data(), h.data(), st.data(), &sub));
+                if (sub.index >= 0 && (first.index < 0 || s0 + idx[sub.index] < first.index)) {
+                    first.index = s0 + idx[sub.index];
+                    std::snprintf(first.text, sizeof first.text, "%s", sub.text);
+                }
+            } else {
+                FNX_TRY(jpeg_decode_batch_device(ctx, k, f.data(), fs.data(), d.data(), dstr.data(), w.data(), h.data(), st.data()));
+            }
+            for (int q = 0; q < k; q++) { ws[s0 + idx[q]] = w[q]; hs[s0 + idx[q]] = h[q]; status[s0 + idx[q]] = st[q]; }
+        }
+        std::vector<char> skip(m);
+        std::vector<const uint8_t *> srcs(m);
+        for (int j = 0; j < m; j++) {
+            skip[j] = status[s0 + j] != FNX_OK;
+            srcs[j] = dst[j];
+        }
+        FNX_TRY(png_compress_items(ctx, s0, m, srcs.data(), dstride.data(), ws + s0, hs + s0, outs + s0, caps + s0, nbytes + s0, kinds + s0, status + s0,
+                                   skip.data(), &first));
+        s0 = s1;
+    }
     if (first.index >= 0) set_error("%s", first.text);
     return FNX_OK;
 }

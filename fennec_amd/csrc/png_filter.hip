@@ -27,10 +27,16 @@
 // Resources (hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage): no scratch in any kernel;
 // VGPRs: png_filter_kernel RGB 49, RGBA 46, GRAY 52; png_pack_kernel 8-bit 26, 4-bit 21, 2-bit 29, 1-bit 45;
 // png_alpha_kernel 17.  LDS: 160 bytes (png_filter_kernel), 256 (png_alpha_kernel's block-wide OR).  8 waves per SIMD.
+//
+//  * png_filter_batch_kernel<MODE>, png_pack_batch_kernel<DEPTH> (fnx_png_compress_batch): the same bodies (png_filter_rows.inc,
+//    png_pack_rows.inc, included into both kernels) with a workgroup per unit {image, first row, end row} of any image of the
+//    chunk that takes the form, the image's record read through the scalar cache.  No scratch; VGPRs: filter RGB 49, RGBA 46,
+//    GRAY 50; pack 8-bit 26, 4-bit 22, 2-bit 30, 1-bit 46; LDS as the single kernels'.
 #include "common.hpp"
 #include "devutil.hpp"
 
 #include <algorithm>
+#include <cstddef>
 
 namespace fnx {
 
@@ -160,85 +166,27 @@ struct PngFilterArgs {
 template <int MODE>
 __global__ __launch_bounds__(PF_T) void png_filter_kernel(PngFilterArgs a)
 {
-    constexpr int K = pf_k(MODE), BPP = pf_bpp(MODE);
-    __shared__ uint32_t s_sum[2][PF_T / 64][5];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const uint32_t n = static_cast<uint32_t>(a.n);
-    const uint32_t units = (n + 4 * K - 1) / (4 * K);
-    const bool al4 = a.al4 != 0;
-    int parity = 0;
-    for (int y = blockIdx.x; y < a.h; y += gridDim.x, parity ^= 1) {
-        const uint8_t *cur = a.src + static_cast<size_t>(y) * a.sstride;
-        const uint8_t *prev = cur - a.sstride;                       // read for y > 0 only
-        // ---- pass 1: the five sums, in the order of the type numbers: None, Sub, Up, Average, Paeth
-        uint32_t sum[5] = {0, 0, 0, 0, 0};
-        for (uint32_t u = tid; u < units; u += PF_T) {
-            uint32_t C[5], P[5] = {0, 0, 0, 0, 0};
-            const int nvalid = pf_load<MODE>(cur, u, a.w, al4, C);
-            if (y > 0) pf_load<MODE>(prev, u, a.w, al4, P);
-#pragma unroll
-            for (int j = 0; j < K; j++) {
-                // a residual behind the row's end is not part of the sum (Sub, Average and Paeth see a left neighbour there)
-                const int v = nvalid - 4 * j;
-                const uint32_t m = v >= 4 ? 0xffffffffu : (v <= 0 ? 0u : (1u << (8 * v)) - 1u);
-                const uint32_t c = C[1 + j], up = P[1 + j];
-                const uint32_t l = left_of<BPP>(C[j], c), ul = left_of<BPP>(P[j], up);
-                sum[0] = cost8(c, sum[0]);
-                sum[1] = cost8(sub8(c, l) & m, sum[1]);
-                sum[2] = cost8(sub8(c, up), sum[2]);
-                sum[3] = cost8(sub8(c, avg8(l, up)) & m, sum[3]);
-                sum[4] = cost8(sub8(c, paeth8(l, up, ul)) & m, sum[4]);
-            }
-        }
-#pragma unroll
-        for (int f = 0; f < 5; f++) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) sum[f] += __shfl_xor(sum[f], off, 64);
-        }
-        // two sets of words, by the parity of the workgroup's row count: a wave can be at most one barrier ahead of another
-        if (lane == 0) {
-#pragma unroll
-            for (int f = 0; f < 5; f++) s_sum[parity][wave][f] = sum[f];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int f = 0; f < 5; f++) sum[f] = s_sum[parity][0][f] + s_sum[parity][1][f] + s_sum[parity][2][f] + s_sum[parity][3][f];
-        // tried in the order Up, Paeth, None, Sub, Average; a later one wins only when strictly smaller
-        int ft = 2;
-        uint32_t best = sum[2];
-        if (sum[4] < best) { best = sum[4]; ft = 4; }
-        if (sum[0] < best) { best = sum[0]; ft = 0; }
-        if (sum[1] < best) { best = sum[1]; ft = 1; }
-        if (sum[3] < best) { best = sum[3]; ft = 3; }
+#define PF_FIRST_ROW blockIdx.x
+#define PF_ROW_STEP gridDim.x
+#include "png_filter_rows.inc"
+#undef PF_FIRST_ROW
+#undef PF_ROW_STEP
+}
 
-        // ---- pass 2: the chosen filter, stored
-        uint8_t *orow = a.out + static_cast<size_t>(y) * (static_cast<size_t>(n) + 1);
-        if (tid == 0) orow[0] = static_cast<uint8_t>(ft);
-        const bool need_prev = ft >= 2 && y > 0;
-        for (uint32_t base = wave * 64; base < units; base += PF_T) {
-            const uint32_t u = base + lane;
-            const bool active = u < units;
-            uint32_t C[5] = {0, 0, 0, 0, 0}, P[5] = {0, 0, 0, 0, 0}, D[K];
-            int nvalid = 0;
-            if (active) {
-                nvalid = pf_load<MODE>(cur, u, a.w, al4, C);
-                if (need_prev) pf_load<MODE>(prev, u, a.w, al4, P);
-            }
-#pragma unroll
-            for (int j = 0; j < K; j++) {
-                const uint32_t c = C[1 + j], up = P[1 + j];
-                const uint32_t l = left_of<BPP>(C[j], c), ul = left_of<BPP>(P[j], up);
-                uint32_t d = c;
-                if (ft == 1) d = sub8(c, l);
-                else if (ft == 2) d = sub8(c, up);
-                else if (ft == 3) d = sub8(c, avg8(l, up));
-                else if (ft == 4) d = sub8(c, paeth8(l, up, ul));
-                D[j] = d;
-            }
-            const uint32_t i0 = 4u * K * u;
-            pf_store<K>(orow + 1, i0, D, nvalid, active, i0 + 8u * K <= n, lane);
-        }
-    }
+// The compress batch: a workgroup per unit -- rows [first, end) of one image of the chunk whose rows take this form.  The unit
+// and the image's record come through the scalar cache; the rows are the single kernel's rows (a row's bytes depend on the row
+// and the one above alone).
+template <int MODE>
+__global__ __launch_bounds__(PF_T) void png_filter_batch_kernel(const PngCbUnit *__restrict__ work, const PngFilterArgs *__restrict__ images)
+{
+    const PngCbUnit u = work[blockIdx.x];
+    PngFilterArgs a = images[u.image];
+    a.h = static_cast<int>(u.end);                                   // the rows below it are other units'
+#define PF_FIRST_ROW static_cast<int>(u.first)
+#define PF_ROW_STEP 1
+#include "png_filter_rows.inc"
+#undef PF_FIRST_ROW
+#undef PF_ROW_STEP
 }
 
 struct PngPackArgs {
@@ -252,53 +200,24 @@ struct PngPackArgs {
 template <int DEPTH>
 __global__ __launch_bounds__(PF_T) void png_pack_kernel(PngPackArgs a)
 {
-    constexpr int K = DEPTH == 8 ? 4 : 1, PPB = 8 / DEPTH;           // raw dwords per unit, pixels per raw byte
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const uint32_t n = static_cast<uint32_t>(a.n);
-    const uint32_t units = (n + 4 * K - 1) / (4 * K);
-    for (int y = blockIdx.x; y < a.h; y += gridDim.x) {
-        const uint8_t *row = a.src + static_cast<size_t>(y) * a.sstride;
-        uint8_t *orow = a.out + static_cast<size_t>(y) * (static_cast<size_t>(n) + 1);
-        if (tid == 0) orow[0] = 0;                                   // paletted rows are never filtered
-        for (uint32_t base = wave * 64; base < units; base += PF_T) {
-            const uint32_t u = base + lane;
-            const bool active = u < units;
-            uint32_t D[K];
-            int nvalid = 0;
-            if (DEPTH == 8) {
-                uint32_t R[5] = {0, 0, 0, 0, 0};
-                if (active) nvalid = pf_load<PNG_ROW_GRAY>(row, u, a.w, a.al4 != 0, R);
-#pragma unroll
-                for (int j = 0; j < K; j++) D[j] = R[1 + j];
-            } else {
-                D[0] = 0;
-                if (active) {
-                    nvalid = min(4, static_cast<int>(n - 4u * u));
-                    const int x0 = 4 * PPB * static_cast<int>(u);    // 4 raw bytes of PPB pixels each
-                    if (a.al4 && x0 + 4 * PPB <= a.w) {
-#pragma unroll
-                        for (int q = 0; q < PPB; q++) {              // source dword q: pixels 4q .. 4q + 3, raw byte 4q / PPB
-                            const uint32_t v = *(g_u32 *)(row + x0 + 4 * q);
-#pragma unroll
-                            for (int e = 0; e < 4; e++) {
-                                const int px = 4 * q + e, k = px / PPB, slot = PPB - 1 - px % PPB;
-                                D[0] |= (((v >> (8 * e)) & 0xffu) << (DEPTH * slot) & 0xffu) << (8 * k);
-                            }
-                        }
-                    } else {
-#pragma unroll
-                        for (int px = 0; px < 4 * PPB; px++) {
-                            const int k = px / PPB, slot = PPB - 1 - px % PPB;
-                            const uint32_t v = x0 + px < a.w ? row[x0 + px] : 0u;
-                            D[0] |= ((v << (DEPTH * slot)) & 0xffu) << (8 * k);
-                        }
-                    }
-                }
-            }
-            const uint32_t i0 = 4u * K * u;
-            pf_store<K>(orow + 1, i0, D, nvalid, active, i0 + 8u * K <= n, lane);
-        }
-    }
+#define PF_FIRST_ROW blockIdx.x
+#define PF_ROW_STEP gridDim.x
+#include "png_pack_rows.inc"
+#undef PF_FIRST_ROW
+#undef PF_ROW_STEP
+}
+
+template <int DEPTH>
+__global__ __launch_bounds__(PF_T) void png_pack_batch_kernel(const PngCbUnit *__restrict__ work, const PngPackArgs *__restrict__ images)
+{
+    const PngCbUnit u = work[blockIdx.x];
+    PngPackArgs a = images[u.image];
+    a.h = static_cast<int>(u.end);
+#define PF_FIRST_ROW static_cast<int>(u.first)
+#define PF_ROW_STEP 1
+#include "png_pack_rows.inc"
+#undef PF_FIRST_ROW
+#undef PF_ROW_STEP
 }
 
 // image.NRGBA.Opaque(): *flag (zero before the launch) becomes 1 when a VISIBLE pixel has alpha != 255
@@ -370,6 +289,49 @@ int launch_png_filter(fnx_ctx *ctx, int form, const uint8_t *src, int sstride, i
     }
     FNX_HIP(hipGetLastError());
     FNX_TRY(prof_end(ctx));
+    return FNX_OK;
+}
+
+// The row stage of a chunk of the compress batch: per form present one launch over that form's units.  d_units: the units of
+// forms 0, 1, ... back to back (nunits[k] of form k); d_rows: m records (DEVICE; a record is PngFilterArgs and PngPackArgs alike).
+#define PF_SAME_FIELD(f) \
+    static_assert(offsetof(PngCbRows, f) == offsetof(PngFilterArgs, f) && offsetof(PngCbRows, f) == offsetof(PngPackArgs, f) && \
+                  sizeof(PngCbRows::f) == sizeof(PngFilterArgs::f) && sizeof(PngCbRows::f) == sizeof(PngPackArgs::f), "one record for both kernels: " #f)
+PF_SAME_FIELD(src);
+PF_SAME_FIELD(sstride);
+PF_SAME_FIELD(w);
+PF_SAME_FIELD(h);
+PF_SAME_FIELD(n);
+PF_SAME_FIELD(al4);
+PF_SAME_FIELD(out);
+#undef PF_SAME_FIELD
+static_assert(sizeof(PngCbRows) == sizeof(PngFilterArgs) && sizeof(PngCbRows) == sizeof(PngPackArgs), "one record for both kernels");
+
+int png_cb_al4(const uint8_t *src, int sstride) { return pf_al4(src, sstride); }
+
+int launch_png_rows_batch(fnx_ctx *ctx, const PngCbUnit *d_units, const int nunits[PNG_CB_FORMS], const PngCbRows *d_rows)
+{
+    const dim3 block(PF_T);
+    const PngCbUnit *u = d_units;
+    const PngFilterArgs *fa = reinterpret_cast<const PngFilterArgs *>(d_rows);
+    const PngPackArgs *pa = reinterpret_cast<const PngPackArgs *>(d_rows);
+    for (int k = 0; k < PNG_CB_FORMS; k++) {
+        if (nunits[k] == 0) continue;
+        const dim3 grid(nunits[k]);
+        FNX_TRY(prof_begin(ctx));
+        switch (k) {
+        case PNG_CB_RGB: hipLaunchKernelGGL(png_filter_batch_kernel<PNG_ROW_RGB>, grid, block, 0, ctx->stream, u, fa); break;
+        case PNG_CB_RGBA: hipLaunchKernelGGL(png_filter_batch_kernel<PNG_ROW_RGBA>, grid, block, 0, ctx->stream, u, fa); break;
+        case PNG_CB_GRAY: hipLaunchKernelGGL(png_filter_batch_kernel<PNG_ROW_GRAY>, grid, block, 0, ctx->stream, u, fa); break;
+        case PNG_CB_PACK8: hipLaunchKernelGGL(png_pack_batch_kernel<8>, grid, block, 0, ctx->stream, u, pa); break;
+        case PNG_CB_PACK4: hipLaunchKernelGGL(png_pack_batch_kernel<4>, grid, block, 0, ctx->stream, u, pa); break;
+        case PNG_CB_PACK2: hipLaunchKernelGGL(png_pack_batch_kernel<2>, grid, block, 0, ctx->stream, u, pa); break;
+        default: hipLaunchKernelGGL(png_pack_batch_kernel<1>, grid, block, 0, ctx->stream, u, pa); break;
+        }
+        FNX_HIP(hipGetLastError());
+        FNX_TRY(prof_end(ctx));
+        u += nunits[k];
+    }
     return FNX_OK;
 }
 

@@ -17,6 +17,11 @@
 //    allows) or, in gray mode, toGray's plane (R of every pixel).  The index form is launched unconditionally behind the
 //    finish and returns at once when the set overflowed: the common paths take ONE synchronisation.
 //
+//  * png_colors_batch_kernel, png_finish_batch_kernel, png_plane_batch_kernel (fnx_png_compress_batch): the three bodies over
+//    a chunk of images in one launch each -- a unit is workgroup b of the G an image gets, the finish a workgroup per image,
+//    every image with its own result record -- and png_flags_batch_kernel, which makes the two flags the single route fetches
+//    separately.  No scratch; VGPRs 40, 24, 25 (their twins' figures) and 20; LDS 24848, 59664, 8192 and 256 bytes.
+//
 // Palette order: the reference ranges over a Go map (compress.go:134), whose order is random by specification -- every
 // order is a reference answer.  This one is fixed: ascending row-major index of each colour's first occurrence, what an
 // insertion-ordered map gives.  It does not depend on the grid or on timing: the first index of a colour is a minimum
@@ -106,12 +111,13 @@ struct PngColorsArgs {
     uint2 *lists;                        // [G][PNG_LIST]: (colour, first index)
 };
 
-__global__ __launch_bounds__(PNG_T) void png_colors_kernel(PngColorsArgs a)
+// workgroup b of the G that share the image `a` describes, every lane: both colours kernels are this body
+__device__ __forceinline__ void png_colors_body(const PngColorsArgs &a, const int b, const int G)
 {
     __shared__ unsigned long long s_keys[PNG_WG_SLOTS];
     __shared__ uint32_t s_first[PNG_WG_SLOTS];
     __shared__ uint32_t s_count, s_stop, s_n;
-    const int tid = threadIdx.x, b = blockIdx.x, G = gridDim.x;
+    const int tid = threadIdx.x;
     for (int i = tid; i < PNG_WG_SLOTS; i += PNG_T) { s_keys[i] = 0ull; s_first[i] = 0xffffffffu; }
     if (tid == 0) { s_count = 0; s_stop = 0; s_n = 0; }
     __syncthreads();
@@ -180,6 +186,11 @@ __global__ __launch_bounds__(PNG_T) void png_colors_kernel(PngColorsArgs a)
     if (tid == 0) a.counts[b] = s_count;
 }
 
+__global__ __launch_bounds__(PNG_T) void png_colors_kernel(PngColorsArgs a)
+{
+    png_colors_body(a, blockIdx.x, gridDim.x);
+}
+
 struct PngFinishArgs {
     int G, max_colors;
     const uint32_t *counts;
@@ -188,7 +199,7 @@ struct PngFinishArgs {
     unsigned long long *map;             // [PNG_MAP_SLOTS]: 0, or bit 63 | index << 32 | colour
 };
 
-__global__ __launch_bounds__(PNG_FIN_T) void png_finish_kernel(PngFinishArgs a)
+__device__ __forceinline__ void png_finish_body(const PngFinishArgs &a)
 {
     __shared__ unsigned long long s_keys[PNG_FIN_SLOTS];             // 32 KB
     __shared__ uint32_t s_first[PNG_FIN_SLOTS];                      // 16 KB
@@ -239,6 +250,11 @@ __global__ __launch_bounds__(PNG_FIN_T) void png_finish_kernel(PngFinishArgs a)
     if (tid == 0) a.res->ncolors = static_cast<uint32_t>(n);
 }
 
+__global__ __launch_bounds__(PNG_FIN_T) void png_finish_kernel(PngFinishArgs a)
+{
+    png_finish_body(a);
+}
+
 struct PngPlaneArgs {
     const uint8_t *src;
     int sstride, w;
@@ -250,10 +266,10 @@ struct PngPlaneArgs {
     int pstride;
 };
 
-__global__ __launch_bounds__(PNG_T) void png_plane_kernel(PngPlaneArgs a)
+__device__ __forceinline__ void png_plane_body(const PngPlaneArgs &a, const int b, const int G)
 {
     __shared__ unsigned long long s_map[PNG_MAP_SLOTS];
-    const int tid = threadIdx.x, b = blockIdx.x, G = gridDim.x;
+    const int tid = threadIdx.x;
     if (!a.gray) {
         if (a.res->over != 0u) return;                               // not paletted: nothing is written
         for (int i = tid; i < PNG_MAP_SLOTS; i += PNG_T) s_map[i] = a.map[i];
@@ -302,6 +318,65 @@ __global__ __launch_bounds__(PNG_T) void png_plane_kernel(PngPlaneArgs a)
             }
         }
     }
+}
+
+__global__ __launch_bounds__(PNG_T) void png_plane_kernel(PngPlaneArgs a)
+{
+    png_plane_body(a, blockIdx.x, gridDim.x);
+}
+
+// ---- the compress batch: the same passes over a chunk of images in one launch each --------------------------------------------
+// A unit {image, first, end} is workgroup `first` of the `end` that share the image; the unit and the image's record come
+// through the scalar cache.  Every image has its own result words, so a photograph's "over" stops its own workgroups only.
+struct PngCbClassify {
+    PngColorsArgs c;
+    int G;                               // the image's workgroups of the colours pass = its lists
+    unsigned long long *map;
+};
+
+__global__ __launch_bounds__(PNG_T) void png_colors_batch_kernel(const PngCbUnit *__restrict__ units, const PngCbClassify *__restrict__ images)
+{
+    const PngCbUnit u = units[blockIdx.x];
+    png_colors_body(images[u.image].c, static_cast<int>(u.first), static_cast<int>(u.end));
+}
+
+__global__ __launch_bounds__(PNG_FIN_T) void png_finish_batch_kernel(const PngCbClassify *__restrict__ images)
+{
+    const PngCbClassify &im = images[blockIdx.x];
+    PngFinishArgs a;
+    a.G = im.G; a.max_colors = im.c.max_colors; a.counts = im.c.counts; a.lists = im.c.lists; a.res = im.c.res; a.map = im.map;
+    png_finish_body(a);
+}
+
+// The two flags the single route fetches one by one, for rows [first, end) of an image: bit 0 -- some VISIBLE pixel with
+// alpha != 255 (image.NRGBA.Opaque, png_alpha_kernel's answer); bit 1 -- some pixel of the FLAT Pix walk, row padding included,
+// with r != g or g != b (isGrayscale, convert.go:76-84: every row but the last is sstride / 4 pixels long there).  OR-ed into
+// the image's fourth result word, which nothing else writes.
+__global__ __launch_bounds__(PNG_T) void png_flags_batch_kernel(const PngCbUnit *__restrict__ units, const PngCbClassify *__restrict__ images)
+{
+    const PngCbUnit u = units[blockIdx.x];
+    const PngColorsArgs &a = images[u.image].c;
+    const int h = a.walk.by_row ? a.walk.rows : static_cast<int>(a.walk.row_px / static_cast<uint32_t>(a.w));
+    uint32_t all = 0xff000000u, mixed = 0;
+    for (int y = static_cast<int>(u.first); y < static_cast<int>(u.end); y++) {
+        const uint8_t *row = a.src + static_cast<size_t>(y) * a.sstride;
+        const int flat = y + 1 == h ? a.w : a.sstride >> 2;
+        for (int x = threadIdx.x; x < flat; x += PNG_T) {
+            const uint32_t p = ld_px(row, x);
+            mixed |= (p ^ (p >> 8)) & 0xffffu;
+            if (x < a.w) all &= p;
+        }
+    }
+    const int translucent = __syncthreads_or((all >> 24) != 0xffu ? 1 : 0);
+    const int nongray = __syncthreads_or(mixed != 0u ? 1 : 0);
+    const uint32_t bits = (translucent ? 1u : 0u) | (nongray ? 2u : 0u);
+    if (bits && threadIdx.x == 0) atomicOr(&a.res->pad, bits);
+}
+
+__global__ __launch_bounds__(PNG_T) void png_plane_batch_kernel(const PngCbUnit *__restrict__ units, const PngPlaneArgs *__restrict__ images)
+{
+    const PngCbUnit u = units[blockIdx.x];
+    png_plane_body(images[u.image], static_cast<int>(u.first), static_cast<int>(u.end));
 }
 
 namespace {
@@ -378,6 +453,121 @@ int launch_png_plane(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h
     pa.plane = d_plane; pa.pstride = pstride;
     FNX_TRY(prof_begin(ctx));
     hipLaunchKernelGGL(png_plane_kernel, dim3(png_grid(ctx, pa.walk)), dim3(PNG_T), 0, ctx->stream, pa);
+    FNX_HIP(hipGetLastError());
+    FNX_TRY(prof_end(ctx));
+    return FNX_OK;
+}
+
+// ---- the compress batch's launchers ------------------------------------------------------------------------------------------
+namespace {
+
+// SLOT_PNG_CB_WORK of a chunk of m images: the m results (what the host fetches: png_result_bytes() each), the m colour ->
+// index tables, then per image its counts and lists
+struct CbWork {
+    std::vector<int> G;
+    std::vector<size_t> lists_off;
+    size_t maps_off = 0, total = 0;
+};
+
+static_assert(sizeof(PngResult) + sizeof(unsigned long long) * PNG_MAP_SLOTS + PNG_CB_GRID * (sizeof(uint32_t) + sizeof(uint2) * PNG_LIST) + 16 <=
+                  PNG_CB_WORK_BYTES, "the planner counts an image's share of the work area");
+
+CbWork cb_work(int m, const PngCbSrc *imgs)
+{
+    CbWork k;
+    k.maps_off = sizeof(PngResult) * static_cast<size_t>(m);
+    k.total = k.maps_off + sizeof(unsigned long long) * PNG_MAP_SLOTS * static_cast<size_t>(m);
+    for (int i = 0; i < m; i++) {
+        k.G.push_back(png_cb_grid(imgs[i].w, imgs[i].h, imgs[i].sstride == 4 * imgs[i].w));
+        k.lists_off.push_back(k.total);
+        k.total += ((sizeof(uint32_t) * static_cast<size_t>(k.G[i]) + 15) & ~size_t(15)) + sizeof(uint2) * PNG_LIST * static_cast<size_t>(k.G[i]);
+    }
+    return k;
+}
+
+}  // namespace
+
+// tryPalettize's colour set of every image of a chunk (max_colors 256) and its two flags, nothing waited for.  *d_results: m
+// records of png_result_bytes() -- words 0 over, 2 ncolors, 3 the flags (bit 0: a visible pixel is translucent, bit 1: the flat
+// walk met a non-grey pixel), then the palette; word 1 is the single route's shortcut and means nothing here.
+int launch_png_classify_batch(fnx_ctx *ctx, int m, const PngCbSrc *imgs, const void **d_results)
+{
+    const CbWork k = cb_work(m, imgs);
+    void *wp = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_PNG_CB_WORK, k.total + 16, &wp));
+    uint8_t *base = static_cast<uint8_t *>(wp);
+    std::vector<PngCbClassify> tab(m);
+    std::vector<PngCbUnit> cu, fu;
+    for (int i = 0; i < m; i++) {
+        const PngCbSrc &im = imgs[i];
+        PngCbClassify &t = tab[i];
+        std::memset(&t, 0, sizeof t);
+        t.c.src = im.src; t.c.sstride = im.sstride; t.c.w = im.w;
+        t.c.walk = png_walk(im.src, im.sstride, im.w, im.h, im.sstride == 4 * im.w);
+        t.c.max_colors = 256;
+        t.c.res = reinterpret_cast<PngResult *>(base) + i;
+        t.c.counts = reinterpret_cast<uint32_t *>(base + k.lists_off[i]);
+        t.c.lists = reinterpret_cast<uint2 *>(base + k.lists_off[i] + ((sizeof(uint32_t) * static_cast<size_t>(k.G[i]) + 15) & ~size_t(15)));
+        t.G = k.G[i];
+        t.map = reinterpret_cast<unsigned long long *>(base + k.maps_off) + static_cast<size_t>(PNG_MAP_SLOTS) * i;
+        for (int b = 0; b < k.G[i]; b++) cu.push_back(PngCbUnit{static_cast<uint32_t>(i), static_cast<uint32_t>(b), static_cast<uint32_t>(k.G[i])});
+        const int per = png_cb_unit_rows(4 * static_cast<size_t>(im.w));
+        for (int y = 0; y < im.h; y += per)
+            fu.push_back(PngCbUnit{static_cast<uint32_t>(i), static_cast<uint32_t>(y), static_cast<uint32_t>(std::min(im.h, y + per))});
+    }
+    const void *hosts[3] = {tab.data(), cu.data(), fu.data()};
+    const size_t sizes[3] = {sizeof(PngCbClassify) * tab.size(), sizeof(PngCbUnit) * cu.size(), sizeof(PngCbUnit) * fu.size()};
+    void *dp[3];
+    FNX_TRY(upload_tables(ctx, SLOT_PNG_CB_TAB0, hosts, sizes, 3, dp));
+    const PngCbClassify *d_tab = static_cast<const PngCbClassify *>(dp[0]);
+    FNX_HIP(hipMemsetAsync(base, 0, sizeof(PngResult) * static_cast<size_t>(m), ctx->stream));
+    FNX_TRY(prof_begin(ctx));
+    hipLaunchKernelGGL(png_colors_batch_kernel, dim3(static_cast<unsigned>(cu.size())), dim3(PNG_T), 0, ctx->stream, static_cast<const PngCbUnit *>(dp[1]), d_tab);
+    FNX_HIP(hipGetLastError());
+    FNX_TRY(prof_end(ctx));
+    FNX_TRY(prof_begin(ctx));
+    hipLaunchKernelGGL(png_finish_batch_kernel, dim3(m), dim3(PNG_FIN_T), 0, ctx->stream, d_tab);
+    FNX_HIP(hipGetLastError());
+    FNX_TRY(prof_end(ctx));
+    FNX_TRY(prof_begin(ctx));
+    hipLaunchKernelGGL(png_flags_batch_kernel, dim3(static_cast<unsigned>(fu.size())), dim3(PNG_T), 0, ctx->stream, static_cast<const PngCbUnit *>(dp[2]), d_tab);
+    FNX_HIP(hipGetLastError());
+    FNX_TRY(prof_end(ctx));
+    *d_results = base;
+    return FNX_OK;
+}
+
+// The planes of the chunk's paletted (which[i] == 1: the index plane, from what launch_png_classify_batch left for the SAME
+// images) and gray (2: toGray's plane) images in one launch; which[i] == 0: none.  planes[i] / pstrides[i]: DEVICE planes.
+int launch_png_planes_batch(fnx_ctx *ctx, int m, const PngCbSrc *imgs, const int *which, uint8_t *const *planes, const int *pstrides)
+{
+    const CbWork k = cb_work(m, imgs);
+    uint8_t *base = static_cast<uint8_t *>(ctx->slot[SLOT_PNG_CB_WORK].p);
+    std::vector<PngPlaneArgs> tab(m);
+    std::vector<PngCbUnit> pu;
+    for (int i = 0; i < m; i++) {
+        const PngCbSrc &im = imgs[i];
+        PngPlaneArgs &t = tab[i];
+        std::memset(&t, 0, sizeof t);
+        if (!which[i]) continue;
+        const bool tight = im.sstride == 4 * im.w && pstrides[i] == im.w;
+        t.src = im.src; t.sstride = im.sstride; t.w = im.w;
+        t.walk = png_walk(im.src, im.sstride, im.w, im.h, tight);
+        t.gray = which[i] == 2 ? 1 : 0;
+        t.res = reinterpret_cast<const PngResult *>(base) + i;
+        t.map = reinterpret_cast<const unsigned long long *>(base + k.maps_off) + static_cast<size_t>(PNG_MAP_SLOTS) * i;
+        t.plane = planes[i]; t.pstride = pstrides[i];
+        const int G = png_cb_grid(im.w, im.h, tight);
+        for (int b = 0; b < G; b++) pu.push_back(PngCbUnit{static_cast<uint32_t>(i), static_cast<uint32_t>(b), static_cast<uint32_t>(G)});
+    }
+    if (pu.empty()) return FNX_OK;
+    const void *hosts[2] = {tab.data(), pu.data()};
+    const size_t sizes[2] = {sizeof(PngPlaneArgs) * tab.size(), sizeof(PngCbUnit) * pu.size()};
+    void *dp[2];
+    FNX_TRY(upload_tables(ctx, SLOT_PNG_CB_TAB1, hosts, sizes, 2, dp));
+    FNX_TRY(prof_begin(ctx));
+    hipLaunchKernelGGL(png_plane_batch_kernel, dim3(static_cast<unsigned>(pu.size())), dim3(PNG_T), 0, ctx->stream, static_cast<const PngCbUnit *>(dp[1]),
+                       static_cast<const PngPlaneArgs *>(dp[0]));
     FNX_HIP(hipGetLastError());
     FNX_TRY(prof_end(ctx));
     return FNX_OK;

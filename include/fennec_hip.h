@@ -789,6 +789,55 @@ int fnx_png_decode(fnx_ctx *ctx, const uint8_t *data, size_t n, int space, uint8
 int fnx_png_decode_batch(fnx_ctx *ctx, int n, const uint8_t *const *files, const size_t *sizes, uint8_t *const *dsts,
                          const int *dstrides, int workers, int *ws /* n */, int *hs /* n */, int *status /* n */);
 
+/* ---- compressPNG for a list of images or files in one call (compress.go:90-153 per item of batch.go:88-122) -------------- */
+/* The largest file fnx_png_encode, fnx_png_compress_batch and fnx_png_recompress_batch can return for a w x h image, whatever
+ * it holds: the signature, IHDR, IDAT's and IEND's twelve bytes each, and the larger of an RGBA stream's bound
+ * (fnx_deflate_bound(h * (4w + 1))) and a paletted image's layout -- a PLTE of 256 entries, a tRNS of 256 alphas,
+ * fnx_deflate_bound(h * (w + 1)).  Pure; no context.  Monotonic in w and in h; 0 for a dimension outside 1..65535. */
+size_t fnx_png_file_bound(int w, int h);
+/* compressPNG (compress.go:90-108) of n resident images in one call.  srcs[i]: DEVICE memory, NRGBA, 4-byte aligned, stride
+ * sstrides[i] >= 4 ws[i] and a multiple of 4, the flat Pix -- (h - 1) stride + 4w bytes -- readable; the images may differ in
+ * every respect (size, stride, content).  outs[i]: HOST memory of caps[i] bytes.  Item i's file is the one
+ * fnx_png_reduce(max_colors 256) followed by fnx_png_encode(kind, the image or its plane, ncolors, opaque = -1, palette)
+ * returns for the same image, BYTE FOR BYTE, and kinds[i] is that kind (FNX_PNG_PALETTED, FNX_PNG_GRAY or FNX_PNG_NRGBA);
+ * nbytes[i] its size.  Every stage is a function of the image alone -- the palette in first-occurrence order, the bit-exact row
+ * stage, a deflate whose bytes depend on (src, n, row) only --, so neither the batch, nor an image's place in it, nor the
+ * launch geometry shows in a file.
+ * Refused, that item alone, outs[i] untouched, status[i] = FNX_ERR_INVALID: srcs[i] NULL; outs[i] NULL with a cap that is not
+ * 0; ws[i] or hs[i] outside 1..65535; a stride below 4w or not a multiple of 4; a pointer that is not 4-byte aligned
+ * (nbytes[i] = kinds[i] = 0 for these); caps[i] below the file's size (nbytes[i] and kinds[i] set: call again;
+ * fnx_png_file_bound(w, h) always suffices).  fnx_last_error has the message of the lowest-indexed refused item.
+ * The list is cut into chunks of at most FNX_PNG_COMPRESS_CHUNK images and FNX_PNG_COMPRESS_CHUNK_BYTES of device scratch --
+ * counted for the worst case (RGBA rows: planes, streams, deflate's token words, slots, bounds: about 200 MB for a 4K image)
+ * from the DIMENSIONS alone, before anything is classified, so the cut never depends on content; an image that alone passes
+ * the byte cap is a chunk of its own.  Per chunk ONE set of launches with a workgroup per unit of any image --
+ * png_colors_batch_kernel, png_finish_batch_kernel (the colour sets, an "over" word per image), png_flags_batch_kernel
+ * (image.NRGBA.Opaque over the visible pixels; isGrayscale's flat walk, row padding included), png_plane_batch_kernel,
+ * png_filter_batch_kernel / png_pack_batch_kernel once per row form present, deflate_chunk_batch_kernel,
+ * deflate_gather_batch_kernel -- and THREE host waits whatever the number of images: the classification words, the streams'
+ * sizes, the streams' own bytes (back to back at their true sizes, one copy); one more where the ctx's pinned ring, which
+ * the fetches and the table uploads use, grows or wraps.  The chunks of the file and their CRCs are made
+ * on the host, as fnx_png_encode's.  Blocking.  Returns FNX_OK when the batch ran; an error for n outside 1..FNX_BATCH_MAX or a
+ * NULL array before anything is launched (and before the ctx is looked at).
+ * fnx_ctx_last_kernel(ctx, FNX_PROF_MAIN) names the batch kernels after a call that ran a chunk. */
+#define FNX_PNG_COMPRESS_CHUNK 32                       /* images per set of launches, at most */
+#define FNX_PNG_COMPRESS_CHUNK_BYTES ((size_t)1 << 30)  /* device scratch of a chunk, at most */
+int fnx_png_compress_batch(fnx_ctx *ctx, int n, const uint8_t *const *srcs /* DEVICE, NRGBA */, const int *sstrides, const int *ws,
+                           const int *hs, uint8_t *const *outs /* HOST */, const size_t *caps, size_t *nbytes /* n */, int *kinds /* n */,
+                           int *status /* n */);
+/* CompressBatch's item body (batch.go:88-122) for n files in host memory that end as PNG: loadImage (io.go:65-88) and
+ * compressPNG.  A file that opens with the eight PNG signature bytes is decoded by fnx_png_decode_batch's chunk path (`workers`
+ * as there), every other file by fnx_jpeg_decode_batch's -- the sniff fennec_CompressFilePNG makes --, into images that stay
+ * on the device; then the compress batch above.  Per item the file's bytes, kinds[i], ws[i] and hs[i] equal decoding files[i]
+ * with fnx_png_decode / fnx_jpeg_decode and compressing the image with fnx_png_reduce + fnx_png_encode.  status[i] is the
+ * decoder's answer for a file it refused (nbytes[i] = 0; Adam7 stays FNX_ERR_UNSUPPORTED), FNX_ERR_OOM for a file whose image
+ * alone the device has no room for, else as above.  Nothing depends on
+ * `workers` or on thread timing.  No options (orientation, resize): those are fennec_CompressFilePNG's.  Returns FNX_OK when
+ * the batch ran; an error for n outside 1..FNX_BATCH_MAX, a NULL array or workers outside 0..64 before anything else. */
+int fnx_png_recompress_batch(fnx_ctx *ctx, int n, const uint8_t *const *files /* HOST */, const size_t *sizes, int workers,
+                             uint8_t *const *outs /* HOST */, const size_t *caps, size_t *nbytes /* n */, int *kinds /* n */,
+                             int *ws /* n */, int *hs /* n */, int *status /* n */);
+
 /* ======================================================================= */
 /* fennec_* : the reference's function set (names and argument meaning as in
  * the Go source), mirrored above fnx_*.                                     */

@@ -4,12 +4,17 @@
 // The source and the destination are placed src_offset / dst_offset bytes behind a 16-byte boundary (the kernels take other
 // branches when they are not dword aligned); the destination is exactly as long as the stream's bound and is fenced by 64
 // sentinel bytes either side.
+// deflate_hostsim --batch ROW OUT IN1 IN2 ...: the batched kernels (launch_deflate_batch) over several inputs at once -- input
+// i is laid i % 4 bytes behind a 16-byte boundary of one source area, its units and stream record are made as the PNG compress
+// batch's planner makes them -- and stream i written to OUT.i.  The program checks that the streams lie back to back at their
+// true sizes and that nothing behind the last one was written.
 // Built by the Makefile beside it from a COPY of fennec_amd/csrc/deflate.hip against the stand-in common.hpp / devutil.hpp of
 // this directory; meant for sanitizer builds (-fsanitize=address,undefined) and for reading a stream without a GPU.
 #include "deflate_hip.inc"
 
 #include <cstdio>
 #include <cstring>
+#include <string>
 
 static int fail(const char *what)
 {
@@ -17,8 +22,66 @@ static int fail(const char *what)
     return 1;
 }
 
+static bool read_file(const char *name, std::vector<uint8_t> *out)
+{
+    FILE *f = fopen(name, "rb");
+    if (!f) return false;
+    uint8_t buf[65536];
+    for (size_t k; (k = fread(buf, 1, sizeof buf, f)) > 0;) out->insert(out->end(), buf, buf + k);
+    fclose(f);
+    return true;
+}
+
+static int batch(int argc, char **argv)
+{
+    if (argc < 5) return fail("usage: deflate_hostsim --batch ROW OUT IN1 [IN2 ...]");
+    const int row = atoi(argv[2]);
+    const int m = argc - 4;
+    std::vector<std::vector<uint8_t>> in(m);
+    std::vector<size_t> at(m);
+    size_t area = 0, bounds = 0;
+    for (int i = 0; i < m; i++) {
+        if (!read_file(argv[4 + i], &in[i]) || in[i].empty()) return fail("cannot read an input, or it is empty");
+        at[i] = ((area + 15) & ~size_t(15)) + static_cast<size_t>(i % 4);
+        area = at[i] + in[i].size();
+        bounds += fnx::deflate_bound(in[i].size());
+    }
+    uint8_t *src = static_cast<uint8_t *>(aligned_alloc(16, (area + 15) & ~size_t(15)));
+    if (!src) return fail("out of memory");
+    std::vector<fnx::DeflateBatchUnit> units;
+    std::vector<fnx::DeflateBatchImage> images(m);
+    for (int i = 0; i < m; i++) {
+        memcpy(src + at[i], in[i].data(), in[i].size());
+        const size_t n = in[i].size(), k = fnx::deflate_chunks(n);
+        images[i] = fnx::DeflateBatchImage{n, static_cast<uint32_t>(units.size()), static_cast<uint32_t>(k)};
+        for (size_t c = 0; c < k; c++) {
+            const size_t off = c * fnx::DF_C;
+            units.push_back(fnx::DeflateBatchUnit{src + at[i] + off, static_cast<uint32_t>(std::min<size_t>(fnx::DF_C, n - off)), fnx::deflate_row_hint(row),
+                                                  c + 1 == k ? 1u : 0u, static_cast<uint32_t>(i)});
+        }
+    }
+    fnx_ctx ctx{};
+    const uint8_t *out = nullptr;
+    const unsigned long long *sizes = nullptr;
+    if (fnx::launch_deflate_batch(&ctx, units.data(), images.data(), static_cast<uint32_t>(units.size()), static_cast<uint32_t>(m), bounds, &out, &sizes) != FNX_OK)
+        return fail("launch_deflate_batch failed");
+    size_t off = 0;
+    for (int i = 0; i < m; i++) {
+        const size_t nb = static_cast<size_t>(sizes[i]);
+        if (nb > fnx::deflate_bound(in[i].size()) || off + nb > bounds) return fail("a stream is longer than its bound");
+        const std::string name = std::string(argv[3]) + "." + std::to_string(i);
+        FILE *f = fopen(name.c_str(), "wb");
+        if (!f || fwrite(out + off, 1, nb, f) != nb || fclose(f) != 0) return fail("cannot write a stream");
+        off += nb;
+    }
+    for (void *p : ctx.slot) free(p);
+    free(src);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc > 1 && strcmp(argv[1], "--batch") == 0) return batch(argc, argv);
     if (argc < 3) return fail("usage: deflate_hostsim IN OUT [row [src_offset [dst_offset [TOKENS]]]]");
     const int row = argc > 3 ? atoi(argv[3]) : 0;
     const size_t soff = argc > 4 ? static_cast<size_t>(atoi(argv[4])) : 0, doff = argc > 5 ? static_cast<size_t>(atoi(argv[5])) : 0;
