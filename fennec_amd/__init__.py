@@ -156,6 +156,8 @@ def load_library() -> C.CDLL:
         _sig(L, "fnx_ctx_last_kernel", C.c_char_p, [ctx, i])
         _sig(L, "fnx_ctx_set_form", i, [ctx, C.c_char_p, C.c_char_p])
         _sig(L, "fnx_ctx_set_ssim_mode", i, [ctx, i])
+        _sig(L, "fnx_ctx_set_png_adam7", i, [ctx, i])
+        _sig(L, "fnx_png_adam7_passes", i, [i, i, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)])
         _sig(L, "fnx_malloc", i, [ctx, C.c_size_t, C.POINTER(C.c_void_p)])
         _sig(L, "fnx_free", i, [ctx, C.c_void_p])
         _sig(L, "fnx_upload", i, [ctx, C.c_void_p, i, C.c_void_p, i, i, i])
@@ -381,6 +383,7 @@ class Context:
         self._h = h
         self.device = int(device)
         self._lent = -1            # handle of the torch stream the ctx currently launches on (-1: its own stream)
+        self._png_adam7 = False    # set_png_adam7: what the wrappers' own header checks follow
 
     # -- plumbing ---------------------------------------------------------------------
     def _err(self) -> str:
@@ -430,6 +433,12 @@ class Context:
     def set_ssim_mode(self, fast: bool) -> None:
         """fnx_ctx_set_ssim_mode: fp32 moments (<= 1e-6) instead of fp64 (<= 1e-9) for full-resolution SSIM planes"""
         self._chk(self._lib.fnx_ctx_set_ssim_mode(self._h, 1 if fast else 0), "fnx_ctx_set_ssim_mode")
+
+    def set_png_adam7(self, accept: bool) -> None:
+        """fnx_ctx_set_png_adam7: the PNG entries of this ctx decode Adam7-interlaced files (True) instead of answering
+        FennecUnsupported for them (False, the default)"""
+        self._chk(self._lib.fnx_ctx_set_png_adam7(self._h, 1 if accept else 0), "fnx_ctx_set_png_adam7")
+        self._png_adam7 = bool(accept)
 
     def set_form(self, name: str, value=None) -> None:
         """fnx_ctx_set_form: which of several kernels that compute the same bytes this ctx takes (tests, A/B timing);
@@ -1638,7 +1647,7 @@ class Context:
         if space not in ("device", "host"):
             raise FennecError('space is "device" or "host"')
         w, h, _, _, interlace = png_info(data)             # IHDR alone: the call below walks the file, once
-        if interlace or w > 65535 or h > 65535:
+        if (interlace and not self._png_adam7) or w > 65535 or h > 65535:
             raise FennecUnsupported("fnx_png_decode: Adam7 interlace or a dimension above 65535 -- decode it on the host")
         buf = np.frombuffer(data, dtype=np.uint8)
         if out is not None:
@@ -1671,7 +1680,7 @@ class Context:
         for f in files:                                   # a file whose header does not parse goes in with no destination
             try:
                 w, h, _, _, interlace = png_info(f)
-                if interlace or w > 65535 or h > 65535:   # refused by the call; no memory is sized by such a header
+                if (interlace and not self._png_adam7) or w > 65535 or h > 65535:   # refused by the call; no memory is sized by such a header
                     dsts.append(None)
                 else:
                     dsts.append(torch.empty((h, w, 4), dtype=torch.uint8, device=f"cuda:{self.device}"))
@@ -2069,6 +2078,17 @@ def png_info(data: bytes):
     if rc < 0:
         raise FennecError(f"fnx_png_info failed ({rc}): {L.fnx_last_error().decode()}")
     return tuple(x.value for x in v)
+
+
+def png_adam7_passes(w: int, h: int, color_type: int, depth: int):
+    """Adam7's pass geometry (fnx_png_adam7_passes: host code) -> (pw[7], ph[7], rowbytes[7], stream_bytes); an absent pass
+    has zeros.  FennecError for a pair outside the 15 colour type / depth pairs or a dimension outside 1..65535."""
+    L = load_library()
+    pw, ph, rb, total = (C.c_int * 7)(), (C.c_int * 7)(), (C.c_size_t * 7)(), C.c_size_t()
+    rc = L.fnx_png_adam7_passes(int(w), int(h), int(color_type), int(depth), pw, ph, rb, C.byref(total))
+    if rc < 0:
+        raise FennecError(f"fnx_png_adam7_passes failed ({rc}): {L.fnx_last_error().decode()}")
+    return list(pw), list(ph), list(rb), total.value
 
 def png_reduce(img, max_colors=256, want_plane=True): return default_context(_dev_of(img)).png_reduce(img, max_colors, want_plane)
 def tryPalettize(img, max_colors=256): return default_context(_dev_of(img)).tryPalettize(img, max_colors)

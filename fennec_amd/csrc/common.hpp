@@ -238,6 +238,7 @@ struct fnx_ctx {
     // fnx_ctx_last_kernel: the kernel the last call of each class really launched (static strings), so that a report can
     // name the route the library took instead of inferring it from environment switches
     const char *route[8] = {"", "", "", "", "", "", "", ""};
+    int png_adam7 = 0;           // fnx_ctx_set_png_adam7: 1 -- the PNG entries decode Adam7-interlaced files instead of refusing them
     int ssim_mode = 0;           // fnx_ctx_set_ssim_mode: FNX_SSIM_EXACT (fp64 moments) / FNX_SSIM_FAST (fp32 moments for full-resolution planes)
     // fnx_ctx_set_form: the kernel forms this ctx was told to take ("" = the product's own choice)
     char form[fnx::FORM_COUNT][8] = {};
@@ -729,32 +730,49 @@ struct PngFile {
     uint8_t plte[768], trns[256];
     uint16_t trns16[3] = {0, 0, 0};   // the tRNS sample(s) of colour types 0 and 2
     std::vector<uint8_t> idat;   // the IDAT bodies back to back: one zlib stream
+    // an accepted Adam7 file (interlace == 1, fnx_ctx_set_png_adam7): the seven passes as images of their own -- pw x ph pixels,
+    // rows of 1 + prow bytes from poff of the inflated stream on; a pass without pixels has ph = 0 and no bytes
+    int pw[7] = {0, 0, 0, 0, 0, 0, 0}, ph[7] = {0, 0, 0, 0, 0, 0, 0};
+    size_t prow[7] = {0, 0, 0, 0, 0, 0, 0}, poff[7] = {0, 0, 0, 0, 0, 0, 0};
+    size_t pstream = 0;          // the passes' bytes together
 };
 int png_corrupt(const char *what);          // set_error + FNX_ERR_INVALID
 int png_unsupported(const char *what);      // set_error + FNX_ERR_UNSUPPORTED
 // the signature and IHDR alone (CRC checked): the dimensions, and FNX_ERR_UNSUPPORTED for what the device does not take -- the
 // file-level probe of host_api.cpp, which decodes next and so leaves the walk of the other chunks to that call
-int png_probe(const uint8_t *data, size_t n, PngFile *f);
-int png_parse(const uint8_t *data, size_t n, PngFile *f);
+// adam7: the ctx's fnx_ctx_set_png_adam7 -- an Adam7 file passes, its pass geometry filled in, instead of being unsupported
+int png_probe(const uint8_t *data, size_t n, PngFile *f, bool adam7 = false);
+int png_parse(const uint8_t *data, size_t n, PngFile *f, bool adam7 = false);
+// Adam7's pass geometry (the rule above fnx_png_decode): pass p holds the pixels (x0 + i dx, y0 + j dy); bits = channels * depth.
+// A pass with pw == 0 or ph == 0 is absent: all three of its values are 0.  Returns the sum of ph (1 + rowbytes)
+constexpr int ADAM7_X0[7] = {0, 4, 0, 2, 0, 1, 0}, ADAM7_Y0[7] = {0, 0, 4, 0, 2, 0, 1};
+constexpr int ADAM7_DX[7] = {8, 8, 4, 4, 2, 2, 1}, ADAM7_DY[7] = {8, 8, 8, 4, 4, 2, 2};
+size_t png_adam7_geometry(int w, int h, int bits, int pw[7], int ph[7], size_t rowbytes[7]);
 // the zlib stream src[0 .. n) into out[0 .. cap); *nbytes: the bytes written.  A stream with more than cap bytes is refused
 // with *nbytes = cap + 1
 int png_inflate(const uint8_t *src, size_t n, uint8_t *out, size_t cap, size_t *nbytes);
-// h * (1 + rowbytes), the size the inflated stream must have -- refused when the file's IDAT bytes cannot hold that much
+// h * (1 + rowbytes) -- an Adam7 file: the sum of that over its passes --, the size the inflated stream must have
+size_t png_stream_bytes(const PngFile &f);
+// the same, refused when the file's IDAT bytes cannot hold that much
 int png_stream_size(const PngFile &f, size_t *want);
 // png_unfilter_kernel's work: a workgroup keeps PNG_DEC_ROWS rows in flight, one per lane.  The chain-segment table (a row of
 // type None or Sub, and row 0, starts a segment; segments are independent) is cut into UNITS of whole segments, one workgroup
 // each: a unit ends at the first segment boundary at which it holds PNG_UNIT_MIN_ROWS rows, so a long chain is one unit however
 // long, and short segments share a workgroup instead of taking one each.  units: [first row, end row) pairs.  Refuses a
-// filter type above 4.
+// filter type above 4.  An Adam7 file's passes are planned one by one, each as an image of its own: a pass's row 0 starts a
+// segment, no unit spans two passes, the rows count from the pass's first, and passes (when asked for) gets each unit's pass.
 constexpr int PNG_DEC_ROWS = FNX_PNG_DECODE_ROWS;
 constexpr int PNG_UNIT_MIN_ROWS = 64;
-int png_row_plan(const uint8_t *stream, const PngFile &f, std::vector<uint32_t> *units);
+int png_row_plan(const uint8_t *stream, const PngFile &f, std::vector<uint32_t> *units, std::vector<uint8_t> *passes = nullptr);
 void png_palette_table(const PngFile &f, uint32_t table[256]);   // r | g << 8 | b << 16 | a << 24 of every index, toNRGBA applied
 struct PngExpand {                          // what png_expand_kernel needs of the file
     int w, h, color_type, depth, has_trns;
     uint32_t key[3];                        // the tRNS sample(s)
 };
 size_t png_plane_pitch(const PngFile &f);   // bytes between the reconstructed rows: rowbytes rounded up to 16
+// the reconstructed rows' bytes: h rows of png_plane_pitch -- an Adam7 file: a plane per present pass, ph rows of the pass's
+// row bytes rounded up to 16, back to back (so every plane starts on a 16-byte boundary)
+size_t png_planes_bytes(const PngFile &f);
 // fnx_png_decode_batch's host side: everything fnx_png_decode does to a file before its first launch, for m files on up to
 // `workers` threads (1: the calling thread alone, no thread started; more: the calling thread is one of them), handed out by
 // an atomic index.  No HIP call, no ctx.  In: stream / cap, where the file's inflated stream goes (the batch's pinned staging;
@@ -767,12 +785,13 @@ struct PngPrepared {
     PngFile f;
     size_t want = 0;                        // the stream's bytes
     std::vector<uint32_t> units;            // png_row_plan
+    std::vector<uint8_t> unit_pass;         // an Adam7 file: the pass each unit belongs to (empty otherwise)
     uint32_t table[256] = {};               // png_palette_table (colour type 3; zeros otherwise)
     int status = FNX_OK;
     const char *what = nullptr;
 };
 int png_workers(int workers, int m);        // the threads png_prepare_many runs m files on: 0 -> min(8, m), never above m
-void png_prepare_many(const uint8_t *const *files, const size_t *sizes, int m, int workers, PngPrepared *items);
+void png_prepare_many(const uint8_t *const *files, const size_t *sizes, int m, int workers, PngPrepared *items, bool adam7 = false);
 int png_reissue(const PngPrepared &it);     // the item's set_error again, on this thread; returns its status
 // a chunk of prepared files through one set of launches (png_decode.hip): per file what the two batched kernels read
 struct PngBatchFile {
@@ -790,10 +809,26 @@ struct PngBatchFile {
 struct PngBatchUnit {
     uint32_t file, r0, r1;                  // rows [r0, r1) of file `file` of the chunk
 };
+// an Adam7 file for png_expand_adam7_kernel (its argument) and png_expand_adam7_batch_kernel (a descriptor per file): the
+// passes' reconstructed planes; e.w x e.h is the whole image.  An absent pass is never asked for (no pixel maps to it)
+struct PngAdam7File {
+    const uint8_t *plane[7];
+    uint32_t ppitch[7];
+    PngExpand e;
+    const uint32_t *table;
+    uint8_t *dst;
+    int dstride;
+    uint32_t tile0;                         // the batch kernel: the file's first workgroup
+};
 // d_units: the chunk's units sorted by bpp, nunits[k] of them with bpp PNG_BPPS[k]; d_files: m descriptors; tiles: the sum of
 // the files' workgroups of the expand kernel
 constexpr int PNG_BPPS[6] = {1, 2, 3, 4, 6, 8};
-int launch_png_decode_chunk(fnx_ctx *ctx, const PngBatchUnit *d_units, const int nunits[6], const PngBatchFile *d_files, int m, uint32_t tiles);
+// d_files[0 .. m) are the non-interlaced files (the expand kernel's); the Adam7 files' pass descriptors lie behind them, for the
+// unfilter kernel alone.  d_adam7: ma descriptors and atiles workgroups of png_expand_adam7_batch_kernel (ma = 0: none)
+int launch_png_decode_chunk(fnx_ctx *ctx, const PngBatchUnit *d_units, const int nunits[6], const PngBatchFile *d_files, int m, uint32_t tiles,
+                            const PngAdam7File *d_adam7, int ma, uint32_t atiles);
+// one Adam7 file: all passes' units in one launch of png_unfilter_batch_kernel<bpp>, then png_expand_adam7_kernel
+int launch_png_adam7(fnx_ctx *ctx, int bpp, const PngBatchUnit *d_units, int nunits, const PngBatchFile *d_passes, const PngAdam7File &a);
 int launch_png_unfilter(fnx_ctx *ctx, const uint8_t *d_stream, const PngFile &f, const uint32_t *d_units, int nunits, uint8_t *d_rows);
 int launch_png_expand(fnx_ctx *ctx, const uint8_t *d_rows, const PngFile &f, const uint32_t *d_table, uint8_t *dst, int dstride);
 int launch_scan(fnx_ctx *ctx, const uint32_t *in, unsigned long long *out, unsigned long long *totals, int n, unsigned long long *grand);

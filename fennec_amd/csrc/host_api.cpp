@@ -426,7 +426,7 @@ static int decode_file(fnx_ctx *ctx, const uint8_t *data, size_t n, int space, u
     if (!is_png(data, n)) return fnx_jpeg_decode(ctx, data, n, space, dst, dstride, w, h);
     if (dst == nullptr) {                       // the dimension probe: IHDR alone -- the decode that follows walks every chunk, once
         PngFile f;
-        FNX_TRY(png_probe(data, n, &f));
+        FNX_TRY(png_probe(data, n, &f, ctx && ctx->png_adam7));
         *w = f.w; *h = f.h;
         return FNX_OK;
     }

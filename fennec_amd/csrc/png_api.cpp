@@ -1,7 +1,8 @@
 // The deflate entry points: fnx_deflate_bound, fnx_deflate (deflate.hip's two kernels behind the argument checks and the
 // staging of the three spaces) and fnx_png_encode (png_filter.hip's row stage, then the deflate, on the device; the file's
 // chunks and their CRCs on the host); and fnx_png_decode, the other direction: png_parse.cpp's host side (chunk walk, inflate,
-// the filter bytes), then png_decode.hip's two kernels; and fnx_png_decode_batch, which does the host side of a chunk of files
+// the filter bytes), then png_decode.hip's two kernels (an Adam7 file on a ctx that accepts it: a descriptor per pass, the batched
+// unfilter kernel once, png_expand_adam7_kernel); and fnx_png_decode_batch, which does the host side of a chunk of files
 // on several threads and sends the chunk through one set of launches; and fnx_png_compress_batch / fnx_png_recompress_batch,
 // compressPNG for a list of resident images (or of files) with one set of launches and three host waits per chunk.
 #include "common.hpp"
@@ -162,8 +163,7 @@ int png_decode_chunk(fnx_ctx *ctx, const std::vector<BatchEntry> &chunk, const s
     std::vector<const uint8_t *> cf(m);
     std::vector<size_t> cs(m);
     for (int j = 0; j < m; j++) {
-        const PngFile &h = heads[j];
-        const size_t want = static_cast<size_t>(h.h) * (1 + h.rowbytes);
+        const size_t want = png_stream_bytes(heads[j]);
         cf[j] = files[chunk[j].index];
         cs[j] = sizes[chunk[j].index];
         if (want / 1032 <= cs[j]) {                      // else png_stream_size refuses the file: it gets no room
@@ -171,13 +171,19 @@ int png_decode_chunk(fnx_ctx *ctx, const std::vector<BatchEntry> &chunk, const s
             items[j].cap = want;
         }
     }
-    png_prepare_many(cf.data(), cs.data(), m, workers, items.data());
+    png_prepare_many(cf.data(), cs.data(), m, workers, items.data(), ctx->png_adam7 != 0);
 
-    // verdicts in index order; the files that passed get a descriptor each, and their units are sorted by bpp
+    // verdicts in index order; the files that passed get a descriptor each -- an Adam7 file one per present pass, behind the
+    // non-interlaced files' (png_expand_batch_kernel searches descriptors [0, nplain) alone) --, and the units are sorted by bpp
     std::vector<PngBatchFile> desc;
+    std::vector<PngAdam7File> adesc;
     std::vector<int> ok;
     std::vector<PngBatchUnit> units[6];
     size_t npal = 0;
+    uint32_t nplain = 0, npass = 0, plain_seen = 0;
+    for (int j = 0; j < m; j++) {
+        if (items[j].status == FNX_OK && items[j].f.interlace != 1) nplain++;
+    }
     for (int j = 0; j < m; j++) {
         const int i = chunk[j].index;
         status[i] = items[j].status;
@@ -188,8 +194,17 @@ int png_decode_chunk(fnx_ctx *ctx, const std::vector<BatchEntry> &chunk, const s
         }
         int k = 0;
         while (k < 5 && PNG_BPPS[k] != items[j].f.bpp) k++;
-        for (size_t u = 0; u + 1 < items[j].units.size(); u += 2)
-            units[k].push_back(PngBatchUnit{static_cast<uint32_t>(ok.size()), items[j].units[u], items[j].units[u + 1]});
+        if (items[j].f.interlace == 1) {
+            // the passes' descriptors follow in pass order (below): slot[p] is pass p's
+            uint32_t slot[7];
+            for (int p = 0; p < 7; p++) slot[p] = items[j].f.ph[p] ? nplain + npass++ : 0;
+            for (size_t u = 0; u + 1 < items[j].units.size(); u += 2)
+                units[k].push_back(PngBatchUnit{slot[items[j].unit_pass[u / 2]], items[j].units[u], items[j].units[u + 1]});
+        } else {
+            for (size_t u = 0; u + 1 < items[j].units.size(); u += 2)
+                units[k].push_back(PngBatchUnit{plain_seen, items[j].units[u], items[j].units[u + 1]});
+            plain_seen++;
+        }
         if (items[j].f.color_type == 3) npal++;
         ok.push_back(j);
     }
@@ -211,24 +226,21 @@ int png_decode_chunk(fnx_ctx *ctx, const std::vector<BatchEntry> &chunk, const s
         sorted.insert(sorted.end(), units[k].begin(), units[k].end());
     }
     std::vector<uint32_t> pals(256 * (npal ? npal : 1), 0);
-    const size_t tsizes[3] = {sizeof(PngBatchUnit) * sorted.size(), sizeof(PngBatchFile) * ok.size(), sizeof(uint32_t) * pals.size()};
+    const size_t na = ok.size() - nplain;
+    const size_t tsizes[4] = {sizeof(PngBatchUnit) * sorted.size(), sizeof(PngBatchFile) * (nplain + npass), sizeof(uint32_t) * pals.size(),
+                              sizeof(PngAdam7File) * na};
     void *tab = nullptr;
-    FNX_TRY(scratch(ctx, SLOT_PNG_DEC_TAB, align16(tsizes[0]) + align16(tsizes[1]) + align16(tsizes[2]), &tab));
+    FNX_TRY(scratch(ctx, SLOT_PNG_DEC_TAB, align16(tsizes[0]) + align16(tsizes[1]) + align16(tsizes[2]) + align16(tsizes[3]), &tab));
     const uint32_t *d_pals = reinterpret_cast<const uint32_t *>(static_cast<uint8_t *>(tab) + align16(tsizes[0]) + align16(tsizes[1]));
-    unsigned long long tiles = 0;
+    unsigned long long tiles = 0, atiles = 0;
     size_t pal = 0;
-    desc.reserve(ok.size());
+    desc.assign(nplain + npass, PngBatchFile());
+    size_t plain_at = 0, pass_at = nplain;
     for (int j : ok) {
         const PngFile &f = items[j].f;
         const int i = chunk[j].index;
         PngBatchFile d;
         std::memset(&d, 0, sizeof d);
-        d.stream = static_cast<const uint8_t *>(ds) + chunk[j].stream_off;
-        d.spitch = 1 + f.rowbytes;
-        d.rows = static_cast<uint8_t *>(dr) + chunk[j].rows_off;
-        d.ppitch = png_plane_pitch(f);
-        d.rowbytes = static_cast<int>(f.rowbytes);
-        d.npix = static_cast<int>(f.rowbytes / f.bpp);
         d.e.w = f.w; d.e.h = f.h; d.e.color_type = f.color_type; d.e.depth = f.depth;
         d.e.has_trns = f.has_trns ? 1 : 0;
         for (int k = 0; k < 3; k++) d.e.key[k] = f.trns16[k];
@@ -239,23 +251,61 @@ int png_decode_chunk(fnx_ctx *ctx, const std::vector<BatchEntry> &chunk, const s
         }
         d.dst = dsts[i];
         d.dstride = dstrides[i];
+        const uint8_t *stream = static_cast<const uint8_t *>(ds) + chunk[j].stream_off;
+        uint8_t *rows = static_cast<uint8_t *>(dr) + chunk[j].rows_off;
+        if (f.interlace == 1) {
+            PngAdam7File a;
+            std::memset(&a, 0, sizeof a);
+            a.e = d.e; a.table = d.table; a.dst = d.dst; a.dstride = d.dstride;
+            a.tile0 = static_cast<uint32_t>(atiles);
+            atiles += static_cast<unsigned long long>((f.w + 255) / 256) * f.h;
+            for (int p = 0; p < 7; p++) {
+                if (f.ph[p] == 0) continue;
+                PngBatchFile dp = d;                      // the unfilter kernel's view of the pass: an image of its own
+                dp.stream = stream + f.poff[p];
+                dp.spitch = 1 + f.prow[p];
+                dp.rows = rows;
+                dp.ppitch = align16(f.prow[p]);
+                dp.rowbytes = static_cast<int>(f.prow[p]);
+                dp.npix = static_cast<int>(f.prow[p] / f.bpp);
+                dp.e.w = f.pw[p]; dp.e.h = f.ph[p];
+                dp.dst = nullptr;
+                desc[pass_at++] = dp;
+                a.plane[p] = rows;
+                a.ppitch[p] = static_cast<uint32_t>(dp.ppitch);
+                rows += dp.ppitch * f.ph[p];
+            }
+            adesc.push_back(a);
+            continue;
+        }
+        d.stream = stream;
+        d.spitch = 1 + f.rowbytes;
+        d.rows = rows;
+        d.ppitch = png_plane_pitch(f);
+        d.rowbytes = static_cast<int>(f.rowbytes);
+        d.npix = static_cast<int>(f.rowbytes / f.bpp);
         d.tile0 = static_cast<uint32_t>(tiles);
         tiles += static_cast<unsigned long long>((f.w + 255) / 256) * f.h;
-        desc.push_back(d);
+        desc[plain_at++] = d;
     }
-    if (tiles > 0x7fffffffull) {
-        set_error("internal: a chunk of %llu workgroups of png_expand_batch_kernel", tiles);
+    if (tiles > 0x7fffffffull || atiles > 0x7fffffffull) {
+        set_error("internal: a chunk of %llu workgroups of png_expand_batch_kernel", tiles > atiles ? tiles : atiles);
         return FNX_ERR_INVALID;
     }
-    const void *hosts[3] = {sorted.data(), desc.data(), pals.data()};
-    void *dp[3];
-    FNX_TRY(upload_tables(ctx, SLOT_PNG_DEC_TAB, hosts, tsizes, 3, dp));
+    if (plain_at != nplain || pass_at != nplain + npass || adesc.size() != na) {
+        set_error("internal: the chunk's descriptors do not add up");
+        return FNX_ERR_INVALID;
+    }
+    const void *hosts[4] = {sorted.data(), desc.data(), pals.data(), adesc.data()};
+    void *dp[4];
+    FNX_TRY(upload_tables(ctx, SLOT_PNG_DEC_TAB, hosts, tsizes, na ? 4 : 3, dp));
     if (dp[2] != static_cast<const void *>(d_pals)) {
         set_error("internal: the table slot moved between two requests of one size");
         return FNX_ERR_INVALID;
     }
     return launch_png_decode_chunk(ctx, static_cast<const PngBatchUnit *>(dp[0]), nunits, static_cast<const PngBatchFile *>(dp[1]),
-                                   static_cast<int>(ok.size()), static_cast<uint32_t>(tiles));
+                                   static_cast<int>(nplain), static_cast<uint32_t>(tiles), na ? static_cast<const PngAdam7File *>(dp[3]) : nullptr,
+                                   static_cast<int>(na), static_cast<uint32_t>(atiles));
 }
 
 int png_decode_batch_device(fnx_ctx *ctx, int n, const uint8_t *const *files, const size_t *sizes, uint8_t *const *dsts, const int *dstrides,
@@ -390,12 +440,12 @@ int fnx_png_decode(fnx_ctx *ctx, const uint8_t *data, size_t n, int space, uint8
     FNX_REQUIRE(space == FNX_HOST || space == FNX_DEVICE, "space: FNX_HOST or FNX_DEVICE (also where only the dimensions are asked for)");
     PngFile f;
     if (dst == nullptr) {                        // png.DecodeConfig: the dimensions only (and whether the device takes the file);
-        FNX_TRY(png_parse(data, n, &f));         // host work, no ctx needed
+        FNX_TRY(png_parse(data, n, &f, ctx && ctx->png_adam7));   // host work, no ctx needed (with one: its fnx_ctx_set_png_adam7)
         *w = f.w; *h = f.h;
         return FNX_OK;
     }
     FNX_ENTER(ctx);
-    FNX_TRY(png_parse(data, n, &f));
+    FNX_TRY(png_parse(data, n, &f, ctx->png_adam7 != 0));
     *w = f.w; *h = f.h;
     FNX_TRY(check_img(dst, dstride, f.w, f.h, "dst"));
     FNX_REQUIRE(space != FNX_DEVICE || (reinterpret_cast<uintptr_t>(dst) & 3u) == 0, "a device image is 4-byte aligned");
@@ -409,16 +459,56 @@ int fnx_png_decode(fnx_ctx *ctx, const uint8_t *data, size_t n, int space, uint8
     FNX_TRY(png_inflate(f.idat.data(), f.idat.size(), stream, want, &got));
     if (got != want) return png_corrupt("not enough pixel data");
     std::vector<uint32_t> units;
-    FNX_TRY(png_row_plan(stream, f, &units));    // a filter type above 4 is refused here: nothing has been launched
+    std::vector<uint8_t> unit_pass;
+    FNX_TRY(png_row_plan(stream, f, &units, &unit_pass));    // a filter type above 4 is refused here: nothing has been launched
     DevOut d;
     FNX_TRY(stage_out(ctx, space, dst, dstride, f.w, f.h, SLOT_OUT, &d));
     void *ds = nullptr, *dr = nullptr;
     FNX_TRY(scratch(ctx, SLOT_PNG_DEC_STREAM, want + 64, &ds));            // the kernel's 16-byte loads reach up to 15 bytes past a row
-    FNX_TRY(scratch(ctx, SLOT_PNG_DEC_ROWS, png_plane_pitch(f) * f.h + 16, &dr));
+    FNX_TRY(scratch(ctx, SLOT_PNG_DEC_ROWS, png_planes_bytes(f) + 16, &dr));
     FNX_HIP(hipMemcpyAsync(ds, stream, want, hipMemcpyHostToDevice, ctx->stream));
     uint32_t table[256];
     std::memset(table, 0, sizeof table);
     if (f.color_type == 3) png_palette_table(f, table);
+    if (f.interlace == 1) {
+        // the passes as a list of images of one bpp: a descriptor per present pass, every pass's units in one launch.  A pass's
+        // 16-byte loads past a row's end read the next pass's bytes; the slot's 64 spare bytes stand behind the last one
+        PngBatchFile passes[7];
+        PngAdam7File a;
+        std::memset(passes, 0, sizeof passes);
+        std::memset(&a, 0, sizeof a);
+        a.e.w = f.w; a.e.h = f.h; a.e.color_type = f.color_type; a.e.depth = f.depth;
+        a.e.has_trns = f.has_trns ? 1 : 0;
+        for (int k = 0; k < 3; k++) a.e.key[k] = f.trns16[k];
+        a.dst = d.p;
+        a.dstride = d.stride;
+        uint32_t slot[7] = {0, 0, 0, 0, 0, 0, 0}, npass = 0;
+        uint8_t *rows = static_cast<uint8_t *>(dr);
+        for (int p = 0; p < 7; p++) {
+            if (f.ph[p] == 0) continue;
+            PngBatchFile &dp = passes[npass];
+            dp.stream = static_cast<const uint8_t *>(ds) + f.poff[p];
+            dp.spitch = 1 + f.prow[p];
+            dp.rows = rows;
+            dp.ppitch = align16(f.prow[p]);
+            dp.rowbytes = static_cast<int>(f.prow[p]);
+            dp.npix = static_cast<int>(f.prow[p] / f.bpp);
+            a.plane[p] = rows;
+            a.ppitch[p] = static_cast<uint32_t>(dp.ppitch);
+            rows += dp.ppitch * f.ph[p];
+            slot[p] = npass++;
+        }
+        std::vector<PngBatchUnit> bu;
+        for (size_t u = 0; u + 1 < units.size(); u += 2) bu.push_back(PngBatchUnit{slot[unit_pass[u / 2]], units[u], units[u + 1]});
+        const void *hosts[3] = {bu.data(), passes, table};
+        const size_t sizes[3] = {sizeof(PngBatchUnit) * bu.size(), sizeof(PngBatchFile) * npass, sizeof table};
+        void *dp[3];
+        FNX_TRY(upload_tables(ctx, SLOT_PNG_DEC_TAB, hosts, sizes, 3, dp));
+        a.table = static_cast<const uint32_t *>(dp[2]);
+        FNX_TRY(launch_png_adam7(ctx, f.bpp, static_cast<const PngBatchUnit *>(dp[0]), static_cast<int>(bu.size()),
+                                 static_cast<const PngBatchFile *>(dp[1]), a));
+        return finish(ctx, space, &d);
+    }
     const void *hosts[2] = {units.data(), table};
     const size_t sizes[2] = {sizeof(uint32_t) * units.size(), sizeof table};
     void *dp[2];
@@ -473,7 +563,7 @@ int png_decode_batch_device(fnx_ctx *ctx, int n, const uint8_t *const *files, co
         // the signature and IHDR on this thread: the dimensions, what the device does not take, and the item's own arguments --
         // the order of fnx_png_decode's refusals.  The rest of the file is the workers' business
         PngFile head;
-        const int rc = png_probe(files[i], sizes[i], &head);
+        const int rc = png_probe(files[i], sizes[i], &head, ctx->png_adam7 != 0);
         if (rc == FNX_OK || rc == FNX_ERR_UNSUPPORTED) { ws[i] = head.w; hs[i] = head.h; }
         if (rc < 0) {
             status[i] = rc;
@@ -494,9 +584,9 @@ int png_decode_batch_device(fnx_ctx *ctx, int n, const uint8_t *const *files, co
             first.note(i);
             continue;
         }
-        const size_t want = static_cast<size_t>(head.h) * (1 + head.rowbytes);
+        const size_t want = png_stream_bytes(head);
         const bool room = want / 1032 <= sizes[i];       // else the file cannot hold its rows: refused before its inflate, no room needed
-        const size_t sbytes = room ? align16(want + 64) : 0, rbytes = room ? align16(png_plane_pitch(head) * head.h + 16) : 0;
+        const size_t sbytes = room ? align16(want + 64) : 0, rbytes = room ? align16(png_planes_bytes(head) + 16) : 0;
         if (!chunk.empty() && (static_cast<int>(chunk.size()) >= FNX_PNG_DECODE_CHUNK || stage_bytes + rows_bytes + sbytes + rbytes > PNG_BATCH_SCRATCH)) {
             const int frc = flush();
             if (frc < 0) return frc;
@@ -744,7 +834,7 @@ int fnx_png_recompress_batch(fnx_ctx *ctx, int n, const uint8_t *const *files, c
             const bool isp = files[s1] && is_png_file(files[s1], sizes[s1]);
             if (isp) {
                 PngFile head;
-                if (png_probe(files[s1], sizes[s1], &head) == FNX_OK) { w = head.w; h = head.h; }
+                if (png_probe(files[s1], sizes[s1], &head, ctx->png_adam7 != 0) == FNX_OK) { w = head.w; h = head.h; }
             } else if (files[s1]) {
                 JpegFile f;
                 if (jpeg_parse(files[s1], sizes[s1], &f) >= 0) { w = f.w; h = f.h; }

@@ -2,7 +2,9 @@
 // filtered row) -> the reconstructed rows (png_unfilter_kernel) -> image.Decode's pixels through toNRGBA (png_expand_kernel).
 // The rule both kernels follow is restated above fnx_png_decode in include/fennec_hip.h.  fnx_png_decode_batch runs the same
 // two bodies over a chunk of files at once: png_unfilter_batch_kernel, png_expand_batch_kernel (per-file descriptors in device
-// memory instead of kernel arguments; one workgroup per unit of any file, 256 pixels of a row of any file).
+// memory instead of kernel arguments; one workgroup per unit of any file, 256 pixels of a row of any file).  An Adam7 file
+// (fnx_ctx_set_png_adam7) is seven small images to png_unfilter_batch_kernel -- a descriptor per present pass, every pass's
+// units in one launch -- and png_expand_adam7_kernel gathers the passes' pixels into the image (below).
 //
 // png_unfilter_kernel.  Average and Paeth need the pixel to the left and the row above, so a chain of dependent rows is
 // walked as a skewed wavefront: a lane owns a row and trails the lane that owns the row above by one pixel (one step), so at
@@ -351,6 +353,77 @@ __global__ __launch_bounds__(256) void png_expand_batch_kernel(const PngBatchFil
     *reinterpret_cast<uint32_t *>(f.dst + static_cast<size_t>(y) * f.dstride + 4 * static_cast<size_t>(x)) = out;
 }
 
+// ---- Adam7: the passes' planes -> the image ----------------------------------------------------------------------------------
+// The gather form: a thread per OUTPUT pixel, a workgroup 256 pixels of one output row, so every lane's store is the 4 bytes
+// next to its neighbour's.  (x & 7, y & 7) names the pass in Adam7's 8 x 8 map; the row y is the workgroup's, so which passes
+// a row draws from is uniform: an odd row reads pass 7 alone, rows 2 and 6 of the eight passes 5 and 6, row 4 passes 3, 4 and
+// 6, row 0 passes 1, 2, 4 and 6.  Pass p starts at (x0, y0) < (dx, dy) and dx, dy are powers of two, so the pixel's place in
+// its pass is (x >> log2 dx, y >> log2 dy).  The seven plane pointers and pitches are kernel arguments (the batch form: a
+// descriptor indexed by blockIdx.x alone), scalar registers the lane's own pair is SELECTED from -- an indexed read would make
+// them a per-lane load.  The reads of one pass are a lane in 2, 4 or 8 apart over densely packed pass rows: neighbouring lanes of
+// the same pass read neighbouring pass pixels.
+__device__ __forceinline__ uint32_t adam7_pixel(const PngAdam7File &f, const int x, const uint32_t y)
+{
+    const uint32_t yc = y & 7u;
+    int p;                                               // 0-based pass
+    if (yc & 1u) p = 6;
+    else if (yc & 2u) p = (x & 1) ? 5 : 4;
+    else if (yc & 4u) p = (x & 1) ? 5 : ((x & 2) ? 3 : 2);
+    else p = (x & 1) ? 5 : ((x & 2) ? 3 : ((x & 4) ? 1 : 0));
+    const int xs = 3 - (p >> 1);                         // log2 dx: 3 3 2 2 1 1 0
+    const int ys = 3 - ((p > 0 ? p - 1 : 0) >> 1);       // log2 dy: 3 3 3 2 2 1 1
+    const uint8_t *plane = f.plane[0];
+    uint32_t pitch = f.ppitch[0];
+#pragma unroll
+    for (int k = 1; k < 7; k++) {
+        plane = p == k ? f.plane[k] : plane;
+        pitch = p == k ? f.ppitch[k] : pitch;
+    }
+    return expand_pixel(f.e, f.table, plane + static_cast<size_t>(y >> ys) * pitch, x >> xs);
+}
+
+__global__ __launch_bounds__(256) void png_expand_adam7_kernel(PngAdam7File A)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t y = blockIdx.y;
+    if (x >= A.e.w) return;
+    *reinterpret_cast<uint32_t *>(A.dst + static_cast<size_t>(y) * A.dstride + 4 * static_cast<size_t>(x)) = adam7_pixel(A, x, y);
+}
+
+// the Adam7 files of a chunk in one launch: png_expand_batch_kernel's tiling and search over descriptors of their own
+__global__ __launch_bounds__(256) void png_expand_adam7_batch_kernel(const PngAdam7File *__restrict__ files, const int m)
+{
+    int lo = 0, hi = m - 1;                              // the last file whose tile0 <= blockIdx.x
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (files[mid].tile0 <= blockIdx.x) lo = mid;
+        else hi = mid - 1;
+    }
+    const PngAdam7File &f = files[lo];
+    const uint32_t tile = blockIdx.x - f.tile0, tiles_x = (static_cast<uint32_t>(f.e.w) + 255u) / 256u;
+    const uint32_t y = tile / tiles_x;
+    const int x = static_cast<int>((tile - y * tiles_x) * 256u + threadIdx.x);
+    if (x >= f.e.w || y >= static_cast<uint32_t>(f.e.h)) return;
+    *reinterpret_cast<uint32_t *>(f.dst + static_cast<size_t>(y) * f.dstride + 4 * static_cast<size_t>(x)) = adam7_pixel(f, x, y);
+}
+
+int launch_unfilter_batch(fnx_ctx *ctx, int bpp, const PngBatchUnit *u, int nunits, const PngBatchFile *d_files)
+{
+    const dim3 grid(nunits), block(UF_T);
+    FNX_TRY(prof_begin(ctx));
+    switch (bpp) {
+    case 1: hipLaunchKernelGGL(png_unfilter_batch_kernel<1>, grid, block, 0, ctx->stream, u, d_files); break;
+    case 2: hipLaunchKernelGGL(png_unfilter_batch_kernel<2>, grid, block, 0, ctx->stream, u, d_files); break;
+    case 3: hipLaunchKernelGGL(png_unfilter_batch_kernel<3>, grid, block, 0, ctx->stream, u, d_files); break;
+    case 4: hipLaunchKernelGGL(png_unfilter_batch_kernel<4>, grid, block, 0, ctx->stream, u, d_files); break;
+    case 6: hipLaunchKernelGGL(png_unfilter_batch_kernel<6>, grid, block, 0, ctx->stream, u, d_files); break;
+    case 8: hipLaunchKernelGGL(png_unfilter_batch_kernel<8>, grid, block, 0, ctx->stream, u, d_files); break;
+    default: set_error("internal: png_unfilter_batch_kernel has no form for bpp %d", bpp); return FNX_ERR_INVALID;
+    }
+    FNX_HIP(hipGetLastError());
+    return prof_end(ctx);
+}
+
 }  // namespace
 
 size_t png_plane_pitch(const PngFile &f) { return (f.rowbytes + 15) & ~size_t(15); }
@@ -398,29 +471,38 @@ int launch_png_expand(fnx_ctx *ctx, const uint8_t *d_rows, const PngFile &f, con
     return prof_end(ctx);
 }
 
-int launch_png_decode_chunk(fnx_ctx *ctx, const PngBatchUnit *d_units, const int nunits[6], const PngBatchFile *d_files, int m, uint32_t tiles)
+int launch_png_decode_chunk(fnx_ctx *ctx, const PngBatchUnit *d_units, const int nunits[6], const PngBatchFile *d_files, int m, uint32_t tiles,
+                            const PngAdam7File *d_adam7, int ma, uint32_t atiles)
 {
-    note_route(ctx, FNX_PROF_MAIN, "png_unfilter_batch_kernel, png_expand_batch_kernel");
-    const dim3 block(UF_T);
+    note_route(ctx, FNX_PROF_MAIN, ma ? "png_unfilter_batch_kernel, png_expand_batch_kernel, png_expand_adam7_batch_kernel"
+                                      : "png_unfilter_batch_kernel, png_expand_batch_kernel");
     const PngBatchUnit *u = d_units;
     for (int k = 0; k < 6; k++) {
         if (nunits[k] == 0) continue;
-        const dim3 grid(nunits[k]);
-        FNX_TRY(prof_begin(ctx));
-        switch (PNG_BPPS[k]) {
-        case 1: hipLaunchKernelGGL(png_unfilter_batch_kernel<1>, grid, block, 0, ctx->stream, u, d_files); break;
-        case 2: hipLaunchKernelGGL(png_unfilter_batch_kernel<2>, grid, block, 0, ctx->stream, u, d_files); break;
-        case 3: hipLaunchKernelGGL(png_unfilter_batch_kernel<3>, grid, block, 0, ctx->stream, u, d_files); break;
-        case 4: hipLaunchKernelGGL(png_unfilter_batch_kernel<4>, grid, block, 0, ctx->stream, u, d_files); break;
-        case 6: hipLaunchKernelGGL(png_unfilter_batch_kernel<6>, grid, block, 0, ctx->stream, u, d_files); break;
-        default: hipLaunchKernelGGL(png_unfilter_batch_kernel<8>, grid, block, 0, ctx->stream, u, d_files); break;
-        }
-        FNX_HIP(hipGetLastError());
-        FNX_TRY(prof_end(ctx));
+        FNX_TRY(launch_unfilter_batch(ctx, PNG_BPPS[k], u, nunits[k], d_files));
         u += nunits[k];
     }
+    if (m > 0) {                                         // (a chunk of Adam7 files alone has no workgroup for this kernel)
+        FNX_TRY(prof_begin(ctx));
+        hipLaunchKernelGGL(png_expand_batch_kernel, dim3(tiles), dim3(256), 0, ctx->stream, d_files, m);
+        FNX_HIP(hipGetLastError());
+        FNX_TRY(prof_end(ctx));
+    }
+    if (ma > 0) {
+        FNX_TRY(prof_begin(ctx));
+        hipLaunchKernelGGL(png_expand_adam7_batch_kernel, dim3(atiles), dim3(256), 0, ctx->stream, d_adam7, ma);
+        FNX_HIP(hipGetLastError());
+        FNX_TRY(prof_end(ctx));
+    }
+    return FNX_OK;
+}
+
+int launch_png_adam7(fnx_ctx *ctx, int bpp, const PngBatchUnit *d_units, int nunits, const PngBatchFile *d_passes, const PngAdam7File &a)
+{
+    note_route(ctx, FNX_PROF_MAIN, "png_unfilter_batch_kernel, png_expand_adam7_kernel");
+    FNX_TRY(launch_unfilter_batch(ctx, bpp, d_units, nunits, d_passes));
     FNX_TRY(prof_begin(ctx));
-    hipLaunchKernelGGL(png_expand_batch_kernel, dim3(tiles), dim3(256), 0, ctx->stream, d_files, m);
+    hipLaunchKernelGGL(png_expand_adam7_kernel, dim3((a.e.w + 255) / 256, a.e.h), dim3(256), 0, ctx->stream, a);
     FNX_HIP(hipGetLastError());
     return prof_end(ctx);
 }

@@ -3,6 +3,8 @@
 //   png_parse        the chunk walk (signature, CRCs, IHDR / PLTE / tRNS / IDAT / IEND and their order)
 //   png_inflate      RFC 1950 / 1951 inflate (the library links no zlib)
 //   png_row_plan     the h filter-type bytes of the inflated stream -> the work units of png_unfilter_kernel
+//   png_adam7_geometry  the seven passes of an Adam7 file (accepted where the ctx says so: fnx_ctx_set_png_adam7) as images of
+//                    their own; png_probe fills PngFile's pass table from it, png_stream_size and png_row_plan go pass by pass
 //   png_palette_table  a colour-type-3 file's 256 pixel values, toNRGBA already applied
 //   png_prepare_many those four for a list of files on several threads (fnx_png_decode_batch; tools/png_batch_host.cpp runs it
 //                    under the address and the thread sanitizer)
@@ -109,17 +111,40 @@ int read_ihdr(const uint8_t *data, size_t n, PngFile *f)
 
 }  // namespace
 
-int png_probe(const uint8_t *data, size_t n, PngFile *f)
+size_t png_adam7_geometry(int w, int h, int bits, int pw[7], int ph[7], size_t rowbytes[7])
+{
+    size_t total = 0;
+    for (int p = 0; p < 7; p++) {
+        const int cw = w > ADAM7_X0[p] ? (w - ADAM7_X0[p] + ADAM7_DX[p] - 1) / ADAM7_DX[p] : 0;
+        const int ch = h > ADAM7_Y0[p] ? (h - ADAM7_Y0[p] + ADAM7_DY[p] - 1) / ADAM7_DY[p] : 0;
+        const bool present = cw > 0 && ch > 0;
+        pw[p] = present ? cw : 0;
+        ph[p] = present ? ch : 0;
+        rowbytes[p] = present ? (static_cast<size_t>(cw) * bits + 7) / 8 : 0;
+        total += static_cast<size_t>(ph[p]) * (1 + rowbytes[p]);
+    }
+    return total;
+}
+
+int png_probe(const uint8_t *data, size_t n, PngFile *f, bool adam7)
 {
     FNX_TRY(read_ihdr(data, n, f));
-    if (f->interlace == 1) return png_unsupported("Adam7 interlace");
+    if (f->interlace == 1 && !adam7) return png_unsupported("Adam7 interlace");
     if (f->w > 65535 || f->h > 65535) return png_unsupported("a dimension above 65535");
+    if (f->interlace == 1) {
+        f->pstream = png_adam7_geometry(f->w, f->h, f->channels * f->depth, f->pw, f->ph, f->prow);
+        size_t off = 0;
+        for (int p = 0; p < 7; p++) {
+            f->poff[p] = off;
+            off += static_cast<size_t>(f->ph[p]) * (1 + f->prow[p]);
+        }
+    }
     return FNX_OK;
 }
 
-int png_parse(const uint8_t *data, size_t n, PngFile *f)
+int png_parse(const uint8_t *data, size_t n, PngFile *f, bool adam7)
 {
-    FNX_TRY(png_probe(data, n, f));
+    FNX_TRY(png_probe(data, n, f, adam7));
     f->npal = f->ntrns = 0;
     f->has_trns = false;
     f->idat.clear();
@@ -461,21 +486,32 @@ int png_inflate(const uint8_t *src, size_t n, uint8_t *out, size_t cap, size_t *
     return FNX_OK;
 }
 
+size_t png_stream_bytes(const PngFile &f) { return f.interlace == 1 ? f.pstream : static_cast<size_t>(f.h) * (1 + f.rowbytes); }
+
+size_t png_planes_bytes(const PngFile &f)
+{
+    if (f.interlace != 1) return ((f.rowbytes + 15) & ~size_t(15)) * f.h;
+    size_t total = 0;
+    for (int p = 0; p < 7; p++) total += ((f.prow[p] + 15) & ~size_t(15)) * f.ph[p];
+    return total;
+}
+
 int png_stream_size(const PngFile &f, size_t *want)
 {
-    *want = static_cast<size_t>(f.h) * (1 + f.rowbytes);
+    *want = png_stream_bytes(f);
     // a deflate stream grows at most 1032-fold (258 bytes from a one-bit length code and a one-bit distance code): a header
     // that promises more than its IDAT bytes can hold is refused before a byte of memory is sized by it
     if (*want / 1032 > f.idat.size()) return png_corrupt("not enough pixel data");
     return FNX_OK;
 }
 
-int png_row_plan(const uint8_t *stream, const PngFile &f, std::vector<uint32_t> *units)
+namespace {
+
+// the units of one image of h rows, `pitch` bytes apart, appended
+int plan_rows(const uint8_t *stream, size_t pitch, int h, std::vector<uint32_t> *units)
 {
-    const size_t pitch = 1 + f.rowbytes;
-    units->clear();
     uint32_t start = 0;
-    for (int y = 0; y < f.h; y++) {
+    for (int y = 0; y < h; y++) {
         const uint8_t t = stream[static_cast<size_t>(y) * pitch];
         if (t > 4) return png_corrupt("a filter type above 4");
         // a None or Sub row does not read the row above: a chain segment starts here, and with it -- once the unit in hand
@@ -487,7 +523,22 @@ int png_row_plan(const uint8_t *stream, const PngFile &f, std::vector<uint32_t> 
         }
     }
     units->push_back(start);
-    units->push_back(static_cast<uint32_t>(f.h));
+    units->push_back(static_cast<uint32_t>(h));
+    return FNX_OK;
+}
+
+}  // namespace
+
+int png_row_plan(const uint8_t *stream, const PngFile &f, std::vector<uint32_t> *units, std::vector<uint8_t> *passes)
+{
+    units->clear();
+    if (passes) passes->clear();
+    if (f.interlace != 1) return plan_rows(stream, 1 + f.rowbytes, f.h, units);
+    for (int p = 0; p < 7; p++) {
+        if (f.ph[p] == 0) continue;
+        FNX_TRY(plan_rows(stream + f.poff[p], 1 + f.prow[p], f.ph[p], units));
+        if (passes) passes->resize(units->size() / 2, static_cast<uint8_t>(p));
+    }
     return FNX_OK;
 }
 
@@ -514,15 +565,15 @@ void png_palette_table(const PngFile &f, uint32_t table[256])
 // ---- a list of files on several threads (fnx_png_decode_batch) ------------------------------------------------------------
 namespace {
 
-int prepare_one(const uint8_t *data, size_t n, PngPrepared *it)
+int prepare_one(const uint8_t *data, size_t n, PngPrepared *it, bool adam7)
 {
-    FNX_TRY(png_parse(data, n, &it->f));
+    FNX_TRY(png_parse(data, n, &it->f, adam7));
     FNX_TRY(png_stream_size(it->f, &it->want));
     if (it->stream == nullptr || it->want > it->cap) return png_corrupt("internal: no staging for a file's stream");
     size_t got = 0;
     FNX_TRY(png_inflate(it->f.idat.data(), it->f.idat.size(), it->stream, it->want, &got));
     if (got != it->want) return png_corrupt("not enough pixel data");
-    FNX_TRY(png_row_plan(it->stream, it->f, &it->units));
+    FNX_TRY(png_row_plan(it->stream, it->f, &it->units, &it->unit_pass));
     if (it->f.color_type == 3) png_palette_table(it->f, it->table);
     return FNX_OK;
 }
@@ -535,7 +586,7 @@ int png_workers(int workers, int m)
     return workers < m ? workers : m;
 }
 
-void png_prepare_many(const uint8_t *const *files, const size_t *sizes, int m, int workers, PngPrepared *items)
+void png_prepare_many(const uint8_t *const *files, const size_t *sizes, int m, int workers, PngPrepared *items, bool adam7)
 {
     std::atomic<int> next(0);
     auto run = [&]() {
@@ -543,7 +594,7 @@ void png_prepare_many(const uint8_t *const *files, const size_t *sizes, int m, i
             PngPrepared &it = items[i];
             std::memset(it.table, 0, sizeof it.table);
             it.what = nullptr;
-            it.status = prepare_one(files[i], sizes[i], &it);
+            it.status = prepare_one(files[i], sizes[i], &it, adam7);
             if (it.status != FNX_OK) it.what = t_what;
             it.f.idat = std::vector<uint8_t>();          // the compressed bytes are not needed again
         }
@@ -588,6 +639,24 @@ int fnx_png_info(const uint8_t *data, size_t n, int *w, int *h, int *color_type,
     fnx::PngFile f;
     FNX_TRY(fnx::read_ihdr(data, n, &f));
     *w = f.w; *h = f.h; *color_type = f.color_type; *bit_depth = f.depth; *interlace = f.interlace;
+    return FNX_OK;
+}
+
+int fnx_png_adam7_passes(int w, int h, int color_type, int depth, int pw[7], int ph[7], size_t rowbytes[7], size_t *stream_bytes)
+{
+    if (!pw || !ph || !rowbytes || !stream_bytes) {
+        fnx::set_error("invalid argument: fnx_png_adam7_passes: a null pointer");
+        return FNX_ERR_INVALID;
+    }
+    const int ct = color_type, d = depth;
+    const bool pair = (ct == 0 && (d == 1 || d == 2 || d == 4 || d == 8 || d == 16)) || (ct == 3 && (d == 1 || d == 2 || d == 4 || d == 8)) ||
+                      ((ct == 2 || ct == 4 || ct == 6) && (d == 8 || d == 16));
+    if (!pair || w < 1 || h < 1 || w > 65535 || h > 65535) {
+        fnx::set_error("invalid argument: fnx_png_adam7_passes: one of the 15 colour type / bit depth pairs, dimensions 1..65535");
+        return FNX_ERR_INVALID;
+    }
+    const int channels = ct == 0 || ct == 3 ? 1 : ct == 4 ? 2 : ct == 2 ? 3 : 4;
+    *stream_bytes = fnx::png_adam7_geometry(w, h, channels * d, pw, ph, rowbytes);
     return FNX_OK;
 }
 

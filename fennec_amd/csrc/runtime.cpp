@@ -535,6 +535,13 @@ int fnx_ctx_profile(fnx_ctx *ctx, int enable)
     return FNX_OK;
 }
 
+int fnx_ctx_set_png_adam7(fnx_ctx *ctx, int accept)
+{
+    if (!ctx || (accept != 0 && accept != 1)) { fnx::set_error("fnx_ctx_set_png_adam7: bad argument"); return FNX_ERR_INVALID; }
+    ctx->png_adam7 = accept;
+    return FNX_OK;
+}
+
 int fnx_ctx_set_ssim_mode(fnx_ctx *ctx, int mode)
 {
     if (!ctx || (mode != FNX_SSIM_EXACT && mode != FNX_SSIM_FAST)) { fnx::set_error("fnx_ctx_set_ssim_mode: bad argument"); return FNX_ERR_INVALID; }

@@ -162,6 +162,14 @@ const char *fnx_ctx_last_kernel(fnx_ctx *ctx, int prof_class);
 #define FNX_SSIM_EXACT 0
 #define FNX_SSIM_FAST 1
 int fnx_ctx_set_ssim_mode(fnx_ctx *ctx, int mode);
+/* Whether the PNG entries of ONE ctx decode Adam7-interlaced files: accept 0 (default) -- such a file is FNX_ERR_UNSUPPORTED,
+ * as callers that route on that answer expect; 1 -- it is decoded on the device (the rule: above fnx_png_decode).  Holds for
+ * every entry that takes this ctx and PNG bytes: fnx_png_decode (its dst == NULL probe too, when this ctx is passed; with
+ * ctx == NULL the probe keeps the default's answer), fnx_png_decode_batch, fnx_png_recompress_batch, fennec_CompressFileJPEG /
+ * PNG / PNGReduce / PNGStream.  The fennec_CompressBatch* pools create their own contexts and keep the default; fnx_png_info
+ * and the limit of 65535 a dimension are untouched.  ctx == NULL or accept outside 0..1: FNX_ERR_INVALID.  A property of the
+ * ctx for the reason fnx_ctx_set_ssim_mode is one; the Go shim leaves the default. */
+int fnx_ctx_set_png_adam7(fnx_ctx *ctx, int accept);
 /* Kernel-form selection of ONE ctx, for tests and A/B timing: every form computes the same bytes as the default, the
  * selection only says which kernel does it, so that a fallback the product takes for rare tables (the fp64
  * reference-order kernels, the two-pass twin of a fused launch ...) can be run on any image and compared.  name / value:
@@ -718,6 +726,14 @@ int fnx_inflate(const uint8_t *src, size_t n, uint8_t *out, size_t cap, size_t *
 /* What a PNG file's signature and IHDR say (CRC checked): FNX_OK for every well-formed header -- also the interlaced and
  * oversized ones fnx_png_decode answers FNX_ERR_UNSUPPORTED to -- else FNX_ERR_INVALID.  Pure host code, no context. */
 int fnx_png_info(const uint8_t *data, size_t n, int *w, int *h, int *color_type, int *bit_depth, int *interlace);
+/* Adam7's pass geometry for a w x h image (1..65535 each) of one of the 15 colour type / bit depth pairs, else
+ * FNX_ERR_INVALID.  Pass p = 1..7 starts at (x0, y0) and steps by (dx, dy) =
+ *   (0,0,8,8)  (4,0,8,8)  (0,4,4,8)  (2,0,4,4)  (0,2,2,4)  (1,0,2,2)  (0,1,1,2)
+ * pw[p-1] = ceil((w - x0) / dx), ph[p-1] = ceil((h - y0) / dy), 0 where that is not positive; a pass with pw == 0 or ph == 0 is
+ * ABSENT: pw, ph and rowbytes are all 0 for it and it contributes no byte, not even filter bytes.  rowbytes = ceil(pw *
+ * channels * depth / 8); *stream_bytes = the sum of ph * (1 + rowbytes) over the present passes, the size the inflated IDAT
+ * stream must have.  Pure host code, no context. */
+int fnx_png_adam7_passes(int w, int h, int color_type, int depth, int pw[7], int ph[7], size_t rowbytes[7], size_t *stream_bytes);
 /* dst = toNRGBA(image.Decode(data)) for a PNG file, *w x *h.  The contract is fnx_jpeg_decode's: `data` is HOST memory, dst is
  * in `space` (FNX_HOST or FNX_DEVICE; a device dst is 4-byte aligned); dst == NULL: the dimensions only and whether the device
  * takes the file (host work: ctx may be NULL; `space` is checked there too).  Bad arguments and damaged files are refused
@@ -730,7 +746,8 @@ int fnx_png_info(const uint8_t *data, size_t n, int *w, int *h, int *color_type,
  * type 0, three for type 2, illegal for 4 and 6; consecutive IDATs concatenated; IEND ends the file; every other chunk is
  * skipped after its CRC.  A violation is FNX_ERR_INVALID.  The IDAT stream goes through fnx_inflate's code and must yield
  * exactly h * (1 + rowbytes) bytes, rowbytes = ceil(w * channels * depth / 8); each row's first byte is its filter type, above
- * 4: FNX_ERR_INVALID.  FNX_ERR_UNSUPPORTED (decode it on the host): Adam7-interlaced files, w or h above 65535.
+ * 4: FNX_ERR_INVALID.  FNX_ERR_UNSUPPORTED (decode it on the host): Adam7-interlaced files (unless the ctx accepts them, below),
+ * w or h above 65535.
  * Reconstruction (png_unfilter_kernel), the inverse of fnx_png_filter's table: with bpp = max(1, channels * depth / 8),
  * a = the reconstructed byte bpp to the left (0 for i < bpp), b = the byte above (0 for row 0), c = the byte above-left (0
  * for i < bpp or row 0), f the stream's byte, mod 256:
@@ -758,8 +775,19 @@ int fnx_png_info(const uint8_t *data, size_t n, int *w, int *h, int *color_type,
  *     A16 = t * 0x101: t == 255 -> (r, g, b, 255); t == 0 -> (0, 0, 0, 0); else r' = (r * 0x101) * t / 0xff and the pixel is
  *     ((r' * 0xffff / A16) >> 8, ..., t) -- lossy on purpose, it is the reference's round trip.  An index behind the palette's
  *     end reads as opaque black (under tRNS[i] where tRNS is longer than PLTE).  The 256 pixel values are made on the host.
+ * Adam7 (interlace method 1), on a ctx after fnx_ctx_set_png_adam7(ctx, 1); restated like the rest.  The inflated IDAT stream
+ * is the PRESENT passes back to back in pass order (fnx_png_adam7_passes: geometry, and which passes are present).  Each pass
+ * is an image of pw x ph pixels with its own packed rows -- samples of depth 1, 2, 4 are packed per PASS row, MSB first -- and
+ * each pass row carries its own filter byte; the row above a pass's first row is all zeros, bpp is the file's.  The stream
+ * must hold exactly stream_bytes: fewer or more is FNX_ERR_INVALID, and so is a filter type above 4 in any pass, refused before
+ * anything is launched.  Pass pixel (i, j) is image pixel (x0 + i * dx, y0 + j * dy).  The pixel model -- tRNS, 16-bit samples,
+ * the palette's table, indices behind the palette's end -- is the non-interlaced one, and Go returns the same image type, so
+ * the table above applies unchanged.  On the device the passes are seven small images of one bpp: ONE launch of
+ * png_unfilter_batch_kernel reconstructs all of them (a pass's row 0 starts a chain, no unit spans two passes) into a plane
+ * per pass, and png_expand_adam7_kernel writes the image, a thread per OUTPUT pixel that finds its pass from (x & 7, y & 7).
  * Inflate is one serial bit stream and stays on the host; the stream goes up as it is, 1/8 to 8 bytes a pixel.
- * Kernels: csrc/png_decode.hip; fnx_ctx_last_kernel(ctx, FNX_PROF_MAIN) answers "png_unfilter_kernel, png_expand_kernel". */
+ * Kernels: csrc/png_decode.hip; fnx_ctx_last_kernel(ctx, FNX_PROF_MAIN) answers "png_unfilter_kernel, png_expand_kernel", for
+ * an Adam7 file "png_unfilter_batch_kernel, png_expand_adam7_kernel". */
 #define FNX_PNG_DECODE_ROWS 1024   /* rows a workgroup of png_unfilter_kernel keeps in flight */
 int fnx_png_decode(fnx_ctx *ctx, const uint8_t *data, size_t n, int space, uint8_t *dst, int dstride, int *w, int *h);
 /* image.Decode + toNRGBA of n PNG files in host memory (the loadImage of CompressBatch's items, batch.go:88-122 ->
@@ -783,7 +811,11 @@ int fnx_png_decode(fnx_ctx *ctx, const uint8_t *data, size_t n, int space, uint8
  * on `workers` or on which thread finished first.  Returns FNX_OK when the batch ran; an error for bad arguments (n outside
  * 1..FNX_BATCH_MAX, a NULL array, workers outside 0..64) before anything is launched or any thread is started.  When it
  * returns, the images are enqueued on the ctx's stream (as fnx_png_decode with FNX_DEVICE).
- * fnx_ctx_last_kernel(ctx, FNX_PROF_MAIN) answers "png_unfilter_batch_kernel, png_expand_batch_kernel". */
+ * On a ctx that accepts Adam7 files (fnx_ctx_set_png_adam7) they take part like the others: their passes' units join the
+ * unfilter launch of their bpp, and png_expand_adam7_batch_kernel runs once over the chunk's Adam7 files; a chunk without one
+ * runs the launches above and nothing else.
+ * fnx_ctx_last_kernel(ctx, FNX_PROF_MAIN) answers "png_unfilter_batch_kernel, png_expand_batch_kernel", with
+ * ", png_expand_adam7_batch_kernel" behind it for a chunk that holds Adam7 files. */
 #define FNX_PNG_DECODE_CHUNK 32   /* files per set of launches, at most */
 #define FNX_PNG_DECODE_CHUNK_BYTES ((size_t)1 << 30)   /* device scratch of a chunk's streams + planes, at most (as the JPEG batch's) */
 int fnx_png_decode_batch(fnx_ctx *ctx, int n, const uint8_t *const *files, const size_t *sizes, uint8_t *const *dsts,
