@@ -45,6 +45,8 @@ FNX_PNG_DECODE_ROWS = 1024                                    # png_decode.hip: 
 FNX_PNG_DECODE_CHUNK = 32                                     # fnx_png_decode_batch: files per set of launches, at most
 FNX_PNG_COMPRESS_CHUNK = 32                                   # fnx_png_compress_batch: images per set of launches, at most
 FNX_DEFLATE_CHUNK, FNX_DEFLATE_SUB = 32768, 128               # deflate.hip: bytes per chunk (= per workgroup, per block) and per lane
+FNX_DEFLATE_LEVEL_FAST, FNX_DEFLATE_LEVEL_DENSE = 0, 1         # fnx_ctx_set_deflate_level
+FNX_DEFLATE_DENSE_DEPTH = 32                                   # the dense level: the most chain candidates a position tries
 PROF_MAIN, PROF_SSIM, PROF_RESIZE, PROF_FX, PROF_JPEG = 1, 2, 4, 8, 16
 
 _u8p = C.c_void_p
@@ -157,6 +159,7 @@ def load_library() -> C.CDLL:
         _sig(L, "fnx_ctx_set_form", i, [ctx, C.c_char_p, C.c_char_p])
         _sig(L, "fnx_ctx_set_ssim_mode", i, [ctx, i])
         _sig(L, "fnx_ctx_set_png_adam7", i, [ctx, i])
+        _sig(L, "fnx_ctx_set_deflate_level", i, [ctx, i])
         _sig(L, "fnx_png_adam7_passes", i, [i, i, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)])
         _sig(L, "fnx_malloc", i, [ctx, C.c_size_t, C.POINTER(C.c_void_p)])
         _sig(L, "fnx_free", i, [ctx, C.c_void_p])
@@ -439,6 +442,18 @@ class Context:
         FennecUnsupported for them (False, the default)"""
         self._chk(self._lib.fnx_ctx_set_png_adam7(self._h, 1 if accept else 0), "fnx_ctx_set_png_adam7")
         self._png_adam7 = bool(accept)
+
+    def set_deflate_level(self, level) -> None:
+        """fnx_ctx_set_deflate_level: "fast" (FNX_DEFLATE_LEVEL_FAST, the default: the bytes the library always gave) or
+        "dense" (FNX_DEFLATE_LEVEL_DENSE: hash chains, lazy and cross-chunk matches -- a smaller stream of the same layout)
+        for every device deflate of this ctx: deflate, png_encode, compress_png(device_deflate=True), png_compress_batch,
+        png_recompress_batch.  The integer constants are accepted too."""
+        if isinstance(level, str):
+            names = {"fast": FNX_DEFLATE_LEVEL_FAST, "dense": FNX_DEFLATE_LEVEL_DENSE}
+            if level not in names:
+                raise FennecError(f"set_deflate_level: 'fast' or 'dense', not {level!r}")
+            level = names[level]
+        self._chk(self._lib.fnx_ctx_set_deflate_level(self._h, int(level)), "fnx_ctx_set_deflate_level")
 
     def set_form(self, name: str, value=None) -> None:
         """fnx_ctx_set_form: which of several kernels that compute the same bytes this ctx takes (tests, A/B timing);

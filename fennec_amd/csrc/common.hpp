@@ -239,6 +239,7 @@ struct fnx_ctx {
     // name the route the library took instead of inferring it from environment switches
     const char *route[8] = {"", "", "", "", "", "", "", ""};
     int png_adam7 = 0;           // fnx_ctx_set_png_adam7: 1 -- the PNG entries decode Adam7-interlaced files instead of refusing them
+    int deflate_level = 0;       // fnx_ctx_set_deflate_level: FNX_DEFLATE_LEVEL_FAST / _DENSE -- which chunk kernels launch_deflate and launch_deflate_batch run
     int ssim_mode = 0;           // fnx_ctx_set_ssim_mode: FNX_SSIM_EXACT (fp64 moments) / FNX_SSIM_FAST (fp32 moments for full-resolution planes)
     // fnx_ctx_set_form: the kernel forms this ctx was told to take ("" = the product's own choice)
     char form[fnx::FORM_COUNT][8] = {};

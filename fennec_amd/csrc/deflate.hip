@@ -49,9 +49,15 @@
 // cache; the gather places a chunk by the prefix over its own stream's units and the stream by the sum over the units in front,
 // so the streams lie back to back at their true sizes.  The chunk body is deflate_chunk.inc, included into both chunk kernels.
 //
+// deflate_dense_chunk_kernel, deflate_dense_chunk_batch_kernel (fnx_ctx_set_deflate_level, FNX_DEFLATE_LEVEL_DENSE): the same
+// layout, slots and gather behind another parse -- hash chains, a window that reaches into the previous chunk, uncut matches,
+// one lazy step; see the comment in front of them, deflate_dense_chunk.inc and DESIGN.md section 5.12.  The codes / form / emit
+// half of a chunk body is deflate_codes.inc, shared by deflate_chunk.inc and deflate_dense_chunk.inc.
+//
 // Resources (hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage): no scratch in any kernel;
 // VGPRs: see DESIGN.md section 5.7 (the figures are the compiler's and are restated there with the LDS sizes); the batched
-// kernels have their twins' figures: 60 VGPRs / 53296 bytes of LDS (chunk), 34 / 32 (gather) -- DESIGN.md section 5.10.
+// kernels have their twins' figures: 60 VGPRs / 53296 bytes of LDS (chunk), 34 / 32 (gather) -- DESIGN.md section 5.10; the
+// dense chunk kernels 61 VGPRs / 152116 bytes of LDS -- section 5.12.
 #include "common.hpp"
 #include "devutil.hpp"
 #include "deflate_batch.hpp"
@@ -67,6 +73,7 @@ constexpr int DF_HBITS = 12;
 constexpr int DF_SLOT = DEFLATE_SLOT_BYTES;        // a chunk's output slot: stored bound C + 10, dword reads one past the end
 constexpr uint32_t DF_ADLER = 65521u;
 constexpr int DF_STORED = 0, DF_FIXED = 1, DF_DYNAMIC = 2;   // BTYPE
+constexpr int DF_DENSE_WORDS = 2 * DF_C + DF_C / 2; // the dense level's scratch words per chunk: tokens, the (L, D) table, the previous chunk's links (16 bits each)
 static_assert(DF_S * DF_T == DF_C && DF_S >= 64, "equal sub-chunks of at least 64 bytes");
 static_assert(DF_C <= 32768, "distances are at most 32768; a stored block's LEN is 16 bits");
 
@@ -249,6 +256,52 @@ __global__ __launch_bounds__(DF_T) void deflate_chunk_batch_kernel(DeflateBatchA
 #undef DF_CHUNK_INDEX
 }
 
+// ---- the dense level (fnx_ctx_set_deflate_level): the same launches, arguments, slots and gather, another
+// parse.  The window is the previous chunk and the own one, 64 KiB of LDS; hash chains FNX_DEFLATE_DENSE_DEPTH deep, uncut
+// matches, one step of lazy evaluation -- deflate_dense_chunk.inc.  152 116 bytes of LDS: a workgroup has its CU to itself.
+
+// bytes i .. i + 3 of the window's words (v_alignbyte over two aligned dwords)
+__device__ __forceinline__ uint32_t df_ld4(const uint32_t *w, int i) { return __builtin_amdgcn_alignbyte(w[(i >> 2) + 1], w[i >> 2], i & 3); }
+// how many of the maxl bytes from a on equal those from b on, a dword at a time (reads up to 7 bytes behind a + maxl)
+__device__ __forceinline__ int df_match_len(const uint32_t *w, int a, int b, int maxl)
+{
+    int l = 0;
+    while (l < maxl) {
+        const uint32_t x = df_ld4(w, a + l) ^ df_ld4(w, b + l);
+        if (x) { l += __builtin_ctz(x) >> 3; break; }
+        l += 4;
+    }
+    return min(l, maxl);
+}
+
+__global__ __launch_bounds__(DF_T) void deflate_dense_chunk_kernel(DeflateArgs a)
+{
+#define DF_CHUNK_INDEX blockIdx.x
+#define DF_STREAM_POS base
+#include "deflate_dense_chunk.inc"
+#undef DF_STREAM_POS
+#undef DF_CHUNK_INDEX
+}
+
+// unit c as chunk 0 of a stream of its own bytes, as in deflate_chunk_batch_kernel -- but the bytes in front of it are its
+// stream's: the unit's place in the stream is its distance from the stream's first unit
+__global__ __launch_bounds__(DF_T) void deflate_dense_chunk_batch_kernel(DeflateBatchArgs b)
+{
+    const DeflateBatchUnit u = b.units[blockIdx.x];
+    const uint32_t first = b.images[u.image].chunk0;
+    DeflateArgs a;
+    a.src = u.src; a.n = u.len; a.row = u.row;
+    a.nchunks = u.last ? 1u : 2u;
+    a.tok = b.tok + static_cast<size_t>(blockIdx.x) * DF_DENSE_WORDS;
+    a.slots = b.slots + static_cast<size_t>(blockIdx.x) * DF_SLOT;
+    a.meta = b.meta + 4 * static_cast<size_t>(blockIdx.x);
+#define DF_CHUNK_INDEX 0u
+#define DF_STREAM_POS (static_cast<size_t>(blockIdx.x - first) * DF_C)
+#include "deflate_dense_chunk.inc"
+#undef DF_STREAM_POS
+#undef DF_CHUNK_INDEX
+}
+
 struct GatherArgs {
     const uint8_t *slots;
     const uint32_t *meta;
@@ -367,8 +420,9 @@ __global__ __launch_bounds__(DF_T) void deflate_gather_batch_kernel(DeflateBatch
 int launch_deflate(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, uint8_t *d_out, size_t cap, const unsigned long long **d_size)
 {
     const size_t nchunks = deflate_chunks(n);
+    const bool dense = ctx->deflate_level == FNX_DEFLATE_LEVEL_DENSE;
     void *dt = nullptr, *ds = nullptr;
-    FNX_TRY(scratch(ctx, SLOT_DEFLATE_TOK, nchunks * DF_C * sizeof(uint32_t) + 16, &dt));
+    FNX_TRY(scratch(ctx, SLOT_DEFLATE_TOK, nchunks * (dense ? DF_DENSE_WORDS : DF_C) * sizeof(uint32_t) + 16, &dt));
     // the result word, the chunks' (bytes, a, b, len), the chunks' slots
     const size_t meta_bytes = (16 * nchunks + 16 + 15) & ~size_t(15);
     FNX_TRY(scratch(ctx, SLOT_DEFLATE_SLOTS, meta_bytes + nchunks * DF_SLOT + 16, &ds));
@@ -378,9 +432,10 @@ int launch_deflate(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, uint8_
     da.tok = static_cast<uint32_t *>(dt);
     da.meta = reinterpret_cast<uint32_t *>(p + 16);
     da.slots = p + meta_bytes;
-    note_route(ctx, FNX_PROF_MAIN, "deflate_chunk_kernel");
+    note_route(ctx, FNX_PROF_MAIN, dense ? "deflate_dense_chunk_kernel" : "deflate_chunk_kernel");
     FNX_TRY(prof_begin(ctx));
-    hipLaunchKernelGGL(deflate_chunk_kernel, dim3(da.nchunks), dim3(DF_T), 0, ctx->stream, da);
+    if (dense) hipLaunchKernelGGL(deflate_dense_chunk_kernel, dim3(da.nchunks), dim3(DF_T), 0, ctx->stream, da);
+    else hipLaunchKernelGGL(deflate_chunk_kernel, dim3(da.nchunks), dim3(DF_T), 0, ctx->stream, da);
     FNX_HIP(hipGetLastError());
     FNX_TRY(prof_end(ctx));
     GatherArgs ga{};
@@ -399,8 +454,9 @@ int launch_deflate(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, uint8_
 int launch_deflate_batch(fnx_ctx *ctx, const DeflateBatchUnit *d_units, const DeflateBatchImage *d_images, uint32_t nunits, uint32_t m,
                          size_t out_bytes, const uint8_t **d_out, const unsigned long long **d_sizes)
 {
+    const bool dense = ctx->deflate_level == FNX_DEFLATE_LEVEL_DENSE;
     void *dt = nullptr, *ds = nullptr, *dz = nullptr;
-    FNX_TRY(scratch(ctx, SLOT_DEFLATE_TOK, static_cast<size_t>(nunits) * DF_C * sizeof(uint32_t) + 16, &dt));
+    FNX_TRY(scratch(ctx, SLOT_DEFLATE_TOK, static_cast<size_t>(nunits) * (dense ? DF_DENSE_WORDS : DF_C) * sizeof(uint32_t) + 16, &dt));
     // the streams' sizes, the units' (bytes, a, b, len), the units' slots
     const size_t sizes_bytes = (8 * static_cast<size_t>(m) + 15) & ~size_t(15);
     const size_t meta_bytes = 16 * static_cast<size_t>(nunits);
@@ -415,7 +471,8 @@ int launch_deflate_batch(fnx_ctx *ctx, const DeflateBatchUnit *d_units, const De
     a.slots = p + sizes_bytes + meta_bytes;
     a.out = static_cast<uint8_t *>(dz);
     FNX_TRY(prof_begin(ctx));
-    hipLaunchKernelGGL(deflate_chunk_batch_kernel, dim3(nunits), dim3(DF_T), 0, ctx->stream, a);
+    if (dense) hipLaunchKernelGGL(deflate_dense_chunk_batch_kernel, dim3(nunits), dim3(DF_T), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(deflate_chunk_batch_kernel, dim3(nunits), dim3(DF_T), 0, ctx->stream, a);
     FNX_HIP(hipGetLastError());
     FNX_TRY(prof_end(ctx));
     FNX_TRY(prof_begin(ctx));

@@ -607,6 +607,9 @@ int png_decode_batch_device(fnx_ctx *ctx, int n, const uint8_t *const *files, co
 constexpr const char *PNG_CB_ROUTE =
     "png_colors_batch_kernel, png_finish_batch_kernel, png_flags_batch_kernel, png_plane_batch_kernel, png_filter_batch_kernel, "
     "png_pack_batch_kernel, deflate_chunk_batch_kernel, deflate_gather_batch_kernel";
+constexpr const char *PNG_CB_ROUTE_DENSE =                            // on a ctx at FNX_DEFLATE_LEVEL_DENSE
+    "png_colors_batch_kernel, png_finish_batch_kernel, png_flags_batch_kernel, png_plane_batch_kernel, png_filter_batch_kernel, "
+    "png_pack_batch_kernel, deflate_dense_chunk_batch_kernel, deflate_gather_batch_kernel";
 
 // `bytes` device bytes into pinned host memory, waited for: one of a chunk's three host waits
 int png_cb_fetch(fnx_ctx *ctx, const void *d, size_t bytes, const uint8_t **host)
@@ -626,7 +629,7 @@ int png_cb_fetch(fnx_ctx *ctx, const void *d, size_t bytes, const uint8_t **host
 int png_compress_chunk(fnx_ctx *ctx, int m, const PngCbSrc *imgs, const int *at, int base, uint8_t *const *outs, const size_t *caps, size_t *nbytes,
                        int *kinds, int *status, FirstRefusal *first)
 {
-    note_route(ctx, FNX_PROF_MAIN, PNG_CB_ROUTE);
+    note_route(ctx, FNX_PROF_MAIN, ctx->deflate_level == FNX_DEFLATE_LEVEL_DENSE ? PNG_CB_ROUTE_DENSE : PNG_CB_ROUTE);
     const void *d_results = nullptr;
     FNX_TRY(launch_png_classify_batch(ctx, m, imgs, &d_results));
     const size_t rb = png_result_bytes();

@@ -542,6 +542,13 @@ int fnx_ctx_set_png_adam7(fnx_ctx *ctx, int accept)
     return FNX_OK;
 }
 
+int fnx_ctx_set_deflate_level(fnx_ctx *ctx, int level)
+{
+    if (!ctx || (level != FNX_DEFLATE_LEVEL_FAST && level != FNX_DEFLATE_LEVEL_DENSE)) { fnx::set_error("fnx_ctx_set_deflate_level: bad argument"); return FNX_ERR_INVALID; }
+    ctx->deflate_level = level;
+    return FNX_OK;
+}
+
 int fnx_ctx_set_ssim_mode(fnx_ctx *ctx, int mode)
 {
     if (!ctx || (mode != FNX_SSIM_EXACT && mode != FNX_SSIM_FAST)) { fnx::set_error("fnx_ctx_set_ssim_mode: bad argument"); return FNX_ERR_INVALID; }

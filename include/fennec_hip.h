@@ -702,6 +702,37 @@ size_t fnx_deflate_bound(size_t n);
  * anything is launched.  One host wait for the size (a second one behind the copy when the stream goes to host memory).
  * Kernels: deflate_chunk_kernel (the one fnx_ctx_last_kernel(ctx, FNX_PROF_MAIN) names), deflate_gather_kernel. */
 int fnx_deflate(fnx_ctx *ctx, int space, const uint8_t *src, size_t n, int row, uint8_t *out, size_t cap, size_t *nbytes);
+/* The deflate LEVEL of ONE ctx.  FNX_DEFLATE_LEVEL_FAST (default): the stream described above, byte for byte what the library
+ * gave before the setting existed.  FNX_DEFLATE_LEVEL_DENSE: the same layout -- ceil(n / FNX_DEFLATE_CHUNK) data blocks, block c
+ * yields exactly chunk c's bytes and starts on a byte, an empty stored block behind each but the last, BFINAL on the last, header
+ * 78 01, the Adler-32 behind; each block the smallest of dynamic, fixed and stored; the same Huffman construction -- so
+ * fnx_deflate_bound and fnx_png_file_bound hold unchanged.  What differs is the parse:
+ *  - matches: 3 <= length <= 258, never past the chunk's end; distance <= min(p, 32768) with p the position in the STREAM: a
+ *    match may reach into the previous chunk (an empty stored block does not reset inflate's window), never in front of the
+ *    stream, never further than 32768.  A 3-byte match further than 4096 back is not taken.  No cut at multiples of
+ *    FNX_DEFLATE_SUB.
+ *  - candidates of a position: the distances 1, 2, 3, 4, 6, 8 and `row`, and up to FNX_DEFLATE_DENSE_DEPTH positions of its hash
+ *    chain, nearest first.  The hash is ((b0 | b1 << 8 | b2 << 16) * 0x9e3779b1 mod 2^32) >> 20 of the position's three bytes.
+ *    Chains are laid over the window -- the previous chunk from its first byte, then the own chunk: a position's link goes to
+ *    the LARGEST EARLIER position of the window with its hash (none when that is further than 32768 back), so a chain visits,
+ *    nearest first, every earlier position of the window that hashes alike, foreign three-byte words included.  (The kernel
+ *    builds the links in segments of 256 positions -- against the earlier segments through a table, inside the segment by a
+ *    search -- and the result does not depend on that.)  The longest
+ *    match wins, the smaller distance on ties.  The set is a function of (src, n, row) alone.
+ *  - parse: with (L, D) the best match of every position (L clipped to the chunk's end), from the chunk's first byte:
+ *      at p: l = L[p];  l >= 3, p + 1 inside the chunk and L[p + 1] > l: the literal at p, go to p + 1;
+ *            else l >= 3: the match (l, D[p]), go to p + l;   else: the literal, go to p + 1
+ *    -- one step of lazy evaluation.  The tokens are those of this serial walk, however the kernel finds them.
+ * Expect a size within a few per cent of zlib level 9 on photographic content (DESIGN.md section 5.12 has the measured
+ * figures).  Followed by every entry that deflates on the device with this ctx: fnx_deflate, fnx_png_encode,
+ * fennec_CompressFilePNG, fnx_png_compress_batch, fnx_png_recompress_batch -- the batch's files stay byte for byte the single
+ * route's on the same ctx.  The fennec_CompressBatch* pools, the host's deflate and the Go shim are untouched.  After a dense
+ * fnx_deflate fnx_ctx_last_kernel(ctx, FNX_PROF_MAIN) names deflate_dense_chunk_kernel; the batch's twin is
+ * deflate_dense_chunk_batch_kernel.  ctx == NULL or any other level: FNX_ERR_INVALID, nothing changed. */
+#define FNX_DEFLATE_LEVEL_FAST  0
+#define FNX_DEFLATE_LEVEL_DENSE 1
+#define FNX_DEFLATE_DENSE_DEPTH 32   /* the most chain candidates a position tries */
+int fnx_ctx_set_deflate_level(fnx_ctx *ctx, int level);
 /* fnx_png_filter's row stage and fnx_deflate in one call: the complete PNG file of a resident (or host) image, the filtered
  * stream never leaving the device.  kind, src, sstride, w, h, ncolors, opaque: as fnx_png_filter's; palette: HOST,
  * ncolors x 4 bytes r,g,b,a, for FNX_PNG_PALETTED (ignored otherwise).  space: FNX_HOST, FNX_DEVICE or FNX_DEVICE_SRC say

@@ -62,6 +62,7 @@ inline uint32_t __brev(uint32_t v)
     return r;
 }
 inline int min(int a, int b) { return a < b ? a : b; }
+inline int max(int a, int b) { return a > b ? a : b; }
 // every lane of the workgroup calls it; a lane's partner is in its own wave of 64 for every offset below 64
 inline unsigned long long __shfl_xor(unsigned long long v, int off, int width)
 {
@@ -77,7 +78,7 @@ inline unsigned long long __shfl_xor(unsigned long long v, int off, int width)
     static_cast<uint32_t>(((static_cast<uint64_t>(hi) << 32) | static_cast<uint64_t>(lo)) >> (8 * ((sel) & 3)))
 
 // ---- the host side of launch_deflate: a context that only hands out memory
-struct fnx_ctx { void *slot[3]; void *stream; };
+struct fnx_ctx { void *slot[3]; void *stream; int deflate_level; };
 namespace fnx {
 enum Slot { SLOT_DEFLATE_TOK, SLOT_DEFLATE_SLOTS, SLOT_DEFLATE_OUT };
 inline int scratch(fnx_ctx *ctx, Slot s, size_t bytes, void **out)

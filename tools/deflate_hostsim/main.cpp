@@ -8,6 +8,9 @@
 // i is laid i % 4 bytes behind a 16-byte boundary of one source area, its units and stream record are made as the PNG compress
 // batch's planner makes them -- and stream i written to OUT.i.  The program checks that the streams lie back to back at their
 // true sizes and that nothing behind the last one was written.
+// Switches, anywhere on the line, that leave the other arguments' meaning as it is: --dense runs the dense level's kernels
+// (FNX_DEFLATE_LEVEL_DENSE; TOKENS then holds the lazy walk's tokens); --table FILE (with --dense, single stream) writes the
+// dense parse's per-position table beside them, per chunk its length and that many words L << 16 | D - 1 (0: no match).
 // Built by the Makefile beside it from a COPY of fennec_amd/csrc/deflate.hip against the stand-in common.hpp / devutil.hpp of
 // this directory; meant for sanitizer builds (-fsanitize=address,undefined) and for reading a stream without a GPU.
 #include "deflate_hip.inc"
@@ -31,6 +34,9 @@ static bool read_file(const char *name, std::vector<uint8_t> *out)
     fclose(f);
     return true;
 }
+
+static int g_level = FNX_DEFLATE_LEVEL_FAST;
+static const char *g_table = nullptr;
 
 static int batch(int argc, char **argv)
 {
@@ -61,6 +67,7 @@ static int batch(int argc, char **argv)
         }
     }
     fnx_ctx ctx{};
+    ctx.deflate_level = g_level;
     const uint8_t *out = nullptr;
     const unsigned long long *sizes = nullptr;
     if (fnx::launch_deflate_batch(&ctx, units.data(), images.data(), static_cast<uint32_t>(units.size()), static_cast<uint32_t>(m), bounds, &out, &sizes) != FNX_OK)
@@ -81,6 +88,15 @@ static int batch(int argc, char **argv)
 
 int main(int argc, char **argv)
 {
+    int kept = 1;
+    for (int i = 1; i < argc; i++) {
+        if (strcmp(argv[i], "--dense") == 0) g_level = FNX_DEFLATE_LEVEL_DENSE;
+        else if (strcmp(argv[i], "--table") == 0 && i + 1 < argc) g_table = argv[++i];
+        else argv[kept++] = argv[i];
+    }
+    argc = kept;
+    const bool dense = g_level == FNX_DEFLATE_LEVEL_DENSE;
+    if (g_table && !dense) return fail("--table goes with --dense");
     if (argc > 1 && strcmp(argv[1], "--batch") == 0) return batch(argc, argv);
     if (argc < 3) return fail("usage: deflate_hostsim IN OUT [row [src_offset [dst_offset [TOKENS]]]]");
     const int row = argc > 3 ? atoi(argv[3]) : 0;
@@ -105,6 +121,7 @@ int main(int argc, char **argv)
     uint8_t *out = dst + FENCE + doff;
 
     fnx_ctx ctx{};
+    ctx.deflate_level = g_level;
     const unsigned long long *size = nullptr;
     if (fnx::launch_deflate(&ctx, src + soff, n, row, out, cap, &size) != FNX_OK) return fail("launch_deflate failed");
     const size_t nb = static_cast<size_t>(*size);
@@ -119,6 +136,16 @@ int main(int argc, char **argv)
         for (size_t c = 0; c * fnx::DF_C < n; c++) {
             const size_t len = std::min<size_t>(fnx::DF_C, n - c * fnx::DF_C), first = words.size();
             words.push_back(0);
+            if (dense) {                                              // a token belongs to the lane in whose sub-chunk it starts
+                const uint32_t *ct = tok + c * fnx::DF_DENSE_WORDS;
+                size_t lane = ~size_t(0), k = 0;
+                for (size_t p = 0; p < len;) {
+                    if (p / fnx::DF_S != lane) { lane = p / fnx::DF_S; k = 0; }
+                    const uint32_t t = ct[lane * fnx::DF_S + k++];
+                    words.push_back(t);
+                    p += (t >> 31) ? ((t >> 16) & 0xffu) + 3 : 1;
+                }
+            } else
             for (size_t s0 = 0; s0 < len; s0 += fnx::DF_S) {          // a lane's tokens lie from its sub-chunk's first word on
                 const uint32_t *t = tok + c * fnx::DF_C + s0;
                 for (size_t p = s0, e = std::min<size_t>(s0 + fnx::DF_S, len); p < e; t++) {
@@ -130,6 +157,18 @@ int main(int argc, char **argv)
         }
         f = fopen(argv[6], "wb");
         if (!f || fwrite(words.data(), 4, words.size(), f) != words.size() || fclose(f) != 0) return fail("cannot write TOKENS");
+    }
+    if (g_table) {
+        const uint32_t *tok = static_cast<const uint32_t *>(ctx.slot[fnx::SLOT_DEFLATE_TOK]);
+        std::vector<uint32_t> words;
+        for (size_t c = 0; c * fnx::DF_C < n; c++) {
+            const size_t len = std::min<size_t>(fnx::DF_C, n - c * fnx::DF_C);
+            const uint32_t *tab = tok + c * fnx::DF_DENSE_WORDS + fnx::DF_C;
+            words.push_back(static_cast<uint32_t>(len));
+            words.insert(words.end(), tab, tab + len);
+        }
+        f = fopen(g_table, "wb");
+        if (!f || fwrite(words.data(), 4, words.size(), f) != words.size() || fclose(f) != 0) return fail("cannot write the table");
     }
     for (void *p : ctx.slot) free(p);
     free(src);

@@ -1,7 +1,8 @@
-"""fnx_png_encode at 4K against the host route, per image: the HIP-event time of each launch (fnx_ctx_profile: the row stage,
-deflate_chunk_kernel, deflate_gather_kernel), the call's wall time from a resident image to the PNG file in host memory, and
-beside it png_filter to host memory followed by zlib.compress at levels 1, 6 and 9 on one thread -- with every file's size.
-    python tools/time_deflate.py [W H]"""
+"""fnx_png_encode at 4K against the host route, per image and per deflate level (Context.set_deflate_level: a row for "fast", a
+row for "dense"): the HIP-event time of each launch (fnx_ctx_profile: the row stage, deflate_chunk_kernel or
+deflate_dense_chunk_kernel, deflate_gather_kernel), the call's wall time from a resident image to the PNG file in host memory,
+and beside it png_filter to host memory followed by zlib.compress at levels 1, 6 and 9 on one thread -- with every file's size.
+    python tools/time_deflate.py [W H [REPS]]"""
 import os
 import sys
 import time
@@ -29,27 +30,31 @@ palette[:, 3] = 255
 CASES = [("smooth RGB", smooth, FNX_PNG_NRGBA, 0, 1, None), ("paletted, 256 colours", pal256, FNX_PNG_PALETTED, 256, -1, palette),
          ("flat, 2 colours", flat2, FNX_PNG_PALETTED, 2, -1, palette[:2]), ("noise RGB", noise, FNX_PNG_NRGBA, 0, 1, None)]
 ctx = fennec_amd.Context(0)
-REPS = 7
+REPS = int(sys.argv[3]) if len(sys.argv) > 3 else 7
 print(f"fnx_png_encode against png_filter + host zlib, {W}x{H}, device sources; times in ms (median of {REPS} after warm-up; zlib: one run)")
-print(f"{'image':22s} {'stream MB':>9s} | {'rows':>6s} {'chunk':>8s} {'gather':>7s} {'wall':>8s} {'file KB':>9s} | "
+print(f"{'image':22s} {'level':5s} {'stream MB':>9s} | {'rows':>6s} {'chunk':>8s} {'gather':>7s} {'wall':>8s} {'file KB':>9s} | "
       f"{'filter->host':>12s} | {'zlib 1':>8s} {'file KB':>9s} | {'zlib 6':>8s} {'file KB':>9s} | {'zlib 9':>8s} {'file KB':>9s}")
 for name, src, kind, ncolors, opaque, pal in CASES:
     t = torch.from_numpy(src).cuda()
     torch.cuda.synchronize()
-    for _ in range(2):
-        file = ctx.png_encode(t, kind, ncolors, opaque, pal)
-    wall = []
-    for _ in range(REPS):
-        t0 = time.perf_counter()
-        ctx.png_encode(t, kind, ncolors, opaque, pal)
-        wall.append((time.perf_counter() - t0) * 1e3)
-    ctx.profile(True)
-    ks = []
-    for _ in range(REPS):
-        ctx.png_encode(t, kind, ncolors, opaque, pal)
-        ks.append([ctx.kernel_ms() for _ in range(3)])
-    ctx.profile(False)
-    k = np.median(np.array(ks), axis=0)
+    rows = []
+    for level in ("fast", "dense"):
+        ctx.set_deflate_level(level)
+        for _ in range(2):
+            file = ctx.png_encode(t, kind, ncolors, opaque, pal)
+        wall = []
+        for _ in range(REPS):
+            t0 = time.perf_counter()
+            ctx.png_encode(t, kind, ncolors, opaque, pal)
+            wall.append((time.perf_counter() - t0) * 1e3)
+        ctx.profile(True)
+        ks = []
+        for _ in range(REPS):
+            ctx.png_encode(t, kind, ncolors, opaque, pal)
+            ks.append([ctx.kernel_ms() for _ in range(3)])
+        ctx.profile(False)
+        rows.append((level, np.median(np.array(ks), axis=0), np.median(wall), len(file)))
+    ctx.set_deflate_level("fast")
     host = np.empty(H * (1 + 4 * W), dtype=np.uint8)
     ctx.png_filter(t, kind, ncolors, opaque, host)
     fw = []
@@ -65,5 +70,6 @@ for name, src, kind, ncolors, opaque, pal in CASES:
         ms = (time.perf_counter() - t0) * 1e3
         # the file around the stream: signature, IHDR, IDAT's and IEND's frames (57 bytes), PLTE for the paletted kinds
         cols.append(f"{ms:8.1f} {(len(z) + 57 + (0 if pal is None else 12 + 3 * ncolors)) / 1e3:9.1f}")
-    print(f"{name:22s} {len(raw) / 1e6:9.1f} | {k[0]:6.3f} {k[1]:8.3f} {k[2]:7.3f} {np.median(wall):8.2f} {len(file) / 1e3:9.1f} | "
-          f"{np.median(fw):12.2f} | " + " | ".join(cols))
+    for level, k, wall, size in rows:
+        print(f"{name:22s} {level:5s} {len(raw) / 1e6:9.1f} | {k[0]:6.3f} {k[1]:8.3f} {k[2]:7.3f} {wall:8.2f} {size / 1e3:9.1f} | "
+              f"{np.median(fw):12.2f} | " + " | ".join(cols), flush=True)
