@@ -847,13 +847,15 @@ constexpr int NHEAD = 260 + 257 * 8;   // uint32 words at the head of the table 
 
 // blur_mfma_kernel<SCORE, .>'s set-up, which depends on the geometry alone, as two tables at the end of the blob (r7: every
 // workgroup used to work this out from bx / by through LDS, ~300 vector instructions per wave before its first row set):
-//  * per (tile column, wave, lane) one word: coln | cnt << 20 | in[0..3] << 25 | channel << 29 -- the lane's indicator-matrix
-//    column (box column first + slot of the wave's 16 px, channel ch; lane n = 3 slot + ch, n = 15: nothing), how many of the 16
-//    px lie in it (the seed 128 cnt undoes the A operands' - 128) and its byte offset in a table row (spare column: none)
+//  * per (tile column, wave, lane) one word: coln | cnt << 20 | in[0..3] << 25 | channel << 29 | live << 31 -- the lane's
+//    indicator-matrix column (box column first + slot of the wave's 16 px, channel ch; lane n = 3 slot + ch, n = 15: nothing), how
+//    many of the 16 px lie in it (the seed 128 cnt undoes the A operands' - 128) and its byte offset in a table row (spare
+//    column: none).  live: the column is a box column, somebody reads its sums -- the other lanes (lane 15, slots past the
+//    wave's last box column, a wave with no boxed pixel) issue no box atomics at all (4K: 28 lanes of 64)
 //  * per segment the byte offset, in a box table, of the box row of each of its seg + 16 staged rows (tile rows -6 ..), then of
 //    its seg output rows; rows outside the segment or the image go to the spare row nby
 // Written as the device code it replaces was, value for value, the corner cases included (a tile or a wave with no boxed column:
-// first = 255 matches every column of slot 0, so cnt = 16 there and the sums land in the spare column).
+// first = 255 matches every column of slot 0, so cnt = 16 there; its lanes point at the spare column and are not live).
 static void score_mfma_tables(fnx::ScoreGeom &g, int w, int h)
 {
     const int seg = g.th, nbx = g.nbx, nby = g.nby;
@@ -883,9 +885,10 @@ static void score_mfma_tables(fnx::ScoreGeom &g, int w, int h)
                 for (int i = 0; i < 16; i++) cnt += (r < 15 && colbox[16 * wave + i] == first + slot) ? 1 : 0;
                 for (int e = 0; e < 4; e++)
                     if (r < 15 && first != 255u && colbox[16 * wave + 4 * gq + e] == first + slot) in |= 1u << e;
-                const uint32_t bc = (r < 15 && first != 255u && cnt > 0) ? first + slot : static_cast<uint32_t>(nbx);
+                const bool live = r < 15 && first != 255u && cnt > 0;
+                const uint32_t bc = live ? first + slot : static_cast<uint32_t>(nbx);
                 const uint32_t coln = 16u * bc + 4u * (r < 15 ? ch : 3);
-                col[(4 * tx + wave) * 64 + lane] = coln | cnt << 20 | in << 25 | static_cast<uint32_t>(ch) << 29;
+                col[(4 * tx + wave) * 64 + lane] = coln | cnt << 20 | in << 25 | static_cast<uint32_t>(ch) << 29 | (live ? 1u << 31 : 0u);
             }
         }
     }

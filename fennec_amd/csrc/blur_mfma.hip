@@ -141,8 +141,12 @@ __device__ __forceinline__ uint32_t mf_exact_u(const double *wd, const uint8_t *
 // SCORE: a lane's four rows (4 g .. 4 g + 3) of one box column and channel into the box table.  (Measured and dropped, r5: adding
 // the rows of one box row up in the lane first -- one or two atomics instead of four for ~10 more vector instructions: the fast form
 // unchanged at 21.5 us per image, the exact form 2 % slower; CHANGELOG r5.)
-__device__ __forceinline__ void mf_box_add4(uint32_t *tbl, const u32x4 ro, uint32_t coln, const v4i cb)
+// Only LIVE lanes issue them: a lane whose indicator column is no box column (lane 15, the slots past the wave's last box column,
+// every lane of a wave with no boxed pixel) would add into the spare column, which nobody reads -- and at 4K those 28 lanes of 64
+// share four dwords per table row, a same-address chain twice as deep as the live lanes' (tools/box_atomic_depth.py).
+__device__ __forceinline__ void mf_box_add4(uint32_t *tbl, const u32x4 ro, uint32_t coln, const v4i cb, bool live)
 {
+    if (!live) return;
 #pragma unroll
     for (int k = 0; k < 4; k++)
         __hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(tbl) + ro[k] + coln), static_cast<uint32_t>(cb[k]),
@@ -209,6 +213,7 @@ __global__ __launch_bounds__(256, GUARD ? 3 : 1) void blur_mfma_kernel(MfmaArgs 
     // ---- SCORE set-up: row / column -> table offsets, this wave's indicator matrix ----
     v4i bbox = {0, 0, 0, 0}, sbox = {0, 0, 0, 0};
     uint32_t coln = 0;                                              // byte offset of this lane's (box column, channel) in a table row
+    bool live = false;                                              // ... which is a box column: this lane issues the box atomics
     const int slabn = SCORE ? (a.nbx + 1) * (a.nby + 1) : 0;
     uint32_t *tbl_s = s_box, *tbl_b = s_box + 4 * slabn;
     // (called from the march once the first two row sets' loads are in flight: its table loads then wait beside them)
@@ -223,11 +228,12 @@ __global__ __launch_bounds__(256, GUARD ? 3 : 1) void blur_mfma_kernel(MfmaArgs 
         if (!(a.dbg & 4)) for (int e = tid; e < 2 * slabn; e += 256) reinterpret_cast<u32x4 *>(s_box)[e] = (u32x4){0u, 0u, 0u, 0u};
         if (tid < nrh) reinterpret_cast<u32x4 *>(s_rowh)[tid] = rw;
         else if (tid < nrow) reinterpret_cast<u32x4 *>(s_rowv)[tid - nrh] = rw;
-        // cw: coln | cnt << 20 | (this lane's four K columns are in its box column) << 25 | channel << 29
+        // cw: coln | cnt << 20 | (this lane's four K columns are in its box column) << 25 | channel << 29 | live << 31
         coln = cw & 0xfffffu;
+        live = cw >> 31;
         const int seed = static_cast<int>((cw >> 20) & 31u) << 7;   // 128 cnt: the A operands are (p - 128), the sums come out as sums of p
         sbox = (v4i){seed, seed, seed, seed};
-        const uint32_t sh = (cw >> 29) << 3;
+        const uint32_t sh = ((cw >> 29) & 3u) << 3;
 #pragma unroll
         for (int e = 0; e < 4; e++) bbox[e] = static_cast<int>(((cw >> (25 + e)) & 1u) << sh);
     };
@@ -286,7 +292,7 @@ __global__ __launch_bounds__(256, GUARD ? 3 : 1) void blur_mfma_kernel(MfmaArgs 
             const v4i A = {(int)lo.x, (int)lo.y, (int)hi.x, (int)hi.y};
             const v4i cb = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, bbox, sbox, 0, 0, 0);
             const u32x4 ro = *reinterpret_cast<const u32x4 *>(s_rowh + 16 * s + 4 * g);
-            if (!(a.dbg & 1)) mf_box_add4(tbl_s, ro, coln, cb);
+            if (!(a.dbg & 1)) mf_box_add4(tbl_s, ro, coln, cb, live);
         }
         v4i u[4];
 #pragma unroll
@@ -416,7 +422,7 @@ __global__ __launch_bounds__(256, GUARD ? 3 : 1) void blur_mfma_kernel(MfmaArgs 
             const v4i A = {(int)os[0], (int)os[1], (int)os[2], (int)os[3]};
             const v4i cb = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, bbox, sbox, 0, 0, 0);
             const u32x4 ro = *reinterpret_cast<const u32x4 *>(s_rowv + 16 * j + 4 * g);
-            if (!(a.dbg & 1)) mf_box_add4(tbl_b, ro, coln, cb);
+            if (!(a.dbg & 1)) mf_box_add4(tbl_b, ro, coln, cb, live);
         }
     };
 
@@ -655,6 +661,7 @@ __global__ __launch_bounds__(256, MfWide<NKH>::NKV == 3 ? 1 : 2) void blur_mfma_
     // ---- SCORE set-up (blur_mfma_kernel's, with the wide frame's row offset) ----
     v4i bbox = {0, 0, 0, 0}, sbox = {0, 0, 0, 0};
     uint32_t coln = 0;
+    bool live = false;                                              // (blur_mfma_kernel's: only live lanes issue the box atomics)
     const int slabn = SCORE ? (a.nbx + 1) * (a.nby + 1) : 0;
     uint32_t *tbl_s = s_box, *tbl_b = s_box + 4 * slabn;
     auto score_setup = [&]() {
@@ -687,7 +694,8 @@ __global__ __launch_bounds__(256, MfWide<NKH>::NKV == 3 ? 1 : 2) void blur_mfma_
         }
         const int seed = 128 * cnt;
         sbox = (v4i){seed, seed, seed, seed};
-        const uint32_t bc = (r < 15 && first != 255u && cnt > 0) ? first + slot : static_cast<uint32_t>(a.nbx);
+        live = r < 15 && first != 255u && cnt > 0;
+        const uint32_t bc = live ? first + slot : static_cast<uint32_t>(a.nbx);
         coln = 16u * bc + 4u * (r < 15 ? ch : 3);
     };
 
@@ -709,10 +717,7 @@ __global__ __launch_bounds__(256, MfWide<NKH>::NKV == 3 ? 1 : 2) void blur_mfma_
             const v4i A = {(int)lo.x, (int)lo.y, (int)hi.x, (int)hi.y};
             const v4i cb = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, bbox, sbox, 0, 0, 0);
             const u32x4 ro = *reinterpret_cast<const u32x4 *>(s_rowh + 16 * s + 4 * g);
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-                __hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(tbl_s) + ro[k] + coln), static_cast<uint32_t>(cb[k]),
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            mf_box_add4(tbl_s, ro, coln, cb, live);
         }
 #pragma unroll
         for (int kk = 0; kk < NKH; kk++)
@@ -849,10 +854,7 @@ __global__ __launch_bounds__(256, MfWide<NKH>::NKV == 3 ? 1 : 2) void blur_mfma_
             const v4i A = {(int)os[0], (int)os[1], (int)os[2], (int)os[3]};
             const v4i cb = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, bbox, sbox, 0, 0, 0);
             const u32x4 ro = *reinterpret_cast<const u32x4 *>(s_rowv + 16 * j + 4 * g);
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-                __hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(tbl_b) + ro[k] + coln), static_cast<uint32_t>(cb[k]),
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            mf_box_add4(tbl_b, ro, coln, cb, live);
         }
     };
 
