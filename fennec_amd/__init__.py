@@ -100,6 +100,15 @@ class FileOptions(C.Structure):
     _fields_ = [("orient", C.c_int32), ("max_w", C.c_int32), ("max_h", C.c_int32), ("auto_format", C.c_int32), ("target_ssim", C.c_double)]
 
 
+class TargetOptions(C.Structure):
+    """fennec_TargetOptions (include/fennec_hip.h): CompressFile's options in target-size mode."""
+    _fields_ = [("file", FileOptions), ("target_bytes", C.c_int64), ("strategies", C.c_int32), ("reserved", C.c_int32)]
+
+    @classmethod
+    def make(cls, target_bytes: int, orient: int = 1, max_w: int = 0, max_h: int = 0, strategies: int = FNX_TS_ALL):
+        return cls(FileOptions(int(orient), int(max_w), int(max_h), 0, 0.0), int(target_bytes), int(strategies), 0)
+
+
 class FennecError(RuntimeError):
     pass
 
@@ -212,6 +221,12 @@ def load_library() -> C.CDLL:
         _sig(L, "fennec_CompressBatchJPEGOpts", i, [i, i, i, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(FileOptions),
                                                      C.POINTER(C.POINTER(FileOptions)), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                                      C.POINTER(NativeBatchResult), C.POINTER(i), C.POINTER(i), C.c_void_p, C.c_void_p])
+        _sig(L, "fennec_CompressFileTargetSize", i, [ctx, _u8p, C.c_size_t, C.POINTER(TargetOptions), C.POINTER(i), C.POINTER(SizeCandidate),
+                                                      C.POINTER(i), _u8p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i)])
+        _sig(L, "fennec_CompressBatchTargetSize", i, [i, i, i, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(TargetOptions),
+                                                       C.POINTER(C.POINTER(TargetOptions)), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                       C.POINTER(NativeBatchResult), C.POINTER(SizeCandidate), C.POINTER(i), C.POINTER(i),
+                                                       C.c_void_p, C.c_void_p])
         _sig(L, "fennec_pool_release", None, [])
         _sig(L, "fennec_SummarizeResults", d, [i, C.POINTER(NativeBatchResult), _i64p])
         _sig(L, "fnx_jpeg_size_search", i, [ctx, i] + img + [i, i, C.c_longlong, i, _f64p, _u8p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i),
@@ -1126,6 +1141,29 @@ class Context:
         if rc == FNX_NOOP:
             return None, 0, 1.0, 0, (dims[0], dims[1]), (dims[2], dims[3])
         self._chk(rc, "fennec_CompressFileJPEG")
+
+    def compress_file_target_size(self, data: bytes, target_bytes: int, orient: int = 1, max_w: int = 0, max_h: int = 0,
+                                  strategies: int = FNX_TS_ALL, cancel=None):
+        """CompressFile for a JPEG or PNG source (the signature decides) in target-size mode, every pixel stage on the device
+        (fennec_CompressFileTargetSize): decode, ApplyOrientation(orient), smartResize(max_w, max_h), hitTargetSize's JPEG
+        strategies -> a dict: `data` (the winner's file, or None), `candidates` and `winner` as jpeg_target_size's, `dims`
+        ((original w, h), (final w, h)) and `status` (FNX_OK / FNX_NOOP).  `cancel`: a ctypes.c_int, as jpeg_target_size's."""
+        if cancel is not None and not isinstance(cancel, C.c_int):
+            raise FennecError("compress_file_target_size: cancel must be a ctypes.c_int (or None)")
+        src = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, dtype=np.uint8)
+        o = TargetOptions.make(target_bytes, orient, max_w, max_h, strategies)
+        cand = (SizeCandidate * 4)()
+        win, n = C.c_int(-1), C.c_size_t(0)
+        dims = (C.c_int * 4)()
+        pc = C.byref(cancel) if cancel is not None else None
+        # a winner within the target fits; one over it (the fallback, strategy 4's encode at bestQ) asks again with its size
+        rc, buf = _into_buffer(lambda b, c: self._lib.fennec_CompressFileTargetSize(self._h, src.ctypes.data_as(_u8p), len(data), C.byref(o), pc,
+                                                                                    cand, C.byref(win), b.ctypes.data_as(_u8p), c, C.byref(n),
+                                                                                    dims), max(4096, int(target_bytes) + 4096), n)
+        self._chk(rc, "fennec_CompressFileTargetSize")
+        out = {"candidates": [c.as_dict() for c in cand], "winner": win.value if rc == FNX_OK else None,
+               "data": buf[:n.value].tobytes() if rc == FNX_OK else None, "dims": ((dims[0], dims[1]), (dims[2], dims[3])), "status": rc}
+        return out
 
     def jpeg_quality_search(self, img, target_ssim: float, window=None):
         """compressJPEGOptimal's binary search with every candidate round-tripped and scored on the device

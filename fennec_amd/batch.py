@@ -604,3 +604,89 @@ def compress_batch_jpeg_native(files: Sequence[bytes], target_ssim: float = TARG
                 r2[k].host_decoded = True
                 results[i], out_files[i] = r2[k], f2[k]
     return results, out_files, summarize_local(results)
+
+
+def _better_fit_pick(cands, target: int):
+    """the index betterFit (targetsize.go:92-115) picks over the candidates in order, a tie keeping the earlier one; None: no candidate"""
+    best = None
+    for k, c in enumerate(cands):
+        if not c["strategy"]:
+            continue
+        if best is None:
+            best = k
+            continue
+        b = cands[best]
+        cu, bu = c["nbytes"] <= target, b["nbytes"] <= target
+        if cu != bu:
+            better = cu
+        elif cu:
+            better = c["ssim"] > b["ssim"] if c["ssim"] != b["ssim"] else c["quality"] > b["quality"]
+        else:
+            better = c["nbytes"] < b["nbytes"]
+        if better:
+            best = k
+    return best
+
+
+def compress_batch_target_size_native(files: Sequence[bytes], target_bytes: int, workers: int = 4, device: int = 0, orient: int = 1,
+                                      max_w: int = 0, max_h: int = 0, strategies: Optional[int] = None, item_opts: Optional[Sequence] = None,
+                                      cancel=None):
+    """fennec_CompressBatchTargetSize: CompressBatch over JPEG or PNG FILES in target-size mode (Options.TargetSize) -- the C++
+    pool, per item decode, orientation, smartResize and hitTargetSize's JPEG strategies on the device
+    (fennec_CompressFileTargetSize).  The keyword options are BatchOptions.DefaultOpts; item_opts[i] (a fennec_amd.TargetOptions,
+    or None) is item i's own.  An item whose winner is over its target, and so over its buffer, runs once more into a buffer of
+    the size it reported.  -> (results, files, summary); each result also carries status, steps, device, winner (index or None),
+    candidates (four dicts) and dims ((original w, h), (final w, h))."""
+    import ctypes as C
+
+    import fennec_amd as fa
+    L = fa.load_library()
+    n = len(files)
+    if n == 0:
+        return [], [], BatchSummary()
+    if cancel is not None and not isinstance(cancel, C.c_int):
+        raise fa.FennecError("compress_batch_target_size_native: cancel must be a ctypes.c_int (or None)")
+    default = fa.TargetOptions.make(target_bytes, orient, max_w, max_h, fa.FNX_TS_ALL if strategies is None else strategies)
+    own = list(item_opts) if item_opts is not None else [None] * n
+    if len(own) != n:
+        raise fa.FennecError(f"compress_batch_target_size_native: {len(own)} item options for {n} files")
+    popts = (C.POINTER(fa.TargetOptions) * n)(*[C.pointer(o) if o is not None else C.POINTER(fa.TargetOptions)() for o in own])
+    arrs = [np.frombuffer(f, dtype=np.uint8) if len(f) else np.zeros(1, dtype=np.uint8) for f in files]
+    srcs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
+    sizes = (C.c_size_t * n)(*[len(f) for f in files])
+    capl = [max(4096, int((own[i] or default).target_bytes) + 4096) for i in range(n)]
+    bufs = [np.empty(c, dtype=np.uint8) for c in capl]
+    outs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    caps = (C.c_size_t * n)(*capl)
+    res = (fa.NativeBatchResult * n)()
+    cands = (fa.SizeCandidate * (4 * n))()
+    dims = (C.c_int * (4 * n))()
+    pc = C.byref(cancel) if cancel is not None else None
+    rc = L.fennec_CompressBatchTargetSize(int(device), int(workers), n, srcs, sizes, C.byref(default), popts, outs, caps, res, cands, dims, pc,
+                                          None, None)
+    if rc != fa.FNX_OK:
+        raise fa.FennecError(f"fennec_CompressBatchTargetSize: {L.fnx_last_error().decode()}")
+    for i in range(n):
+        if res[i].failed and res[i].status == fa.FNX_ERR_INVALID and int(res[i].compressed_size) > capl[i]:
+            big = np.empty(int(res[i].compressed_size), dtype=np.uint8)
+            one, c1, d1 = (fa.NativeBatchResult * 1)(), (fa.SizeCandidate * 4)(), (C.c_int * 4)()
+            L.fennec_CompressBatchTargetSize(int(device), 1, 1, (C.c_void_p * 1)(arrs[i].ctypes.data), (C.c_size_t * 1)(len(files[i])),
+                                             C.byref(own[i] or default), None, (C.c_void_p * 1)(big.ctypes.data), (C.c_size_t * 1)(big.size),
+                                             one, c1, d1, pc, None, None)
+            one[0].index = i
+            res[i] = one[0]
+            cands[4 * i:4 * i + 4] = list(c1)
+            dims[4 * i:4 * i + 4] = list(d1)
+            bufs[i] = big
+    results, out_files = [], []
+    for i in range(n):
+        r = res[i]
+        br = BatchResult(Index=r.index, OriginalSize=int(r.original_size), CompressedSize=int(r.compressed_size), SSIM=float(r.ssim),
+                         Quality=int(r.quality), Err=None if not r.failed else f"status {r.status}", has_result=bool(r.has_result))
+        br.status, br.steps, br.device = int(r.status), int(r.steps), int(r.device)
+        br.candidates = [cands[4 * i + k].as_dict() for k in range(4)]
+        br.winner = _better_fit_pick(br.candidates, int((own[i] or default).target_bytes))
+        br.dims = ((dims[4 * i], dims[4 * i + 1]), (dims[4 * i + 2], dims[4 * i + 3]))
+        results.append(br)
+        out_files.append(bufs[i][:int(r.compressed_size)].tobytes() if not r.failed else b"")
+    return results, out_files, summarize_local(results)

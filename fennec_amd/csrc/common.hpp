@@ -44,6 +44,7 @@ enum Form {
     FORM_MSSSIM_BOXFLY,      // "msssim_boxfly":   "1" = levels 1..4's boxes taken on the fly
     FORM_PALETTE_GRID,       // "palette_grid":    "0" every image walks the whole palette / "1" every image takes the grid
     FORM_RESIZE_BOX,         // "resize_box":      "1" = resize_box_kernel where its domain allows (default: the resize kernels, then the box kernel)
+    FORM_JPEG_SIZE,          // "jpeg_size":       "1" = a size-only JPEG query counts the stuffed bytes from the strips, one wait (default: packed and stuffed as a file is)
     FORM_COUNT
 };
 
@@ -101,6 +102,7 @@ enum Slot {
     SLOT_JPEG2,
     SLOT_JPEG3,
     SLOT_JPEG_ENC, SLOT_JPEG_ENC2, SLOT_JPEG_LUT, SLOT_JPEG_ECS,   // jpeg.hip's entropy coder
+    SLOT_JPEG_FF,    // jpeg_ffcount_strips_kernel's 0xff total, zero between queries
     SLOT_FILE0, SLOT_FILE1, SLOT_FILE_SAMPLES,                     // host_api.cpp: fennec_CompressFileJPEG's images between its stages
     SLOT_JPEG_DEC, SLOT_JPEG_DEC_PLANES, SLOT_JPEG_DEC_IMG,        // jpeg_dec.hip: the decoder's work arrays, its planes, toNRGBARef's image
     SLOT_AN_HASH0, SLOT_AN_HASH1,   // analyze.hip: the colour-set tables of this call and the next (the launch that uses one zeroes the other)
@@ -628,6 +630,8 @@ void jpeg_header(int w, int h, int quality, std::vector<uint8_t> &out);
 int jpeg_entropy_code(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *const planes[3], unsigned long long *totals);
 size_t jpeg_ecs_capacity(unsigned long long total_bits);
 int jpeg_entropy_pack(fnx_ctx *ctx, int w, int h, unsigned long long total_bits, uint8_t *ecs, unsigned long long *totals);
+// behind jpeg_entropy_code on the same stream: totals[1] = the 0xff bytes of the string, counted from the blocks' strips (no packed string)
+int jpeg_entropy_ffcount(fnx_ctx *ctx, int w, int h, unsigned long long *totals);
 int launch_jpeg_blocks(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *const in[3], uint8_t *const out[3]);
 // ---- batched forms (fnx_jpeg_compress_batch): n images of one geometry, the image index in grid x ----
 constexpr int JPEG_QTAB_WORDS = 101 * 2 * 2 * 64;   // [quality 0..100][luma, chroma][step, magic][64]: the per-ctx quality table

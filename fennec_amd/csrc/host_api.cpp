@@ -780,6 +780,86 @@ int fennec_CompressBatchJPEGOpts(int device, int workers, int n, const uint8_t *
     });
 }
 
+// Options.TargetSize > 0 (fennec.go:143-160): a non-empty subset of the four strategies, nothing in the reserved word
+static int check_target_options(const fennec_TargetOptions *o, const char *what)
+{
+    if (o->target_bytes <= 0) {
+        set_error("invalid argument: %s: target_bytes must be > 0", what);
+        return FNX_ERR_INVALID;
+    }
+    if (o->strategies <= 0 || (o->strategies & ~(FNX_TS_QUALITY | FNX_TS_QUALITY_SCALE | FNX_TS_SCALE | FNX_TS_FALLBACK)) != 0) {
+        set_error("invalid argument: %s: strategies must be a non-empty subset of bits 1, 2, 4, 8", what);
+        return FNX_ERR_INVALID;
+    }
+    if (o->reserved != 0) {
+        set_error("invalid argument: %s: reserved must be 0", what);
+        return FNX_ERR_INVALID;
+    }
+    return FNX_OK;
+}
+
+// CompressFile in target-size mode (fennec.go:107-160) from the file's bytes: fennec_CompressFileJPEG's stages, then
+// hitTargetSize's JPEG legs on the resident image in one call.
+int fennec_CompressFileTargetSize(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_TargetOptions *o, const volatile int *cancel,
+                                  fnx_size_candidate cand[4], int *winner, uint8_t *out, size_t cap, size_t *nbytes, int dims[4])
+{
+    if (!data || !o || !cand || !winner || !nbytes || !dims || (!out && cap)) {
+        set_error("invalid argument: CompressFileTargetSize: NULL argument");
+        return FNX_ERR_INVALID;
+    }
+    FNX_TRY(check_target_options(o, "CompressFileTargetSize"));
+    if (!ctx) {
+        set_error("invalid argument: CompressFileTargetSize: null ctx");
+        return FNX_ERR_INVALID;
+    }
+    std::memset(cand, 0, sizeof(fnx_size_candidate) * 4);
+    *winner = -1;
+    *nbytes = 0;
+    dims[0] = dims[1] = dims[2] = dims[3] = 0;
+    int w = 0, h = 0;
+    FNX_TRY(decode_file(ctx, data, n, FNX_HOST, nullptr, 0, &w, &h));          // dimensions; refuses what the device decoder does not take
+    const uint8_t *img = nullptr;
+    FNX_TRY(file_stages(ctx, data, n, &o->file, w, h, &img, &w, &h, dims));
+    const int rc = fnx_jpeg_target_size(ctx, FNX_DEVICE, img, w * 4, w, h, o->target_bytes, o->strategies, ssim_window(), cancel, cand, winner,
+                                        out, cap, nbytes, nullptr, 0);
+    if (*winner >= 0) {                                                        // fennec.go:153: FinalDimensions = the size result's
+        dims[2] = cand[*winner].final_w;
+        dims[3] = cand[*winner].final_h;
+    }
+    return rc;
+}
+
+int fennec_CompressBatchTargetSize(int device, int workers, int n, const uint8_t *const *files, const size_t *sizes,
+                                   const fennec_TargetOptions *default_opts, const fennec_TargetOptions *const *item_opts, uint8_t *const *outs,
+                                   const size_t *caps, fennec_BatchResult *results, fnx_size_candidate *cands, int *dims,
+                                   const volatile int *cancel, fennec_on_item on_item, void *user)
+{
+    if (n <= 0) return FNX_OK;                                   // batch.go:59-61
+    if (!files || !sizes || !default_opts || !outs || !caps || !results) {
+        set_error("invalid argument: CompressBatch arrays");
+        return FNX_ERR_INVALID;
+    }
+    FNX_TRY(check_target_options(default_opts, "CompressBatchTargetSize: default_opts"));
+    return run_batch_pool(device, workers, n, results, cancel, on_item, user, [&](fnx_ctx *ctx, int idx, fennec_BatchResult &r) {
+        r.device = fnx_ctx_device(ctx);
+        const fennec_TargetOptions &o = item_opts && item_opts[idx] ? *item_opts[idx] : *default_opts;      // batch.go:101-105
+        fnx_size_candidate c4[4] = {};
+        size_t nbytes = 0;
+        int win = -1, d4[4] = {0, 0, 0, 0};
+        const int rc = fennec_CompressFileTargetSize(ctx, files[idx], sizes[idx], &o, cancel, c4, &win, outs[idx], caps[idx], &nbytes, d4);
+        if (cands) std::memcpy(cands + 4 * idx, c4, sizeof(c4));
+        if (dims) std::memcpy(dims + 4 * idx, d4, sizeof(d4));
+        r.status = rc;                                           // FNX_NOOP: no candidate; FNX_ERR_UNSUPPORTED: host decode
+        r.failed = rc == FNX_OK ? 0 : 1;
+        r.has_result = rc == FNX_OK ? 1 : 0;
+        r.quality = win >= 0 ? c4[win].quality : 0;
+        r.ssim = win >= 0 ? c4[win].ssim : 0.0;
+        r.steps = c4[0].steps + c4[1].steps + c4[2].steps + c4[3].steps;
+        r.original_size = static_cast<int64_t>(sizes[idx]);
+        r.compressed_size = static_cast<int64_t>(nbytes);
+    });
+}
+
 double fennec_SummarizeResults(int n, const fennec_BatchResult *results, int64_t out4[4])
 {   // batch.go:140-158
     int64_t succeeded = 0, nfailed = 0, saved = 0;

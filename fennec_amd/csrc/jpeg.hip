@@ -961,6 +961,68 @@ int jpeg_entropy_pack(fnx_ctx *ctx, int w, int h, unsigned long long total_bits,
         hipLaunchKernelGGL(jpeg_stuff_kernel, dim3((nwords + 255) / 256), dim3(256), 0, ctx->stream, sa);
     }
     FNX_HIP(hipGetLastError());
+    note_route(ctx, FNX_PROF_JPEG, "jpeg_pack_kernel");
+    return FNX_OK;
+}
+
+// ---- the size of the file without its bytes: the 0xff bytes of the string, counted from the strips ----
+// A size query needs (bits + 7) / 8 + the number of stuffed bytes, and the second term can be had without the packed string:
+// lane = block counts the bytes whose first bit lies in its block (jpeg_ffcount_strips.inc: the ownership rule), the wave
+// adds its lanes' counts up and adds the sum to `total` (integer sums: the order does not matter); jpeg_ffcount_finish_kernel,
+// the next launch on the stream, hands the total to the host's pinned slot and puts `total` back to zero for the next query.
+// (A hand-over by the workgroup that finishes last needs a device-scope fence per workgroup, and on this part each of them
+// writes back the L2 the coder's kernels have just filled: ~45 us of a 4K query, measured.  A launch boundary orders the same
+// for ~5 us.)
+struct FfStripArgs {
+    const uint32_t *strip, *nbits;
+    const unsigned long long *pos;
+    unsigned long long *total;         // device, zero between queries
+    int nblk;
+};
+
+__global__ __launch_bounds__(256) void jpeg_ffcount_strips_kernel(FfStripArgs a)
+{
+    const int blk = blockIdx.x * 256 + threadIdx.x;
+    uint32_t count = 0;
+    if (blk < a.nblk) {
+        const uint32_t *strip = a.strip, *nbits = a.nbits;
+        const unsigned long long *pos = a.pos;
+        const int nblk = a.nblk;
+#include "jpeg_ffcount_strips.inc"
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) count += __shfl_down(count, off, 64);
+    if ((threadIdx.x & 63) == 0 && count) atomicAdd(a.total, static_cast<unsigned long long>(count));
+}
+
+__global__ __launch_bounds__(64) void jpeg_ffcount_finish_kernel(unsigned long long *total, unsigned long long *out)
+{
+    if (threadIdx.x == 0) out[0] = atomicExch(total, 0ull);
+}
+
+int jpeg_entropy_ffcount(fnx_ctx *ctx, int w, int h, unsigned long long *totals)
+{
+    int ys, yh, cs, chh;
+    jpeg_plane_dims(w, h, &ys, &yh, &cs, &chh);
+    const int nblk = (ys / 16) * (yh / 16) * 6;
+    auto al = [](size_t n) { return (n + 255) & ~size_t(255); };
+    // jpeg_entropy_code's layout (same slot, same sizes: nothing moves)
+    const size_t b_coef = al(sizeof(int16_t) * 64 * nblk), b_strip = al(4 * static_cast<size_t>(nblk) * JPEG_STRIP), b_nbits = al(4 * size_t(nblk));
+    void *sc = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_JPEG_ENC, b_coef + b_strip + b_nbits + al(8 * size_t(nblk)) + al(8 * (size_t(nblk) / SCAN_PER_WG + 2)), &sc));
+    unsigned char *p = static_cast<unsigned char *>(sc) + b_coef;
+    const uint32_t *strip = reinterpret_cast<const uint32_t *>(p); p += b_strip;
+    const uint32_t *nbits = reinterpret_cast<const uint32_t *>(p); p += b_nbits;
+    const unsigned long long *pos = reinterpret_cast<const unsigned long long *>(p);
+    const void *before = ctx->slot[SLOT_JPEG_FF].p;
+    void *ff = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_JPEG_FF, 16, &ff));
+    if (ff != before) FNX_HIP(hipMemsetAsync(ff, 0, 16, ctx->stream));      // first use: the finish kernel keeps it zero from here on
+    FfStripArgs fa{strip, nbits, pos, static_cast<unsigned long long *>(ff), nblk};
+    hipLaunchKernelGGL(jpeg_ffcount_strips_kernel, dim3((nblk + 255) / 256), dim3(256), 0, ctx->stream, fa);
+    hipLaunchKernelGGL(jpeg_ffcount_finish_kernel, dim3(1), dim3(64), 0, ctx->stream, fa.total, totals + 1);
+    FNX_HIP(hipGetLastError());
+    note_route(ctx, FNX_PROF_JPEG, "jpeg_ffcount_strips_kernel");
     return FNX_OK;
 }
 

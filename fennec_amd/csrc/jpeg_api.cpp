@@ -154,6 +154,14 @@ size_t jpeg_file_frame(const std::vector<uint8_t> &hdr, size_t ecs, uint8_t *out
     return total;
 }
 
+// the "jpeg_size" form: "1" = a size-only query takes the one-wait route; "0" and unset = the file's two steps (opt-in: DESIGN.md
+// 5.1 has the measurement and the rule it has to pass to become the default)
+bool jpeg_size_one_wait(const fnx_ctx *ctx)
+{
+    const char *v = form_value(ctx, FORM_JPEG_SIZE);
+    return v && v[0] == '1';
+}
+
 // the file of `orig`'s image at `quality` into host memory (see fnx_jpeg_encode)
 int jpeg_file_from_planes(fnx_ctx *ctx, const JpegPlanes &orig, int w, int h, int quality, uint8_t *out, size_t cap, size_t *nbytes)
 {
@@ -164,6 +172,16 @@ int jpeg_file_from_planes(fnx_ctx *ctx, const JpegPlanes &orig, int w, int h, in
     totals[0] = totals[1] = ~0ull;
     const uint8_t *planes[3] = {orig.p[0], orig.p[1], orig.p[2]};
     FNX_TRY(jpeg_entropy_code(ctx, w, h, quality, planes, totals));
+    if (out == nullptr && cap == 0 && jpeg_size_one_wait(ctx)) {
+        // a size query never needs the packed string: the stuffed bytes are counted from the blocks' strips behind the scan,
+        // and both totals come back in ONE wait (jpeg.hip: jpeg_ffcount_strips_kernel)
+        FNX_TRY(jpeg_entropy_ffcount(ctx, w, h, totals));
+        FNX_HIP(hipStreamSynchronize(ctx->stream));
+        std::vector<uint8_t> hdr;
+        jpeg_header(w, h, quality, hdr);
+        *nbytes = jpeg_file_frame(hdr, jpeg_ecs_bytes(totals[0], totals[1]), nullptr, 0);
+        return FNX_OK;
+    }
     FNX_HIP(hipStreamSynchronize(ctx->stream));
     const unsigned long long tbits = totals[0];
     void *ecs = nullptr;

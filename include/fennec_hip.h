@@ -183,6 +183,13 @@ int fnx_ctx_set_png_adam7(fnx_ctx *ctx, int accept);
  *   "palette_grid" "0|1"   applyPalette: whole-palette walk for every image / the candidate grid for every image
  *   "resize_box" "1"       fnx_lanczos_box_downsample, fnx_ssim_fast_resized, target-size mode: resize_box_kernel where its
  *                          domain allows ("0" and the default: lanczosResize into scratch, then the box kernel)
+ *   "jpeg_size" "1"        a size-only JPEG query (out == NULL with cap == 0 in fnx_jpeg_encode / _encode_scaled, every query of
+ *                          fnx_jpeg_size_search, fnx_jpeg_target_size and fennec_CompressFileTargetSize): the stuffed bytes are
+ *                          counted from the blocks' strips (jpeg_ffcount_strips_kernel) and the size comes back in one wait
+ *                          ("0" and the default: the string is packed and stuffed as for a file, two waits; files always
+ *                          are).  Opt-in: DESIGN.md 5.1 has the measurement.  fnx_ctx_last_kernel(ctx, FNX_PROF_JPEG) names
+ *                          jpeg_ffcount_strips_kernel or jpeg_pack_kernel after such a query.  The fennec_CompressBatch* pools
+ *                          create their own contexts and keep the default
  * value NULL: back to the default.  Unknown name or a value longer than 7 characters: FNX_ERR_INVALID.  No reference counterpart. */
 int fnx_ctx_set_form(fnx_ctx *ctx, const char *name, const char *value);
 
@@ -1007,8 +1014,9 @@ int fennec_CompressBatchNRGBADevices(const int *devices, int ndev, int workers, 
  * smartResize when max_w or max_h > 0 (Options.MaxWidth / MaxHeight), analyzeFormat when auto_format (Format: Auto),
  * compressJPEGOptimal at target_ssim.  dims = {OriginalDimensions (after orientation), FinalDimensions}.
  * FNX_NOOP: analyzeFormat chose PNG (a translucent sampled pixel, which only a PNG source can have, or fewer than 256 sampled
- * colours) -- the caller's compressPNG takes the item, dims are set.  FNX_ERR_UNSUPPORTED as fnx_jpeg_decode / fnx_png_decode.  Target-size mode is a call of its own: hitTargetSize's JPEG
- * strategies run on the device in fnx_jpeg_target_size (the PNG strategy stays the caller's). */
+ * colours) -- the caller's compressPNG takes the item, dims are set.  FNX_ERR_UNSUPPORTED as fnx_jpeg_decode / fnx_png_decode.  Target-size mode
+ * (Options.TargetSize) has a file entry of its own, fennec_CompressFileTargetSize below, and its pool,
+ * fennec_CompressBatchTargetSize. */
 typedef struct fennec_FileOptions {
     int32_t orient;      /* EXIF orientation 1..8; <= 1: none */
     int32_t max_w, max_h;
@@ -1065,6 +1073,43 @@ int fennec_CompressBatchJPEGOpts(int device, int workers, int n, const uint8_t *
                                  const fennec_FileOptions *default_opts, const fennec_FileOptions *const *item_opts /* may be NULL */,
                                  uint8_t *const *outs, const size_t *caps, fennec_BatchResult *results, int *dims /* may be NULL */,
                                  const volatile int *cancel /* may be NULL */, fennec_on_item on_item /* may be NULL */, void *user);
+/* CompressFile for a JPEG or PNG source in target-size mode (fennec.go:107-160 with Options.TargetSize > 0) from the file's
+ * bytes, every pixel stage on the device: image.Decode + toNRGBA, ApplyOrientation and smartResize staged exactly as
+ * fennec_CompressFileJPEG stages them (opts->file; its auto_format and target_ssim are ignored), then ONE
+ * fnx_jpeg_target_size on the resident image with the library's SSIM window: cand, *winner, out / cap / *nbytes and cancel are
+ * that call's.  `strategies` with all four bits is hitTargetSize under Format: JPEG (targetsize.go:26-75 with wantJPEG).
+ * Format: Auto runs quantizeStrategy between strategies 1 and 3, and that one stays the caller's: such a caller passes
+ * strategy subsets (FNX_TS_QUALITY, then its own quantizeStrategy, then the rest) and applies betterFit over all candidates
+ * itself, as go/fennec_hip.go's hitTargetSize does over decoded images.
+ * dims[0..1] = OriginalDimensions (after orientation); dims[2..3] = the winner's final_w x final_h (fennec.go:153 overwrites
+ * FinalDimensions with the size result's) -- the staged image's size when there is no winner.
+ * FNX_OK: a winner, its file in out.  FNX_NOOP: no candidate (possible only without FNX_TS_FALLBACK).  FNX_ERR_UNSUPPORTED
+ * as fnx_jpeg_decode / fnx_png_decode.  FNX_ERR_INVALID before any device work: a NULL among ctx, data, opts, cand, winner,
+ * nbytes, dims (out may be NULL with cap == 0: the size only), target_bytes <= 0, strategies not a non-empty subset of the
+ * four bits, reserved != 0.  FNX_ERR_INVALID with *nbytes, cand, *winner and dims filled: cap is below the file's size -- call
+ * again with *nbytes.  A winner that fits the target fits a buffer of target_bytes, so this happens only for winners OVER the
+ * target: the fallback's file, and strategy 4's encode at bestQ. */
+typedef struct fennec_TargetOptions {
+    fennec_FileOptions file; /* orient, max_w, max_h as for fennec_CompressFileJPEG; auto_format and target_ssim ignored */
+    int64_t target_bytes;    /* Options.TargetSize, > 0 */
+    int32_t strategies;      /* FNX_TS_* mask; all four bits = Format: JPEG */
+    int32_t reserved;        /* 0 */
+} fennec_TargetOptions;      /* 40 bytes */
+int fennec_CompressFileTargetSize(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_TargetOptions *opts,
+                                  const volatile int *cancel /* may be NULL */, fnx_size_candidate cand[4], int *winner,
+                                  uint8_t *out, size_t cap, size_t *nbytes, int dims[4]);
+/* The pool of fennec_CompressBatchJPEGOpts over files in target-size mode: per item fennec_CompressFileTargetSize under
+ * item_opts[i] when that is not NULL, else under *default_opts (batch.go:101-105); `cancel` is the pool's (checked before each
+ * item) and each item's (checked where hitTargetSize checks ctx.Err()).  Per result: quality and ssim the winner's,
+ * compressed_size = the file's size, steps = the four candidates' steps added up, original_size = sizes[i], status the
+ * item call's status, failed for anything but FNX_OK (an item whose buffer was too small comes back FNX_ERR_INVALID with
+ * compressed_size set).  cands (may be NULL): 4 per item; dims (may be NULL): 4 ints per item.  FNX_ERR_INVALID before the
+ * pool starts: a NULL array, or *default_opts refused as above. */
+int fennec_CompressBatchTargetSize(int device, int workers, int n, const uint8_t *const *files, const size_t *sizes,
+                                   const fennec_TargetOptions *default_opts, const fennec_TargetOptions *const *item_opts /* may be NULL */,
+                                   uint8_t *const *outs, const size_t *caps, fennec_BatchResult *results,
+                                   fnx_size_candidate *cands /* 4 per item, may be NULL */, int *dims /* 4 per item, may be NULL */,
+                                   const volatile int *cancel /* may be NULL */, fennec_on_item on_item /* may be NULL */, void *user);
 /* The pool's idle worker contexts (kept between batches, per device) are destroyed. */
 void fennec_pool_release(void);
 /* Summarize (batch.go:140-158) of such results: out4 = {Total, Succeeded, Failed, TotalSaved}; returns AvgSSIM. */

@@ -1,12 +1,15 @@
-"""Target-size mode's JPEG legs (hitTargetSize, targetsize.go:26-357) per 4K item, three routes:
+"""Target-size mode's JPEG legs (hitTargetSize, targetsize.go:26-357) per 4K item, five routes:
 
   (a) the composed route the Go shim took before fnx_jpeg_target_size: host-space fnx_jpeg_size_search for strategy 1;
       a resident source with fnx_box_downsample(FNX_DEVICE_SRC) + a host-space size search per scale step; host-space
       Lanczos and SSIMFast for computeSSIMNRGBA
   (b) fnx_jpeg_target_size from a host source
-  (c) the same from a device-resident source
+  (c) the same from a device-resident source, size queries by the two-step route (form "jpeg_size" "0")
+  (d) the same with the size queries answered in one wait (form "jpeg_size" "1": jpeg_ffcount_strips_kernel)
+  (e) fennec_CompressFileTargetSize from the source's JPEG file (quality 95), form "jpeg_size" "1": decode, search and the
+      winner's file, nothing but file bytes crossing (its image is the decoded file, so its winner is its own)
 
-per row: ms per item (median of --reps), size queries, the winning strategy and its file size.  Then the fused
+(a) and (b) run under the ctx's default form, which the first line names.  per row: ms per item (median of --reps, and the runs' minimum and maximum), size queries, the winning strategy and its file size.  Then the fused
 box-downsample + colour conversion (fnx_jpeg_encode_scaled's size query) against box_tiled_kernel into an image followed
 by jpeg_ycc_kernel (fennec_boxDownsample + fnx_jpeg_encode's size query) for the same geometries; both include the same
 entropy-coded size query, so the difference is the kernels'.
@@ -125,13 +128,20 @@ def route_a(ctx, img, dev, target):
     return best, nq
 
 
+class Ms(float):
+    """the median of a timed() call's runs, their minimum and maximum beside it"""
+    lo = hi = 0.0
+
+
 def timed(fn, reps):
     out, ts = None, []
     for _ in range(reps):
         t0 = time.perf_counter()
         out = fn()
         ts.append((time.perf_counter() - t0) * 1e3)
-    return out, statistics.median(ts)
+    ms = Ms(statistics.median(ts))
+    ms.lo, ms.hi = min(ts), max(ts)
+    return out, ms
 
 
 def main():
@@ -142,8 +152,11 @@ def main():
     ctx = fennec_amd.Context(0)
     sources = {"photo": synth.large_photo(3840, 2160, 1),
                "noise": ctx.GaussianBlur(synth.noise_image(3840, 2160, 2), 1.0, exact=True)}
-    print(f"# {torch.cuda.get_device_name(0)}; 3840 x 2160 sources; ms = median of {args.reps}")
-    print(f"{'source':6} {'target':>9} {'route':5} {'ms':>9} {'queries':>7} {'winner':>6} {'q':>3} {'bytes':>9}")
+    print(f"# {torch.cuda.get_device_name(0)}; 3840 x 2160 sources; ms = median of {args.reps} (their minimum .. maximum)")
+    print(f"{'source':6} {'target':>9} {'route':5} {'ms':>9} {'min .. max':>17} {'queries':>7} {'winner':>6} {'q':>3} {'bytes':>9}")
+    files = {name: ctx.jpeg_encode(img, 95) for name, img in sources.items()}
+    ctx.jpeg_encoded_size(sources["photo"][:64, :64].copy(), 50)
+    print(f"# default size-query route of this build: {ctx.last_kernel(16)}")
     for name, img in sources.items():
         dev = torch.from_numpy(img).cuda()
         torch.cuda.synchronize()
@@ -154,8 +167,13 @@ def main():
         for target in (q100 // 4, q20 // 3, 700):
             wa, ms_a = timed(lambda: route_a(ctx, img, dev, target), args.reps)
             rb, ms_b = timed(lambda: ctx.jpeg_target_size(img, target, FNX_TS_ALL), args.reps)
-            rc, ms_c = timed(lambda: ctx.jpeg_target_size(dev, target, FNX_TS_ALL), args.reps)
-            for route, ms, res in (("a", ms_a, None), ("b", ms_b, rb), ("c", ms_c, rc)):
+            with ctx.forms(jpeg_size="0"):
+                rc, ms_c = timed(lambda: ctx.jpeg_target_size(dev, target, FNX_TS_ALL), args.reps)
+            with ctx.forms(jpeg_size="1"):
+                rd, ms_d = timed(lambda: ctx.jpeg_target_size(dev, target, FNX_TS_ALL), args.reps)
+                re_, ms_e = timed(lambda: ctx.compress_file_target_size(files[name], target), args.reps)
+            assert (rc["candidates"], rc["winner"], rc["data"]) == (rd["candidates"], rd["winner"], rd["data"]), "forms disagree"
+            for route, ms, res in (("a", ms_a, None), ("b", ms_b, rb), ("c", ms_c, rc), ("d", ms_d, rd), ("e", ms_e, re_)):
                 if res is None:
                     c, nq = wa
                     win = {1: 1, 2: 3, 4: 4, 8: "fb"}[c["strategy"]]
@@ -163,7 +181,7 @@ def main():
                     c = res["candidates"][res["winner"]]
                     nq = sum(x["steps"] for x in res["candidates"])
                     win = {1: 1, 2: 3, 4: 4, 8: "fb"}[c["strategy"]]
-                print(f"{name:6} {target:9d} {route:5} {ms:9.1f} {nq:7d} {win!s:>6} {c['quality']:3d} {c['nbytes']:9d}")
+                print(f"{name:6} {target:9d} {route:5} {ms:9.1f} {f'{ms.lo:.1f} .. {ms.hi:.1f}':>17} {nq:7d} {win!s:>6} {c['quality']:3d} {c['nbytes']:9d}")
             assert (wa[0]["quality"], wa[0]["nbytes"]) == (rb["candidates"][rb["winner"]]["quality"], len(rb["data"])), "routes disagree"
     # the fused kernel against box_tiled_kernel + jpeg_ycc_kernel (each with the same size query behind it)
     print("\n# one scale step's size query at quality 50: fused planes vs downsampled image + colour conversion (device source)")
