@@ -1568,6 +1568,17 @@ class Context:
                 space, ptr, stride = FNX_HOST, src.ctypes.data, int(src.strides[0]) if h > 1 else w
         return kind, space, ptr, stride, w, h
 
+    @staticmethod
+    def _flat_out(out, space):
+        """(pointer, space of the call) for png_filter's / deflate's `out`, a flat uint8 buffer: a device tensor (device sources
+        only) or a numpy array, which a device source fills through FNX_DEVICE_SRC"""
+        on_device = _is_torch(out)
+        if on_device and space != FNX_DEVICE:
+            raise FennecError("a device stream needs a device source")
+        if out.ndim != 1 or not (out.is_contiguous() if on_device else (out.dtype == np.uint8 and out.flags.c_contiguous)):
+            raise FennecError("out must be a flat contiguous uint8 buffer")
+        return (out.data_ptr() if on_device else out.ctypes.data), (space if on_device or space == FNX_HOST else FNX_DEVICE_SRC)
+
     def png_filter(self, src, kind: int | None = None, ncolors: int = 0, opaque: int = -1, out=None):
         """The PNG encoder's row stage (fnx_png_filter; compress.go:94-107) -> (stream (h, 1 + n) uint8, color_type, bit_depth):
         every row packed, filtered by the cheapest of the five PNG filters and led by its type byte -- the bytes zlib reads.
@@ -1583,14 +1594,9 @@ class Context:
             return self._lib.fnx_png_filter(self._h, sp, int(kind), ptr, stride, w, h, int(ncolors), int(opaque), optr, cap, C.byref(n),
                                             C.byref(ct), C.byref(bd))
         if out is not None:
-            on_device = _is_torch(out)
-            if on_device and space != FNX_DEVICE:
-                raise FennecError("a device stream needs a device source")
-            if out.ndim != 1 or not (out.is_contiguous() if on_device else (out.dtype == np.uint8 and out.flags.c_contiguous)):
-                raise FennecError("out must be a flat contiguous uint8 buffer")
-            optr = out.data_ptr() if on_device else out.ctypes.data
+            optr, sp = self._flat_out(out, space)
             with self._ordered(src, out):
-                self._chk(call(space if on_device or space == FNX_HOST else FNX_DEVICE_SRC, optr, int(out.shape[0])), "fnx_png_filter")
+                self._chk(call(sp, optr, int(out.shape[0])), "fnx_png_filter")
             return out[:n.value].reshape(h, n.value // h), ct.value, bd.value
         # one call: an image whose opacity the call itself finds gets room for RGBA rows, and the stream is a view of its front
         cap = h * (1 + (4 * w if kind == FNX_PNG_NRGBA and opaque != 1 else 3 * w if kind == FNX_PNG_NRGBA else w))
@@ -1650,12 +1656,7 @@ class Context:
         else:
             fresh = False
         on_device = _is_torch(out)
-        if on_device and space != FNX_DEVICE:
-            raise FennecError("a device stream needs a device source")
-        if out.ndim != 1 or not (out.is_contiguous() if on_device else (out.dtype == np.uint8 and out.flags.c_contiguous)):
-            raise FennecError("out must be a flat contiguous uint8 buffer")
-        optr = out.data_ptr() if on_device else out.ctypes.data
-        sp = space if on_device or space == FNX_HOST else FNX_DEVICE_SRC
+        optr, sp = self._flat_out(out, space)
         with self._ordered(buf if space == FNX_DEVICE else None, out if on_device else None):
             self._chk(self._lib.fnx_deflate(self._h, sp, ptr, n, int(row), optr, int(out.shape[0]), C.byref(size)), "fnx_deflate")
         view = out[:size.value]

@@ -1674,162 +1674,3 @@ int fnx_orient(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, 
 }
 
 }  // extern "C"
-
-// ---- compressPNG's pixel stages: tryPalettize, isGrayscale + toGray (compress.go:90-153, convert.go:76-100) ----------
-namespace fnx {
-
-int png_reduce_device(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, int max_colors, uint8_t *d_plane, int pstride,
-                      int *kind, uint8_t *palette, int *ncolors)
-{
-    const void *dres = nullptr;
-    FNX_TRY(launch_png_palettize(ctx, src, sstride, w, h, max_colors, d_plane, pstride, &dres));
-    std::vector<uint32_t> res(png_result_bytes() / sizeof(uint32_t));
-    FNX_TRY(fetch_bytes(ctx, dres, res.data(), png_result_bytes()));
-    *ncolors = 0;
-    if (!res[0]) {                                                   // compress.go:92-96
-        *kind = FNX_PNG_PALETTED;
-        *ncolors = static_cast<int>(res[2]);
-        std::memcpy(palette, &res[4], sizeof(uint32_t) * res[2]);    // r, g, b, a: the words' bytes in memory order
-        if (d_plane) note_route(ctx, FNX_PROF_MAIN, "png_plane_kernel");
-        return FNX_OK;
-    }
-    // compress.go:98: isGrayscale walks the flat Pix, row padding included.  A non-grey VISIBLE pixel met by the colours
-    // pass already answers it (every photograph); otherwise the flat scan decides.
-    bool gray = false;
-    if (!res[1]) {
-        void *df = nullptr;
-        FNX_TRY(scratch(ctx, SLOT_RESULT, 16, &df));
-        FNX_TRY(launch_scan_flags(ctx, src, static_cast<size_t>(h - 1) * sstride + static_cast<size_t>(w) * 4, static_cast<uint32_t *>(df)));
-        uint32_t flags = 0;
-        FNX_TRY(fetch_bytes(ctx, df, &flags, sizeof(flags)));
-        gray = !(flags & 2u);
-    }
-    *kind = gray ? FNX_PNG_GRAY : FNX_PNG_NRGBA;
-    if (gray && d_plane) {                                           // compress.go:99-103: toGray
-        FNX_TRY(launch_png_plane(ctx, src, sstride, w, h, true, d_plane, pstride));
-        note_route(ctx, FNX_PROF_MAIN, "png_plane_kernel");
-    }
-    return FNX_OK;
-}
-
-}  // namespace fnx
-
-extern "C" {
-
-int fnx_png_reduce(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int max_colors, int *kind, uint8_t *palette,
-                   int *ncolors, uint8_t *plane, int pstride)
-{
-    FNX_ENTER(ctx);
-    FNX_TRY(check_space_io(space));
-    FNX_REQUIRE(max_colors >= 1 && max_colors <= 256, "max_colors: 1..256 (image.Paletted indices are uint8)");
-    FNX_REQUIRE(kind != nullptr && palette != nullptr && ncolors != nullptr, "kind, palette and ncolors are outputs");
-    FNX_REQUIRE(w <= 65535 && h <= 65535, "dims: at most 65535 (first-occurrence indices are 32-bit)");
-    FNX_TRY(check_img(src, sstride, w, h, "src"));
-    if (plane) FNX_REQUIRE(pstride >= w, "plane stride");
-    if (w <= 0 || h <= 0) {                                           // an empty colorMap: a palette of no colours (compress.go:116-141)
-        *kind = FNX_PNG_PALETTED;
-        *ncolors = 0;
-        return FNX_OK;
-    }
-    DevImg s;
-    FNX_TRY(stage_in_flat(ctx, space, src, sstride, w, h, SLOT_IN_A, &s));
-    uint8_t *dplane = plane;
-    int dpitch = pstride;
-    if (plane && space != FNX_DEVICE) {
-        dpitch = (w + 3) & ~3;
-        void *t = nullptr;
-        FNX_TRY(scratch(ctx, SLOT_OUT, static_cast<size_t>(dpitch) * h + 16, &t));
-        dplane = static_cast<uint8_t *>(t);
-    }
-    FNX_TRY(png_reduce_device(ctx, s.p, s.stride, w, h, max_colors, dplane, dpitch, kind, palette, ncolors));
-    if (*kind == FNX_PNG_NRGBA) return FNX_OK;                        // the plane stays as it was
-    if (plane && space != FNX_DEVICE) {
-        FNX_HIP(hipMemcpy2DAsync(plane, pstride, dplane, dpitch, w, h, hipMemcpyDeviceToHost, ctx->stream));
-        FNX_HIP(hipStreamSynchronize(ctx->stream));
-    } else if (plane && *kind == FNX_PNG_GRAY) {
-        FNX_HIP(hipStreamSynchronize(ctx->stream));                   // (the gray plane was launched after the last wait)
-    }
-    return FNX_OK;
-}
-
-}  // extern "C"
-
-// ---- the PNG encoder's row stage: pack, five filters, smallest sum (compress.go:94-107, targetsize.go:189, 342) -------
-namespace fnx {
-
-int png_filter_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors, int opaque, bool out_on_device,
-                      uint8_t *out, size_t cap, size_t *nbytes, int *color_type, int *bit_depth)
-{
-    int form = PNG_ROW_GRAY, depth = 8;
-    if (kind == FNX_PNG_PALETTED) {
-        form = PNG_ROW_PALETTED;
-        depth = ncolors <= 2 ? 1 : (ncolors <= 4 ? 2 : (ncolors <= 16 ? 4 : 8));
-        *color_type = 3;
-    } else if (kind == FNX_PNG_GRAY) {
-        *color_type = 0;
-    } else {
-        if (opaque < 0) {                                            // image.NRGBA.Opaque(): visible pixels only
-            void *df = nullptr;
-            FNX_TRY(scratch(ctx, SLOT_RESULT, 16, &df));
-            FNX_TRY(launch_png_alpha(ctx, src, sstride, w, h, static_cast<uint32_t *>(df)));
-            uint32_t translucent = 0;
-            FNX_TRY(fetch_bytes(ctx, df, &translucent, sizeof(translucent)));
-            opaque = translucent ? 0 : 1;
-        }
-        form = opaque ? PNG_ROW_RGB : PNG_ROW_RGBA;
-        *color_type = opaque ? 2 : 6;
-    }
-    *bit_depth = depth;
-    *nbytes = static_cast<size_t>(h) * (static_cast<size_t>(png_row_bytes(form, w, depth)) + 1);
-    if (cap < *nbytes || !out) {
-        set_error("invalid argument: the PNG stream needs %zu bytes of output, cap is %zu", *nbytes, cap);
-        return FNX_ERR_INVALID;
-    }
-    uint8_t *d_out = out;
-    if (!out_on_device) {
-        void *t = nullptr;
-        FNX_TRY(scratch(ctx, SLOT_PNG_STREAM, *nbytes + 16, &t));
-        d_out = static_cast<uint8_t *>(t);
-    }
-    FNX_TRY(launch_png_filter(ctx, form, src, sstride, w, h, depth, d_out));
-    if (!out_on_device) {
-        FNX_HIP(hipMemcpyAsync(out, d_out, *nbytes, hipMemcpyDeviceToHost, ctx->stream));
-        FNX_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return FNX_OK;
-}
-
-}  // namespace fnx
-
-extern "C" {
-
-int fnx_png_filter(fnx_ctx *ctx, int space, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors, int opaque, uint8_t *out,
-                   size_t cap, size_t *nbytes, int *color_type, int *bit_depth)
-{
-    FNX_ENTER(ctx);
-    FNX_TRY(check_space_io(space));
-    FNX_REQUIRE(kind == FNX_PNG_PALETTED || kind == FNX_PNG_GRAY || kind == FNX_PNG_NRGBA, "kind: 1 (paletted), 2 (gray) or 3 (NRGBA)");
-    FNX_REQUIRE(src != nullptr && nbytes != nullptr && color_type != nullptr && bit_depth != nullptr, "src, nbytes, color_type and bit_depth");
-    FNX_REQUIRE(out != nullptr || cap == 0, "out is null");
-    FNX_REQUIRE(w >= 1 && h >= 1 && w <= 65535 && h <= 65535, "dims: 1..65535");
-    FNX_REQUIRE(kind != FNX_PNG_PALETTED || (ncolors >= 1 && ncolors <= 256), "ncolors: 1..256 (image.Paletted indices are uint8)");
-    FNX_REQUIRE(opaque >= -1 && opaque <= 1, "opaque: 1, 0, or -1 to decide as Opaque() does");
-    const bool nrgba = kind == FNX_PNG_NRGBA;
-    if (nrgba) {
-        FNX_TRY(check_img(src, sstride, w, h, "src"));
-        FNX_REQUIRE(space == FNX_HOST || (reinterpret_cast<uintptr_t>(src) & 3u) == 0, "a device image is 4-byte aligned");
-    } else {
-        FNX_REQUIRE(sstride >= w, "plane stride");
-    }
-    const uint8_t *dsrc = src;
-    if (space == FNX_HOST) {
-        const size_t len = static_cast<size_t>(h - 1) * sstride + static_cast<size_t>(w) * (nrgba ? 4 : 1);
-        void *d = nullptr;
-        FNX_TRY(scratch(ctx, SLOT_IN_A, len + 16, &d));
-        FNX_HIP(hipMemcpyAsync(d, src, len, hipMemcpyHostToDevice, ctx->stream));
-        dsrc = static_cast<const uint8_t *>(d);
-    }
-    return png_filter_device(ctx, kind, dsrc, sstride, w, h, ncolors, opaque, space == FNX_DEVICE, out, cap, nbytes, color_type, bit_depth);
-}
-
-}  // extern "C"

@@ -550,8 +550,8 @@ size_t png_result_bytes();
 int launch_png_palettize(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, int max_colors, uint8_t *d_plane, int pstride,
                          const void **d_result);
 int launch_png_plane(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, bool gray, uint8_t *d_plane, int pstride);
-// the body of fnx_png_reduce for a device image (flat Pix readable: (h-1) sstride + 4w bytes); d_plane: device, or nullptr
-// (classify only).  Blocks; kind / palette / ncolors are host memory.
+// png_api.cpp: the body of fnx_png_reduce for a device image (flat Pix readable: (h-1) sstride + 4w bytes); d_plane: device, or
+// nullptr (classify only).  Blocks; kind / palette / ncolors are host memory.
 int png_reduce_device(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, int max_colors, uint8_t *d_plane, int pstride,
                       int *kind, uint8_t *palette, int *ncolors);
 // png_filter.hip: the encoder's per-row stage (compress.go:94-107, targetsize.go:189, 342) -- rows of 1 + n bytes, the filter
@@ -562,8 +562,8 @@ int png_row_bytes(int form, int w, int depth);          // n
 int launch_png_filter(fnx_ctx *ctx, int form, const uint8_t *src, int sstride, int w, int h, int depth, uint8_t *d_out);
 // image.NRGBA.Opaque(): *d_flag = 1 when a visible pixel has alpha != 255, else 0
 int launch_png_alpha(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, uint32_t *d_flag);
-// the body of fnx_png_filter for a DEVICE image or plane; out: device (out_on_device) or host memory.  Blocks unless the
-// opacity is stated and the stream stays on the device.
+// png_api.cpp: the body of fnx_png_filter for a DEVICE image or plane; out: device (out_on_device) or host memory.  Blocks
+// unless the opacity is stated and the stream stays on the device.
 int png_filter_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors, int opaque, bool out_on_device,
                       uint8_t *out, size_t cap, size_t *nbytes, int *color_type, int *bit_depth);
 // deflate.hip: the zlib stream of n >= 1 device bytes into d_out (device, cap bytes; a larger stream writes nothing);
@@ -575,6 +575,30 @@ int launch_deflate(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, uint8_
 int deflate_device(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, bool out_on_device, uint8_t *out, size_t cap, size_t *nbytes);
 int png_encode_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors, int opaque, const uint8_t *palette,
                       uint8_t *out, size_t cap, size_t *nbytes);
+// the eight bytes a PNG file opens with, and image.Decode's test for them (io.go:65-88)
+constexpr uint8_t PNG_SIG[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+inline bool png_signature(const uint8_t *data, size_t n) { return n >= 8 && std::memcmp(data, PNG_SIG, 8) == 0; }
+// png_frame.cpp (host only): the file around a zlib stream -- signature, IHDR, PLTE + tRNS for colour type 3, one IDAT, IEND
+struct PngFrame {
+    int w, h, color_type, bit_depth;
+    int ncolors;                         // colour type 3: the palette's entries
+    const uint8_t *palette;              // HOST, ncolors x 4 bytes r, g, b, a
+    int ntrns() const                    // the alphas tRNS holds: up to and including the last one that is not 255
+    {
+        int n = 0;
+        if (color_type == 3) {
+            for (int i = 0; i < ncolors; i++) {
+                if (palette[4 * i + 3] != 255) n = i + 1;
+            }
+        }
+        return n;
+    }
+    size_t file_bytes(size_t zsize) const { return 8 + 25 + (color_type == 3 ? png_palette_chunks(ncolors, ntrns()) : 0) + 12 + zsize + 12; }
+};
+// everything in front of the stream; returns where the IDAT chunk starts (its body, the stream, goes to that + 8)
+uint8_t *png_frame_head(const PngFrame &f, uint8_t *out);
+// the IDAT chunk whose zsize body bytes are in place, and IEND
+void png_frame_tail(uint8_t *idat, size_t zsize);
 // ---- fnx_png_compress_batch: a chunk of images through one set of launches (png_compress_plan.hpp has the host plan) ----
 struct PngCbSrc {                        // an image of the chunk: DEVICE, NRGBA, 4-byte aligned, the flat Pix readable
     const uint8_t *src;
@@ -825,6 +849,12 @@ struct PngAdam7File {
     int dstride;
     uint32_t tile0;                         // the batch kernel: the file's first workgroup
 };
+// png_parse.cpp: the file's PngExpand; and an accepted Adam7 file's passes as png_unfilter_batch_kernel's images, in pass order:
+// passes[k], the k-th present pass -- its rows from stream + poff on, its plane (16-byte pitch) behind the planes before it from
+// rows on, nothing else set --, a's planes and pitches, and slot[p] = first + k, the descriptor of pass p (0 for an absent pass).
+// stream, rows: the DEVICE homes of the file's inflated stream and of its png_planes_bytes.  Returns the present passes' number
+PngExpand png_expand_of(const PngFile &f);
+int png_adam7_passes(const PngFile &f, const uint8_t *stream, uint8_t *rows, uint32_t first, PngBatchFile passes[7], PngAdam7File *a, uint32_t slot[7]);
 // d_units: the chunk's units sorted by bpp, nunits[k] of them with bpp PNG_BPPS[k]; d_files: m descriptors; tiles: the sum of
 // the files' workgroups of the expand kernel
 constexpr int PNG_BPPS[6] = {1, 2, 3, 4, 6, 8};

@@ -415,15 +415,9 @@ void fennec_pool_release(void)
 
 // image.Decode's choice of decoder (io.go:65-88): a file that opens with the PNG signature is a PNG source, everything else goes
 // to the JPEG decoder (which refuses what is no JPEG).  Arguments and answers: fnx_jpeg_decode's.
-static bool is_png(const uint8_t *data, size_t n)
-{
-    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
-    return n >= 8 && std::memcmp(data, sig, 8) == 0;
-}
-
 static int decode_file(fnx_ctx *ctx, const uint8_t *data, size_t n, int space, uint8_t *dst, int dstride, int *w, int *h)
 {
-    if (!is_png(data, n)) return fnx_jpeg_decode(ctx, data, n, space, dst, dstride, w, h);
+    if (!png_signature(data, n)) return fnx_jpeg_decode(ctx, data, n, space, dst, dstride, w, h);
     if (dst == nullptr) {                       // the dimension probe: IHDR alone -- the decode that follows walks every chunk, once
         PngFile f;
         FNX_TRY(png_probe(data, n, &f, ctx && ctx->png_adam7));
@@ -480,7 +474,7 @@ int fennec_CompressFileJPEG(fnx_ctx *ctx, const uint8_t *data, size_t n, const f
     *nbytes = 0;
     int w = 0, h = 0;
     FNX_TRY(decode_file(ctx, data, n, FNX_HOST, nullptr, 0, &w, &h));          // dimensions; refuses what the device decoder does not take
-    if (!is_png(data, n) && !(o->orient > 1 && o->orient <= 8) && o->max_w <= 0 && o->max_h <= 0 && !o->auto_format) {
+    if (!png_signature(data, n) && !(o->orient > 1 && o->orient <= 8) && o->max_w <= 0 && o->max_h <= 0 && !o->auto_format) {
         // nothing between the decode and the search: the item body without the decoded image (fnx_jpeg_recompress, r3)
         dims[0] = dims[2] = w; dims[1] = dims[3] = h;
         return fnx_jpeg_recompress(ctx, data, n, o->target_ssim, ssim_window(), out, cap, nbytes, quality, ssim, steps, &w, &h);
@@ -513,8 +507,31 @@ int fennec_CompressFileJPEG(fnx_ctx *ctx, const uint8_t *data, size_t n, const f
     return fnx_jpeg_compress(ctx, FNX_DEVICE, img, w * 4, w, h, o->target_ssim, ssim_window(), out, cap, nbytes, quality, ssim, steps);
 }
 
-// CompressFile's PNG branch for a JPEG source up to the encoder (fennec.go:107-141 -> compressPNG, compress.go:90-153): the
-// same stages, then tryPalettize / isGrayscale + toGray on the resident image; `out` is what png.Encoder is handed.
+// What the three PNG file entries below do first (fennec.go:107-141 -> compressPNG, compress.go:90-153): the dimension probe, the
+// stages above, then tryPalettize / isGrayscale + toGray on the resident image.  *src, *sstride: the reduced w x h image as
+// png.Encoder is handed it -- the image itself where it stays NRGBA, else its tight plane in SLOT_OUT.
+static int file_png_reduced(fnx_ctx *ctx, const char *entry, const uint8_t *data, size_t n, const fennec_FileOptions *o, int dims[4], int *kind,
+                            uint8_t *palette, int *ncolors, const uint8_t **src, int *sstride, int *pw, int *ph)
+{
+    int w = 0, h = 0;
+    FNX_TRY(decode_file(ctx, data, n, FNX_HOST, nullptr, 0, &w, &h));          // dimensions; refuses what the device decoder does not take
+    const uint8_t *img = nullptr;
+    FNX_TRY(file_stages(ctx, data, n, o, w, h, &img, &w, &h, dims));
+    if (w > 65535 || h > 65535) {
+        set_error("invalid argument: %s takes images of at most 65535 x 65535", entry);
+        return FNX_ERR_INVALID;
+    }
+    void *dp = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_OUT, static_cast<size_t>(w) * h + 16, &dp));
+    FNX_TRY(png_reduce_device(ctx, img, w * 4, w, h, 256, static_cast<uint8_t *>(dp), w, kind, palette, ncolors));
+    const bool nrgba = *kind == FNX_PNG_NRGBA;
+    *src = nrgba ? img : static_cast<const uint8_t *>(dp);
+    *sstride = nrgba ? w * 4 : w;
+    *pw = w; *ph = h;
+    return FNX_OK;
+}
+
+// CompressFile's PNG branch for a JPEG source up to the encoder: `out` is what png.Encoder is handed.
 int fennec_CompressFilePNGReduce(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_FileOptions *o, int *kind, uint8_t *palette,
                                  int *ncolors, uint8_t *out, size_t cap, size_t *nbytes, int dims[4])
 {
@@ -525,25 +542,15 @@ int fennec_CompressFilePNGReduce(fnx_ctx *ctx, const uint8_t *data, size_t n, co
     *nbytes = 0;
     *kind = 0;
     *ncolors = 0;
-    int w = 0, h = 0;
-    FNX_TRY(decode_file(ctx, data, n, FNX_HOST, nullptr, 0, &w, &h));          // dimensions; refuses what the device decoder does not take
-    const uint8_t *img = nullptr;
-    FNX_TRY(file_stages(ctx, data, n, o, w, h, &img, &w, &h, dims));
-    if (w > 65535 || h > 65535) {
-        set_error("invalid argument: CompressFilePNGReduce takes images of at most 65535 x 65535");
-        return FNX_ERR_INVALID;
-    }
-    void *dp = nullptr;
-    FNX_TRY(scratch(ctx, SLOT_OUT, static_cast<size_t>(w) * h + 16, &dp));
-    FNX_TRY(png_reduce_device(ctx, img, w * 4, w, h, 256, static_cast<uint8_t *>(dp), w, kind, palette, ncolors));
-    const size_t px = static_cast<size_t>(w) * h;
-    *nbytes = *kind == FNX_PNG_NRGBA ? px * 4 : px;
+    const uint8_t *src = nullptr;
+    int sstride = 0, w = 0, h = 0;
+    FNX_TRY(file_png_reduced(ctx, "CompressFilePNGReduce", data, n, o, dims, kind, palette, ncolors, &src, &sstride, &w, &h));
+    *nbytes = static_cast<size_t>(sstride) * h;
     if (cap < *nbytes) {
         set_error("invalid argument: CompressFilePNGReduce needs %zu bytes of output, cap is %zu", *nbytes, cap);
         return FNX_ERR_INVALID;
     }
-    const void *reduced = *kind == FNX_PNG_NRGBA ? static_cast<const void *>(img) : dp;
-    FNX_HIP(hipMemcpyAsync(out, reduced, *nbytes, hipMemcpyDeviceToHost, ctx->stream));
+    FNX_HIP(hipMemcpyAsync(out, src, *nbytes, hipMemcpyDeviceToHost, ctx->stream));
     FNX_HIP(hipStreamSynchronize(ctx->stream));
     return FNX_OK;
 }
@@ -561,20 +568,10 @@ int fennec_CompressFilePNGStream(fnx_ctx *ctx, const uint8_t *data, size_t n, co
     *ncolors = 0;
     *color_type = 0;
     *bit_depth = 0;
-    int w = 0, h = 0;
-    FNX_TRY(decode_file(ctx, data, n, FNX_HOST, nullptr, 0, &w, &h));          // dimensions; refuses what the device decoder does not take
-    const uint8_t *img = nullptr;
-    FNX_TRY(file_stages(ctx, data, n, o, w, h, &img, &w, &h, dims));
-    if (w > 65535 || h > 65535) {
-        set_error("invalid argument: CompressFilePNGStream takes images of at most 65535 x 65535");
-        return FNX_ERR_INVALID;
-    }
-    void *dp = nullptr;
-    FNX_TRY(scratch(ctx, SLOT_OUT, static_cast<size_t>(w) * h + 16, &dp));
-    FNX_TRY(png_reduce_device(ctx, img, w * 4, w, h, 256, static_cast<uint8_t *>(dp), w, kind, palette, ncolors));
-    const bool nrgba = *kind == FNX_PNG_NRGBA;
-    return png_filter_device(ctx, *kind, nrgba ? img : static_cast<const uint8_t *>(dp), nrgba ? w * 4 : w, w, h, *ncolors, -1, false, out, cap,
-                             nbytes, color_type, bit_depth);
+    const uint8_t *src = nullptr;
+    int sstride = 0, w = 0, h = 0;
+    FNX_TRY(file_png_reduced(ctx, "CompressFilePNGStream", data, n, o, dims, kind, palette, ncolors, &src, &sstride, &w, &h));
+    return png_filter_device(ctx, *kind, src, sstride, w, h, *ncolors, -1, false, out, cap, nbytes, color_type, bit_depth);
 }
 
 // The whole branch: the same stages, then deflate.hip on the resident stream and the file's chunks (fnx_png_encode's body).
@@ -587,22 +584,11 @@ int fennec_CompressFilePNG(fnx_ctx *ctx, const uint8_t *data, size_t n, const fe
     }
     *nbytes = 0;
     *kind = 0;
-    int w = 0, h = 0;
-    FNX_TRY(decode_file(ctx, data, n, FNX_HOST, nullptr, 0, &w, &h));          // dimensions; refuses what the device decoder does not take
-    const uint8_t *img = nullptr;
-    FNX_TRY(file_stages(ctx, data, n, o, w, h, &img, &w, &h, dims));
-    if (w > 65535 || h > 65535) {
-        set_error("invalid argument: CompressFilePNG takes images of at most 65535 x 65535");
-        return FNX_ERR_INVALID;
-    }
-    void *dp = nullptr;
-    FNX_TRY(scratch(ctx, SLOT_OUT, static_cast<size_t>(w) * h + 16, &dp));
     uint8_t palette[256 * 4];
-    int ncolors = 0;
-    FNX_TRY(png_reduce_device(ctx, img, w * 4, w, h, 256, static_cast<uint8_t *>(dp), w, kind, palette, &ncolors));
-    const bool nrgba = *kind == FNX_PNG_NRGBA;
-    return png_encode_device(ctx, *kind, nrgba ? img : static_cast<const uint8_t *>(dp), nrgba ? w * 4 : w, w, h, ncolors, -1, palette, out, cap,
-                             nbytes);
+    const uint8_t *src = nullptr;
+    int ncolors = 0, sstride = 0, w = 0, h = 0;
+    FNX_TRY(file_png_reduced(ctx, "CompressFilePNG", data, n, o, dims, kind, palette, &ncolors, &src, &sstride, &w, &h));
+    return png_encode_device(ctx, *kind, src, sstride, w, h, ncolors, -1, palette, out, cap, nbytes);
 }
 
 }  // extern "C"

@@ -1,10 +1,12 @@
-// The deflate entry points: fnx_deflate_bound, fnx_deflate (deflate.hip's two kernels behind the argument checks and the
-// staging of the three spaces) and fnx_png_encode (png_filter.hip's row stage, then the deflate, on the device; the file's
-// chunks and their CRCs on the host); and fnx_png_decode, the other direction: png_parse.cpp's host side (chunk walk, inflate,
-// the filter bytes), then png_decode.hip's two kernels (an Adam7 file on a ctx that accepts it: a descriptor per pass, the batched
-// unfilter kernel once, png_expand_adam7_kernel); and fnx_png_decode_batch, which does the host side of a chunk of files
-// on several threads and sends the chunk through one set of launches; and fnx_png_compress_batch / fnx_png_recompress_batch,
-// compressPNG for a list of resident images (or of files) with one set of launches and three host waits per chunk.
+// The PNG entry points.  Towards a file: fnx_png_reduce (png_reduce.hip: compressPNG's pixel stages), fnx_png_filter
+// (png_filter.hip's row stage), fnx_deflate_bound and fnx_deflate (deflate.hip's two kernels behind the argument checks and the
+// staging of the three spaces), fnx_png_encode (the row stage, then the deflate, on the device; the file's chunks and their
+// CRCs on the host: png_frame.cpp).  From a file: fnx_png_decode -- png_parse.cpp's host side (chunk walk, inflate, the filter
+// bytes), then png_decode.hip's two kernels (an Adam7 file on a ctx that accepts it: a descriptor per pass, the batched
+// unfilter kernel once, png_expand_adam7_kernel) -- and fnx_png_decode_batch, which does the host side of a chunk of files
+// on several threads and sends the chunk through one set of launches.  Both ways: fnx_png_compress_batch /
+// fnx_png_recompress_batch, compressPNG for a list of resident images (or of files) with one set of launches and three host
+// waits per chunk.
 #include "common.hpp"
 
 #include <algorithm>
@@ -13,104 +15,9 @@ using namespace fnx;
 
 namespace {
 
-// CRC-32 of PNG's chunks (ISO 3309, polynomial 0xedb88320 reflected), eight bytes a step
-struct CrcTables {
-    uint32_t t[8][256];
-    CrcTables()
-    {
-        for (uint32_t i = 0; i < 256; i++) {
-            uint32_t c = i;
-            for (int k = 0; k < 8; k++) c = (c & 1u) ? 0xedb88320u ^ (c >> 1) : c >> 1;
-            t[0][i] = c;
-        }
-        for (uint32_t i = 0; i < 256; i++) {
-            for (int s = 1; s < 8; s++) t[s][i] = t[0][t[s - 1][i] & 0xffu] ^ (t[s - 1][i] >> 8);
-        }
-    }
-};
-
-uint32_t crc32_update(uint32_t crc, const uint8_t *p, size_t n)     // crc: the running register (start 0xffffffff, invert at the end)
-{
-    static const CrcTables tab;
-    while (n >= 8) {
-        uint32_t a, b;
-        std::memcpy(&a, p, 4);
-        std::memcpy(&b, p + 4, 4);
-        a ^= crc;
-        crc = tab.t[7][a & 0xffu] ^ tab.t[6][(a >> 8) & 0xffu] ^ tab.t[5][(a >> 16) & 0xffu] ^ tab.t[4][a >> 24] ^
-              tab.t[3][b & 0xffu] ^ tab.t[2][(b >> 8) & 0xffu] ^ tab.t[1][(b >> 16) & 0xffu] ^ tab.t[0][b >> 24];
-        p += 8;
-        n -= 8;
-    }
-    for (; n; n--) crc = tab.t[0][(crc ^ *p++) & 0xffu] ^ (crc >> 8);
-    return crc;
-}
-
-void put_be32(uint8_t *p, uint32_t v)
-{
-    p[0] = static_cast<uint8_t>(v >> 24); p[1] = static_cast<uint8_t>(v >> 16); p[2] = static_cast<uint8_t>(v >> 8); p[3] = static_cast<uint8_t>(v);
-}
-
-// a chunk whose `len` body bytes already sit at at + 8: length and tag in front, CRC behind; returns the chunk's end
-uint8_t *close_chunk(uint8_t *at, const char *tag, size_t len)
-{
-    put_be32(at, static_cast<uint32_t>(len));
-    std::memcpy(at + 4, tag, 4);
-    put_be32(at + 8 + len, ~crc32_update(0xffffffffu, at + 4, 4 + len));
-    return at + 12 + len;
-}
-
-// ---- the file around a zlib stream: signature, IHDR, PLTE + tRNS for colour type 3, one IDAT, IEND ---------------------------
-struct PngFrame {
-    int w, h, color_type, bit_depth;
-    int ncolors;                         // colour type 3: the palette's entries
-    const uint8_t *palette;              // HOST, ncolors x 4 bytes r, g, b, a
-    int ntrns() const                    // the alphas tRNS holds: up to and including the last one that is not 255
-    {
-        int n = 0;
-        if (color_type == 3) {
-            for (int i = 0; i < ncolors; i++) {
-                if (palette[4 * i + 3] != 255) n = i + 1;
-            }
-        }
-        return n;
-    }
-    size_t file_bytes(size_t zsize) const { return 8 + 25 + (color_type == 3 ? png_palette_chunks(ncolors, ntrns()) : 0) + 12 + zsize + 12; }
-};
-
-// everything in front of the stream; returns where the IDAT chunk starts (its body, the stream, goes to that + 8)
-uint8_t *png_frame_head(const PngFrame &f, uint8_t *out)
-{
-    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
-    std::memcpy(out, sig, 8);
-    uint8_t *at = out + 8;
-    put_be32(at + 8, static_cast<uint32_t>(f.w));
-    put_be32(at + 12, static_cast<uint32_t>(f.h));
-    at[16] = static_cast<uint8_t>(f.bit_depth); at[17] = static_cast<uint8_t>(f.color_type); at[18] = 0; at[19] = 0; at[20] = 0;
-    at = close_chunk(at, "IHDR", 13);
-    if (f.color_type == 3) {
-        const int ntrns = f.ntrns();
-        for (int i = 0; i < f.ncolors; i++) std::memcpy(at + 8 + 3 * i, f.palette + 4 * i, 3);
-        at = close_chunk(at, "PLTE", 3 * static_cast<size_t>(f.ncolors));
-        if (ntrns) {
-            for (int i = 0; i < ntrns; i++) at[8 + i] = f.palette[4 * i + 3];
-            at = close_chunk(at, "tRNS", static_cast<size_t>(ntrns));
-        }
-    }
-    return at;
-}
-
-// the IDAT chunk whose zsize body bytes are in place, and IEND
-void png_frame_tail(uint8_t *idat, size_t zsize)
-{
-    close_chunk(close_chunk(idat, "IDAT", zsize), "IEND", 0);
-}
-
 // ---- fnx_png_decode_batch ---------------------------------------------------------------------------------------------------
 // the device scratch (inflated streams + reconstructed planes) a chunk may ask for; a file that alone needs more is a chunk of one
 constexpr size_t PNG_BATCH_SCRATCH = FNX_PNG_DECODE_CHUNK_BYTES;
-
-size_t align16(size_t v) { return (v + 15) & ~size_t(15); }
 
 struct BatchEntry {              // a file of the chunk in hand
     int index = 0;               // in the caller's arrays
@@ -122,11 +29,22 @@ struct BatchEntry {              // a file of the chunk in hand
 struct FirstRefusal {
     int index = -1;
     char text[512] = "";
-    void note(int i)             // item i was refused just now: its message is this thread's last error
+    void take(int i, const char *msg)
     {
         if (index >= 0 && index < i) return;
         index = i;
-        std::snprintf(text, sizeof text, "%s", fnx_last_error());
+        std::snprintf(text, sizeof text, "%s", msg);
+    }
+    void note(int i) { take(i, fnx_last_error()); }     // item i was refused just now: its message is this thread's last error
+    // a sub-batch's first refusal, where the sub-batch's item k is this batch's item base + at[k]
+    void merge(const FirstRefusal &sub, int base, const int *at)
+    {
+        if (sub.index >= 0) take(base + at[sub.index], sub.text);
+    }
+    int publish() const          // the batch call's last word: the first refusal's text is its error text
+    {
+        if (index >= 0) set_error("%s", text);
+        return FNX_OK;
     }
 };
 
@@ -174,16 +92,10 @@ int png_decode_chunk(fnx_ctx *ctx, const std::vector<BatchEntry> &chunk, const s
     png_prepare_many(cf.data(), cs.data(), m, workers, items.data(), ctx->png_adam7 != 0);
 
     // verdicts in index order; the files that passed get a descriptor each -- an Adam7 file one per present pass, behind the
-    // non-interlaced files' (png_expand_batch_kernel searches descriptors [0, nplain) alone) --, and the units are sorted by bpp
-    std::vector<PngBatchFile> desc;
-    std::vector<PngAdam7File> adesc;
+    // non-interlaced files' (png_expand_batch_kernel searches descriptors [0, nplain) alone)
     std::vector<int> ok;
-    std::vector<PngBatchUnit> units[6];
-    size_t npal = 0;
-    uint32_t nplain = 0, npass = 0, plain_seen = 0;
-    for (int j = 0; j < m; j++) {
-        if (items[j].status == FNX_OK && items[j].f.interlace != 1) nplain++;
-    }
+    size_t npal = 0, nunit = 0;
+    uint32_t nplain = 0, npass = 0;
     for (int j = 0; j < m; j++) {
         const int i = chunk[j].index;
         status[i] = items[j].status;
@@ -192,20 +104,11 @@ int png_decode_chunk(fnx_ctx *ctx, const std::vector<BatchEntry> &chunk, const s
             first->note(i);
             continue;
         }
-        int k = 0;
-        while (k < 5 && PNG_BPPS[k] != items[j].f.bpp) k++;
-        if (items[j].f.interlace == 1) {
-            // the passes' descriptors follow in pass order (below): slot[p] is pass p's
-            uint32_t slot[7];
-            for (int p = 0; p < 7; p++) slot[p] = items[j].f.ph[p] ? nplain + npass++ : 0;
-            for (size_t u = 0; u + 1 < items[j].units.size(); u += 2)
-                units[k].push_back(PngBatchUnit{slot[items[j].unit_pass[u / 2]], items[j].units[u], items[j].units[u + 1]});
-        } else {
-            for (size_t u = 0; u + 1 < items[j].units.size(); u += 2)
-                units[k].push_back(PngBatchUnit{plain_seen, items[j].units[u], items[j].units[u + 1]});
-            plain_seen++;
-        }
-        if (items[j].f.color_type == 3) npal++;
+        const PngFile &f = items[j].f;
+        if (f.interlace != 1) nplain++;
+        else for (int p = 0; p < 7; p++) npass += f.ph[p] != 0;
+        nunit += items[j].units.size() / 2;
+        if (f.color_type == 3) npal++;
         ok.push_back(j);
     }
     if (ok.empty()) return FNX_OK;
@@ -217,67 +120,52 @@ int png_decode_chunk(fnx_ctx *ctx, const std::vector<BatchEntry> &chunk, const s
     FNX_HIP(hipEventRecord(ctx->png_stage_ev, ctx->stream));
     ctx->png_stage_busy = true;
 
-    // the tables: the sorted units, the descriptors, a palette's 256 pixel values per paletted file.  The descriptors hold
-    // pointers into the table slot itself, so its address is asked for first (same size: the same buffer)
-    std::vector<PngBatchUnit> sorted;
-    int nunits[6];
-    for (int k = 0; k < 6; k++) {
-        nunits[k] = static_cast<int>(units[k].size());
-        sorted.insert(sorted.end(), units[k].begin(), units[k].end());
-    }
+    // the tables: the units sorted by bpp, the descriptors, a palette's 256 pixel values per paletted file.  The descriptors
+    // hold pointers into the table slot itself, so its address is asked for first (same size: the same buffer)
     std::vector<uint32_t> pals(256 * (npal ? npal : 1), 0);
     const size_t na = ok.size() - nplain;
-    const size_t tsizes[4] = {sizeof(PngBatchUnit) * sorted.size(), sizeof(PngBatchFile) * (nplain + npass), sizeof(uint32_t) * pals.size(),
+    const size_t tsizes[4] = {sizeof(PngBatchUnit) * nunit, sizeof(PngBatchFile) * (nplain + npass), sizeof(uint32_t) * pals.size(),
                               sizeof(PngAdam7File) * na};
     void *tab = nullptr;
     FNX_TRY(scratch(ctx, SLOT_PNG_DEC_TAB, align16(tsizes[0]) + align16(tsizes[1]) + align16(tsizes[2]) + align16(tsizes[3]), &tab));
     const uint32_t *d_pals = reinterpret_cast<const uint32_t *>(static_cast<uint8_t *>(tab) + align16(tsizes[0]) + align16(tsizes[1]));
     unsigned long long tiles = 0, atiles = 0;
     size_t pal = 0;
-    desc.assign(nplain + npass, PngBatchFile());
+    std::vector<PngBatchFile> desc(nplain + npass);
+    std::vector<PngAdam7File> adesc;
+    std::vector<PngBatchUnit> units[6];
     size_t plain_at = 0, pass_at = nplain;
     for (int j : ok) {
         const PngFile &f = items[j].f;
         const int i = chunk[j].index;
-        PngBatchFile d;
-        std::memset(&d, 0, sizeof d);
-        d.e.w = f.w; d.e.h = f.h; d.e.color_type = f.color_type; d.e.depth = f.depth;
-        d.e.has_trns = f.has_trns ? 1 : 0;
-        for (int k = 0; k < 3; k++) d.e.key[k] = f.trns16[k];
-        d.table = d_pals;
+        int k = 0;
+        while (k < 5 && PNG_BPPS[k] != f.bpp) k++;
+        const uint32_t *table = d_pals;
         if (f.color_type == 3) {
             std::memcpy(pals.data() + 256 * pal, items[j].table, sizeof items[j].table);
-            d.table = d_pals + 256 * pal++;
+            table = d_pals + 256 * pal++;
         }
-        d.dst = dsts[i];
-        d.dstride = dstrides[i];
         const uint8_t *stream = static_cast<const uint8_t *>(ds) + chunk[j].stream_off;
         uint8_t *rows = static_cast<uint8_t *>(dr) + chunk[j].rows_off;
+        const unsigned long long ftiles = static_cast<unsigned long long>((f.w + 255) / 256) * f.h;
         if (f.interlace == 1) {
             PngAdam7File a;
             std::memset(&a, 0, sizeof a);
-            a.e = d.e; a.table = d.table; a.dst = d.dst; a.dstride = d.dstride;
+            a.e = png_expand_of(f); a.table = table; a.dst = dsts[i]; a.dstride = dstrides[i];
             a.tile0 = static_cast<uint32_t>(atiles);
-            atiles += static_cast<unsigned long long>((f.w + 255) / 256) * f.h;
-            for (int p = 0; p < 7; p++) {
-                if (f.ph[p] == 0) continue;
-                PngBatchFile dp = d;                      // the unfilter kernel's view of the pass: an image of its own
-                dp.stream = stream + f.poff[p];
-                dp.spitch = 1 + f.prow[p];
-                dp.rows = rows;
-                dp.ppitch = align16(f.prow[p]);
-                dp.rowbytes = static_cast<int>(f.prow[p]);
-                dp.npix = static_cast<int>(f.prow[p] / f.bpp);
-                dp.e.w = f.pw[p]; dp.e.h = f.ph[p];
-                dp.dst = nullptr;
-                desc[pass_at++] = dp;
-                a.plane[p] = rows;
-                a.ppitch[p] = static_cast<uint32_t>(dp.ppitch);
-                rows += dp.ppitch * f.ph[p];
-            }
+            atiles += ftiles;
+            uint32_t slot[7];
+            pass_at += png_adam7_passes(f, stream, rows, static_cast<uint32_t>(pass_at), desc.data() + pass_at, &a, slot);
+            for (size_t u = 0; u + 1 < items[j].units.size(); u += 2)
+                units[k].push_back(PngBatchUnit{slot[items[j].unit_pass[u / 2]], items[j].units[u], items[j].units[u + 1]});
             adesc.push_back(a);
             continue;
         }
+        for (size_t u = 0; u + 1 < items[j].units.size(); u += 2)
+            units[k].push_back(PngBatchUnit{static_cast<uint32_t>(plain_at), items[j].units[u], items[j].units[u + 1]});
+        PngBatchFile d;
+        std::memset(&d, 0, sizeof d);
+        d.e = png_expand_of(f); d.table = table; d.dst = dsts[i]; d.dstride = dstrides[i];
         d.stream = stream;
         d.spitch = 1 + f.rowbytes;
         d.rows = rows;
@@ -285,14 +173,20 @@ int png_decode_chunk(fnx_ctx *ctx, const std::vector<BatchEntry> &chunk, const s
         d.rowbytes = static_cast<int>(f.rowbytes);
         d.npix = static_cast<int>(f.rowbytes / f.bpp);
         d.tile0 = static_cast<uint32_t>(tiles);
-        tiles += static_cast<unsigned long long>((f.w + 255) / 256) * f.h;
+        tiles += ftiles;
         desc[plain_at++] = d;
+    }
+    std::vector<PngBatchUnit> sorted;
+    int nunits[6];
+    for (int k = 0; k < 6; k++) {
+        nunits[k] = static_cast<int>(units[k].size());
+        sorted.insert(sorted.end(), units[k].begin(), units[k].end());
     }
     if (tiles > 0x7fffffffull || atiles > 0x7fffffffull) {
         set_error("internal: a chunk of %llu workgroups of png_expand_batch_kernel", tiles > atiles ? tiles : atiles);
         return FNX_ERR_INVALID;
     }
-    if (plain_at != nplain || pass_at != nplain + npass || adesc.size() != na) {
+    if (plain_at != nplain || pass_at != nplain + npass || adesc.size() != na || sorted.size() != nunit) {
         set_error("internal: the chunk's descriptors do not add up");
         return FNX_ERR_INVALID;
     }
@@ -315,21 +209,111 @@ int png_decode_batch_device(fnx_ctx *ctx, int n, const uint8_t *const *files, co
 
 namespace fnx {
 
+// ---- compressPNG's pixel stages: tryPalettize, isGrayscale + toGray (compress.go:90-153, convert.go:76-100) ----------
+int png_reduce_device(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, int max_colors, uint8_t *d_plane, int pstride,
+                      int *kind, uint8_t *palette, int *ncolors)
+{
+    const void *dres = nullptr;
+    FNX_TRY(launch_png_palettize(ctx, src, sstride, w, h, max_colors, d_plane, pstride, &dres));
+    std::vector<uint32_t> res(png_result_bytes() / sizeof(uint32_t));
+    FNX_TRY(fetch_bytes(ctx, dres, res.data(), png_result_bytes()));
+    *ncolors = 0;
+    if (!res[0]) {                                                   // compress.go:92-96
+        *kind = FNX_PNG_PALETTED;
+        *ncolors = static_cast<int>(res[2]);
+        std::memcpy(palette, &res[4], sizeof(uint32_t) * res[2]);    // r, g, b, a: the words' bytes in memory order
+        if (d_plane) note_route(ctx, FNX_PROF_MAIN, "png_plane_kernel");
+        return FNX_OK;
+    }
+    // compress.go:98: isGrayscale walks the flat Pix, row padding included.  A non-grey VISIBLE pixel met by the colours
+    // pass already answers it (every photograph); otherwise the flat scan decides.
+    bool gray = false;
+    if (!res[1]) {
+        void *df = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_RESULT, 16, &df));
+        FNX_TRY(launch_scan_flags(ctx, src, static_cast<size_t>(h - 1) * sstride + static_cast<size_t>(w) * 4, static_cast<uint32_t *>(df)));
+        uint32_t flags = 0;
+        FNX_TRY(fetch_bytes(ctx, df, &flags, sizeof(flags)));
+        gray = !(flags & 2u);
+    }
+    *kind = gray ? FNX_PNG_GRAY : FNX_PNG_NRGBA;
+    if (gray && d_plane) {                                           // compress.go:99-103: toGray
+        FNX_TRY(launch_png_plane(ctx, src, sstride, w, h, true, d_plane, pstride));
+        note_route(ctx, FNX_PROF_MAIN, "png_plane_kernel");
+    }
+    return FNX_OK;
+}
+
+// ---- the PNG encoder's row stage: pack, five filters, smallest sum (compress.go:94-107, targetsize.go:189, 342) -------
+int png_filter_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors, int opaque, bool out_on_device,
+                      uint8_t *out, size_t cap, size_t *nbytes, int *color_type, int *bit_depth)
+{
+    int form = PNG_ROW_GRAY, depth = 8;
+    if (kind == FNX_PNG_PALETTED) {
+        form = PNG_ROW_PALETTED;
+        depth = png_palette_depth(ncolors);
+        *color_type = 3;
+    } else if (kind == FNX_PNG_GRAY) {
+        *color_type = 0;
+    } else {
+        if (opaque < 0) {                                            // image.NRGBA.Opaque(): visible pixels only
+            void *df = nullptr;
+            FNX_TRY(scratch(ctx, SLOT_RESULT, 16, &df));
+            FNX_TRY(launch_png_alpha(ctx, src, sstride, w, h, static_cast<uint32_t *>(df)));
+            uint32_t translucent = 0;
+            FNX_TRY(fetch_bytes(ctx, df, &translucent, sizeof(translucent)));
+            opaque = translucent ? 0 : 1;
+        }
+        form = opaque ? PNG_ROW_RGB : PNG_ROW_RGBA;
+        *color_type = opaque ? 2 : 6;
+    }
+    *bit_depth = depth;
+    *nbytes = static_cast<size_t>(h) * (static_cast<size_t>(png_row_bytes(form, w, depth)) + 1);
+    if (cap < *nbytes || !out) {
+        set_error("invalid argument: the PNG stream needs %zu bytes of output, cap is %zu", *nbytes, cap);
+        return FNX_ERR_INVALID;
+    }
+    uint8_t *d_out = out;
+    if (!out_on_device) {
+        void *t = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_PNG_STREAM, *nbytes + 16, &t));
+        d_out = static_cast<uint8_t *>(t);
+    }
+    FNX_TRY(launch_png_filter(ctx, form, src, sstride, w, h, depth, d_out));
+    if (!out_on_device) {
+        FNX_HIP(hipMemcpyAsync(out, d_out, *nbytes, hipMemcpyDeviceToHost, ctx->stream));
+        FNX_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return FNX_OK;
+}
+
+// ---- the deflate, and the file around it ---------------------------------------------------------------------------
+// the zlib stream of n device bytes into d_out (device, cap bytes), its size waited for
+static int deflate_into(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, uint8_t *d_out, size_t cap, size_t *size)
+{
+    const unsigned long long *d_size = nullptr;
+    FNX_TRY(launch_deflate(ctx, d_src, n, row, d_out, cap, &d_size));
+    unsigned long long got = 0;
+    FNX_TRY(fetch_bytes(ctx, d_size, &got, sizeof(got)));
+    *size = static_cast<size_t>(got);
+    return FNX_OK;
+}
+
+// the same, gathered on the device in SLOT_DEFLATE_OUT (*d_out), from where it is copied once its size is known
+static int deflate_gathered(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, uint8_t **d_out, size_t *size)
+{
+    void *t = nullptr;
+    const size_t cap = deflate_bound(n);
+    FNX_TRY(scratch(ctx, SLOT_DEFLATE_OUT, cap + 16, &t));
+    *d_out = static_cast<uint8_t *>(t);
+    return deflate_into(ctx, d_src, n, row, *d_out, cap, size);
+}
+
 int deflate_device(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, bool out_on_device, uint8_t *out, size_t cap, size_t *nbytes)
 {
     uint8_t *d_out = out;
-    size_t d_cap = cap;
-    if (!out_on_device) {                                            // the stream is gathered on the device and copied once its size is known
-        void *t = nullptr;
-        d_cap = deflate_bound(n);
-        FNX_TRY(scratch(ctx, SLOT_DEFLATE_OUT, d_cap + 16, &t));
-        d_out = static_cast<uint8_t *>(t);
-    }
-    const unsigned long long *d_size = nullptr;
-    FNX_TRY(launch_deflate(ctx, d_src, n, row, d_out, d_cap, &d_size));
-    unsigned long long size = 0;
-    FNX_TRY(fetch_bytes(ctx, d_size, &size, sizeof(size)));
-    *nbytes = static_cast<size_t>(size);
+    if (out_on_device) FNX_TRY(deflate_into(ctx, d_src, n, row, out, cap, nbytes));
+    else FNX_TRY(deflate_gathered(ctx, d_src, n, row, &d_out, nbytes));
     if (cap < *nbytes || !out) {
         set_error("invalid argument: the zlib stream needs %zu bytes of output, cap is %zu", *nbytes, cap);
         return FNX_ERR_INVALID;
@@ -349,22 +333,15 @@ int png_encode_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, i
     const size_t stream_cap = static_cast<size_t>(h) * (row_max + 1);
     void *dstream = nullptr;
     FNX_TRY(scratch(ctx, SLOT_PNG_STREAM, stream_cap + 16, &dstream));
-    size_t stream_bytes = 0;
+    size_t stream_bytes = 0, zsize = 0;
     int color_type = 0, bit_depth = 0;
     FNX_TRY(png_filter_device(ctx, kind, src, sstride, w, h, ncolors, opaque, true, static_cast<uint8_t *>(dstream), stream_cap, &stream_bytes,
                               &color_type, &bit_depth));
-    // the deflate, gathered on the device
-    const size_t zcap = deflate_bound(stream_bytes);
-    void *dz = nullptr;
-    FNX_TRY(scratch(ctx, SLOT_DEFLATE_OUT, zcap + 16, &dz));
-    const unsigned long long *d_size = nullptr;
-    FNX_TRY(launch_deflate(ctx, static_cast<const uint8_t *>(dstream), stream_bytes, static_cast<int>(stream_bytes / h), static_cast<uint8_t *>(dz),
-                           zcap, &d_size));
-    unsigned long long zsize = 0;
-    FNX_TRY(fetch_bytes(ctx, d_size, &zsize, sizeof(zsize)));
+    uint8_t *dz = nullptr;
+    FNX_TRY(deflate_gathered(ctx, static_cast<const uint8_t *>(dstream), stream_bytes, static_cast<int>(stream_bytes / h), &dz, &zsize));
 
     const PngFrame frame{w, h, color_type, bit_depth, ncolors, palette};
-    *nbytes = frame.file_bytes(static_cast<size_t>(zsize));
+    *nbytes = frame.file_bytes(zsize);
     if (cap < *nbytes || !out) {
         set_error("invalid argument: the PNG file needs %zu bytes of output, cap is %zu", *nbytes, cap);
         return FNX_ERR_INVALID;
@@ -374,15 +351,102 @@ int png_encode_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, i
         return FNX_ERR_INVALID;
     }
     uint8_t *at = png_frame_head(frame, out);
-    FNX_HIP(hipMemcpyAsync(at + 8, dz, static_cast<size_t>(zsize), hipMemcpyDeviceToHost, ctx->stream));
+    FNX_HIP(hipMemcpyAsync(at + 8, dz, zsize, hipMemcpyDeviceToHost, ctx->stream));
     FNX_HIP(hipStreamSynchronize(ctx->stream));
-    png_frame_tail(at, static_cast<size_t>(zsize));
+    png_frame_tail(at, zsize);
     return FNX_OK;
 }
 
 }  // namespace fnx
 
+namespace {
+
+// the checks fnx_png_filter and fnx_png_encode make of their source and output arguments, in their order; ptrs / ptrs_text:
+// the entry's own non-NULL test and what it is called; palette_ok: false where the entry needs a paletted image's palette
+int check_rows_source(int space, int kind, bool ptrs, const char *ptrs_text, const uint8_t *src, int sstride, int w, int h, int ncolors,
+                      bool palette_ok, int opaque, const uint8_t *out, size_t cap)
+{
+    FNX_TRY(check_space_io(space));
+    FNX_REQUIRE(kind == FNX_PNG_PALETTED || kind == FNX_PNG_GRAY || kind == FNX_PNG_NRGBA, "kind: 1 (paletted), 2 (gray) or 3 (NRGBA)");
+    FNX_REQUIRE(ptrs, ptrs_text);
+    FNX_REQUIRE(out != nullptr || cap == 0, "out is null");
+    FNX_REQUIRE(w >= 1 && h >= 1 && w <= 65535 && h <= 65535, "dims: 1..65535");
+    FNX_REQUIRE(kind != FNX_PNG_PALETTED || (ncolors >= 1 && ncolors <= 256), "ncolors: 1..256 (image.Paletted indices are uint8)");
+    FNX_REQUIRE(kind != FNX_PNG_PALETTED || palette_ok, "a paletted image needs its palette");
+    FNX_REQUIRE(opaque >= -1 && opaque <= 1, "opaque: 1, 0, or -1 to decide as Opaque() does");
+    if (kind == FNX_PNG_NRGBA) {
+        FNX_TRY(check_img(src, sstride, w, h, "src"));
+        FNX_REQUIRE(space == FNX_HOST || (reinterpret_cast<uintptr_t>(src) & 3u) == 0, "a device image is 4-byte aligned");
+    } else {
+        FNX_REQUIRE(sstride >= w, "plane stride");
+    }
+    return FNX_OK;
+}
+
+// the row stage's source on the device: a host image or plane goes into SLOT_IN_A as it lies, the caller's stride kept
+// (stage_in_flat for a pixel of 1 or 4 bytes, and with FNX_DEVICE_SRC's source in place)
+int stage_rows_source(fnx_ctx *ctx, int space, int kind, const uint8_t *src, int sstride, int w, int h, const uint8_t **dsrc)
+{
+    *dsrc = src;
+    if (space != FNX_HOST) return FNX_OK;
+    const size_t len = static_cast<size_t>(h - 1) * sstride + static_cast<size_t>(w) * (kind == FNX_PNG_NRGBA ? 4 : 1);
+    void *d = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_IN_A, len + 16, &d));
+    FNX_HIP(hipMemcpyAsync(d, src, len, hipMemcpyHostToDevice, ctx->stream));
+    *dsrc = static_cast<const uint8_t *>(d);
+    return FNX_OK;
+}
+
+}  // namespace
+
 extern "C" {
+
+int fnx_png_reduce(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int max_colors, int *kind, uint8_t *palette,
+                   int *ncolors, uint8_t *plane, int pstride)
+{
+    FNX_ENTER(ctx);
+    FNX_TRY(check_space_io(space));
+    FNX_REQUIRE(max_colors >= 1 && max_colors <= 256, "max_colors: 1..256 (image.Paletted indices are uint8)");
+    FNX_REQUIRE(kind != nullptr && palette != nullptr && ncolors != nullptr, "kind, palette and ncolors are outputs");
+    FNX_REQUIRE(w <= 65535 && h <= 65535, "dims: at most 65535 (first-occurrence indices are 32-bit)");
+    FNX_TRY(check_img(src, sstride, w, h, "src"));
+    if (plane) FNX_REQUIRE(pstride >= w, "plane stride");
+    if (w <= 0 || h <= 0) {                                           // an empty colorMap: a palette of no colours (compress.go:116-141)
+        *kind = FNX_PNG_PALETTED;
+        *ncolors = 0;
+        return FNX_OK;
+    }
+    DevImg s;
+    FNX_TRY(stage_in_flat(ctx, space, src, sstride, w, h, SLOT_IN_A, &s));
+    uint8_t *dplane = plane;
+    int dpitch = pstride;
+    if (plane && space != FNX_DEVICE) {
+        dpitch = (w + 3) & ~3;
+        void *t = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_OUT, static_cast<size_t>(dpitch) * h + 16, &t));
+        dplane = static_cast<uint8_t *>(t);
+    }
+    FNX_TRY(png_reduce_device(ctx, s.p, s.stride, w, h, max_colors, dplane, dpitch, kind, palette, ncolors));
+    if (*kind == FNX_PNG_NRGBA) return FNX_OK;                        // the plane stays as it was
+    if (plane && space != FNX_DEVICE) {
+        FNX_HIP(hipMemcpy2DAsync(plane, pstride, dplane, dpitch, w, h, hipMemcpyDeviceToHost, ctx->stream));
+        FNX_HIP(hipStreamSynchronize(ctx->stream));
+    } else if (plane && *kind == FNX_PNG_GRAY) {
+        FNX_HIP(hipStreamSynchronize(ctx->stream));                   // (the gray plane was launched after the last wait)
+    }
+    return FNX_OK;
+}
+
+int fnx_png_filter(fnx_ctx *ctx, int space, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors, int opaque, uint8_t *out,
+                   size_t cap, size_t *nbytes, int *color_type, int *bit_depth)
+{
+    FNX_ENTER(ctx);
+    FNX_TRY(check_rows_source(space, kind, src != nullptr && nbytes != nullptr && color_type != nullptr && bit_depth != nullptr,
+                              "src, nbytes, color_type and bit_depth", src, sstride, w, h, ncolors, true, opaque, out, cap));
+    const uint8_t *dsrc = nullptr;
+    FNX_TRY(stage_rows_source(ctx, space, kind, src, sstride, w, h, &dsrc));
+    return png_filter_device(ctx, kind, dsrc, sstride, w, h, ncolors, opaque, space == FNX_DEVICE, out, cap, nbytes, color_type, bit_depth);
+}
 
 size_t fnx_deflate_bound(size_t n) { return deflate_bound(n); }
 
@@ -408,29 +472,10 @@ int fnx_png_encode(fnx_ctx *ctx, int space, int kind, const uint8_t *src, int ss
                    const uint8_t *palette, uint8_t *out, size_t cap, size_t *nbytes)
 {
     FNX_ENTER(ctx);
-    FNX_TRY(check_space_io(space));
-    FNX_REQUIRE(kind == FNX_PNG_PALETTED || kind == FNX_PNG_GRAY || kind == FNX_PNG_NRGBA, "kind: 1 (paletted), 2 (gray) or 3 (NRGBA)");
-    FNX_REQUIRE(src != nullptr && nbytes != nullptr, "src and nbytes");
-    FNX_REQUIRE(out != nullptr || cap == 0, "out is null");
-    FNX_REQUIRE(w >= 1 && h >= 1 && w <= 65535 && h <= 65535, "dims: 1..65535");
-    FNX_REQUIRE(kind != FNX_PNG_PALETTED || (ncolors >= 1 && ncolors <= 256), "ncolors: 1..256 (image.Paletted indices are uint8)");
-    FNX_REQUIRE(kind != FNX_PNG_PALETTED || palette != nullptr, "a paletted image needs its palette");
-    FNX_REQUIRE(opaque >= -1 && opaque <= 1, "opaque: 1, 0, or -1 to decide as Opaque() does");
-    const bool nrgba = kind == FNX_PNG_NRGBA;
-    if (nrgba) {
-        FNX_TRY(check_img(src, sstride, w, h, "src"));
-        FNX_REQUIRE(space == FNX_HOST || (reinterpret_cast<uintptr_t>(src) & 3u) == 0, "a device image is 4-byte aligned");
-    } else {
-        FNX_REQUIRE(sstride >= w, "plane stride");
-    }
-    const uint8_t *dsrc = src;
-    if (space == FNX_HOST) {
-        const size_t len = static_cast<size_t>(h - 1) * sstride + static_cast<size_t>(w) * (nrgba ? 4 : 1);
-        void *d = nullptr;
-        FNX_TRY(scratch(ctx, SLOT_IN_A, len + 16, &d));
-        FNX_HIP(hipMemcpyAsync(d, src, len, hipMemcpyHostToDevice, ctx->stream));
-        dsrc = static_cast<const uint8_t *>(d);
-    }
+    FNX_TRY(check_rows_source(space, kind, src != nullptr && nbytes != nullptr, "src and nbytes", src, sstride, w, h, ncolors, palette != nullptr,
+                              opaque, out, cap));
+    const uint8_t *dsrc = nullptr;
+    FNX_TRY(stage_rows_source(ctx, space, kind, src, sstride, w, h, &dsrc));
     return png_encode_device(ctx, kind, dsrc, sstride, w, h, ncolors, opaque, palette, out, cap, nbytes);
 }
 
@@ -475,29 +520,12 @@ int fnx_png_decode(fnx_ctx *ctx, const uint8_t *data, size_t n, int space, uint8
         // 16-byte loads past a row's end read the next pass's bytes; the slot's 64 spare bytes stand behind the last one
         PngBatchFile passes[7];
         PngAdam7File a;
-        std::memset(passes, 0, sizeof passes);
         std::memset(&a, 0, sizeof a);
-        a.e.w = f.w; a.e.h = f.h; a.e.color_type = f.color_type; a.e.depth = f.depth;
-        a.e.has_trns = f.has_trns ? 1 : 0;
-        for (int k = 0; k < 3; k++) a.e.key[k] = f.trns16[k];
+        a.e = png_expand_of(f);
         a.dst = d.p;
         a.dstride = d.stride;
-        uint32_t slot[7] = {0, 0, 0, 0, 0, 0, 0}, npass = 0;
-        uint8_t *rows = static_cast<uint8_t *>(dr);
-        for (int p = 0; p < 7; p++) {
-            if (f.ph[p] == 0) continue;
-            PngBatchFile &dp = passes[npass];
-            dp.stream = static_cast<const uint8_t *>(ds) + f.poff[p];
-            dp.spitch = 1 + f.prow[p];
-            dp.rows = rows;
-            dp.ppitch = align16(f.prow[p]);
-            dp.rowbytes = static_cast<int>(f.prow[p]);
-            dp.npix = static_cast<int>(f.prow[p] / f.bpp);
-            a.plane[p] = rows;
-            a.ppitch[p] = static_cast<uint32_t>(dp.ppitch);
-            rows += dp.ppitch * f.ph[p];
-            slot[p] = npass++;
-        }
+        uint32_t slot[7];
+        const int npass = png_adam7_passes(f, static_cast<const uint8_t *>(ds), static_cast<uint8_t *>(dr), 0, passes, &a, slot);
         std::vector<PngBatchUnit> bu;
         for (size_t u = 0; u + 1 < units.size(); u += 2) bu.push_back(PngBatchUnit{slot[unit_pass[u / 2]], units[u], units[u + 1]});
         const void *hosts[3] = {bu.data(), passes, table};
@@ -528,8 +556,7 @@ int fnx_png_decode_batch(fnx_ctx *ctx, int n, const uint8_t *const *files, const
     FNX_REQUIRE(workers >= 0 && workers <= 64, "decode batch: workers must be 0..64 (0: min(8, files in the chunk))");
     FirstRefusal first;
     FNX_TRY(png_decode_batch_device(ctx, n, files, sizes, dsts, dstrides, workers, ws, hs, status, &first));
-    if (first.index >= 0) set_error("%s", first.text);
-    return FNX_OK;
+    return first.publish();
 }
 
 }  // extern "C"
@@ -789,12 +816,6 @@ int png_compress_items(fnx_ctx *ctx, int base, int n, const uint8_t *const *srcs
     return FNX_OK;
 }
 
-bool is_png_file(const uint8_t *data, size_t n)
-{
-    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
-    return n >= 8 && std::memcmp(data, sig, 8) == 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -808,8 +829,7 @@ int fnx_png_compress_batch(fnx_ctx *ctx, int n, const uint8_t *const *srcs, cons
     FNX_REQUIRE(ctx->res_count == 0, "enqueued batches are waiting for fnx_results_fetch: fetch them before a blocking batch call");
     FirstRefusal first;
     FNX_TRY(png_compress_items(ctx, 0, n, srcs, sstrides, ws, hs, outs, caps, nbytes, kinds, status, nullptr, &first));
-    if (first.index >= 0) set_error("%s", first.text);
-    return FNX_OK;
+    return first.publish();
 }
 
 // CompressBatch's item body for n files that end as PNG: the files of a span -- as many as decode into
@@ -834,7 +854,7 @@ int fnx_png_recompress_batch(fnx_ctx *ctx, int n, const uint8_t *const *files, c
         png.clear();
         for (; s1 < n; s1++) {
             int w = 0, h = 0;
-            const bool isp = files[s1] && is_png_file(files[s1], sizes[s1]);
+            const bool isp = files[s1] && png_signature(files[s1], sizes[s1]);
             if (isp) {
                 PngFile head;
                 if (png_probe(files[s1], sizes[s1], &head, ctx->png_adam7 != 0) == FNX_OK) { w = head.w; h = head.h; }
@@ -888,10 +908,7 @@ int fnx_png_recompress_batch(fnx_ctx *ctx, int n, const uint8_t *const *files, c
             if (pass == 0) {
                 FirstRefusal sub;
                 FNX_TRY(png_decode_batch_device(ctx, k, f.data(), fs.data(), d.data(), dstr.data(), workers, w.data(), h.data(), st.data(), &sub));
-                if (sub.index >= 0 && (first.index < 0 || s0 + idx[sub.index] < first.index)) {
-                    first.index = s0 + idx[sub.index];
-                    std::snprintf(first.text, sizeof first.text, "%s", sub.text);
-                }
+                first.merge(sub, s0, idx.data());
             } else {
                 FNX_TRY(jpeg_decode_batch_device(ctx, k, f.data(), fs.data(), d.data(), dstr.data(), w.data(), h.data(), st.data()));
             }
@@ -907,8 +924,7 @@ int fnx_png_recompress_batch(fnx_ctx *ctx, int n, const uint8_t *const *files, c
                                    skip.data(), &first));
         s0 = s1;
     }
-    if (first.index >= 0) set_error("%s", first.text);
-    return FNX_OK;
+    return first.publish();
 }
 
 }  // extern "C"

@@ -7,8 +7,6 @@ namespace fnx {
 
 namespace {
 
-size_t align16(size_t v) { return (v + 15) & ~size_t(15); }
-
 // the arrays of an image whose rows have n raw bytes (pitch: its plane's, 0 for none), the work area aside
 struct Cost {
     size_t stream, plane, tok, slot, out;

@@ -10,6 +10,8 @@
 
 namespace fnx {
 
+inline size_t align16(size_t v) { return (v + 15) & ~size_t(15); }
+
 // what a workgroup of a batched kernel takes: rows [first, end) of an image of the chunk -- or, in the colours and plane passes,
 // workgroup `first` of the `end` that share the image
 struct PngCbUnit {

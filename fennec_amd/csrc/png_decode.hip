@@ -29,6 +29,8 @@
 //     instruction each, which is what the per-lane stream issues anyway -- without the LDS round trip.
 #include "common.hpp"
 
+#include <type_traits>
+
 namespace fnx {
 
 namespace {
@@ -407,18 +409,27 @@ __global__ __launch_bounds__(256) void png_expand_adam7_batch_kernel(const PngAd
     *reinterpret_cast<uint32_t *>(f.dst + static_cast<size_t>(y) * f.dstride + 4 * static_cast<size_t>(x)) = adam7_pixel(f, x, y);
 }
 
+// launch(std::integral_constant<int, BPP>()) for the unfilter kernels' six pixel distances; false: bpp is none of them
+template <typename Launch> bool with_bpp(int bpp, Launch launch)
+{
+    switch (bpp) {
+    case 1: launch(std::integral_constant<int, 1>()); return true;
+    case 2: launch(std::integral_constant<int, 2>()); return true;
+    case 3: launch(std::integral_constant<int, 3>()); return true;
+    case 4: launch(std::integral_constant<int, 4>()); return true;
+    case 6: launch(std::integral_constant<int, 6>()); return true;
+    case 8: launch(std::integral_constant<int, 8>()); return true;
+    default: return false;
+    }
+}
+
 int launch_unfilter_batch(fnx_ctx *ctx, int bpp, const PngBatchUnit *u, int nunits, const PngBatchFile *d_files)
 {
     const dim3 grid(nunits), block(UF_T);
     FNX_TRY(prof_begin(ctx));
-    switch (bpp) {
-    case 1: hipLaunchKernelGGL(png_unfilter_batch_kernel<1>, grid, block, 0, ctx->stream, u, d_files); break;
-    case 2: hipLaunchKernelGGL(png_unfilter_batch_kernel<2>, grid, block, 0, ctx->stream, u, d_files); break;
-    case 3: hipLaunchKernelGGL(png_unfilter_batch_kernel<3>, grid, block, 0, ctx->stream, u, d_files); break;
-    case 4: hipLaunchKernelGGL(png_unfilter_batch_kernel<4>, grid, block, 0, ctx->stream, u, d_files); break;
-    case 6: hipLaunchKernelGGL(png_unfilter_batch_kernel<6>, grid, block, 0, ctx->stream, u, d_files); break;
-    case 8: hipLaunchKernelGGL(png_unfilter_batch_kernel<8>, grid, block, 0, ctx->stream, u, d_files); break;
-    default: set_error("internal: png_unfilter_batch_kernel has no form for bpp %d", bpp); return FNX_ERR_INVALID;
+    if (!with_bpp(bpp, [&](auto b) { hipLaunchKernelGGL(png_unfilter_batch_kernel<b()>, grid, block, 0, ctx->stream, u, d_files); })) {
+        set_error("internal: png_unfilter_batch_kernel has no form for bpp %d", bpp);
+        return FNX_ERR_INVALID;
     }
     FNX_HIP(hipGetLastError());
     return prof_end(ctx);
@@ -440,14 +451,9 @@ int launch_png_unfilter(fnx_ctx *ctx, const uint8_t *d_stream, const PngFile &f,
     a.ppitch = png_plane_pitch(f);
     const dim3 grid(nunits), block(UF_T);
     FNX_TRY(prof_begin(ctx));
-    switch (f.bpp) {
-    case 1: hipLaunchKernelGGL(png_unfilter_kernel<1>, grid, block, 0, ctx->stream, a); break;
-    case 2: hipLaunchKernelGGL(png_unfilter_kernel<2>, grid, block, 0, ctx->stream, a); break;
-    case 3: hipLaunchKernelGGL(png_unfilter_kernel<3>, grid, block, 0, ctx->stream, a); break;
-    case 4: hipLaunchKernelGGL(png_unfilter_kernel<4>, grid, block, 0, ctx->stream, a); break;
-    case 6: hipLaunchKernelGGL(png_unfilter_kernel<6>, grid, block, 0, ctx->stream, a); break;
-    case 8: hipLaunchKernelGGL(png_unfilter_kernel<8>, grid, block, 0, ctx->stream, a); break;
-    default: set_error("internal: png_unfilter_kernel has no form for bpp %d", f.bpp); return FNX_ERR_INVALID;
+    if (!with_bpp(f.bpp, [&](auto b) { hipLaunchKernelGGL(png_unfilter_kernel<b()>, grid, block, 0, ctx->stream, a); })) {
+        set_error("internal: png_unfilter_kernel has no form for bpp %d", f.bpp);
+        return FNX_ERR_INVALID;
     }
     FNX_HIP(hipGetLastError());
     return prof_end(ctx);
@@ -458,9 +464,7 @@ int launch_png_expand(fnx_ctx *ctx, const uint8_t *d_rows, const PngFile &f, con
     ExpandArgs a;
     a.rows = d_rows;
     a.ppitch = png_plane_pitch(f);
-    a.e.w = f.w; a.e.h = f.h; a.e.color_type = f.color_type; a.e.depth = f.depth;
-    a.e.has_trns = f.has_trns ? 1 : 0;
-    for (int k = 0; k < 3; k++) a.e.key[k] = f.trns16[k];
+    a.e = png_expand_of(f);
     a.table = d_table;
     a.dst = dst;
     a.dstride = dstride;

@@ -8,6 +8,7 @@
 //   png_palette_table  a colour-type-3 file's 256 pixel values, toNRGBA already applied
 //   png_prepare_many those four for a list of files on several threads (fnx_png_decode_batch; tools/png_batch_host.cpp runs it
 //                    under the address and the thread sanitizer)
+//   png_expand_of, png_adam7_passes  the file as the kernels' descriptors: what fnx_png_decode and the decode batch upload
 #include "common.hpp"
 
 #include <atomic>
@@ -67,8 +68,6 @@ uint32_t crc32(const uint8_t *p, size_t n)
 
 bool tag_is(const uint8_t *p, const char *t) { return std::memcmp(p, t, 4) == 0; }
 
-const uint8_t PNG_SIG[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
-
 // the chunk at data[pos ..): its body's offset and length once length, bounds and CRC hold
 int next_chunk(const uint8_t *data, size_t n, size_t pos, size_t *body, uint32_t *len)
 {
@@ -82,7 +81,7 @@ int next_chunk(const uint8_t *data, size_t n, size_t pos, size_t *body, uint32_t
 
 int read_ihdr(const uint8_t *data, size_t n, PngFile *f)
 {
-    if (n < 8 || std::memcmp(data, PNG_SIG, 8) != 0) return png_corrupt("no PNG signature");
+    if (!png_signature(data, n)) return png_corrupt("no PNG signature");
     size_t body = 0;
     uint32_t len = 0;
     FNX_TRY(next_chunk(data, n, 8, &body, &len));
@@ -494,6 +493,33 @@ size_t png_planes_bytes(const PngFile &f)
     size_t total = 0;
     for (int p = 0; p < 7; p++) total += ((f.prow[p] + 15) & ~size_t(15)) * f.ph[p];
     return total;
+}
+
+PngExpand png_expand_of(const PngFile &f)
+{
+    return PngExpand{f.w, f.h, f.color_type, f.depth, f.has_trns ? 1 : 0, {f.trns16[0], f.trns16[1], f.trns16[2]}};
+}
+
+int png_adam7_passes(const PngFile &f, const uint8_t *stream, uint8_t *rows, uint32_t first, PngBatchFile passes[7], PngAdam7File *a, uint32_t slot[7])
+{
+    int n = 0;
+    for (int p = 0; p < 7; p++) {
+        slot[p] = 0;
+        if (f.ph[p] == 0) continue;
+        PngBatchFile &dp = passes[n];                 // the unfilter kernel's view of the pass: an image of its own
+        std::memset(&dp, 0, sizeof dp);
+        dp.stream = stream + f.poff[p];
+        dp.spitch = 1 + f.prow[p];
+        dp.rows = rows;
+        dp.ppitch = align16(f.prow[p]);
+        dp.rowbytes = static_cast<int>(f.prow[p]);
+        dp.npix = static_cast<int>(f.prow[p] / f.bpp);
+        a->plane[p] = rows;
+        a->ppitch[p] = static_cast<uint32_t>(dp.ppitch);
+        rows += dp.ppitch * f.ph[p];
+        slot[p] = first + n++;
+    }
+    return n;
 }
 
 int png_stream_size(const PngFile &f, size_t *want)
