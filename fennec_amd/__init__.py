@@ -274,6 +274,8 @@ def load_library() -> C.CDLL:
         _sig(L, "fnx_ycbcr_to_nrgba", i, [ctx, i, _u8p, i, _u8p, _u8p, i, i, i, i] + img)
         _sig(L, "fnx_ssim_fast_against_ycbcr", i, [ctx, C.c_void_p, i, _u8p, i, _u8p, _u8p, i, i, _f64p, _f64p])
         _sig(L, "fnx_apply_palette", i, [ctx, i] + img + [i, i, _u8p, i, _u8p, i, _u8p, i])
+        _sig(L, "fnx_median_cut", i, [ctx, i] + img + [i, i, i, C.POINTER(i), _u8p, C.POINTER(i)])
+        _sig(L, "fnx_quantize", i, [ctx, i] + img + [i, i, i, _u8p, C.POINTER(i), _u8p, i, _u8p, i, _f64p, _f64p])
         _sig(L, "fnx_png_reduce", i, [ctx, i] + img + [i, i, i, C.POINTER(i), _u8p, C.POINTER(i), _u8p, i])
         _sig(L, "fennec_CompressFilePNGReduce", i, [ctx, _u8p, C.c_size_t, C.POINTER(FileOptions), C.POINTER(i), _u8p, C.POINTER(i), _u8p,
                                                      C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i)])
@@ -1472,6 +1474,47 @@ class Context:
                       "applyPalette")
         return idx, q
 
+    def median_cut(self, img, levels=(16, 32, 64, 128, 256)):
+        """medianCut (targetsize.go:422-486; fnx_median_cut) at every palette size of `levels` (strictly ascending, 1..256) in one
+        run -> a list of (ncolors, 4) uint8 arrays.  Tied samples split in the order they were taken (the library's tie rule: the
+        reference's order is pdqsort's, so any is a reference answer).  img: tight rows."""
+        v = _Img(img)
+        lv = (C.c_int * len(levels))(*[int(c) for c in levels])
+        pal = np.zeros((len(levels), 256, 4), dtype=np.uint8)
+        n = (C.c_int * max(len(levels), 1))()
+        with self._ordered(img):
+            self._chk(self._lib.fnx_median_cut(self._h, v.space, v.ptr, v.stride, v.w, v.h, len(levels), lv, pal.ctypes.data, n),
+                      "fnx_median_cut")
+        return [pal[l, :n[l]].copy() for l in range(len(levels))]
+
+    def quantize(self, img, max_colors: int, want_indices: bool = True, want_quantized: bool = True, want_ssim: bool = True, window=None):
+        """One iteration of quantizeStrategy's loop (targetsize.go:183-205; fnx_quantize) without the PNG size test ->
+        (palette (n, 4) uint8, indices (h, w) uint8, quantized (h, w, 4), ssim): medianCut at max_colors, applyPalette +
+        palettedToNRGBA, SSIMFast(img, quantized).  An output not wanted is None."""
+        v = _Img(img)
+        idx = q = None
+        iptr, qptr, qstride = None, None, 0
+        if want_indices:
+            if v.space == FNX_DEVICE:
+                import torch
+                idx = torch.empty((v.h, v.w), dtype=torch.uint8, device=img.device)
+                iptr = idx.data_ptr()
+            else:
+                idx = np.empty((v.h, v.w), dtype=np.uint8)
+                iptr = idx.ctypes.data
+        if want_quantized:
+            q = v.like(v.w, v.h)
+            qv = _Img(q)
+            qptr, qstride = qv.ptr, qv.stride
+        win, winp = _f64(self.gaussianKernel() if window is None else window)
+        pal = np.zeros((256, 4), dtype=np.uint8)
+        n, out = C.c_int(0), C.c_double(0.0)
+        with self._ordered(img, idx, q):
+            self._chk(self._lib.fnx_quantize(self._h, v.space, v.ptr, v.stride, v.w, v.h, int(max_colors), pal.ctypes.data, C.byref(n),
+                                             iptr, v.w, qptr, qstride, winp if want_ssim else None, C.byref(out) if want_ssim else None),
+                      "fnx_quantize")
+        return pal[:n.value].copy(), idx, q, (out.value if want_ssim else None)
+
     def png_reduce(self, img, max_colors: int = 256, want_plane: bool = True, plane=None):
         """compressPNG's decision and reduced image (compress.go:90-153; fnx_png_reduce) -> (kind, palette (n, 4) uint8, plane):
         FNX_PNG_PALETTED with tryPalettize's palette (first-occurrence order) and index plane, FNX_PNG_GRAY with toGray's
@@ -2144,6 +2187,8 @@ def png_adam7_passes(w: int, h: int, color_type: int, depth: int):
         raise FennecError(f"fnx_png_adam7_passes failed ({rc}): {L.fnx_last_error().decode()}")
     return list(pw), list(ph), list(rb), total.value
 
+def median_cut(img, levels=(16, 32, 64, 128, 256)): return default_context(_dev_of(img)).median_cut(img, levels)
+def quantize(img, max_colors): return default_context(_dev_of(img)).quantize(img, max_colors)
 def png_reduce(img, max_colors=256, want_plane=True): return default_context(_dev_of(img)).png_reduce(img, max_colors, want_plane)
 def tryPalettize(img, max_colors=256): return default_context(_dev_of(img)).tryPalettize(img, max_colors)
 

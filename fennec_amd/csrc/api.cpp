@@ -1653,6 +1653,121 @@ int fnx_apply_palette(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, 
     return FNX_OK;
 }
 
+// ---- medianCut (targetsize.go:422-486) and one iteration of quantizeStrategy (targetsize.go:183-205) ------------------------
+// what both entries ask of the image and the levels, before the ctx is looked at
+static int check_median_cut(int space, const uint8_t *src, int sstride, int w, int h, int nlevels, const int *max_colors)
+{
+    FNX_TRY(check_space(space));
+    FNX_REQUIRE(w >= 0 && h >= 0, "negative dims");
+    FNX_REQUIRE(max_colors != nullptr && nlevels >= 1, "max_colors: at least one level");
+    for (int l = 0; l < nlevels; l++) {
+        FNX_REQUIRE(max_colors[l] >= 1 && max_colors[l] <= 256, "a level outside 1..256");
+        FNX_REQUIRE(l == 0 || max_colors[l] > max_colors[l - 1], "levels must be strictly ascending");
+    }
+    if (w > 0 && h > 0) {
+        FNX_REQUIRE(src != nullptr, "src pixel pointer is null");
+        // medianCut indexes the flat Pix slice (off := i*4, targetsize.go:437), not rows: a padded image's samples would be
+        // taken from its padding
+        FNX_REQUIRE(sstride == 4 * w, "median cut takes tight images only (sstride == 4*w): the reference samples the flat Pix slice");
+    }
+    return FNX_OK;
+}
+
+// a level's entries from the kernel's words; the rest of the 256 zeroed
+static int unpack_palette(const uint32_t *words, uint32_t n, uint8_t *palette)
+{
+    FNX_REQUIRE(n >= 1 && n <= 256, "median cut: the kernel's colour count");
+    std::memset(palette, 0, 1024);
+    for (uint32_t i = 0; i < n; i++)
+        for (int c = 0; c < 4; c++) palette[4 * i + c] = static_cast<uint8_t>(words[i] >> (8 * c));
+    return FNX_OK;
+}
+
+int fnx_median_cut(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int nlevels, const int *max_colors,
+                   uint8_t *palettes, int *ncolors)
+{
+    FNX_TRY(check_median_cut(space, src, sstride, w, h, nlevels, max_colors));
+    FNX_REQUIRE(palettes != nullptr && ncolors != nullptr, "palettes/ncolors is null");
+    FNX_ENTER(ctx);
+    if (w == 0 || h == 0) {   // targetsize.go:443-445
+        std::memset(palettes, 0, static_cast<size_t>(nlevels) * 1024);
+        for (int l = 0; l < nlevels; l++) { palettes[static_cast<size_t>(l) * 1024 + 3] = 255; ncolors[l] = 1; }
+        return FNX_OK;
+    }
+    const uint32_t *d_out = nullptr;
+    FNX_TRY(launch_median_cut(ctx, space, src, w, h, nlevels, max_colors, &d_out));
+    std::vector<uint32_t> words(static_cast<size_t>(nlevels) * 257);
+    FNX_TRY(fetch_bytes(ctx, d_out, words.data(), sizeof(uint32_t) * words.size()));
+    for (int l = 0; l < nlevels; l++) {
+        const uint32_t n = words[static_cast<size_t>(nlevels) * 256 + l];
+        FNX_TRY(unpack_palette(words.data() + static_cast<size_t>(l) * 256, n, palettes + static_cast<size_t>(l) * 1024));
+        ncolors[l] = static_cast<int>(n);
+    }
+    return FNX_OK;
+}
+
+int fnx_quantize(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int max_colors, uint8_t *palette, int *ncolors,
+                 uint8_t *indices, int istride, uint8_t *quantized, int qstride, const double *window, double *ssim)
+{
+    FNX_TRY(check_median_cut(space, src, sstride, w, h, 1, &max_colors));
+    FNX_REQUIRE(w > 0 && h > 0, "quantize: an empty image");
+    FNX_REQUIRE(palette != nullptr && ncolors != nullptr, "palette/ncolors is null");
+    FNX_REQUIRE(indices != nullptr || quantized != nullptr || ssim != nullptr, "no output requested");
+    if (indices) FNX_REQUIRE(istride >= w, "index stride");
+    if (quantized) FNX_TRY(check_img(quantized, qstride, w, h, "quantized"));
+    FNX_REQUIRE(ssim == nullptr || window != nullptr, "window is null");
+    FNX_ENTER(ctx);
+    ctx->kept.valid = false;
+    DevImg s;
+    FNX_TRY(stage_in(ctx, space, src, sstride, w, h, SLOT_IN_A, &s));        // the image's one crossing
+    const uint32_t *d_out = nullptr;
+    FNX_TRY(launch_median_cut(ctx, FNX_DEVICE, s.p, w, h, 1, &max_colors, &d_out));
+    // applyPalette with the palette where the kernel left it
+    DevOut q;
+    uint8_t *dq = nullptr;
+    int dqs = 0;
+    if (quantized) {
+        FNX_TRY(stage_out(ctx, space, quantized, qstride, w, h, SLOT_OUT, &q));
+        dq = q.p; dqs = q.stride;
+    } else if (ssim) {
+        void *t = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_IN_B, static_cast<size_t>(w) * 4 * h + 16, &t));
+        dq = static_cast<uint8_t *>(t); dqs = w * 4;
+    }
+    uint8_t *didx = indices;
+    int dpitch = istride;
+    if (indices && space == FNX_HOST) {
+        dpitch = (w + 3) & ~3;
+        void *t = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_TMP0, static_cast<size_t>(dpitch) * h + 16, &t));
+        didx = static_cast<uint8_t *>(t);
+    }
+    FNX_TRY(launch_apply_palette_device(ctx, s.p, s.stride, w, h, d_out, d_out + 256, didx, dpitch, dq, dqs));
+    if (indices && space == FNX_HOST)
+        FNX_HIP(hipMemcpy2DAsync(indices, istride, didx, dpitch, w, h, hipMemcpyDeviceToHost, ctx->stream));
+    if (quantized) FNX_TRY(finish_enqueue(ctx, space, &q));
+    // computeSSIMNRGBA at equal dims = SSIMFast (targetsize.go:563-568), as fnx_ssim_fast runs it
+    double *dres = nullptr;
+    if (ssim) {
+        const double *dwin = nullptr;
+        FNX_TRY(upload_window(ctx, window, &dwin));
+        int nw, nh;
+        if (!ssim_fast_dims(w, h, &nw, &nh) && (w < 8 || h < 8)) FNX_TRY(check_pix_lens(w, h, s.stride, dqs));
+        FNX_TRY(result_slot(ctx, 1, &dres));
+        FNX_TRY(ssim_fast_device(ctx, one_pair(s.p, s.stride, dq, dqs, w, h), window, dwin, dres));
+    }
+    void *pin = nullptr;                                                      // (the ring's last allocation of the call)
+    FNX_TRY(pinned_alloc(ctx, sizeof(uint32_t) * 257, &pin));
+    FNX_HIP(hipMemcpyAsync(pin, d_out, sizeof(uint32_t) * 257, hipMemcpyDeviceToHost, ctx->stream));
+    // the one wait
+    if (ssim) FNX_TRY(result_wait(ctx, dres, ssim, 1));
+    FNX_HIP(hipStreamSynchronize(ctx->stream));
+    const uint32_t *words = static_cast<const uint32_t *>(pin);
+    FNX_TRY(unpack_palette(words, words[256], palette));
+    *ncolors = static_cast<int>(words[256]);
+    return FNX_OK;
+}
+
 // ---- orientation -------------------------------------------------------------------------
 int fnx_orient(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int orient,
                uint8_t *dst, int dstride)

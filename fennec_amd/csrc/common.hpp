@@ -116,6 +116,7 @@ enum Slot {
     // fnx_png_compress_batch: the colours pass's work area (results, tables, lists), the chunk's planes, its filtered streams, the
     // unit and image tables of its four stages; fnx_png_recompress_batch: the decoded images of a span
     SLOT_PNG_CB_WORK, SLOT_PNG_CB_PLANES, SLOT_PNG_CB_STREAMS, SLOT_PNG_CB_TAB0, SLOT_PNG_CB_TAB1, SLOT_PNG_CB_TAB2, SLOT_PNG_CB_TAB3, SLOT_PNG_CB_IMG,
+    SLOT_MEDIAN_CUT, SLOT_MEDIAN_CUT_TAB,   // median_cut.hip: both sample buffers and the palettes; palette.hip: apply_palette's tables made on the device from them
     SLOT_DONE,       // workgroup counters of the kernels that finish their own reduction (ssim.hip), zero between launches
     SLOT_COUNT
 };
@@ -631,6 +632,15 @@ int jpeg_decode_batch_device(fnx_ctx *ctx, int n, const uint8_t *const *files, c
 // applyPalette (+ palettedToNRGBA): palette = n x 4 host bytes (opaque); idx and/or quant may be null
 int launch_apply_palette(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, const uint8_t *palette, int n,
                          uint8_t *idx, int istride, uint8_t *quant, int qstride);
+// the same with the palette still on the device (fnx_quantize): d_palette = 256 words r | g << 8 | b << 16 | 255 << 24, *d_ncolors of
+// them valid; pal_tables_kernel makes the tables the host makes above
+int launch_apply_palette_device(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, const uint32_t *d_palette, const uint32_t *d_ncolors,
+                                uint8_t *idx, int istride, uint8_t *quant, int qstride);
+// median_cut.hip: medianCut's samples (targetsize.go:426-441) of an image of n pixels, and the palettes of a tight w x h image
+// (w h >= 1) in `space` at nlevels strictly ascending sizes within 1 .. 256; *d_out (device): [nlevels][256] entries
+// r | g << 8 | b << 16 | 255 << 24, then ncolors[nlevels].  Nothing is waited for.
+void median_cut_samples(long long n, long long *step, long long *ns);
+int launch_median_cut(fnx_ctx *ctx, int space, const uint8_t *src, int w, int h, int nlevels, const int *max_colors, const uint32_t **d_out);
 // image.YCbCr / image.Gray planes -> NRGBA (convert.hip); device pointers; cb == cr == nullptr: Gray
 // boxDownsample(toNRGBARef(planes)) without the image (ssim.hip); *done = false: not its case, convert and downsample instead
 int launch_box_downsample_ycc(fnx_ctx *ctx, const uint8_t *y, int ystride, const uint8_t *cb, const uint8_t *cr, int cstride,

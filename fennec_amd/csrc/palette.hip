@@ -1,7 +1,6 @@
 // applyPalette (targetsize.go:488-527) + palettedToNRGBA (targetsize.go:529-546) on gfx950.
 // the per-pixel part of the PNG quantisation strategy (targetsize.go:180-206);
-// medianCut stays with the caller (<= 100 000 samples, and its splits depend on Go's unstable
-// sort.Slice -- not restated).
+// medianCut is median_cut.hip (its splits depend on Go's unstable sort.Slice: the library fixes one tie order).
 //
 // Nearest palette entry by squared RGB distance, first minimum wins (strict `<`, :513).  The
 // reference memoises per colour in a map; brute force gives the same answer.  Per entry i and
@@ -41,13 +40,16 @@ struct PalArgs {
     const uint32_t *rgb;     // [n] packed r | g<<8 | b<<16
     const uint32_t *comp;    // [npad] packed (255-r) | (255-g)<<8 | (255-b)<<16
     const uint32_t *konst;   // [npad] |p|^2 * 256 + i   (padding: 0xffffffff)
+    const uint32_t *n_dev;   // not null: n (and npad) are read from here -- the palette was made on the device (fnx_quantize)
 };
 
 __global__ __launch_bounds__(256) void apply_palette_kernel(PalArgs a)
 {
     __shared__ uint32_t s_pal[256];
     const int tid = threadIdx.x;
-    if (tid < a.n) s_pal[tid] = a.rgb[tid] | 0xff000000u;
+    const int n = a.n_dev ? static_cast<int>(*a.n_dev) : a.n;
+    const int npad = a.n_dev ? (n + 7) & ~7 : a.npad;
+    if (tid < n) s_pal[tid] = a.rgb[tid] | 0xff000000u;
     __syncthreads();
     const int x = 4 * (blockIdx.x * 64 + (tid & 63));
     const int y = blockIdx.y * 4 + (tid >> 6);
@@ -60,7 +62,7 @@ __global__ __launch_bounds__(256) void apply_palette_kernel(PalArgs a)
     uint32_t best[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
     const uint32_t *__restrict__ comp = a.comp;
     const uint32_t *__restrict__ konst = a.konst;
-    for (int i0 = 0; i0 < a.npad; i0 += 8) {
+    for (int i0 = 0; i0 < npad; i0 += 8) {
         uint32_t p[8], k[8];
 #pragma unroll
         for (int j = 0; j < 8; j++) { p[j] = comp[i0 + j]; k[j] = konst[i0 + j]; }   // uniform: s_load_dwordx8
@@ -98,6 +100,7 @@ struct PalGridArgs {
     const uint32_t *rgb;     // [n] packed r | g<<8 | b<<16
     int n;
     uint8_t *grid;           // [PG_CELLS][PG_REC]
+    const uint32_t *n_dev;   // not null: n is read from here
 };
 
 // smallest and largest squared distance from entry value p to the interval [lo, lo + 7] of one channel
@@ -118,13 +121,14 @@ __global__ __launch_bounds__(256) void pal_grid_kernel(PalGridArgs a)
     __shared__ uint32_t s_cnt[64];
     __shared__ uint8_t s_list[64][PG_REC];
     const int tid = threadIdx.x, lc = tid >> 2, q = tid & 3;
-    if (tid < a.n) s_rgb[tid] = a.rgb[tid];
+    const int n = a.n_dev ? static_cast<int>(*a.n_dev) : a.n;
+    if (tid < n) s_rgb[tid] = a.rgb[tid];
     if (tid < 64) { s_u[tid] = 0x7fffffff; s_cnt[tid] = 0u; }
     __syncthreads();
     const int cell = blockIdx.x * 64 + lc;
     const int r0 = (cell & 31) << 3, g0 = ((cell >> 5) & 31) << 3, b0 = ((cell >> 10) & 31) << 3;
     int u = 0x7fffffff;
-    for (int i = q; i < a.n; i += 4) {
+    for (int i = q; i < n; i += 4) {
         const uint32_t p = s_rgb[i];
         int mn = 0, mx = 0;
         pg_chan(p & 0xffu, r0, mn, mx); pg_chan((p >> 8) & 0xffu, g0, mn, mx); pg_chan((p >> 16) & 0xffu, b0, mn, mx);
@@ -133,7 +137,7 @@ __global__ __launch_bounds__(256) void pal_grid_kernel(PalGridArgs a)
     atomicMin(&s_u[lc], u);
     __syncthreads();
     u = s_u[lc];
-    for (int i = q; i < a.n; i += 4) {
+    for (int i = q; i < n; i += 4) {
         const uint32_t p = s_rgb[i];
         int mn = 0, mx = 0;
         pg_chan(p & 0xffu, r0, mn, mx); pg_chan((p >> 8) & 0xffu, g0, mn, mx); pg_chan((p >> 16) & 0xffu, b0, mn, mx);
@@ -175,7 +179,8 @@ __global__ __launch_bounds__(256) void apply_palette_grid_kernel(PalGridApply ga
     __shared__ uint32_t s_pal[256];
     __shared__ u32x2 s_pair[256];
     const int tid = threadIdx.x;
-    if (tid < a.n) s_pal[tid] = a.rgb[tid] | 0xff000000u;
+    const int n = a.n_dev ? static_cast<int>(*a.n_dev) : a.n;
+    if (tid < n) s_pal[tid] = a.rgb[tid] | 0xff000000u;
     s_pair[tid] = *reinterpret_cast<const u32x2 *>(ga.pairs + 2 * tid);
     __syncthreads();
     const int x = 4 * (blockIdx.x * 64 + (tid & 63));
@@ -196,9 +201,9 @@ __global__ __launch_bounds__(256) void apply_palette_grid_kernel(PalGridApply ga
     }
 #pragma unroll
     for (int e = 0; e < 4; e++) {
-        const uint32_t n = l0[e].x & 0xffu;
-        over = over || n == 0xffu;
-        most = max(most, n == 0xffu ? 0u : n);
+        const uint32_t len = l0[e].x & 0xffu;
+        over = over || len == 0xffu;
+        most = max(most, len == 0xffu ? 0u : len);
     }
     auto visit = [&](int e, uint32_t idx) {
         const u32x2 pr = s_pair[idx];
@@ -235,7 +240,7 @@ __global__ __launch_bounds__(256) void apply_palette_grid_kernel(PalGridApply ga
 #pragma unroll
         for (int e = 0; e < 4; e++)
             if ((l0[e].x & 0xffu) == 0xffu)
-                for (int i = 0; i < a.n; i++) visit(e, static_cast<uint32_t>(i));
+                for (int i = 0; i < n; i++) visit(e, static_cast<uint32_t>(i));
     }
     if (a.idx) {
         uint8_t *ip = a.idx + static_cast<size_t>(y) * a.istride + x;
@@ -309,6 +314,62 @@ int launch_apply_palette(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, i
     a.comp = a.rgb + npad;
     a.konst = a.rgb + 2 * npad;
     hipLaunchKernelGGL(apply_palette_kernel, dim3((w + 255) / 256, (h + 3) / 4), dim3(256), 0, ctx->stream, a);
+    FNX_HIP(hipGetLastError());
+    return FNX_OK;
+}
+
+// ---- the palette still on the device (fnx_quantize): the tables above made by one small launch ----
+struct PalTabArgs {
+    const uint32_t *pal;     // [256] r | g << 8 | b << 16 | a << 24
+    const uint32_t *n;
+    uint32_t *tab;           // grid: rgb[256] | pairs[256][2]; else rgb[256] | comp[256] | konst[256]
+    int grid;
+};
+
+__global__ __launch_bounds__(256) void pal_tables_kernel(PalTabArgs a)
+{
+    const uint32_t i = threadIdx.x;
+    const bool real = i < *a.n;
+    const uint32_t p = real ? a.pal[i] : 0u;
+    const uint32_t r = p & 0xffu, g = (p >> 8) & 0xffu, b = (p >> 16) & 0xffu;
+    const uint32_t comp = real ? (255u - r) | ((255u - g) << 8) | ((255u - b) << 16) : 0u;
+    const uint32_t konst = real ? (r * r + g * g + b * b) * 256u + i : 0xffffffffu;      // past n: an entry that cannot win
+    a.tab[i] = p & 0x00ffffffu;
+    a.tab[a.grid ? 256u + 2u * i : 256u + i] = comp;
+    a.tab[a.grid ? 256u + 2u * i + 1u : 512u + i] = konst;
+}
+
+int launch_apply_palette_device(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, const uint32_t *d_palette, const uint32_t *d_ncolors,
+                                uint8_t *idx, int istride, uint8_t *quant, int qstride)
+{
+    if (w <= 0 || h <= 0) return FNX_OK;
+    const int mode = palette_grid_mode(ctx);
+    const bool grid = mode == 1 || (mode != 0 && static_cast<long>(w) * h >= 262144L);      // as launch_apply_palette chooses
+    void *d = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_MEDIAN_CUT_TAB, sizeof(uint32_t) * 768, &d));
+    PalTabArgs ta{d_palette, d_ncolors, static_cast<uint32_t *>(d), grid ? 1 : 0};
+    hipLaunchKernelGGL(pal_tables_kernel, dim3(1), dim3(256), 0, ctx->stream, ta);
+    PalArgs p{};
+    p.src = src; p.idx = idx; p.quant = quant;
+    p.sstride = sstride; p.istride = istride; p.qstride = qstride; p.w = w; p.h = h;
+    p.rgb = ta.tab;
+    p.n_dev = d_ncolors;
+    if (grid) {
+        void *cells = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_TMP1, static_cast<size_t>(PG_CELLS) * PG_REC, &cells));
+        PalGridArgs ba{};
+        ba.rgb = ta.tab; ba.grid = static_cast<uint8_t *>(cells); ba.n_dev = d_ncolors;
+        hipLaunchKernelGGL(pal_grid_kernel, dim3(PG_CELLS / 64), dim3(256), 0, ctx->stream, ba);
+        PalGridApply ga{};
+        ga.p = p;
+        ga.grid = ba.grid;
+        ga.pairs = ta.tab + 256;
+        hipLaunchKernelGGL(apply_palette_grid_kernel, dim3((w + 255) / 256, (h + 3) / 4), dim3(256), 0, ctx->stream, ga);
+    } else {
+        p.comp = ta.tab + 256;
+        p.konst = ta.tab + 512;
+        hipLaunchKernelGGL(apply_palette_kernel, dim3((w + 255) / 256, (h + 3) / 4), dim3(256), 0, ctx->stream, p);
+    }
     FNX_HIP(hipGetLastError());
     return FNX_OK;
 }

@@ -616,11 +616,54 @@ int fnx_ssim_fast_against_ycbcr(fnx_ctx *ctx, const fnx_prepared *ref, int space
 /* Nearest palette entry per pixel by squared RGB distance, first minimum wins (targetsize.go:
  * 505-517); `indices` = image.Paletted.Pix (w x h bytes, stride istride), `quantized` =
  * palettedToNRGBA of it (NRGBA, alpha 255).  Either output may be NULL.  palette: ncolors x 4
- * HOST bytes r,g,b,a with a == 255 (what medianCut emits; medianCut itself stays with the
- * caller).  Integer arithmetic: bit-exact. */
+ * HOST bytes r,g,b,a with a == 255 (what medianCut emits: fnx_median_cut below, or the
+ * caller's own).  Integer arithmetic: bit-exact. */
 int fnx_apply_palette(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h,
                       const uint8_t *palette, int ncolors, uint8_t *indices, int istride,
                       uint8_t *quantized, int qstride);
+
+/* ---- medianCut (targetsize.go:352-486): the palettes of quantizeStrategy (targetsize.go:180-206) --------------------- */
+/* The rule -- the arithmetic of targetsize.go:352-486 restated, with ONE tie order fixed:
+ *   Samples (targetsize.go:426-441).  n = w*h in 64 bits; step = n / 100000 when n > 100000, else 1.  Sample j is the R, G, B of
+ *     the flat 4-byte group at byte 4*j*step, for j*step < n; alpha is not looked at.  1 .. 199 999 samples (447 x 447: 199 809
+ *     at step 1; 448 x 447: 100 128 at step 2).  The reference indexes the flat Pix slice (`off := i*4`, :437), not rows, so a
+ *     padded image's samples would come out of its padding: this entry takes TIGHT images only, sstride != 4*w is
+ *     FNX_ERR_INVALID.
+ *   Boxes (targetsize.go:352-385, 447).  A box is a set of samples with its per-channel minima and maxima; the run starts with
+ *     one box holding every sample.
+ *   Split loop (targetsize.go:449-479), while there are fewer boxes than max_colors: among the boxes with two samples or more
+ *     take the FIRST one of the largest score (rMax-rMin+1)*(gMax-gMin+1)*(bMax-bMin+1) * count (:452-461; 64 bits here: a
+ *     64 x 64 noise image already scores 2^36); stop when no box has two samples (:462-464).  Axis (:387-398): R when rRange >=
+ *     gRange and rRange >= bRange, else G when gRange >= bRange, else B.  Order the box by (value on the axis, sample number j)
+ *     -- THIS IS THE LIBRARY'S TIE RULE: the reference's sort.Slice (:469-471) is pdqsort, which leaves tied samples in an
+ *     order of its own, so ANY tie order is a reference answer (as with fnx_png_reduce's palette order) and this library fixes
+ *     one; it makes every split a function of sets, so launch geometry cannot reach the bytes.  mid = count / 2 (:473): the
+ *     first mid samples replace the box in place, the rest become a new box appended at the end (:474-478).  A box of
+ *     identical samples still splits (volume 1, score = count).
+ *   Palette (targetsize.go:400-414, 481-485).  Per box in list order (rSum / count, gSum / count, bSum / count, 255), truncating.
+ *   Levels.  max_colors[0 .. nlevels) is strictly ascending, each in 1 .. 256.  The split sequence does not depend on max_colors,
+ *     so medianCut(img, 16)'s boxes are medianCut(img, 256)'s after 15 splits: level l's palette is the box list when it first
+ *     has max_colors[l] boxes, or the final list when the loop stopped earlier -- what medianCut(img, max_colors[l]) returns.
+ *     ncolors[l] is that list's length; palettes + l*1024 holds its entries, the rest of the 256 zeroed.
+ *   Empty image (targetsize.go:443-445).  w*h == 0: one entry (0,0,0,255) at every level, FNX_OK, no device work.
+ * space FNX_DEVICE gathers the samples from the resident image on the device; FNX_HOST gathers them on the host and uploads
+ * only them (<= 800 KB instead of the image); both return the same bytes.  FNX_ERR_INVALID before any device work: NULL ctx,
+ * src (with w*h > 0), max_colors, palettes or ncolors; nlevels < 1; a level outside 1 .. 256 or a list that does not ascend;
+ * sstride != 4*w; negative dims.  Kernel: csrc/median_cut.hip, one workgroup for the whole run (median_cut_kernel in
+ * fnx_ctx_last_kernel(ctx, FNX_PROF_MAIN); tools/median_cut_hostsim runs the same text on the CPU).  Integers: two calls
+ * return identical bytes. */
+int fnx_median_cut(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h,
+                   int nlevels, const int *max_colors,
+                   uint8_t *palettes /* HOST, nlevels x 256 x 4 */, int *ncolors /* nlevels */);
+/* One iteration of quantizeStrategy's loop (targetsize.go:183-205) without its PNG size test: fnx_median_cut at one level,
+ * fnx_apply_palette with that palette into `indices` and / or `quantized` (either may be NULL), and -- ssim != NULL --
+ * fnx_ssim_fast(src, quantized, window) (computeSSIMNRGBA at equal dims; the quantized image goes to scratch when the caller did
+ * not ask for it).  The palette never leaves the device between the three; a host image crosses the link once; one wait at the
+ * end.  Every output equals the three calls composed.  src is tight (sstride == 4*w) and w*h > 0. */
+int fnx_quantize(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int max_colors,
+                 uint8_t *palette /* HOST, 256 x 4 */, int *ncolors,
+                 uint8_t *indices, int istride, uint8_t *quantized, int qstride,
+                 const double *window, double *ssim);
 
 /* ---- compressPNG's pixel stages (compress.go:90-153, convert.go:76-100) ------------------- */
 /* What compressPNG decides and builds before png.Encoder sees a byte, for an NRGBA w x h image (w, h <= 65535):
@@ -1078,8 +1121,9 @@ int fennec_CompressBatchJPEGOpts(int device, int workers, int n, const uint8_t *
  * fennec_CompressFileJPEG stages them (opts->file; its auto_format and target_ssim are ignored), then ONE
  * fnx_jpeg_target_size on the resident image with the library's SSIM window: cand, *winner, out / cap / *nbytes and cancel are
  * that call's.  `strategies` with all four bits is hitTargetSize under Format: JPEG (targetsize.go:26-75 with wantJPEG).
- * Format: Auto runs quantizeStrategy between strategies 1 and 3, and that one stays the caller's: such a caller passes
- * strategy subsets (FNX_TS_QUALITY, then its own quantizeStrategy, then the rest) and applies betterFit over all candidates
+ * Format: Auto runs quantizeStrategy between strategies 1 and 3, and its loop stays the caller's: such a caller passes
+ * strategy subsets (FNX_TS_QUALITY, then its own quantizeStrategy -- fnx_quantize is one iteration of it up to the png.Encode
+ * size test -- then the rest) and applies betterFit over all candidates
  * itself, as go/fennec_hip.go's hitTargetSize does over decoded images.
  * dims[0..1] = OriginalDimensions (after orientation); dims[2..3] = the winner's final_w x final_h (fennec.go:153 overwrites
  * FinalDimensions with the size result's) -- the staged image's size when there is no winner.
