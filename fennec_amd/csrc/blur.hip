@@ -16,7 +16,7 @@
 //    SSIMFast(src, blurred) needs no second pass over either (launch_blur_scored).
 #include <hip/hip_ext.h>
 
-#include "common.hpp"
+#include "blur_launch.hpp"
 #include "devutil.hpp"
 
 #include <algorithm>
@@ -86,8 +86,6 @@ __global__ __launch_bounds__(256) void blur_pass_kernel(PassArgs<T> a)
 // ------------------------------------------------------------------------------------
 // fused fast path
 // ------------------------------------------------------------------------------------
-constexpr int FUSED_RMAX = 16;    // radius <= 16 (sigma <= 5.33): the tile kernel; r3: 9..16 added (the H window streams through, see WIDE)
-constexpr int SCORE_RMAX = 8;     // the one-pass GaussianBlur + SSIMFast form and the 128-lane tile stop here
 
 struct FusedArgs {
     const uint8_t *src;
@@ -106,10 +104,6 @@ struct FusedArgs {
     int cstride;                  // entries between the LDS copies of a box table: >= (nbx+1)(nby+1) and
                                   // = 4 mod 16, so that copy c of an entry sits 8c banks away (32 x 4-byte banks)
 };
-
-// most entries of a per-tile box table, (nbx+1) * (nby+1): the two tables live in dynamic LDS sized
-// per launch (4K: 2 x 176 x 8 B = 2.8 KB); the cap keeps the kernel at >= 3 workgroups per CU
-constexpr int SCORE_NBOX = 512;
 
 // channel sums of one pixel into the box table entry at byte offset `off`: the entry is
 // R | G<<16 | B<<32 | A<<48, a box of <= 256 px cannot carry out of a 16-bit field.  (Two
@@ -617,11 +611,6 @@ __global__ __launch_bounds__(NTH, (GUARD && R > 8) ? 2 : ((GUARD && (NTH == 128 
 // box tables from the slabs of a SCORE launch: the boxDownsample'd source (z < n) and blurred
 // (z >= n) images, identical to box_tiled_kernel's output (integer sums are order-free)
 // ------------------------------------------------------------------------------------
-struct BoxRef {           // where one output column (or row) finds its partial sums
-    int32_t part0, part1; // slab offsets of the (at most two) tiles the box spans; part1 < 0: one tile
-    int32_t len, pad;     // box width (height) in source px
-};
-
 struct SlabArgs {
     const unsigned long long *slabs;
     const uint32_t *magic;    // magic[c] = floor(2^32 / 2c) + 1, c <= 256: (2 n + c) / 2c by one v_mul_hi_u32
@@ -730,19 +719,12 @@ template <int R, int NTH, int IH, bool SCORE, bool GUARD = false>
 static int launch_direct_cfg(fnx_ctx *ctx, int n, FusedArgs &fa)
 {
     constexpr int TW = 64, RG = NTH / 32, TH = ((IH - 2 * R) / RG) * RG;
-    note_route(ctx, FNX_PROF_MAIN, SCORE ? (GUARD ? "blur_direct_kernel<SCORE, GUARD>" : "blur_direct_kernel<SCORE>")
-                                         : (GUARD ? "blur_direct_kernel<GUARD>" : "blur_direct_kernel"));
     fa.tiles_x = (fa.w + TW - 1) / TW;
     fa.tiles = fa.tiles_x * ((fa.h + TH - 1) / TH);
     dim3 grid(8 * ((fa.tiles + 7) / 8), n);
-    // the launch's events ride on its own packet (common.hpp: LaunchEvents): the profile pair when this class is
-    // profiled, and for SCORE launches always a stop event -- the tail on the ctx's second stream waits for it
+    // the launch's events ride on its own packet (common.hpp: blur_bind_events)
     LaunchEvents ev;
-    FNX_TRY(prof_bind(ctx, FNX_PROF_MAIN, &ev));
-    if constexpr (SCORE) {
-        if (!ev.stop) ev.stop = ctx->ev_blur[ctx->parity];
-        ctx->blur_done = ev.stop;
-    }
+    FNX_TRY(blur_bind_events(ctx, SCORE, &ev));
     if constexpr (SCORE) {
         fa.cstride = (((fa.nbx + 1) * (fa.nby + 1) + 11) / 16) * 16 + 4;
         // LDS left per workgroup at 4 (256 lanes) / 7 (128 lanes) workgroups per CU, next to the uint8
@@ -760,41 +742,6 @@ static int launch_direct_cfg(fnx_ctx *ctx, int n, FusedArgs &fa)
     }
     FNX_HIP(hipGetLastError());
     return FNX_OK;
-}
-
-// Two tile shapes (measured on MI355X, 4K: 23.6 vs 22.9 us; 1080p: 5.6 vs 6.0 us per image):
-//   128 lanes x 64 intermediate rows  (TH = 52 at R=6, H-pass row halo 1.23x)
-//   256 lanes x (2*TH+2R) rows         (TH = 104,      halo 1.12x) -- wins when the image height
-//     does not leave a mostly empty last tile row and there are enough tiles to fill the chip.
-// Cost model: H work ~ staged rows, V work ~ output rows (about 55 : 45 of the instructions).
-constexpr int WIDE_IH = 128;      // staged rows of the R > 8 tile (256 lanes): TH = the multiple of 8 below 128 - 2R
-static int direct_tile_rows(int R, bool tall)
-{
-    if (R > SCORE_RMAX && R <= FUSED_RMAX) return ((WIDE_IH - 2 * R) / 8) * 8;
-    const int th0 = R >= 1 && R <= SCORE_RMAX ? ((64 - 2 * R) / 4) * 4 : 4;   // never 0: callers divide by it
-    return tall ? 2 * th0 : th0;
-}
-static bool direct_tall(const fnx_ctx *ctx, int R, int n, int w, int h)
-{
-    if (R > SCORE_RMAX) return true;                            // one tile shape for the wide radii
-    const int TH0 = direct_tile_rows(R, false), TH1 = direct_tile_rows(R, true);
-    const long ty0 = (h + TH0 - 1) / TH0, ty1 = (h + TH1 - 1) / TH1;
-    const double cost0 = ty0 * (0.55 * (TH0 + 2 * R) + 0.45 * TH0);
-    const double cost1 = ty1 * (0.55 * (TH1 + 2 * R) + 0.45 * TH1);
-    const long tiles1 = ty1 * ((w + 63) / 64) * n;
-    return cost1 < 0.95 * cost0 && tiles1 >= 4L * ctx->num_cus;
-}
-
-// The guarded kernel's error bound assumes what GaussianBlur's own kernel guarantees (effects.go:155-165):
-// weights >= 0 that sum to 1, so accumulators stay below 256.
-static bool guard_kernel_ok(const double *kernel, int radius)
-{
-    double sum = 0;
-    for (int i = 0; i < 2 * radius + 1; i++) {
-        if (!(kernel[i] >= 0)) return false;
-        sum += kernel[i];
-    }
-    return sum <= 1.0 + 1e-9;
 }
 
 template <int R, bool SCORE, bool GUARD = false>
@@ -838,248 +785,53 @@ static int launch_direct_radius(fnx_ctx *ctx, int radius, int n, FusedArgs &fa, 
     return FNX_ERR_INVALID;
 }
 
-// GaussianBlur (fast mode) of n images AND the boxDownsample'd dstW x dstH planes of every
-// source and blurred image, for SSIMFast(src, blurred) (ssim.go:48-70), in one pass over the
-// pixels.  Returns FNX_NOOP without launching anything when the shape is outside what the
-// SCORE kernel is built for (the caller then runs the two ops separately).
-// Geometry of a one-pass launch: tile shape, box tables.  Cached on the ctx (batches repeat it).
-constexpr int NHEAD = 260 + 257 * 8;   // uint32 words at the head of the table blob: magic[c] (c <= 256, padded to 260), tiedown[8 c + w]
-
-// blur_mfma_kernel<SCORE, .>'s set-up, which depends on the geometry alone, as two tables at the end of the blob (r7: every
-// workgroup used to work this out from bx / by through LDS, ~300 vector instructions per wave before its first row set):
-//  * per (tile column, wave, lane) one word: coln | cnt << 20 | in[0..3] << 25 | channel << 29 | live << 31 -- the lane's
-//    indicator-matrix column (box column first + slot of the wave's 16 px, channel ch; lane n = 3 slot + ch, n = 15: nothing), how
-//    many of the 16 px lie in it (the seed 128 cnt undoes the A operands' - 128) and its byte offset in a table row (spare
-//    column: none).  live: the column is a box column, somebody reads its sums -- the other lanes (lane 15, slots past the
-//    wave's last box column, a wave with no boxed pixel) issue no box atomics at all (4K: 28 lanes of 64)
-//  * per segment the byte offset, in a box table, of the box row of each of its seg + 16 staged rows (tile rows -6 ..), then of
-//    its seg output rows; rows outside the segment or the image go to the spare row nby
-// Written as the device code it replaces was, value for value, the corner cases included (a tile or a wave with no boxed column:
-// first = 255 matches every column of slot 0, so cnt = 16 there; its lanes point at the spare column and are not live).
-static void score_mfma_tables(fnx::ScoreGeom &g, int w, int h)
+// the fp32 weights of the direct kernel, and (wd) the caller's fp64 weights for the GUARD form's fix-ups at R <= 8
+static void set_weights(FusedArgs &fa, const double *kernel, int radius, bool wd)
 {
-    const int seg = g.th, nbx = g.nbx, nby = g.nby;
-    const int tiles_x = (w + 63) / 64, segs = (h + seg - 1) / seg;
-    const size_t ref_words = 4 * (static_cast<size_t>(g.dstW) + g.dstH);
-    const size_t base = (NHEAD + ref_words + static_cast<size_t>(w) + h + 3) & ~size_t(3);   // 16-byte chunks
-    g.coltab = base;
-    g.rowtab = base + 256 * static_cast<size_t>(tiles_x);
-    g.map.resize(g.rowtab + static_cast<size_t>(segs) * (2 * seg + 16), 0);
-    const int32_t *bx = g.map.data() + NHEAD + ref_words, *by = bx + w;
-    uint32_t *col = reinterpret_cast<uint32_t *>(g.map.data()) + g.coltab, *row = reinterpret_cast<uint32_t *>(g.map.data()) + g.rowtab;
-    for (int tx = 0; tx < tiles_x; tx++) {
-        const int x0 = 64 * tx;
-        uint32_t colbox[64];
-        const int b0x = bx[x0];
-        for (int i = 0; i < 64; i++) {
-            const int v = x0 + i < w ? bx[x0 + i] : -1;
-            colbox[i] = (v >= 0 && b0x >= 0) ? static_cast<uint32_t>(v - b0x) : 255u;
-        }
-        for (int wave = 0; wave < 4; wave++) {
-            uint32_t first = 255u;
-            for (int i = 0; i < 16; i++) first = std::min(first, colbox[16 * wave + i]);
-            for (int lane = 0; lane < 64; lane++) {
-                const int r = lane & 15, gq = lane >> 4;
-                const int slot = r / 3, ch = r - 3 * slot;
-                uint32_t cnt = 0, in = 0;
-                for (int i = 0; i < 16; i++) cnt += (r < 15 && colbox[16 * wave + i] == first + slot) ? 1 : 0;
-                for (int e = 0; e < 4; e++)
-                    if (r < 15 && first != 255u && colbox[16 * wave + 4 * gq + e] == first + slot) in |= 1u << e;
-                const bool live = r < 15 && first != 255u && cnt > 0;
-                const uint32_t bc = live ? first + slot : static_cast<uint32_t>(nbx);
-                const uint32_t coln = 16u * bc + 4u * (r < 15 ? ch : 3);
-                col[(4 * tx + wave) * 64 + lane] = coln | cnt << 20 | in << 25 | static_cast<uint32_t>(ch) << 29 | (live ? 1u << 31 : 0u);
-            }
-        }
-    }
-    const int rowbytes = 16 * (nbx + 1);
-    for (int ty = 0; ty < segs; ty++) {
-        const int y0 = ty * seg, b0y = by[y0];
-        uint32_t *rh = row + static_cast<size_t>(ty) * (2 * seg + 16), *rv = rh + seg + 16;
-        auto off = [&](int t) {
-            const int v = (t >= 0 && t < seg && y0 + t < h) ? by[y0 + t] : -1;
-            return static_cast<uint32_t>(rowbytes * ((v >= 0 && b0y >= 0) ? v - b0y : nby));
-        };
-        for (int u = 0; u < seg + 16; u++) rh[u] = off(u - 6);
-        for (int t = 0; t < seg; t++) rv[t] = off(t);
+    for (int i = 0; i < 2 * radius + 1; i++) {
+        fa.wt[i] = static_cast<float>(kernel[i]);
+        if (wd) fa.wd[i] = kernel[i];
     }
 }
-static bool build_score_geom(fnx::ScoreGeom &g, int w, int h, int radius, int dstW, int dstH, int th_fixed = 0)
-{
-    // (th_fixed: the matrix-pipe kernels' tile, whose rows do not depend on the radius -- radii up to 24 since r5)
-    if (radius < 1 || radius > (th_fixed ? 24 : SCORE_RMAX) || w < dstW || h < dstH || dstW <= 0 || dstH <= 0 || w >= (1 << 24) ||
-        h >= (1 << 24))
-        return false;
-    const double xr = static_cast<double>(w) / static_cast<double>(dstW);   // ssim.go:251-252
-    const double yr = static_cast<double>(h) / static_cast<double>(dstH);
-    // Where the one-pass kernel wins (measured at steady clocks, tools/time_onepass.py, us per image
-    // one-pass / two-call): ratio 3.1 (1600x1200) 10.1 / 9.6, 3.75 (1080p) 9.1 / 9.3, 4.3 (2200 px)
-    // 11.5 / 12.1, 5 (1440p) 13.8 / 15.2, 7.5 (4K) 26.9 / 31.9, 15 (8K) 98.3 / 120.1.  Small boxes mean
-    // many table entries per tile to zero, store and (no room for copies) contend on; below 3.6 the
-    // two ops run back to back.  Upwards the limit is the 16-bit sum fields (boxes of <= 256 px).
-    if (std::fmin(xr, yr) < 3.6) return false;
-    // source column / row -> box index (boxes of a downscale are disjoint and ascending)
-    // one table blob: magic[c], tiedown[c][8] (box_mean_u8) | BoxRef per output column, per output row |
-    // box index of every source column, every source row
-    const size_t ref_words = 4 * (static_cast<size_t>(dstW) + dstH);
-    std::vector<int32_t> &map = g.map;
-    map.assign(NHEAD + ref_words + static_cast<size_t>(w) + h, -1);
-    {
-        uint32_t *magic = reinterpret_cast<uint32_t *>(map.data()), *tiedown = magic + 260;
-        std::fill(magic, magic + NHEAD, 0u);
-        for (uint32_t c = 1; c <= 256; c++) {
-            magic[c] = static_cast<uint32_t>((1ull << 32) / (2ull * c)) + 1u;
-            if (c & 1u) continue;                                    // odd counts have no ties
-            const double inv = 1.0 / static_cast<double>(c);         // inv := 1.0 / count (ssim.go:301)
-            for (uint32_t k = 0; k < 256; k++) {
-                const double n = static_cast<double>(c / 2) * static_cast<double>(2 * k + 1);   // n / c == k + 0.5
-                if (n > 255.0 * c) break;
-                if (n * inv < static_cast<double>(k) + 0.5) tiedown[8 * c + (k >> 5)] |= 1u << (k & 31);
-            }
-        }
-    }
-    BoxRef *xref = reinterpret_cast<BoxRef *>(map.data() + NHEAD), *yref = xref + dstW;
-    int32_t *bx = map.data() + NHEAD + ref_words, *by = bx + w;
-    int maxbw = 0, maxbh = 0;
-    for (int d = 0; d < dstW; d++) {
-        int s0, s1;
-        box_edge(d, xr, w, s0, s1);
-        if (d + 1 < dstW) { int n0, n1; box_edge(d + 1, xr, w, n0, n1); if (n0 < s1) return false; }
-        for (int x = s0; x < s1; x++) bx[x] = d;
-        if (s1 - s0 > maxbw) maxbw = s1 - s0;
-    }
-    for (int d = 0; d < dstH; d++) {
-        int s0, s1;
-        box_edge(d, yr, h, s0, s1);
-        if (d + 1 < dstH) { int n0, n1; box_edge(d + 1, yr, h, n0, n1); if (n0 < s1) return false; }
-        for (int y = s0; y < s1; y++) by[y] = d;
-        if (s1 - s0 > maxbh) maxbh = s1 - s0;
-    }
-    if (static_cast<long>(maxbw) * maxbh > 256) return false;   // 16-bit sum fields
-    // most boxes a tile touches, for the preferred tile shape and then the other one
-    bool tall = g.tall_pref;
-    int th = 0, nbx = 0, nby = 0;
-    for (int attempt = 0; attempt < (th_fixed ? 1 : 2); attempt++, tall = !tall) {
-        th = th_fixed ? th_fixed : direct_tile_rows(radius, tall);
-        nbx = nby = 1;
-        auto span = [](const int32_t *m, int lo, int hi) {   // boxes touched by [lo, hi)
-            int first = -1, last = -1;
-            for (int i = lo; i < hi; i++)
-                if (m[i] >= 0) { if (first < 0) first = m[i]; last = m[i]; }
-            return first < 0 ? 0 : last - first + 1;
-        };
-        for (int x0 = 0; x0 < w; x0 += 64) nbx = std::max(nbx, span(bx, x0, std::min(w, x0 + 64)));
-        for (int y0 = 0; y0 < h; y0 += th) nby = std::max(nby, span(by, y0, std::min(h, y0 + th)));
-        if ((nbx + 1) * (nby + 1) <= (th_fixed > 272 ? 2 * SCORE_NBOX : SCORE_NBOX)) break;   // (th_fixed > 272: the wide matrix kernel's long segments)
-        th = 0;
-    }
-    if (!th) return false;
-    tall = th == direct_tile_rows(radius, true);
-    if (th_fixed) {
-        // blur_mfma_kernel's indicator matrix has five box columns per 16-px group of a tile
-        for (int x0 = 0; x0 < w; x0 += 16) {
-            int first = -1, last = -1;
-            for (int x = x0; x < std::min(w, x0 + 16); x++)
-                if (bx[x] >= 0) { if (first < 0) first = bx[x]; last = bx[x]; }
-            if (first >= 0 && last - first > 4) return false;
-        }
-    }
-    // a tile whose first column / row is in no box must not hold boxed pixels (kernel uses bx[x0])
-    for (int x0 = 0; x0 < w; x0 += 64)
-        if (bx[x0] < 0) for (int x = x0; x < std::min(w, x0 + 64); x++) if (bx[x] >= 0) return false;
-    for (int y0 = 0; y0 < h; y0 += th)
-        if (by[y0] < 0) for (int y = y0; y < std::min(h, y0 + th); y++) if (by[y] >= 0) return false;
 
-    const int slabn = (nbx + 1) * (nby + 1);
-    const int tiles_x = (w + 63) / 64, tiles = tiles_x * ((h + th - 1) / th);
-    if (static_cast<size_t>(tiles) * 2 * slabn >= (1u << 30)) return false;   // 32-bit slab offsets
-    for (int d = 0; d < dstW; d++) {
-        int s0, s1;
-        box_edge(d, xr, w, s0, s1);
-        const int t0 = s0 >> 6, t1 = (s1 - 1) >> 6;
-        if (t1 > t0 + 1) return false;
-        xref[d].part0 = t0 * 2 * slabn + (d - bx[t0 << 6]);
-        xref[d].part1 = t1 > t0 ? t1 * 2 * slabn + (d - bx[t1 << 6]) : -1;
-        xref[d].len = s1 - s0; xref[d].pad = 0;
-    }
-    for (int d = 0; d < dstH; d++) {
-        int s0, s1;
-        box_edge(d, yr, h, s0, s1);
-        const int t0 = s0 / th, t1 = (s1 - 1) / th;
-        if (t1 > t0 + 1) return false;
-        yref[d].part0 = t0 * tiles_x * 2 * slabn + (d - by[t0 * th]) * (nbx + 1);
-        yref[d].part1 = t1 > t0 ? t1 * tiles_x * 2 * slabn + (d - by[t1 * th]) * (nbx + 1) : -1;
-        yref[d].len = s1 - s0; yref[d].pad = 0;
-    }
-
-    g.th = th; g.nbx = nbx; g.nby = nby; g.tall = tall;
-    g.coltab = g.rowtab = 0;
-    if (th_fixed && th_fixed <= 272 && radius <= 6) score_mfma_tables(g, w, h);
-    return true;
-}
-
+// GaussianBlur of n images AND the boxDownsample'd dstW x dstH planes of every source and blurred image, for
+// SSIMFast(src, blurred) (ssim.go:48-70), in one pass over the pixels.  FNX_NOOP, nothing launched: the call's kernel has no
+// one-pass form for this shape (the caller then runs the two ops separately).
 int launch_blur_scored(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstride, int w, int h,
                        const double *kernel, int radius, int flags, uint8_t *const *dsts, int dstride,
                        uint8_t *planes, size_t plane, int dstW, int dstH)
 {
-    if (n > 65535) return FNX_NOOP;   // grid.z
-    const bool exact = flags & FNX_BLUR_EXACT;
-    // radii 7 .. 24 (r5): GaussianBlur alone runs on the matrix pipe (blur_mfma_wide_kernel), whose fast-mode bytes are not this
-    // file's fp32 kernel's; the one-pass form must return what the two calls return, so it is that kernel's SCORE form or none
-    const bool wide = radius > 6 && blur_mfma_wide_scored_covers(kernel, radius, w, h, exact);
-    if (!wide) {
-        if (radius < 1 || radius > SCORE_RMAX) return FNX_NOOP;   // before any tile arithmetic (TH would be <= 0)
-        if (exact && !guard_kernel_ok(kernel, radius)) return FNX_NOOP;
-        if (radius > 6 && blur_mfma_takes(kernel, radius, w, h, exact)) return FNX_NOOP;
-    }
-    const bool tall_pref = wide ? false : direct_tall(ctx, radius, n, w, h);
-    // the matrix-pipe kernel (blur_mfma.hip) where its table and its box geometry fit; its tile is 64 px x seg rows
-    static const int wide_cap = [] { const char *e = dev_env("FNX_MFMA_WIDE_SEG"); return e ? atoi(e) : 544; }();   // development: rows per workgroup
-    const int seg = wide ? blur_mfma_segment(ctx, n, w, h, wide_cap, 2)
-                         : (blur_mfma_covers(kernel, radius, w, h) && (!exact || blur_mfma_exact_enabled()) ? blur_mfma_segment(ctx, n, w, h, 272, 3) : 0);
+    // the one-pass form is the SCORE form of the kernel the plain call takes, or none (blur_plan.cpp: plan_blur_scored)
+    const BlurPlan p = plan_blur(ctx->num_cus, n, w, h, kernel, radius, flags & FNX_BLUR_EXACT);
     ScoreGeom &g = ctx->score_geom;
-    if (!(g.w == w && g.h == h && g.dstW == dstW && g.dstH == dstH && g.radius == radius && g.tall_pref == tall_pref && g.seg == seg)) {
-        g.w = w; g.h = h; g.dstW = dstW; g.dstH = dstH; g.radius = radius; g.tall_pref = tall_pref; g.seg = seg;
-        g.mfma = seg > 0 && build_score_geom(g, w, h, radius, dstW, dstH, seg);
-        // where GaussianBlur alone runs on the matrix pipe but its one-pass geometry does not fit (boxes under 4 px: long side
-        // 1843..2047), this file's fp32 kernel would return fast-mode bytes the two calls do not: the two calls take the step
-        // (tools/fuzz_blur.py: 72 such shapes in 6 528)
-        g.ok = g.mfma || (!wide && seg == 0 && build_score_geom(g, w, h, radius, dstW, dstH));
-    }
-    if (!g.ok) return FNX_NOOP;
-    const std::vector<int32_t> &map = g.map;
+    if (!plan_blur_scored(p, dstW, dstH, g)) return FNX_NOOP;
     const int th = g.th, nbx = g.nbx, nby = g.nby;
-    const bool tall = g.tall;
     const size_t ref_words = 4 * (static_cast<size_t>(dstW) + dstH);
     const int slabn = (nbx + 1) * (nby + 1);
     const int tiles_x = (w + 63) / 64, tiles = tiles_x * ((h + th - 1) / th);
 
     void *dmap = nullptr;
-    FNX_TRY(upload_table(ctx, SLOT_BOXMAP, map.data(), sizeof(int32_t) * map.size(), &dmap));
-    FusedArgs fa{};
-    fa.srcs = srcs; fa.dsts = dsts;
-    fa.sstride = sstride; fa.dstride = dstride; fa.w = w; fa.h = h;
-    for (int i = 0; i < 2 * radius + 1 && !wide; i++) {
-        fa.wt[i] = static_cast<float>(kernel[i]);
-        fa.wd[i] = kernel[i];
-    }
-    fa.bx = static_cast<const int32_t *>(dmap) + NHEAD + ref_words; fa.by = fa.bx + w;
-    fa.nbx = nbx; fa.nby = nby;
+    FNX_TRY(upload_table(ctx, SLOT_BOXMAP, g.map.data(), sizeof(int32_t) * g.map.size(), &dmap));
     void *slabs = nullptr;
     FNX_TRY(scratch(ctx, ctx->parity ? SLOT_SLABS1 : SLOT_SLABS, sizeof(unsigned long long) * 2 * slabn * static_cast<size_t>(tiles) * n, &slabs));
-    fa.slabs = static_cast<unsigned long long *>(slabs);
-    int st;
+    const BlurImages im{nullptr, srcs, nullptr, dsts, sstride, dstride, w, h};
+    BlurScore sc{};
+    sc.bx = static_cast<const int32_t *>(dmap) + NHEAD + ref_words; sc.by = sc.bx + w;
+    sc.coltab = g.coltab ? static_cast<const uint32_t *>(dmap) + g.coltab : nullptr;
+    sc.rowtab = g.rowtab ? static_cast<const uint32_t *>(dmap) + g.rowtab : nullptr;
+    sc.slabs = static_cast<unsigned long long *>(slabs); sc.nbx = nbx; sc.nby = nby; sc.seg = th;
     if (g.mfma) {
-        st = wide ? launch_blur_mfma_wide_scored(ctx, n, srcs, sstride, w, h, kernel, radius, flags, dsts, dstride, fa.bx, fa.by, fa.slabs, nbx, nby, th)
-                  : launch_blur_mfma_scored(ctx, n, srcs, sstride, w, h, kernel, radius, flags, dsts, dstride,
-                                            g.coltab ? static_cast<const uint32_t *>(dmap) + g.coltab : nullptr,
-                                            g.rowtab ? static_cast<const uint32_t *>(dmap) + g.rowtab : nullptr, fa.slabs, nbx, nby, th);
-        if (st == FNX_NOOP) return FNX_NOOP;   // (blur_mfma_covers said yes: not reached) the caller runs the two ops back to back
+        FNX_TRY(launch_blur_mfma(ctx, n, p, im, kernel, &sc));
     } else {
-        st = exact ? launch_direct_radius<true, true>(ctx, radius, n, fa, tall)
-                   : launch_direct_radius<true, false>(ctx, radius, n, fa, tall);
+        FusedArgs fa{};
+        set_images(fa, im);
+        set_weights(fa, kernel, radius, true);
+        fa.bx = sc.bx; fa.by = sc.by; fa.slabs = sc.slabs; fa.nbx = nbx; fa.nby = nby;
+        note_route(ctx, FNX_PROF_MAIN, blur_route(p, true));
+        const int st = p.exact ? launch_direct_radius<true, true>(ctx, radius, n, fa, g.tall)
+                               : launch_direct_radius<true, false>(ctx, radius, n, fa, g.tall);
+        if (st < 0) return st;
     }
-    if (st < 0) return st;
     // the rest of the step runs on the ctx's second stream, behind this blur (api.cpp: one-pass enqueue) -- or, for a blur that
     // only KEEPS the box planes for the scoring call that follows (FNX_BLUR_KEEP_BOX_SUMS), right behind it on the same stream:
     // there is no next blur to hide a tail under, and the two cross-stream hand-overs cost a per-image pair 25 us
@@ -1091,7 +843,7 @@ int launch_blur_scored(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstr
     }
 
     SlabArgs sa{};
-    sa.slabs = fa.slabs; sa.dst = planes; sa.plane = plane;
+    sa.slabs = sc.slabs; sa.dst = planes; sa.plane = plane;
     sa.magic = static_cast<const uint32_t *>(dmap);
     sa.tiedown = sa.magic + 260;
     sa.xref = reinterpret_cast<const BoxRef *>(static_cast<const int32_t *>(dmap) + NHEAD);
@@ -1105,12 +857,11 @@ int launch_blur_scored(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstr
 }
 
 template <typename T>
-static int launch_generic(fnx_ctx *ctx, int n, const uint8_t *src, const uint8_t *const *srcs,
-                          int sstride, int w, int h, const double *kernel, int radius,
-                          uint8_t *dst, uint8_t *const *dsts, int dstride)
+static int launch_generic(fnx_ctx *ctx, int n, const BlurImages &im, const double *kernel, int radius)
 {
+    const uint8_t *const src = im.src, *const *const srcs = im.srcs;
+    const int w = im.w, h = im.h, sstride = im.sstride;
     const int nt = 2 * radius + 1;
-    note_route(ctx, FNX_PROF_MAIN, sizeof(T) == 8 ? "blur_pass_kernel<double> x 2" : "blur_pass_kernel<float> x 2");
     std::vector<T> hk(nt);
     for (int i = 0; i < nt; i++) hk[i] = static_cast<T>(kernel[i]);
     void *dk = nullptr;
@@ -1138,7 +889,7 @@ static int launch_generic(fnx_ctx *ctx, int n, const uint8_t *src, const uint8_t
     FNX_HIP(hipGetLastError());
     PassArgs<T> va = ha;
     va.src = static_cast<const uint8_t *>(tmp); va.srcs = tmps; va.sstride = tpitch;
-    va.dst = dst; va.dsts = dsts; va.dstride = dstride;
+    va.dst = im.dst; va.dsts = im.dsts; va.dstride = im.dstride;
     hipLaunchKernelGGL((blur_pass_kernel<T, true>), grid, dim3(256), 0, ctx->stream, va);
     FNX_HIP(hipGetLastError());
     return FNX_OK;
@@ -1287,7 +1038,6 @@ static int launch_exact(fnx_ctx *ctx, int n, ExactArgs &ea)
     constexpr int TH = ((64 - 2 * R) / 4) * 4;
     ea.tiles_x = (ea.w + 63) / 64;
     ea.tiles = ea.tiles_x * ((ea.h + TH - 1) / TH);
-    note_route(ctx, FNX_PROF_MAIN, "blur_exact_kernel");
     hipLaunchKernelGGL((blur_exact_kernel<R>), dim3(8 * ((ea.tiles + 7) / 8), n), dim3(256), 0, ctx->stream, ea);
     FNX_HIP(hipGetLastError());
     return FNX_OK;
@@ -1298,35 +1048,29 @@ int launch_blur(fnx_ctx *ctx, int n, const uint8_t *src, const uint8_t *const *s
                 uint8_t *const *dsts, int dstride)
 {
     if (w <= 0 || h <= 0 || n <= 0) return FNX_OK;
-    {   // radius <= 6, non-negative weights summing to 1: both passes on the matrix pipe (blur_mfma.hip), fast or exact
-        const int st = launch_blur_mfma(ctx, n, src, srcs, sstride, w, h, kernel, radius, flags, dst, dsts, dstride);
-        if (st != FNX_NOOP) return st;
-    }
-    if (flags & FNX_BLUR_EXACT) {
-        if (radius < 1 || radius > FUSED_RMAX)
-            return launch_generic<double>(ctx, n, src, srcs, sstride, w, h, kernel, radius, dst, dsts, dstride);
-        // any caller-supplied table the guarded kernel's bound does not cover takes the fp64 kernel
-        if (guard_kernel_ok(kernel, radius)) {
-            FusedArgs ga{};
-            ga.src = src; ga.srcs = srcs; ga.dst = dst; ga.dsts = dsts;
-            ga.sstride = sstride; ga.dstride = dstride; ga.w = w; ga.h = h;
-            for (int i = 0; i < 2 * radius + 1; i++) {
-                ga.wt[i] = static_cast<float>(kernel[i]);
-                if (radius <= SCORE_RMAX) ga.wd[i] = kernel[i];
-            }
-            if (radius > SCORE_RMAX) {
-                void *dk = nullptr;
-                FNX_TRY(upload_table(ctx, SLOT_TABLE1, kernel, sizeof(double) * (2 * radius + 1), &dk));
-                ga.wdp = static_cast<const double *>(dk);
-            }
-            return launch_direct_radius<false, true>(ctx, radius, n, ga, direct_tall(ctx, radius, n, w, h));
+    const BlurPlan p = plan_blur(ctx->num_cus, n, w, h, kernel, radius, flags & FNX_BLUR_EXACT);
+    const BlurImages im{src, srcs, dst, dsts, sstride, dstride, w, h};
+    // (the matrix launch names its route itself, behind its events' binding; the others just before they launch)
+    switch (p.family) {
+    case BLUR_MFMA:
+    case BLUR_MFMA_WIDE: return launch_blur_mfma(ctx, n, p, im, kernel, nullptr);
+    case BLUR_DIRECT: {
+        FusedArgs fa{};
+        set_images(fa, im);
+        set_weights(fa, kernel, radius, p.exact && !p.wdp);
+        if (p.wdp) {
+            void *dk = nullptr;
+            FNX_TRY(upload_table(ctx, SLOT_TABLE1, kernel, sizeof(double) * (2 * radius + 1), &dk));
+            fa.wdp = static_cast<const double *>(dk);
         }
-        if (radius > SCORE_RMAX)              // blur_exact_kernel is built for R <= 8
-            return launch_generic<double>(ctx, n, src, srcs, sstride, w, h, kernel, radius, dst, dsts, dstride);
+        note_route(ctx, FNX_PROF_MAIN, blur_route(p, false));
+        return p.exact ? launch_direct_radius<false, true>(ctx, radius, n, fa, p.tall) : launch_direct_radius<false>(ctx, radius, n, fa, p.tall);
+    }
+    case BLUR_EXACT: {
         ExactArgs ea{};
-        ea.src = src; ea.srcs = srcs; ea.dst = dst; ea.dsts = dsts;
-        ea.sstride = sstride; ea.dstride = dstride; ea.w = w; ea.h = h;
+        set_images(ea, im);
         for (int i = 0; i < 2 * radius + 1; i++) ea.wt[i] = kernel[i];
+        note_route(ctx, FNX_PROF_MAIN, blur_route(p, false));
         switch (radius) {
         case 1: return launch_exact<1>(ctx, n, ea);
         case 2: return launch_exact<2>(ctx, n, ea);
@@ -1337,19 +1081,12 @@ int launch_blur(fnx_ctx *ctx, int n, const uint8_t *src, const uint8_t *const *s
         case 7: return launch_exact<7>(ctx, n, ea);
         case 8: return launch_exact<8>(ctx, n, ea);
         }
+        return FNX_ERR_INVALID;
     }
-    if (radius < 1 || radius > FUSED_RMAX) {
-        // what the matrix kernels leave (images under 64 x 32, radii past 62, a weight >= 0.49).  An fp32 accumulator's rounding grows
-        // with the tap count -- tools/fuzz_blur.py, seed 71: 0.4 % of the samples one LSB off at 127 taps, past the fast mode's
-        // 0.1 % -- so beyond 53 taps the fast mode takes the fp64 passes as well (the reference's own arithmetic, 28 % slower)
-        if (radius > 26) return launch_generic<double>(ctx, n, src, srcs, sstride, w, h, kernel, radius, dst, dsts, dstride);
-        return launch_generic<float>(ctx, n, src, srcs, sstride, w, h, kernel, radius, dst, dsts, dstride);
+    case BLUR_GENERIC_F32: note_route(ctx, FNX_PROF_MAIN, blur_route(p, false)); return launch_generic<float>(ctx, n, im, kernel, radius);
+    case BLUR_GENERIC_F64: note_route(ctx, FNX_PROF_MAIN, blur_route(p, false)); return launch_generic<double>(ctx, n, im, kernel, radius);
     }
-    FusedArgs fa{};
-    fa.src = src; fa.srcs = srcs; fa.dst = dst; fa.dsts = dsts;
-    fa.sstride = sstride; fa.dstride = dstride; fa.w = w; fa.h = h;
-    for (int i = 0; i < 2 * radius + 1; i++) fa.wt[i] = static_cast<float>(kernel[i]);
-    return launch_direct_radius<false>(ctx, radius, n, fa, direct_tall(ctx, radius, n, w, h));
+    return FNX_ERR_INVALID;
 }
 
 }  // namespace fnx

@@ -38,7 +38,7 @@
 // then V set s-1; one barrier per step; stores trail by two more steps.  The H halo is 22 rows per SEG, not 12 per 104.
 #include <hip/hip_ext.h>
 
-#include "common.hpp"
+#include "blur_launch.hpp"
 #include "devutil.hpp"
 
 #include <algorithm>
@@ -50,13 +50,10 @@ namespace fnx {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 
-constexpr int MF_RMAX = 6;           // 4 output px + 2 R <= 16 px = the 64-byte K of one H instruction
 constexpr int MF_P = 48;             // bytes per byte column of the ring: 32 rows + 16 (= 16 mod 32: conflict-free 4-row dword writes)
 constexpr int MF_WT = 64 * MF_P + 256;   // ring bytes per wave: 64 byte columns + the skew of each 16-column group (64 bytes each; blur_mfma_kernel: 80, mf_skew)
 constexpr int MF_SP = 352;           // pitch of a staged source row (19 chunks of 16 bytes): conflict-free as the A operand (tools/lds_conflicts.py)
 constexpr int MF_OP = 272;           // pitch of an output row in its stage
-constexpr int MF_SEG_SCORE = 272;    // most rows per workgroup with SCORE (row tables and box tables in LDS)
-constexpr int MF_SEG_SCORE_WIDE = 544;   // ... of blur_mfma_wide_kernel<2, ., SCORE>: two workgroups per CU either way (its ring and stages are 43 KB)
 
 // blur_mfma_kernel's ring: byte offset of 16-column group grp (one pixel group: 4 px x RGBA) on top of its columns -- 0, 80, 160,
 // 240 (ascending by less than MF_WT's 256 spare bytes: the groups do not overlap).  A V set reads ONE channel of the wave's 16 px
@@ -81,7 +78,7 @@ struct MfmaArgs {
     unsigned long long *slabs;        // [image][tile][2][slabn] packed 4 x u16 channel sums (blur.hip: box_from_slabs_kernel)
     int nbx, nby;
     int dbg;                          // development switches (FNX_MFMA_DBG)
-    int narrow;                       // every row offset of source and destination fits 31 bits (launch_mfma_cfg): interior workgroups address
+    int narrow;                       // every row offset of source and destination fits 31 bits (launch_blur_mfma): interior workgroups address
                                       // rows as scalar base + 32-bit lane offset
 };
 
@@ -217,7 +214,7 @@ __global__ __launch_bounds__(256, GUARD ? 3 : 1) void blur_mfma_kernel(MfmaArgs 
     const int slabn = SCORE ? (a.nbx + 1) * (a.nby + 1) : 0;
     uint32_t *tbl_s = s_box, *tbl_b = s_box + 4 * slabn;
     // (called from the march once the first two row sets' loads are in flight: its table loads then wait beside them)
-    // Everything here depends on the launch's geometry alone, so the host builds it once per geometry (blur.hip:
+    // Everything here depends on the launch's geometry alone, so the host builds it once per geometry (blur_plan.cpp:
     // build_score_geom): one packed word per (tile column, wave, lane) and the two row tables per segment.  No barrier of
     // its own: step 0's orders the LDS writes before their first readers (H set 0).
     auto score_setup = [&]() {
@@ -536,9 +533,8 @@ __global__ __launch_bounds__(256, GUARD ? 3 : 1) void blur_mfma_kernel(MfmaArgs 
 // chunks, and the V window as NKV = 2 / 3 chained 64-row instructions over a ring of NS = 4 NKV slots: 16 + 2 RF <= 64 NKV rows,
 // a V set runs NS - 1 steps behind its first H set, its store two more.  NKV = 1 is the kernel as it was.
 template <int NKH> struct MfWide {
-    static constexpr int NKV = NKH <= 4 ? 1 : (NKH <= 7 ? 2 : 3);         // 64-row chunks of the V window
-    static constexpr int RFH = 8 * NKH - 2, RFV = 32 * NKV - 8;
-    static constexpr int RF = RFH < RFV ? RFH : RFV;                      // frame radius: taps sit centred in it (24 at NKH = 4)
+    static constexpr int NKV = mf_wide_nkv(NKH);                          // 64-row chunks of the V window
+    static constexpr int RF = mf_wide_rf(NKH);                            // frame radius: taps sit centred in it (24 at NKH = 4)
     static constexpr int NC = 16 + RF / 2;                                // 16-byte chunks of a staged row: px x0 - RF .. x0 + 63 + RF
     static constexpr int NL = (16 * NC + 255) / 256;                      // chunk loads per lane and H set
     static constexpr int SP = 16 * NC + 48;                               // staged row pitch, conflict-free as the A operand (tools/lds_conflicts.py)
@@ -929,324 +925,76 @@ __global__ __launch_bounds__(256, MfWide<NKH>::NKV == 3 ? 1 : 2) void blur_mfma_
 }
 
 // ------------------------------------------------------------------------------------
-// host side
+// host side: launch what a plan says (blur_plan.cpp decides; the tables are its mfma_table)
 // ------------------------------------------------------------------------------------
-// Fixed-point form of a blur kernel: wq[k] = round(w[k] 2^24), the centre takes what is left of 2^24.
-// Returns false when the table is outside what the three-digit form or the error bound covers.
-constexpr int MF_RWIDE = 62;         // blur_mfma_wide_kernel: 16 + 2 R <= the 64 NKV rows of its V window (NKH = 8: RF = 62)
-struct MfmaWeights {
-    long long wq[2 * MF_RWIDE + 1];
-    double err255;                // 255 * max(sum of the positive, sum of the negative wq[k] - w[k] 2^24): bound of |S - exact sum * 2^24|
-};
-static bool mfma_quantise(const double *kernel, int radius, MfmaWeights *q, int rmax = MF_RMAX)
+using MfmaKernel = void (*)(MfmaArgs);
+template <int NKH>
+static MfmaKernel mfma_wide_kernel(bool guard, bool score)
 {
-    if (radius < 1 || radius > rmax) return false;
-    const int nt = 2 * radius + 1;
-    double sum = 0;
-    for (int i = 0; i < nt; i++) {
-        if (!(kernel[i] >= 0) || !(kernel[i] < 0.49)) return false;   // three signed digits reach 127 * 65793 = 0.498 * 2^24
-        sum += kernel[i];
-    }
-    if (!(std::fabs(sum - 1.0) <= 1e-6)) return false;
-    long long tot = 0;
-    for (int i = 0; i < nt; i++) {
-        q->wq[i] = std::llround(kernel[i] * 16777216.0);
-        tot += q->wq[i];
-    }
-    q->wq[radius] += 16777216 - tot;
-    if (q->wq[radius] < 0 || q->wq[radius] > 8355711) return false;
-    // S - (exact sum) 2^24 = sum_k (wq[k] - w[k] 2^24) p[k] with 0 <= p[k] <= 255: between -255 (sum of the negative
-    // differences) and +255 (sum of the positive ones) -- half of 255 sum |.| when the differences cancel, as they nearly do
-    long double ep = 0, en = 0;
-    for (int i = 0; i < nt; i++) {
-        const long double d = static_cast<long double>(q->wq[i]) - static_cast<long double>(kernel[i]) * 16777216.0L;
-        if (d > 0) ep += d; else en -= d;
-    }
-    q->err255 = static_cast<double>(255.0L * std::max(ep, en));
-    return true;
+    if constexpr (NKH <= MF_SCORE_NKH)
+        if (score) return guard ? blur_mfma_wide_kernel<NKH, true, true> : blur_mfma_wide_kernel<NKH, false, true>;
+    return guard ? blur_mfma_wide_kernel<NKH, true, false> : blur_mfma_wide_kernel<NKH, false, false>;
 }
-static void mfma_digits(long long v, int d[3])
+static MfmaKernel mfma_kernel(const BlurPlan &p, bool score)
 {
-    for (int i = 0; i < 3; i++) {
-        long long lo = ((v % 256) + 256) % 256;
-        if (lo >= 128) lo -= 256;
-        d[i] = static_cast<int>(lo);
-        v = (v - lo) / 256;
+    if (p.family == BLUR_MFMA)
+        return score ? (p.exact ? blur_mfma_kernel<true, true> : blur_mfma_kernel<true, false>)
+                     : (p.exact ? blur_mfma_kernel<false, true> : blur_mfma_kernel<false, false>);
+    switch (p.nkh) {
+    case 2: return mfma_wide_kernel<2>(p.exact, score);
+    case 3: return mfma_wide_kernel<3>(p.exact, score);
+    case 4: return mfma_wide_kernel<4>(p.exact, score);
+    case 5: return mfma_wide_kernel<5>(p.exact, score);      // r5: 25 .. 62, the V window in two or three chained instructions
+    case 6: return mfma_wide_kernel<6>(p.exact, score);
+    case 7: return mfma_wide_kernel<7>(p.exact, score);
+    case 8: return mfma_wide_kernel<8>(p.exact, score);
     }
+    return nullptr;
 }
 
-// device table: BH[3][64] x 16 bytes (digits hi, mid, lo) | BV[3][64] x 8 | 13 fp64 weights
-constexpr size_t MF_TAB_WORDS = 3 * 64 * 4 + 3 * 64 * 2;
-constexpr size_t MF_TAB_ALL = MF_TAB_WORDS + 2 * 16;   // + the fp64 weights: 13, padded to 16 with zeros (mf_exact_u's two s_load_dwordx16)
-static void mfma_build_table(const MfmaWeights &q, int radius, uint32_t *tab)
+// GaussianBlur of n images by plan p (BLUR_MFMA, BLUR_MFMA_WIDE); with `score` the one-pass form: the blur + the tile slabs of both
+// box-sum sides (blur.hip's launch_blur_scored owns the geometry)
+int launch_blur_mfma(fnx_ctx *ctx, int n, const BlurPlan &p, const BlurImages &im, const double *kernel, const BlurScore *score)
 {
-    std::fill(tab, tab + MF_TAB_WORDS, 0u);
-    int8_t *bh = reinterpret_cast<int8_t *>(tab);
-    int8_t *bv = reinterpret_cast<int8_t *>(tab + 3 * 64 * 4);
-    const int nt = 2 * radius + 1, off = MF_RMAX - radius;
-    for (int lane = 0; lane < 64; lane++) {
-        const int n = lane & 15, kc = lane >> 4;
-        for (int b = 0; b < 16; b++) {   // H: K index 16 kc + b = byte of the 64-byte window; output byte n = 4 px + channel
-            const int px = 4 * kc + b / 4, ch = b % 4, c = n % 4, pj = n / 4;
-            const int t = px - pj - off;
-            int d[3] = {0, 0, 0};
-            if (ch == c && c < 3 && t >= 0 && t < nt) mfma_digits(q.wq[t], d);
-            if (ch == c && c == 3 && px == pj + MF_RMAX) d[0] = 1;   // alpha column: the centre pixel's alpha as it is (effects.go:189)
-            for (int l = 0; l < 3; l++) bh[((2 - l) * 64 + lane) * 16 + b] = static_cast<int8_t>(d[l]);
-        }
-        for (int b = 0; b < 8; b++) {    // V: K index 8 kc + b = staged row of the set's 32; output row n
-            const int te = 8 * kc + b - n - off;
-            int de[3] = {0, 0, 0};
-            if (te >= 0 && te < nt) mfma_digits(q.wq[te], de);
-            for (int l = 0; l < 3; l++) bv[((2 - l) * 64 + lane) * 8 + b] = static_cast<int8_t>(de[l]);
-        }
-    }
-}
-
-// FNX_BLUR_EXACT takes this kernel too (FNX_BLUR_MFMA_EXACT=0: blur.hip's guarded fp32 kernel, kept for A/B runs):
-// 4K plain 18.7 us against 23.8, one-pass 26.4 against 29.2 per image
-bool blur_mfma_exact_enabled()
-{
-    static const bool on = [] { const char *e = dev_env("FNX_BLUR_MFMA_EXACT"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
-bool blur_mfma_covers(const double *kernel, int radius, int w, int h)
-{
-    static const bool off = [] { const char *e = dev_env("FNX_BLUR_MFMA"); return e && e[0] == '0'; }();
-    if (off || w < 64 || h < 32) return false;
-    MfmaWeights q;
-    return mfma_quantise(kernel, radius, &q);
-}
-static bool blur_mfma_wide_covers(const double *kernel, int radius, int w, int h)
-{
-    static const bool off = [] { const char *e = dev_env("FNX_BLUR_MFMA"); return e && e[0] == '0'; }();
-    if (off || w < 64 || h < 32 || radius <= MF_RMAX) return false;
-    MfmaWeights q;
-    return mfma_quantise(kernel, radius, &q, MF_RWIDE);
-}
-
-// does launch_blur_mfma take this call?  (blur.hip's one-pass form asks: its fast-mode images must be the two-call route's)
-bool blur_mfma_takes(const double *kernel, int radius, int w, int h, bool exact)
-{
-    if (exact && !blur_mfma_exact_enabled()) return false;
-    return blur_mfma_covers(kernel, radius, w, h) || blur_mfma_wide_covers(kernel, radius, w, h);
-}
-
-// Rows per workgroup.  A workgroup of NJ 16-row sets runs NJ + 4 steps (the pipeline's fill and drain); the grid runs in
-// rounds of occ workgroups per CU.  The segment count that minimises rounds x steps: long segments for batches (the halo
-// is 22 staged rows per segment), one full round of short ones for a single image (4K alone: 17 segments of 128 rows,
-// 18 us against 23 with "at least eight workgroups per CU").
-int blur_mfma_segment(const fnx_ctx *ctx, int n, int w, int h, int cap, int occ)
-{
-    const long tiles_x = (w + 63) / 64, slots = static_cast<long>(occ) * ctx->num_cus;
-    const int sets = (h + 15) / 16;
-    int best_seg = 16, first = 1;
-    double best = 0;
-    for (int nseg = std::max(1, (h + cap - 1) / cap); nseg <= std::max(1, sets / 2); nseg++) {
-        const int nj = (sets + nseg - 1) / nseg, seg = 16 * nj;
-        if (seg > cap) continue;
-        const long segs = (h + seg - 1) / seg, wgs = tiles_x * segs * n;
-        const double cost = static_cast<double>((wgs + slots - 1) / slots) * (nj + 4);
-        if (first || cost < best * 0.98) { best = cost; best_seg = seg; first = 0; }   // ties go to the longer segment
-    }
-    return best_seg;
-}
-
-template <bool SCORE, bool GUARD>
-static int launch_mfma_cfg(fnx_ctx *ctx, int n, MfmaArgs &ma, size_t lds)
-{
-    ma.tiles_x = (ma.w + 63) / 64;
-    ma.tiles = ma.tiles_x * ((ma.h + ma.seg - 1) / ma.seg);
-    dim3 grid(8 * ((ma.tiles + 7) / 8), n);
-    // row offsets as 32-bit lane offsets (the kernel's form 0): a set below the last row included, for both images
-    auto fits = [&](int stride) {
-        return stride > 0 && stride < (1 << 24) &&
-               static_cast<long long>(ma.h - 1) * stride + 4LL * ma.w + 16LL * stride < (1LL << 31);
-    };
-    ma.narrow = fits(ma.sstride) && fits(ma.dstride);
-    // the launch's events ride on its own packet (common.hpp: LaunchEvents); SCORE launches always carry a stop event:
-    // the step's tail on the ctx's second stream waits for it (blur.hip: launch_blur_scored)
-    LaunchEvents ev;
-    FNX_TRY(prof_bind(ctx, FNX_PROF_MAIN, &ev));
-    if constexpr (SCORE) {
-        if (!ev.stop) ev.stop = ctx->ev_blur[ctx->parity];
-        ctx->blur_done = ev.stop;
-    }
-    note_route(ctx, FNX_PROF_MAIN, SCORE ? (GUARD ? "blur_mfma_kernel<SCORE, GUARD>" : "blur_mfma_kernel<SCORE>")
-                                         : (GUARD ? "blur_mfma_kernel<GUARD>" : "blur_mfma_kernel"));
-    hipExtLaunchKernelGGL((blur_mfma_kernel<SCORE, GUARD>), grid, dim3(256), lds, ctx->stream, ev.start, ev.stop, 0, ma);
-    FNX_HIP(hipGetLastError());
-    return FNX_OK;
-}
-
-// weights, seeds and the guard distance of one call; the matrix table goes to its own table slot
-static int mfma_prepare(fnx_ctx *ctx, const double *kernel, int radius, bool exact, MfmaArgs *ma)
-{
-    MfmaWeights q;
-    if (!mfma_quantise(kernel, radius, &q)) return FNX_NOOP;
-    uint32_t tab[MF_TAB_ALL] = {};
-    mfma_build_table(q, radius, tab);
-    memcpy(reinterpret_cast<double *>(tab + MF_TAB_WORDS) + (MF_RMAX - radius), kernel, sizeof(double) * (2 * radius + 1));   // centred, zeros around
+    const bool wide = p.family == BLUR_MFMA_WIDE;
+    const MfmaKernel kern = mfma_kernel(p, score != nullptr);
+    if (!kern) return FNX_ERR_INVALID;
+    MfmaArgs ma{};
+    set_images(ma, im);
+    const std::vector<uint32_t> tab = mfma_table(p, kernel);
     void *dt = nullptr;
-    FNX_TRY(upload_table(ctx, SLOT_TABLE_MFMA, tab, sizeof(tab), &dt));
-    ma->tab = static_cast<const uint32_t *>(dt);
-#ifdef FNX_DEVELOP                     // a development build only (make DEVELOP=1): bits 1 / 2 / 4 skip the box sums -- wrong scores
-    { static const int dbg = [] { const char *e = dev_env("FNX_MFMA_DBG"); return e ? atoi(e) : 0; }(); ma->dbg = dbg; }
-#else
-    ma->dbg = 0;
-#endif
-    ma->radius = radius;
-    // G (units of 2^-24): the fixed-point error bound, the reference's own fp64 chain error (13 roundings below 256:
-    // < 4e-13 = 7e-6 units) and one unit for the bound's own arithmetic
-    const long long gq = exact ? static_cast<long long>(std::ceil(q.err255)) + 2 : 0;
-    if (gq > (1 << 20)) return FNX_NOOP;
-    ma->seed_h = static_cast<int>((1u << 23) + static_cast<uint32_t>(gq));                 // staged bytes come out as (value ^ 0x80)
-    ma->seed_v = static_cast<int>((1u << 23) + (1u << 31) + static_cast<uint32_t>(gq));    // plain bytes
-    ma->thr = static_cast<int>(2 * gq);
-    return FNX_OK;
-}
-
-// blur_mfma_wide_kernel's table: BH[NKH][3][64] x 16 bytes | BV[3][64] x 16 bytes | 2 RF + 1 fp64 weights, centred
-template <int NKH, bool SCORE = false>
-static int launch_mfma_wide(fnx_ctx *ctx, int n, MfmaArgs &ma, const MfmaWeights &q, const double *kernel, int radius, bool exact, size_t lds = 0)
-{
-    using C = MfWide<NKH>;
-    constexpr int RF = C::RF;
-    constexpr int NKV = C::NKV;
-    constexpr size_t words = (3 * NKH + 3 * NKV) * 64 * 4 + 2 * ((C::NT + 7) / 8 * 8);   // (weights padded to whole s_load_dwordx16's)
-    std::vector<uint32_t> tab(words, 0u);
-    int8_t *bh = reinterpret_cast<int8_t *>(tab.data());
-    int8_t *bv = bh + 3 * NKH * 64 * 16;
-    const int nt = 2 * radius + 1, off = RF - radius;
-    for (int lane = 0; lane < 64; lane++) {
-        const int nn = lane & 15, kc = lane >> 4;
-        for (int kk = 0; kk < NKH; kk++)
-            for (int b = 0; b < 16; b++) {   // H: K index 64 kk + 16 kc + b = byte of the window
-                const int px = 16 * kk + 4 * kc + b / 4, ch = b % 4, c = nn % 4, pj = nn / 4;
-                const int t = px - pj - off;
-                int d[3] = {0, 0, 0};
-                if (ch == c && c < 3 && t >= 0 && t < nt) mfma_digits(q.wq[t], d);
-                if (ch == c && c == 3 && px == pj + RF) d[0] = 1;
-                for (int l = 0; l < 3; l++) bh[((3 * kk + (2 - l)) * 64 + lane) * 16 + b] = static_cast<int8_t>(d[l]);
-            }
-        for (int c = 0; c < NKV; c++)
-            for (int b = 0; b < 16; b++) {   // V: K index 64 c + 16 kc + b = staged row of the set's 64 NKV; output row nn
-                const int t = 64 * c + 16 * kc + b - nn - off;
-                int d[3] = {0, 0, 0};
-                if (t >= 0 && t < nt) mfma_digits(q.wq[t], d);
-                for (int l = 0; l < 3; l++) bv[((3 * c + (2 - l)) * 64 + lane) * 16 + b] = static_cast<int8_t>(d[l]);
-            }
-    }
-    memcpy(reinterpret_cast<double *>(tab.data() + (3 * NKH + 3 * NKV) * 64 * 4) + off, kernel, sizeof(double) * nt);
-    void *dt = nullptr;
-    FNX_TRY(upload_table(ctx, SLOT_TABLE_MFMA, tab.data(), sizeof(uint32_t) * words, &dt));
+    FNX_TRY(upload_table(ctx, SLOT_TABLE_MFMA, tab.data(), sizeof(uint32_t) * tab.size(), &dt));
     ma.tab = static_cast<const uint32_t *>(dt);
-    ma.radius = radius;
+    ma.radius = p.radius;
+    ma.seed_h = p.seed_h; ma.seed_v = p.seed_v; ma.thr = p.thr;
+    ma.seg = score ? score->seg : p.seg;
     ma.tiles_x = (ma.w + 63) / 64;
     ma.tiles = ma.tiles_x * ((ma.h + ma.seg - 1) / ma.seg);
-    dim3 grid(8 * ((ma.tiles + 7) / 8), n);
-    LaunchEvents ev;
-    FNX_TRY(prof_bind(ctx, FNX_PROF_MAIN, &ev));
-    if constexpr (SCORE) {               // (launch_mfma_cfg: the step's tail on the ctx's second stream waits for this event)
-        if (!ev.stop) ev.stop = ctx->ev_blur[ctx->parity];
-        ctx->blur_done = ev.stop;
-        note_route(ctx, FNX_PROF_MAIN, exact ? "blur_mfma_wide_kernel<SCORE, GUARD>" : "blur_mfma_wide_kernel<SCORE>");
-    } else {
-        note_route(ctx, FNX_PROF_MAIN, exact ? "blur_mfma_wide_kernel<GUARD>" : "blur_mfma_wide_kernel");
+    const dim3 grid(8 * ((ma.tiles + 7) / 8), n);
+    size_t lds = 0;
+    if (score) {
+        if (wide) { ma.bx = score->bx; ma.by = score->by; }
+        else { ma.coltab = score->coltab; ma.rowtab = score->rowtab; }
+        ma.slabs = score->slabs; ma.nbx = score->nbx; ma.nby = score->nby;
+        lds = sizeof(uint32_t) * 8 * static_cast<size_t>(ma.nbx + 1) * (ma.nby + 1);
     }
-    if (exact) hipExtLaunchKernelGGL((blur_mfma_wide_kernel<NKH, true, SCORE>), grid, dim3(256), lds, ctx->stream, ev.start, ev.stop, 0, ma);
-    else hipExtLaunchKernelGGL((blur_mfma_wide_kernel<NKH, false, SCORE>), grid, dim3(256), lds, ctx->stream, ev.start, ev.stop, 0, ma);
+    if (!wide) {
+#ifdef FNX_DEVELOP                     // a development build only (make DEVELOP=1): bits 1 / 2 / 4 skip the box sums -- wrong scores
+        { static const int dbg = [] { const char *e = dev_env("FNX_MFMA_DBG"); return e ? atoi(e) : 0; }(); ma.dbg = dbg; }
+#endif
+        // row offsets as 32-bit lane offsets (the kernel's form 0): a set below the last row included, for both images
+        auto fits = [&](int stride) {
+            return stride > 0 && stride < (1 << 24) &&
+                   static_cast<long long>(ma.h - 1) * stride + 4LL * ma.w + 16LL * stride < (1LL << 31);
+        };
+        ma.narrow = fits(ma.sstride) && fits(ma.dstride);
+    }
+    LaunchEvents ev;
+    FNX_TRY(blur_bind_events(ctx, score != nullptr, &ev));
+    note_route(ctx, FNX_PROF_MAIN, blur_route(p, score != nullptr));
+    hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, ctx->stream, ev.start, ev.stop, 0, ma);
     FNX_HIP(hipGetLastError());
     return FNX_OK;
-}
-
-// GaussianBlur of n images; FNX_NOOP (nothing launched): the table or the shape is not this kernel's
-int launch_blur_mfma(fnx_ctx *ctx, int n, const uint8_t *src, const uint8_t *const *srcs, int sstride, int w, int h,
-                     const double *kernel, int radius, int flags, uint8_t *dst, uint8_t *const *dsts, int dstride)
-{
-    const bool exact = flags & FNX_BLUR_EXACT;
-    if (exact && !blur_mfma_exact_enabled()) return FNX_NOOP;
-    if (n > 65535) return FNX_NOOP;
-    if (blur_mfma_wide_covers(kernel, radius, w, h)) {     // radius 7 .. 24
-        MfmaWeights q;
-        mfma_quantise(kernel, radius, &q, MF_RWIDE);
-        const long long gq = exact ? static_cast<long long>(std::ceil(q.err255)) + 2 : 0;
-        if (gq > (1 << 20)) return FNX_NOOP;
-        MfmaArgs ma{};
-        ma.src = src; ma.srcs = srcs; ma.dst = dst; ma.dsts = dsts;
-        ma.sstride = sstride; ma.dstride = dstride; ma.w = w; ma.h = h;
-        ma.seed_h = static_cast<int>((1u << 23) + static_cast<uint32_t>(gq));
-        ma.seed_v = static_cast<int>((1u << 23) + (1u << 31) + static_cast<uint32_t>(gq));
-        ma.thr = static_cast<int>(2 * gq);
-        ma.seg = blur_mfma_segment(ctx, n, w, h, 544, 3);
-        if (radius <= MfWide<2>::RF) return launch_mfma_wide<2>(ctx, n, ma, q, kernel, radius, exact);
-        if (radius <= MfWide<3>::RF) return launch_mfma_wide<3>(ctx, n, ma, q, kernel, radius, exact);
-        if (radius > MfWide<4>::RF) {        // r5: 25 .. 62, the V window in two or three chained instructions
-            if (radius <= MfWide<5>::RF) return launch_mfma_wide<5>(ctx, n, ma, q, kernel, radius, exact);
-            if (radius <= MfWide<6>::RF) return launch_mfma_wide<6>(ctx, n, ma, q, kernel, radius, exact);
-            if (radius <= MfWide<7>::RF) return launch_mfma_wide<7>(ctx, n, ma, q, kernel, radius, exact);
-            return launch_mfma_wide<8>(ctx, n, ma, q, kernel, radius, exact);
-        }
-        return launch_mfma_wide<4>(ctx, n, ma, q, kernel, radius, exact);
-    }
-    if (!blur_mfma_covers(kernel, radius, w, h)) return FNX_NOOP;
-    MfmaArgs ma{};
-    const int st = mfma_prepare(ctx, kernel, radius, exact, &ma);
-    if (st != FNX_OK) return st;
-    ma.src = src; ma.srcs = srcs; ma.dst = dst; ma.dsts = dsts;
-    ma.sstride = sstride; ma.dstride = dstride; ma.w = w; ma.h = h;
-    static const int cap = [] { const char *e = dev_env("FNX_MFMA_SEG"); return e ? atoi(e) : 544; }();   // development: rows per workgroup
-    ma.seg = blur_mfma_segment(ctx, n, w, h, cap, exact ? 3 : 4);
-    return exact ? launch_mfma_cfg<false, true>(ctx, n, ma, 0) : launch_mfma_cfg<false, false>(ctx, n, ma, 0);
-}
-
-// the one-pass form: blur + the tile slabs of both box-sum sides (blur.hip's launch_blur_scored owns the geometry)
-int launch_blur_mfma_scored(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstride, int w, int h, const double *kernel,
-                            int radius, int flags, uint8_t *const *dsts, int dstride, const uint32_t *coltab, const uint32_t *rowtab,
-                            unsigned long long *slabs, int nbx, int nby, int seg)
-{
-    if (!coltab || !rowtab || seg > MF_SEG_SCORE) return FNX_NOOP;
-    const bool exact = flags & FNX_BLUR_EXACT;
-    MfmaArgs ma{};
-    const int st = mfma_prepare(ctx, kernel, radius, exact, &ma);
-    if (st != FNX_OK) return st;
-    ma.srcs = srcs; ma.dsts = dsts;
-    ma.sstride = sstride; ma.dstride = dstride; ma.w = w; ma.h = h;
-    ma.seg = seg;
-    ma.coltab = coltab; ma.rowtab = rowtab; ma.slabs = slabs; ma.nbx = nbx; ma.nby = nby;
-    const size_t lds = sizeof(uint32_t) * 8 * static_cast<size_t>(nbx + 1) * (nby + 1);
-    return exact ? launch_mfma_cfg<true, true>(ctx, n, ma, lds) : launch_mfma_cfg<true, false>(ctx, n, ma, lds);
-}
-
-// radii 7 .. 24 (r5): the same through blur_mfma_wide_kernel<2 / 3 / 4, ., SCORE>
-bool blur_mfma_wide_scored_covers(const double *kernel, int radius, int w, int h, bool exact)
-{
-    if (radius > MfWide<4>::RF || (exact && !blur_mfma_exact_enabled())) return false;      // (r5: 7 .. 14, then 15 .. 24)
-    return blur_mfma_wide_covers(kernel, radius, w, h);
-}
-int launch_blur_mfma_wide_scored(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstride, int w, int h, const double *kernel,
-                                 int radius, int flags, uint8_t *const *dsts, int dstride, const int32_t *bx, const int32_t *by,
-                                 unsigned long long *slabs, int nbx, int nby, int seg)
-{
-    const bool exact = flags & FNX_BLUR_EXACT;
-    if (!blur_mfma_wide_scored_covers(kernel, radius, w, h, exact) || seg > MF_SEG_SCORE_WIDE) return FNX_NOOP;
-    MfmaWeights q;
-    mfma_quantise(kernel, radius, &q, MF_RWIDE);
-    const long long gq = exact ? static_cast<long long>(std::ceil(q.err255)) + 2 : 0;
-    if (gq > (1 << 20)) return FNX_NOOP;
-    MfmaArgs ma{};
-    ma.srcs = srcs; ma.dsts = dsts;
-    ma.sstride = sstride; ma.dstride = dstride; ma.w = w; ma.h = h;
-    ma.seed_h = static_cast<int>((1u << 23) + static_cast<uint32_t>(gq));
-    ma.seed_v = static_cast<int>((1u << 23) + (1u << 31) + static_cast<uint32_t>(gq));
-    ma.thr = static_cast<int>(2 * gq);
-    ma.seg = seg;
-    ma.bx = bx; ma.by = by; ma.slabs = slabs; ma.nbx = nbx; ma.nby = nby;
-    const size_t lds = sizeof(uint32_t) * 8 * static_cast<size_t>(nbx + 1) * (nby + 1);
-    if (radius <= MfWide<2>::RF) return launch_mfma_wide<2, true>(ctx, n, ma, q, kernel, radius, exact, lds);
-    if (radius <= MfWide<3>::RF) return launch_mfma_wide<3, true>(ctx, n, ma, q, kernel, radius, exact, lds);
-    return launch_mfma_wide<4, true>(ctx, n, ma, q, kernel, radius, exact, lds);
 }
 
 }  // namespace fnx

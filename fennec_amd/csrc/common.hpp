@@ -10,6 +10,8 @@
 #include <vector>
 
 #include "../../include/fennec_hip.h"
+#include "blur_plan.hpp"
+#include "dev_env.hpp"
 #include "png_compress_plan.hpp"
 
 namespace fnx {
@@ -24,12 +26,7 @@ void set_error(const char *fmt, ...);
 //     tables, the two-pass twin of a fused launch ...) are a per-ctx selection, fnx_ctx_set_form (Form below) -- explicit,
 //     per context, no process-wide state;
 //   * development switches (tile sizes, priorities, thresholds, A/B of two correct kernels) exist in `make DEVELOP=1`
-//     builds only: dev_env() is getenv there and a constant nullptr in a release build, so the compiler drops the branch.
-#ifdef FNX_DEVELOP
-inline const char *dev_env(const char *name) { return std::getenv(name); }
-#else
-inline const char *dev_env(const char *) { return nullptr; }
-#endif
+//     builds only: dev_env() (dev_env.hpp) is getenv there and a constant nullptr in a release build, so the compiler drops the branch.
 
 enum Form {
     FORM_FX_STREAM = 0,      // "fx_stream":       "0" = effects.hip's tile kernel instead of the streaming one
@@ -133,19 +130,6 @@ struct TableCache {
     int contig_taps = 0;     // resize tap tables: resize_contiguous_taps() of the cached table
 };
 
-// Cached geometry of the one-pass blur + SSIMFast launch (blur.hip: launch_blur_scored)
-struct ScoreGeom {
-    int w = 0, h = 0, dstW = 0, dstH = 0, radius = 0;
-    bool tall_pref = false, tall = false, ok = false;
-    bool mfma = false;          // the geometry is blur_mfma_kernel's (tile = 64 px x seg rows)
-    int seg = 0;
-    int th = 0, nbx = 0, nby = 0;
-    std::vector<int32_t> map;   // the table blob uploaded to SLOT_BOXMAP
-    // blur_mfma_kernel<SCORE, .>'s set-up tables at the blob's end (word offsets, 0: none): one packed word per
-    // (tile column, wave, lane); per segment the table offsets of its seg + 16 staged rows, then of its seg output rows
-    size_t coltab = 0, rowtab = 0;
-};
-
 // A CSR tap table of one resize pass (precomputeWeights, resize.go:164-197).  id != 0 marks an immutable
 // table with a process-unique id (host_api.cpp's cache): plans are then looked up by id instead of content.
 struct TapTable {
@@ -170,7 +154,7 @@ struct fnx_ctx {
     // ev_tail[p] first.  A caller that enqueues step s + 1 before fetching step s gets the tail for free.
     hipStream_t stream2 = nullptr;
     hipEvent_t ev_blur[2] = {}, ev_tail[2] = {};
-    hipEvent_t blur_done = nullptr;     // the stop event BOUND to the last one-pass blur dispatch (launch_direct_cfg)
+    hipEvent_t blur_done = nullptr;     // the stop event BOUND to the last one-pass blur dispatch (blur_bind_events)
     bool tail_pending[2] = {false, false};
     unsigned long long tail_gen[2] = {0, 0};   // uses of each buffer set so far
     int parity = 0;
@@ -386,21 +370,6 @@ int launch_blur(fnx_ctx *ctx, int n, const uint8_t *src, const uint8_t *const *s
 int launch_blur_scored(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstride, int w, int h,
                        const double *kernel, int radius, int flags, uint8_t *const *dsts, int dstride,
                        uint8_t *planes, size_t plane, int dstW, int dstH);
-// blur_mfma.hip: GaussianBlur on the i8 matrix pipe (radius <= 6, non-negative weights summing to 1, w >= 64, h >= 32)
-bool blur_mfma_covers(const double *kernel, int radius, int w, int h);
-bool blur_mfma_exact_enabled();
-bool blur_mfma_takes(const double *kernel, int radius, int w, int h, bool exact);
-int blur_mfma_segment(const fnx_ctx *ctx, int n, int w, int h, int cap, int occ);
-int launch_blur_mfma(fnx_ctx *ctx, int n, const uint8_t *src, const uint8_t *const *srcs, int sstride, int w, int h,
-                     const double *kernel, int radius, int flags, uint8_t *dst, uint8_t *const *dsts, int dstride);
-// (coltab / rowtab: build_score_geom's ready-made set-up of the kernel's column and row look-ups)
-int launch_blur_mfma_scored(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstride, int w, int h, const double *kernel,
-                            int radius, int flags, uint8_t *const *dsts, int dstride, const uint32_t *coltab, const uint32_t *rowtab,
-                            unsigned long long *slabs, int nbx, int nby, int seg);
-bool blur_mfma_wide_scored_covers(const double *kernel, int radius, int w, int h, bool exact);
-int launch_blur_mfma_wide_scored(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstride, int w, int h, const double *kernel,
-                                 int radius, int flags, uint8_t *const *dsts, int dstride, const int32_t *bx, const int32_t *by,
-                                 unsigned long long *slabs, int nbx, int nby, int seg);
 int launch_blur3x3(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, uint8_t *dst,
                    int dstride);
 int launch_sharpen(fnx_ctx *ctx, bool adaptive, const uint8_t *src, int sstride, int w, int h,

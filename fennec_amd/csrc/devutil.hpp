@@ -4,6 +4,8 @@
 
 #include <cstdint>
 
+#include "box_edge.hpp"
+
 namespace fnx {
 
 // explicit global-address-space views: pointers fetched from pointer tables are generic to
@@ -144,16 +146,6 @@ __device__ __forceinline__ double block_sum_256(double v, double *s_red)
     double t = 0;
     if (threadIdx.x == 0) t = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
     return t;
-}
-
-// boxDownsample's source range of output index d (ssim.go:262-275)
-__host__ __device__ __forceinline__ void box_edge(int d, double ratio, int srcN, int &s0, int &s1)
-{
-    s0 = static_cast<int>(static_cast<double>(d) * ratio);
-    s1 = static_cast<int>(static_cast<double>(d + 1) * ratio);
-    if (s1 > srcN) s1 = srcN;
-    if (s0 >= s1) s0 = s1 - 1;
-    if (s0 < 0) s0 = 0;
 }
 
 __device__ __forceinline__ uint32_t box_finish(uint32_t r, uint32_t g, uint32_t b, uint32_t al, int count)

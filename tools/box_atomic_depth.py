@@ -4,7 +4,7 @@
 A step of the kernel issues, per side and wave, four ds_add_u32: instruction k adds, from lane (r, g) = (lane & 15, lane >> 4),
 the sum of row 16 j + 4 g + k of the lane's indicator column r = 3 slot + channel into the box table at rowoff[row] + coln
 (blur_mfma.hip: mf_box_add4).  Lanes that hit one dword serialise, and so do lanes that hit different dwords of one of the 64
-LDS banks.  This tool rebuilds the launch geometry as blur.hip does (build_score_geom, score_mfma_tables: box_edge, nbx, nby,
+LDS banks.  This tool rebuilds the launch geometry as blur_plan.cpp does (build_score_geom, score_mfma_tables: box_edge, nbx, nby,
 the five slots of a wave's 16 px, the row offsets of every segment) and reports, over every 16-row block of every segment and
 every wave of every tile column of the blurred side, the mean over instructions of
 
@@ -64,7 +64,7 @@ def span(m, lo, hi):
 
 
 class Geometry:
-    """blur.hip: build_score_geom with th_fixed = seg, then score_mfma_tables"""
+    """blur_plan.cpp: build_score_geom with th_fixed = seg, then score_mfma_tables"""
 
     def __init__(self, w, h, seg=272):
         self.w, self.h, self.seg = w, h, seg
