@@ -84,6 +84,9 @@ FNX_ERR_UNSUPPORTED = -5
 # fnx_jpeg_target_size's strategies (include/fennec_hip.h): strategy 1, 3, 4 of hitTargetSize and its JPEG fallback
 FNX_TS_QUALITY, FNX_TS_QUALITY_SCALE, FNX_TS_SCALE, FNX_TS_FALLBACK = 1, 2, 4, 8
 FNX_TS_ALL = FNX_TS_QUALITY | FNX_TS_QUALITY_SCALE | FNX_TS_SCALE | FNX_TS_FALLBACK
+FNX_TS_QUANTIZE, FNX_TS_SCALE_PNG, FNX_TS_FALLBACK_PNG = 16, 32, 64    # fnx_png_target_size's legs
+FNX_TS_PNG_ALL = FNX_TS_QUANTIZE | FNX_TS_SCALE_PNG | FNX_TS_FALLBACK_PNG
+FNX_FORMAT_AUTO, FNX_FORMAT_JPEG, FNX_FORMAT_PNG = 0, 1, 2             # fnx_hit_target_size's format (types.go:35-42)
 
 
 class SizeCandidate(C.Structure):
@@ -251,6 +254,11 @@ def load_library() -> C.CDLL:
         _sig(L, "fnx_jpeg_encode_scaled", i, [ctx, i] + img + [i, i, i, i, i, _u8p, C.c_size_t, C.POINTER(C.c_size_t)])
         _sig(L, "fnx_jpeg_target_size", i, [ctx, i] + img + [i, i, C.c_longlong, i, _f64p, C.POINTER(C.c_int), C.POINTER(SizeCandidate),
                                              C.POINTER(i), _u8p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, i])
+        for name in ("fnx_png_target_size", "fnx_hit_target_size"):
+            _sig(L, name, i, [ctx, i] + img + [i, i, C.c_longlong, i, _f64p, C.POINTER(C.c_int), C.POINTER(SizeCandidate),
+                              C.POINTER(i), _u8p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, i])
+        _sig(L, "fennec_CompressFileHitTargetSize", i, [ctx, _u8p, C.c_size_t, C.POINTER(FileOptions), C.c_longlong, i, C.POINTER(i),
+                                                         C.POINTER(SizeCandidate), C.POINTER(i), _u8p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i)])
         _sig(L, "fnx_gaussian_blur_ssim_fast", i, [ctx, i] + img + [i, i, _f64p, i, i] + img + [_f64p, _f64p])
         _sig(L, "fnx_ssim_batch_enqueue", i, [ctx, i, C.POINTER(C.c_void_p), i, C.POINTER(C.c_void_p), i, i, i, _f64p])
         _sig(L, "fnx_sharpen_batch", i, [ctx, i, C.POINTER(C.c_void_p), i, i, i, C.c_double, C.POINTER(C.c_void_p), i])
@@ -285,6 +293,7 @@ def load_library() -> C.CDLL:
         _sig(L, "fnx_deflate_bound", C.c_size_t, [C.c_size_t])
         _sig(L, "fnx_deflate", i, [ctx, i, _u8p, C.c_size_t, i, _u8p, C.c_size_t, C.POINTER(C.c_size_t)])
         _sig(L, "fnx_png_encode", i, [ctx, i, i, _u8p, i, i, i, i, i, _u8p, _u8p, C.c_size_t, C.POINTER(C.c_size_t)])
+        _sig(L, "fnx_png_encoded_size", i, [ctx, i, i, _u8p, i, i, i, i, i, _u8p, C.POINTER(C.c_size_t)])
         _sig(L, "fnx_inflate", i, [_u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(C.c_size_t)])
         _sig(L, "fnx_png_info", i, [_u8p, C.c_size_t, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)])
         _sig(L, "fnx_png_decode", i, [ctx, _u8p, C.c_size_t, i, C.c_void_p, i, C.POINTER(i), C.POINTER(i)])
@@ -983,6 +992,77 @@ class Context:
         # call left, at its quality -- no second search
         data = self.jpeg_encode(image, c["quality"]) if too_small else buf[:n.value].tobytes()
         return {"candidates": cands, "winner": win.value, "data": data, "image": image, "status": FNX_OK}
+
+    def _target_size(self, entry: str, ncand: int, img, target_bytes: int, which: int, cancel, window):
+        """fnx_png_target_size / fnx_hit_target_size -> jpeg_target_size's dict.  The first buffer holds two bytes a pixel; a
+        winner that does not fit it (the call is then a second search) is asked for again with the size the call reported."""
+        s = _Img(img)
+        target_bytes = int(target_bytes)
+        if s.w <= 0 or s.h <= 0 or s.w > 65535 or s.h > 65535:
+            raise FennecError(f"{entry}: a {s.w} x {s.h} source (1..65535 each way)")
+        if target_bytes <= 0:
+            raise FennecError(f"{entry}: target_bytes must be > 0")
+        if cancel is not None and not isinstance(cancel, C.c_int):
+            raise FennecError(f"{entry}: cancel must be a ctypes.c_int (or None)")
+        k, pk = _f64(self.gaussianKernel() if window is None else window)
+        cand = (SizeCandidate * ncand)()
+        win, n = C.c_int(-1), C.c_size_t(0)
+        scaled = s.like(s.w, s.h)                  # the winner's final image fits the source's footprint
+        sv = _Img(scaled)
+        fn = getattr(self._lib, entry)
+        with self._ordered(img, scaled):
+            rc, buf = _into_buffer(lambda b, c: fn(self._h, s.space, s.ptr, s.stride, s.w, s.h, target_bytes, int(which), pk,
+                                                   C.byref(cancel) if cancel is not None else None, cand, C.byref(win),
+                                                   b.ctypes.data_as(_u8p), c, C.byref(n), sv.ptr, sv.stride),
+                                   4096 + 2 * s.w * s.h, n)     # room for a winner over the target; a larger one is asked for again
+            self._chk(rc, entry)
+            if s.space == FNX_DEVICE:
+                self.sync()
+        cands = [c.as_dict() for c in cand]
+        if rc == FNX_NOOP:
+            return {"candidates": cands, "winner": None, "data": None, "image": None, "status": rc}
+        c = cands[win.value]
+        own = c["strategy"] in (FNX_TS_QUALITY_SCALE, FNX_TS_SCALE, FNX_TS_QUANTIZE, FNX_TS_SCALE_PNG)
+        image = scaled[:c["final_h"], :c["final_w"]] if own else img
+        return {"candidates": cands, "winner": win.value, "data": buf[:n.value].tobytes(), "image": image, "status": FNX_OK}
+
+    def png_target_size(self, img, target_bytes: int, strategies: int = FNX_TS_PNG_ALL, cancel=None, window=None):
+        """hitTargetSize's PNG legs on the device (fnx_png_target_size): quantizeStrategy, scaleSearch with format PNG, the PNG
+        fallback -> jpeg_target_size's dict with three candidates (quantize, scale, fallback).  Every size is the size of this
+        library's own file under the context's deflate level (set_deflate_level("dense") is the nearer to
+        png.BestCompression); `image`: the quantized image, the Lanczos-scaled image, or the source for the fallback."""
+        strategies = int(strategies)
+        if strategies <= 0 or strategies & ~FNX_TS_PNG_ALL:
+            raise FennecError("png_target_size: strategies must be a non-empty set of FNX_TS_QUANTIZE, FNX_TS_SCALE_PNG, FNX_TS_FALLBACK_PNG")
+        return self._target_size("fnx_png_target_size", 3, img, target_bytes, strategies, cancel, window)
+
+    def hit_target_size(self, img, target_bytes: int, format: int = FNX_FORMAT_AUTO, cancel=None, window=None):
+        """All of hitTargetSize (targetsize.go:26-75) in one call (fnx_hit_target_size) -> jpeg_target_size's dict with five
+        candidates: strategy 1, quantize, strategy 3, strategy 4 and the fallback in the format the reference picks (their
+        `strategy` bits say which).  The winner's file is a PNG when its strategy is one of the FNX_TS_PNG_ALL bits."""
+        if int(format) not in (FNX_FORMAT_AUTO, FNX_FORMAT_JPEG, FNX_FORMAT_PNG):
+            raise FennecError("hit_target_size: format is FNX_FORMAT_AUTO, FNX_FORMAT_JPEG or FNX_FORMAT_PNG")
+        return self._target_size("fnx_hit_target_size", 5, img, target_bytes, int(format), cancel, window)
+
+    def compress_file_hit_target_size(self, data: bytes, target_bytes: int, format: int = FNX_FORMAT_AUTO, orient: int = 1, max_w: int = 0,
+                                      max_h: int = 0, cancel=None):
+        """compress_file_target_size under any Options.Format (fennec_CompressFileHitTargetSize): the same staging, then
+        hit_target_size on the resident image -> the same dict, five candidates."""
+        if cancel is not None and not isinstance(cancel, C.c_int):
+            raise FennecError("compress_file_hit_target_size: cancel must be a ctypes.c_int (or None)")
+        src = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, dtype=np.uint8)
+        o = FileOptions(int(orient), int(max_w), int(max_h), 0, 0.0)
+        cand = (SizeCandidate * 5)()
+        win, n = C.c_int(-1), C.c_size_t(0)
+        dims = (C.c_int * 4)()
+        pc = C.byref(cancel) if cancel is not None else None
+        rc, buf = _into_buffer(lambda b, c: self._lib.fennec_CompressFileHitTargetSize(self._h, src.ctypes.data_as(_u8p), len(data), C.byref(o),
+                                                                                       int(target_bytes), int(format), pc, cand, C.byref(win),
+                                                                                       b.ctypes.data_as(_u8p), c, C.byref(n), dims),
+                               max(4096, int(target_bytes) + 4096), n)
+        self._chk(rc, "fennec_CompressFileHitTargetSize")
+        return {"candidates": [c.as_dict() for c in cand], "winner": win.value if rc == FNX_OK else None,
+                "data": buf[:n.value].tobytes() if rc == FNX_OK else None, "dims": ((dims[0], dims[1]), (dims[2], dims[3])), "status": rc}
 
     @staticmethod
     def jpeg_progressive_coefficients(data: bytes):
@@ -1728,6 +1808,26 @@ class Context:
             self._chk(rc, "fnx_png_encode")
         return buf[:n.value].tobytes()
 
+    def png_encoded_size(self, src, kind: int | None = None, ncolors: int = 0, opaque: int = -1, palette=None) -> int:
+        """len(png_encode(...)) of the same arguments on this context without the file (fnx_png_encoded_size): the row stage,
+        then the deflate kernels' size-only forms -- the parse and the choice of block form, no codes, no bits, no gather --
+        and 8 bytes back.  palette: needed for FNX_PNG_PALETTED as png_encode needs it (its alphas size the tRNS chunk)."""
+        kind, space, ptr, stride, w, h = self._png_src(src, kind)
+        pal = None
+        if kind == FNX_PNG_PALETTED:
+            if palette is None:
+                raise FennecError("a paletted image needs its palette")
+            pal = np.ascontiguousarray(palette, dtype=np.uint8).reshape(-1, 4)
+            ncolors = ncolors or len(pal)
+            if len(pal) < ncolors:
+                raise FennecError("the palette is shorter than ncolors")
+        n = C.c_size_t(0)
+        sp = FNX_DEVICE_SRC if space == FNX_DEVICE else FNX_HOST
+        with self._ordered(src):
+            self._chk(self._lib.fnx_png_encoded_size(self._h, sp, int(kind), ptr, stride, w, h, int(ncolors), int(opaque),
+                                                     pal.ctypes.data if pal is not None else None, C.byref(n)), "fnx_png_encoded_size")
+        return int(n.value)
+
     def png_decode_config(self, data: bytes):
         """png.DecodeConfig as far as the device decoder goes: (w, h); FennecUnsupported for files it does not take (Adam7,
         a dimension above 65535), FennecError for damaged ones.  Host work only."""
@@ -2141,6 +2241,7 @@ def png_filter(src, kind=None, ncolors=0, opaque=-1): return default_context(_de
 def compress_png(img, level=9, device_deflate=False): return default_context(_dev_of(img)).compress_png(img, level, device_deflate)
 def deflate(buf, row=0): return default_context(_dev_of(buf)).deflate(buf, row)
 def png_encode(src, kind=None, ncolors=0, opaque=-1, palette=None): return default_context(_dev_of(src)).png_encode(src, kind, ncolors, opaque, palette)
+def png_encoded_size(src, kind=None, ncolors=0, opaque=-1, palette=None): return default_context(_dev_of(src)).png_encoded_size(src, kind, ncolors, opaque, palette)
 def deflate_bound(n): return int(load_library().fnx_deflate_bound(int(n)))
 def png_file_bound(w, h): return int(load_library().fnx_png_file_bound(int(w), int(h)))
 

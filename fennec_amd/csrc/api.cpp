@@ -1673,16 +1673,6 @@ static int check_median_cut(int space, const uint8_t *src, int sstride, int w, i
     return FNX_OK;
 }
 
-// a level's entries from the kernel's words; the rest of the 256 zeroed
-static int unpack_palette(const uint32_t *words, uint32_t n, uint8_t *palette)
-{
-    FNX_REQUIRE(n >= 1 && n <= 256, "median cut: the kernel's colour count");
-    std::memset(palette, 0, 1024);
-    for (uint32_t i = 0; i < n; i++)
-        for (int c = 0; c < 4; c++) palette[4 * i + c] = static_cast<uint8_t>(words[i] >> (8 * c));
-    return FNX_OK;
-}
-
 int fnx_median_cut(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int nlevels, const int *max_colors,
                    uint8_t *palettes, int *ncolors)
 {

@@ -104,11 +104,13 @@ enum Slot {
     SLOT_JPEG_DEC, SLOT_JPEG_DEC_PLANES, SLOT_JPEG_DEC_IMG,        // jpeg_dec.hip: the decoder's work arrays, its planes, toNRGBARef's image
     SLOT_AN_HASH0, SLOT_AN_HASH1,   // analyze.hip: the colour-set tables of this call and the next (the launch that uses one zeroes the other)
     SLOT_TS_SCALED, SLOT_TS_UP,    // jpeg_api.cpp: fnx_jpeg_target_size's Lanczos-scaled image and its upscale back to the source's size
+    SLOT_TS_PNG_PLANE, SLOT_TS_PNG_QUANT, SLOT_TS_PNG_BOX,   // the PNG legs: a level's index plane (the fallback's reduced plane), the winning level's quantized image, a scale step's box image
     SLOT_JPEG_QTAB, SLOT_JPEG_JOBS,  // fnx_jpeg_compress_batch: the quantiser tables of qualities 1..100, a search step's job list
     SLOT_RZBOX_TABLES, SLOT_RZBOX_SUMS,   // resize_box.hip: both tap tables + the box maps, the image-wide integer box sums
     SLOT_PNG,        // png_reduce.hip: the colour set's result (over, count, palette) and the colour -> index table of the plane pass
     SLOT_PNG_STREAM, // png_filter.hip: the filtered scanlines on their way to a host buffer
     SLOT_DEFLATE_TOK, SLOT_DEFLATE_SLOTS, SLOT_DEFLATE_OUT,   // deflate.hip: the chunks' tokens; the result word, the chunks' sizes and output slots; the stream on its way to a host buffer
+    SLOT_DEFLATE_SIZE,   // deflate.hip's size-only form: the result word and the chunks' meta words (no slots, no stream)
     SLOT_PNG_DEC_STREAM, SLOT_PNG_DEC_ROWS, SLOT_PNG_DEC_TAB,   // png_decode.hip: the inflated stream, the reconstructed rows, the unit table + the palette's pixel values
     // fnx_png_compress_batch: the colours pass's work area (results, tables, lists), the chunk's planes, its filtered streams, the
     // unit and image tables of its four stages; fnx_png_recompress_batch: the decoded images of a span
@@ -540,11 +542,18 @@ int png_filter_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, i
 // *d_size: the device word that holds the stream's size once both kernels have run.  row: a match-distance hint, 0 for none.
 // (deflate_chunks, deflate_bound: deflate_batch.hpp)
 int launch_deflate(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, uint8_t *d_out, size_t cap, const unsigned long long **d_size);
+// the size launch_deflate's stream would have under the ctx's level, and nothing else: the chunk kernels' size-only forms (the
+// parse and the choice of form; no codes, no bits, no slots) and deflate_size_kernel.  *d_size: the device word with the size
+int launch_deflate_size(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, const unsigned long long **d_size);
 // png_api.cpp: the body of fnx_deflate for device bytes (out: device or host memory), and of fnx_png_encode for a DEVICE image or
 // plane (out: host memory; palette: host)
 int deflate_device(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, bool out_on_device, uint8_t *out, size_t cap, size_t *nbytes);
 int png_encode_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors, int opaque, const uint8_t *palette,
                       uint8_t *out, size_t cap, size_t *nbytes);
+// the size png_encode_device's file would have, same arguments: the row stage into SLOT_PNG_STREAM, the size-only deflate, one
+// fetch of 8 bytes.  palette (HOST) is read for the tRNS chunk's length alone
+int png_size_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors, int opaque, const uint8_t *palette,
+                    size_t *nbytes);
 // the eight bytes a PNG file opens with, and image.Decode's test for them (io.go:65-88)
 constexpr uint8_t PNG_SIG[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
 inline bool png_signature(const uint8_t *data, size_t n) { return n >= 8 && std::memcmp(data, PNG_SIG, 8) == 0; }
@@ -610,6 +619,15 @@ int launch_apply_palette_device(fnx_ctx *ctx, const uint8_t *src, int sstride, i
 // r | g << 8 | b << 16 | 255 << 24, then ncolors[nlevels].  Nothing is waited for.
 void median_cut_samples(long long n, long long *step, long long *ns);
 int launch_median_cut(fnx_ctx *ctx, int space, const uint8_t *src, int w, int h, int nlevels, const int *max_colors, const uint32_t **d_out);
+// a level's entries from the kernel's words (HOST copies) into 256 x 4 bytes r, g, b, a; the rest of the 256 zeroed
+inline int unpack_palette(const uint32_t *words, uint32_t n, uint8_t *palette)
+{
+    FNX_REQUIRE(n >= 1 && n <= 256, "median cut: the kernel's colour count");
+    std::memset(palette, 0, 1024);
+    for (uint32_t i = 0; i < n; i++)
+        for (int c = 0; c < 4; c++) palette[4 * i + c] = static_cast<uint8_t>(words[i] >> (8 * c));
+    return FNX_OK;
+}
 // image.YCbCr / image.Gray planes -> NRGBA (convert.hip); device pointers; cb == cr == nullptr: Gray
 // boxDownsample(toNRGBARef(planes)) without the image (ssim.hip); *done = false: not its case, convert and downsample instead
 int launch_box_downsample_ycc(fnx_ctx *ctx, const uint8_t *y, int ystride, const uint8_t *cb, const uint8_t *cr, int cstride,

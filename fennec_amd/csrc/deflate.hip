@@ -54,6 +54,11 @@
 // one lazy step; see the comment in front of them, deflate_dense_chunk.inc and DESIGN.md section 5.12.  The codes / form / emit
 // half of a chunk body is deflate_codes.inc, shared by deflate_chunk.inc and deflate_dense_chunk.inc.
 //
+// deflate_chunk_size_kernel, deflate_dense_chunk_size_kernel, deflate_size_kernel (deflate_size.inc; fnx_png_encoded_size, the PNG legs):
+// the SIZE-ONLY forms -- the chunk bodies with DF_SIZE_ONLY 1 end where lane 0 knows the block's form and bit count and write the
+// chunk's byte count (what the emitting form writes into meta[0]) and nothing else: no codes, no bits, no slot; one workgroup
+// adds the counts and the 6 bytes of framing.  56 / 54 VGPRs, 51568 / 151408 bytes of LDS, no scratch -- DESIGN.md section 5.15.
+//
 // Resources (hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage): no scratch in any kernel;
 // VGPRs: see DESIGN.md section 5.7 (the figures are the compiler's and are restated there with the LDS sizes); the batched
 // kernels have their twins' figures: 60 VGPRs / 53296 bytes of LDS (chunk), 34 / 32 (gather) -- DESIGN.md section 5.10; the
@@ -226,7 +231,9 @@ struct DfBits {
 __global__ __launch_bounds__(DF_T) void deflate_chunk_kernel(DeflateArgs a)
 {
 #define DF_CHUNK_INDEX blockIdx.x
+#define DF_SIZE_ONLY 0
 #include "deflate_chunk.inc"
+#undef DF_SIZE_ONLY
 #undef DF_CHUNK_INDEX
 }
 
@@ -252,7 +259,9 @@ __global__ __launch_bounds__(DF_T) void deflate_chunk_batch_kernel(DeflateBatchA
     a.slots = b.slots + static_cast<size_t>(blockIdx.x) * DF_SLOT;
     a.meta = b.meta + 4 * static_cast<size_t>(blockIdx.x);
 #define DF_CHUNK_INDEX 0u
+#define DF_SIZE_ONLY 0
 #include "deflate_chunk.inc"
+#undef DF_SIZE_ONLY
 #undef DF_CHUNK_INDEX
 }
 
@@ -278,7 +287,9 @@ __global__ __launch_bounds__(DF_T) void deflate_dense_chunk_kernel(DeflateArgs a
 {
 #define DF_CHUNK_INDEX blockIdx.x
 #define DF_STREAM_POS base
+#define DF_SIZE_ONLY 0
 #include "deflate_dense_chunk.inc"
+#undef DF_SIZE_ONLY
 #undef DF_STREAM_POS
 #undef DF_CHUNK_INDEX
 }
@@ -297,7 +308,9 @@ __global__ __launch_bounds__(DF_T) void deflate_dense_chunk_batch_kernel(Deflate
     a.meta = b.meta + 4 * static_cast<size_t>(blockIdx.x);
 #define DF_CHUNK_INDEX 0u
 #define DF_STREAM_POS (static_cast<size_t>(blockIdx.x - first) * DF_C)
+#define DF_SIZE_ONLY 0
 #include "deflate_dense_chunk.inc"
+#undef DF_SIZE_ONLY
 #undef DF_STREAM_POS
 #undef DF_CHUNK_INDEX
 }
@@ -384,6 +397,8 @@ __global__ __launch_bounds__(DF_T) void deflate_gather_kernel(GatherArgs a)
     df_gather(a, c, before, all, s_red);
 }
 
+#include "deflate_size.inc"
+
 // A workgroup per unit: the prefix over its OWN stream's units places the chunk inside the stream, the sum over the units of
 // the streams in front places the stream -- stream i starts at out + 6 i + that sum, so the streams lie back to back at their
 // true sizes and one copy of sum(sizes) bytes brings them all down.  Nothing depends on the order the workgroups run in.
@@ -446,6 +461,35 @@ int launch_deflate(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, uint8_
     FNX_HIP(hipGetLastError());
     FNX_TRY(prof_end(ctx));
     *d_size = ga.result;
+    return FNX_OK;
+}
+
+// launch_deflate's size: the chunk kernels' size-only forms and deflate_size_kernel.  The token words as launch_deflate asks for
+// them (the parse lives there); no slot area and no output -- the result word and the chunks' meta words in a slot of their own
+int launch_deflate_size(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, const unsigned long long **d_size)
+{
+    const size_t nchunks = deflate_chunks(n);
+    const bool dense = ctx->deflate_level == FNX_DEFLATE_LEVEL_DENSE;
+    void *dt = nullptr, *dm = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_DEFLATE_TOK, nchunks * (dense ? DF_DENSE_WORDS : DF_C) * sizeof(uint32_t) + 16, &dt));
+    FNX_TRY(scratch(ctx, SLOT_DEFLATE_SIZE, 16 + 16 * nchunks, &dm));
+    uint8_t *p = static_cast<uint8_t *>(dm);
+    DeflateArgs da{};
+    da.src = d_src; da.n = n; da.row = deflate_row_hint(row); da.nchunks = static_cast<uint32_t>(nchunks);
+    da.tok = static_cast<uint32_t *>(dt);
+    da.meta = reinterpret_cast<uint32_t *>(p + 16);
+    note_route(ctx, FNX_PROF_MAIN, dense ? "deflate_dense_chunk_size_kernel" : "deflate_chunk_size_kernel");
+    FNX_TRY(prof_begin(ctx));
+    if (dense) hipLaunchKernelGGL(deflate_dense_chunk_size_kernel, dim3(da.nchunks), dim3(DF_T), 0, ctx->stream, da);
+    else hipLaunchKernelGGL(deflate_chunk_size_kernel, dim3(da.nchunks), dim3(DF_T), 0, ctx->stream, da);
+    FNX_HIP(hipGetLastError());
+    FNX_TRY(prof_end(ctx));
+    unsigned long long *result = reinterpret_cast<unsigned long long *>(p);
+    FNX_TRY(prof_begin(ctx));
+    hipLaunchKernelGGL(deflate_size_kernel, dim3(1), dim3(DF_T), 0, ctx->stream, da.meta, da.nchunks, result);
+    FNX_HIP(hipGetLastError());
+    FNX_TRY(prof_end(ctx));
+    *d_size = result;
     return FNX_OK;
 }
 

@@ -1,16 +1,19 @@
 // The body of deflate.hip's two chunk kernels, included into each: chunk DF_CHUNK_INDEX of the stream `a` (a DeflateArgs)
 // describes, every lane of its workgroup -- the parse into the chunk's token words, the block into its slot, its four meta
-// words.  It is a file and not a __device__ function because a function, simplified on its own before it is inlined, gives
-// deflate_chunk_kernel other registers than the body written into it, and that kernel's figures are pinned (DESIGN.md 5.7).
+// words (DF_SIZE_ONLY 1: the parse and the block's byte count alone, deflate_codes.inc).  It is a file and not a __device__
+// function because a function, simplified on its own before it is inlined, gives deflate_chunk_kernel other registers than
+// the body written into it, and that kernel's figures are pinned (DESIGN.md 5.7).
     __shared__ uint32_t s_w[(DF_C + 64) / 4];                        // the chunk's bytes, later its output bits
     __shared__ uint32_t s_hash[1 << DF_HBITS];                       // position + 1; later three HuffWork
     __shared__ uint32_t s_llf[288], s_df[32], s_clf[20];
     __shared__ uint8_t s_lll[288], s_dl[32], s_cll[20];
-    __shared__ uint16_t s_llc[288], s_dc[32], s_clc[20];
     __shared__ uint16_t s_cltok[320];                                // symbol | extra value << 8
-    __shared__ uint32_t s_scan[DF_T];
     __shared__ uint32_t s_adler[2];
+#if !DF_SIZE_ONLY                                                    // the emit's: the codes, the lanes' bit counts, what lane 0 found
+    __shared__ uint16_t s_llc[288], s_dc[32], s_clc[20];
+    __shared__ uint32_t s_scan[DF_T];
     __shared__ uint32_t s_form, s_hlit, s_hdist, s_hclen, s_ncl, s_hdr_bits, s_nbytes;
+#endif
     static_assert(3 * sizeof(HuffWork) <= sizeof(uint32_t) << DF_HBITS, "the Huffman work arrays take the hash table's words");
 
     const int tid = threadIdx.x;

@@ -2,6 +2,8 @@
 // histograms, the choice of form, the block into the chunk's slot, its four meta words.  It reads what the including body has
 // set up under these names: tid, a, c, len, last, s0, ntok, tok (lane t's ntok tokens from tok[s0] on), s_b / s_w (the chunk's
 // bytes; (DF_C + 64) / 4 words that become the output bits), hw (three HuffWork) and the s_ arrays of deflate_chunk.inc.
+// DF_SIZE_ONLY (0 or 1, set by the including kernel): 1 stops where the block's form and bit count are known -- no codes, no
+// emit, no slot, no Adler-32 words; meta[0] alone gets the byte count the emitting form writes there for the same chunk.
     // ---- the codes
     df_rank(s_llf, 286, hw[0].order, tid);
     df_rank(s_df, 30, hw[1].order, tid);
@@ -71,6 +73,13 @@
         uint32_t bits = dyn;
         if (fix < bits) { form = DF_FIXED; bits = fix; }
         if (8u * (5u + static_cast<uint32_t>(len)) <= bits) form = DF_STORED;
+#if DF_SIZE_ONLY
+        // what the emit below arrives at: stored is header, LEN, ~LEN, the bytes; a coded block (`bits` counts its header and its
+        // end-of-block) is padded to a byte; behind every chunk but the last the empty stored block: 3 bits, padding, 00 00 ff ff
+        uint32_t nb = form == DF_STORED ? 5u + static_cast<uint32_t>(len) + (last ? 0u : 5u) : (last ? (bits + 7u) >> 3 : ((bits + 3u + 7u) >> 3) + 4u);
+        a.meta[4 * static_cast<size_t>(c)] = nb;
+    }
+#else
         s_form = form; s_hlit = hlit; s_hdist = hdist; s_hclen = hclen; s_ncl = ncl;
         s_hdr_bits = form == DF_DYNAMIC ? hdr : 3;
     }
@@ -190,3 +199,4 @@
         m[2] = s_adler[1] % DF_ADLER;
         m[3] = static_cast<uint32_t>(len);
     }
+#endif

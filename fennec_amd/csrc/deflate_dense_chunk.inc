@@ -19,13 +19,17 @@
     __shared__ uint32_t s_hash[1 << DF_HBITS];                       // position + 1; then the walk's marks; later three HuffWork
     __shared__ uint32_t s_llf[288], s_df[32], s_clf[20];
     __shared__ uint8_t s_lll[288], s_dl[32], s_cll[20];
+#if !DF_SIZE_ONLY                                                    // the emit's codes
     __shared__ uint16_t s_llc[288], s_dc[32], s_clc[20];
+#endif
     __shared__ uint16_t s_cltok[320];                                // symbol | extra value << 8
     __shared__ uint32_t s_scan[DF_T];                                // the lanes' exits; later their bit counts
     __shared__ uint32_t s_adler[2];
     __shared__ uint32_t s_moved;
     __shared__ uint16_t s_segh[DF_T];                                // the hashes of a segment's positions
+#if !DF_SIZE_ONLY                                                    // what lane 0 found, for the emit
     __shared__ uint32_t s_form, s_hlit, s_hdist, s_hclen, s_ncl, s_hdr_bits, s_nbytes;
+#endif
     static_assert(3 * sizeof(HuffWork) <= sizeof(uint32_t) << DF_HBITS, "the Huffman work arrays take the hash table's words");
     static_assert(4 * DF_T <= (1 << DF_HBITS) && DF_S == 128, "a lane's marks are four words of the hash table's");
 
@@ -37,7 +41,9 @@
     const bool has_prev = (DF_STREAM_POS) != 0;
     const uint8_t *src = a.src + base;
     uint8_t *s_wb = reinterpret_cast<uint8_t *>(s_win);
+#if !DF_SIZE_ONLY
     uint32_t *s_w = s_win + DF_C / 4;                                // the own chunk's words
+#endif
     uint8_t *s_b = s_wb + DF_C;
     uint32_t *tok = a.tok + static_cast<size_t>(c) * DF_DENSE_WORDS;
     uint32_t *tab = tok + DF_C;                                      // L << 16 | D - 1 of every own position, 0: no match

@@ -784,6 +784,27 @@ static int check_target_options(const fennec_TargetOptions *o, const char *what)
     return FNX_OK;
 }
 
+// What both target-size file entries do first: their outputs cleared, the dimension probe, fennec_CompressFileJPEG's stages.
+// *img: the resident tight *w x *h image
+static int target_size_front(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_FileOptions *file, fnx_size_candidate *cand, int ncand,
+                             int *winner, size_t *nbytes, int dims[4], const uint8_t **img, int *w, int *h)
+{
+    std::memset(cand, 0, sizeof(fnx_size_candidate) * ncand);
+    *winner = -1;
+    *nbytes = 0;
+    dims[0] = dims[1] = dims[2] = dims[3] = 0;
+    FNX_TRY(decode_file(ctx, data, n, FNX_HOST, nullptr, 0, w, h));            // dimensions; refuses what the device decoder does not take
+    return file_stages(ctx, data, n, file, *w, *h, img, w, h, dims);
+}
+
+// fennec.go:153: FinalDimensions = the size result's
+static void target_size_dims(const fnx_size_candidate *cand, int winner, int dims[4])
+{
+    if (winner < 0) return;
+    dims[2] = cand[winner].final_w;
+    dims[3] = cand[winner].final_h;
+}
+
 // CompressFile in target-size mode (fennec.go:107-160) from the file's bytes: fennec_CompressFileJPEG's stages, then
 // hitTargetSize's JPEG legs on the resident image in one call.
 int fennec_CompressFileTargetSize(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_TargetOptions *o, const volatile int *cancel,
@@ -798,20 +819,42 @@ int fennec_CompressFileTargetSize(fnx_ctx *ctx, const uint8_t *data, size_t n, c
         set_error("invalid argument: CompressFileTargetSize: null ctx");
         return FNX_ERR_INVALID;
     }
-    std::memset(cand, 0, sizeof(fnx_size_candidate) * 4);
-    *winner = -1;
-    *nbytes = 0;
-    dims[0] = dims[1] = dims[2] = dims[3] = 0;
-    int w = 0, h = 0;
-    FNX_TRY(decode_file(ctx, data, n, FNX_HOST, nullptr, 0, &w, &h));          // dimensions; refuses what the device decoder does not take
     const uint8_t *img = nullptr;
-    FNX_TRY(file_stages(ctx, data, n, &o->file, w, h, &img, &w, &h, dims));
+    int w = 0, h = 0;
+    FNX_TRY(target_size_front(ctx, data, n, &o->file, cand, 4, winner, nbytes, dims, &img, &w, &h));
     const int rc = fnx_jpeg_target_size(ctx, FNX_DEVICE, img, w * 4, w, h, o->target_bytes, o->strategies, ssim_window(), cancel, cand, winner,
                                         out, cap, nbytes, nullptr, 0);
-    if (*winner >= 0) {                                                        // fennec.go:153: FinalDimensions = the size result's
-        dims[2] = cand[*winner].final_w;
-        dims[3] = cand[*winner].final_h;
+    target_size_dims(cand, *winner, dims);
+    return rc;
+}
+
+// The same under any Options.Format: the same front, then all of hitTargetSize on the resident image.
+int fennec_CompressFileHitTargetSize(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_FileOptions *file, long long target_bytes, int format,
+                                     const volatile int *cancel, fnx_size_candidate cand[5], int *winner, uint8_t *out, size_t cap, size_t *nbytes,
+                                     int dims[4])
+{
+    if (!data || !file || !cand || !winner || !nbytes || !dims || (!out && cap)) {
+        set_error("invalid argument: CompressFileHitTargetSize: NULL argument");
+        return FNX_ERR_INVALID;
     }
+    if (target_bytes <= 0) {
+        set_error("invalid argument: CompressFileHitTargetSize: target_bytes must be > 0");
+        return FNX_ERR_INVALID;
+    }
+    if (format != FNX_FORMAT_AUTO && format != FNX_FORMAT_JPEG && format != FNX_FORMAT_PNG) {
+        set_error("invalid argument: CompressFileHitTargetSize: format is 0 (Auto), 1 (JPEG) or 2 (PNG)");
+        return FNX_ERR_INVALID;
+    }
+    if (!ctx) {
+        set_error("invalid argument: CompressFileHitTargetSize: null ctx");
+        return FNX_ERR_INVALID;
+    }
+    const uint8_t *img = nullptr;
+    int w = 0, h = 0;
+    FNX_TRY(target_size_front(ctx, data, n, file, cand, 5, winner, nbytes, dims, &img, &w, &h));
+    const int rc = fnx_hit_target_size(ctx, FNX_DEVICE, img, w * 4, w, h, target_bytes, format, ssim_window(), cancel, cand, winner, out, cap, nbytes,
+                                       nullptr, 0);
+    target_size_dims(cand, *winner, dims);
     return rc;
 }
 

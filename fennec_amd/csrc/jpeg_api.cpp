@@ -758,6 +758,227 @@ bool better_fit(const fnx_size_candidate &c, const fnx_size_candidate &b, long l
     return c.nbytes < b.nbytes;
 }
 
+// ---- hitTargetSize's PNG legs (targetsize.go:39-43, 51-90, 180-206, 285-347) on the resident image of a TsRun ----
+// Every "how many bytes?" is png_size_device (the row stage, the deflate kernels' size-only forms, 8 bytes back); a file is made
+// once, for the call's winner (file()).  Slots: a level's index plane / the fallback's reduced plane SLOT_TS_PNG_PLANE, the
+// winning level's quantized image SLOT_TS_PNG_QUANT, a scale step's box image SLOT_TS_PNG_BOX, the Lanczos image SLOT_TS_SCALED
+// (free: the PNG scale leg runs only when no strategy produced a candidate); the palettes stay in SLOT_MEDIAN_CUT.
+constexpr int TS_PNG_LEVELS[5] = {16, 32, 64, 128, 256};   // launch_median_cut's ascending order; the walk goes from 256 down
+
+struct TsPng {
+    TsRun &run;
+    int plane_pitch = 0;
+    // quantize's winner: its colour count and palette (HOST, r g b a)
+    int q_ncolors = 0;
+    uint8_t q_palette[1024];
+    // the fallback's reduction
+    int fb_kind = 0, fb_ncolors = 0;
+    uint8_t fb_palette[1024];
+
+    int plane(uint8_t **p)
+    {
+        plane_pitch = (run.w + 3) & ~3;
+        void *t = nullptr;
+        FNX_TRY(scratch(run.ctx, SLOT_TS_PNG_PLANE, static_cast<size_t>(plane_pitch) * run.h + 16, &t));
+        *p = static_cast<uint8_t *>(t);
+        return FNX_OK;
+    }
+
+    // ---- strategy 2: quantizeStrategy (targetsize.go:180-206) ----
+    int quantize(fnx_size_candidate *c)
+    {
+        fnx_ctx *ctx = run.ctx;
+        const int w = run.w, h = run.h;
+        const uint32_t *d_pal = nullptr;                             // [5][256] entries, then the five colour counts
+        FNX_TRY(launch_median_cut(ctx, FNX_DEVICE, run.s.p, w, h, 5, TS_PNG_LEVELS, &d_pal));
+        std::vector<uint32_t> words(5 * 257);
+        FNX_TRY(fetch_bytes(ctx, d_pal, words.data(), sizeof(uint32_t) * words.size()));
+        uint8_t *idx = nullptr;
+        FNX_TRY(plane(&idx));
+        size_t prev = 0;
+        int n = 0;
+        for (int l = 4; l >= 0; l--) {
+            const uint32_t nc = words[5 * 256 + l];
+            size_t sz = prev;
+            if (l == 4 || nc != words[5 * 256 + l + 1]) {            // else: the same palette, the same file
+                FNX_TRY(unpack_palette(words.data() + 256 * l, nc, q_palette));
+                FNX_TRY(launch_apply_palette_device(ctx, run.s.p, run.s.stride, w, h, d_pal + 256 * l, d_pal + 5 * 256 + l, idx, plane_pitch,
+                                                    nullptr, 0));
+                FNX_TRY(png_size_device(ctx, FNX_PNG_PALETTED, idx, plane_pitch, w, h, static_cast<int>(nc), 1, q_palette, &sz));
+                n++;
+            }
+            c->steps = n;
+            prev = sz;
+            if (static_cast<long long>(sz) > run.target) continue;
+            // the winner: palettedToNRGBA and computeSSIMNRGBA(src, quantized); the index plane stays for file()
+            void *t = nullptr;
+            FNX_TRY(scratch(ctx, SLOT_TS_PNG_QUANT, static_cast<size_t>(w) * h * 4 + 16, &t));
+            FNX_TRY(launch_apply_palette_device(ctx, run.s.p, run.s.stride, w, h, d_pal + 256 * l, d_pal + 5 * 256 + l, nullptr, 0,
+                                                static_cast<uint8_t *>(t), w * 4));
+            FNX_TRY(run.ssim_against(static_cast<const uint8_t *>(t), w * 4, w, h, &c->ssim));
+            q_ncolors = static_cast<int>(nc);
+            c->strategy = FNX_TS_QUANTIZE; c->quality = 0; c->final_w = w; c->final_h = h; c->nbytes = static_cast<int64_t>(sz);
+            return FNX_OK;
+        }
+        return FNX_OK;
+    }
+
+    // ---- strategy 4: scaleSearch(src, target, PNG) (targetsize.go:285-347) ----
+    int scale(fnx_size_candidate *c)
+    {
+        fnx_ctx *ctx = run.ctx;
+        const int w = run.w, h = run.h;
+        void *t = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_TS_PNG_BOX, static_cast<size_t>(w) * h * 4 + 16, &t));    // every step is smaller than the source
+        uint8_t *box = static_cast<uint8_t *>(t);
+        int n = 0;
+        double lo = 0.05, hi = 1.0, best = 0.0;
+        for (int i = 0; i < 12; i++) {
+            if (run.cancelled()) break;
+            const double mid = (lo + hi) / 2;
+            const int nw = static_cast<int>(static_cast<double>(w) * mid), nh = static_cast<int>(static_cast<double>(h) * mid);
+            if (nw < 1 || nh < 1) {
+                lo = mid;
+                continue;
+            }
+            size_t sz = 0;                                           // testScaleFits: png.Encode of the scaled image as it is
+            FNX_TRY(launch_box_downsample(ctx, 1, run.s.p, nullptr, run.s.stride, w, h, box, nw * 4, 0, nw, nh));
+            FNX_TRY(png_size_device(ctx, FNX_PNG_NRGBA, box, nw * 4, nw, nh, 0, -1, nullptr, &sz));
+            n++;
+            if (static_cast<long long>(sz) <= run.target) {
+                best = mid;
+                lo = mid;
+            } else {
+                hi = mid;
+            }
+        }
+        c->steps = n;
+        if (best == 0.0) return FNX_OK;
+        // executeFinalScaleEncode: the Lanczos image's file, which may not fit
+        const int fw = static_cast<int>(static_cast<double>(w) * best), fh = static_cast<int>(static_cast<double>(h) * best);
+        FNX_TRY(scratch(ctx, SLOT_TS_SCALED, static_cast<size_t>(fw) * fh * 4 + 16, &t));
+        uint8_t *img = static_cast<uint8_t *>(t);
+        FNX_TRY(fennec_lanczosResize(ctx, FNX_DEVICE, run.s.p, run.s.stride, w, h, img, fw * 4, fw, fh));
+        size_t sz = 0;
+        FNX_TRY(png_size_device(ctx, FNX_PNG_NRGBA, img, fw * 4, fw, fh, 0, -1, nullptr, &sz));
+        c->steps = n + 1;
+        FNX_TRY(run.ssim_against(img, fw * 4, fw, fh, &c->ssim));
+        c->strategy = FNX_TS_SCALE_PNG; c->quality = 0; c->final_w = fw; c->final_h = fh; c->nbytes = static_cast<int64_t>(sz);
+        return FNX_OK;
+    }
+
+    // what the fallback's file is made from, after its reduction
+    const uint8_t *fb_src() const { return fb_kind == FNX_PNG_NRGBA ? run.s.p : static_cast<const uint8_t *>(run.ctx->slot[SLOT_TS_PNG_PLANE].p); }
+    int fb_stride() const { return fb_kind == FNX_PNG_NRGBA ? run.s.stride : plane_pitch; }
+
+    // ---- fallbackTargetSizeEncode's PNG branch (targetsize.go:86-89): compressPNG(original), ssim 1.0 ----
+    int fallback(fnx_size_candidate *c)
+    {
+        uint8_t *p = nullptr;
+        FNX_TRY(plane(&p));
+        FNX_TRY(png_reduce_device(run.ctx, run.s.p, run.s.stride, run.w, run.h, 256, p, plane_pitch, &fb_kind, fb_palette, &fb_ncolors));
+        size_t sz = 0;
+        FNX_TRY(png_size_device(run.ctx, fb_kind, fb_src(), fb_stride(), run.w, run.h, fb_ncolors, -1, fb_palette, &sz));
+        c->strategy = FNX_TS_FALLBACK_PNG; c->quality = 0; c->final_w = run.w; c->final_h = run.h; c->steps = 1;
+        c->nbytes = static_cast<int64_t>(sz);
+        c->ssim = 1.0;
+        return FNX_OK;
+    }
+
+    // the winner's image where it is not the source (device, tight), else nullptr
+    const uint8_t *image(const fnx_size_candidate &c) const
+    {
+        if (c.strategy == FNX_TS_QUANTIZE) return static_cast<const uint8_t *>(run.ctx->slot[SLOT_TS_PNG_QUANT].p);
+        if (c.strategy == FNX_TS_SCALE_PNG) return static_cast<const uint8_t *>(run.ctx->slot[SLOT_TS_SCALED].p);
+        return nullptr;
+    }
+
+    // the winner's file: the single route's (png_encode_device) over what the leg left on the device
+    int file(const fnx_size_candidate &c, uint8_t *out, size_t cap, size_t *nbytes)
+    {
+        fnx_ctx *ctx = run.ctx;
+        if (c.strategy == FNX_TS_QUANTIZE)
+            return png_encode_device(ctx, FNX_PNG_PALETTED, static_cast<const uint8_t *>(ctx->slot[SLOT_TS_PNG_PLANE].p), plane_pitch, run.w, run.h,
+                                     q_ncolors, 1, q_palette, out, cap, nbytes);
+        if (c.strategy == FNX_TS_SCALE_PNG)
+            return png_encode_device(ctx, FNX_PNG_NRGBA, image(c), c.final_w * 4, c.final_w, c.final_h, 0, -1, nullptr, out, cap, nbytes);
+        return png_encode_device(ctx, fb_kind, fb_src(), fb_stride(), run.w, run.h, fb_ncolors, -1, fb_palette, out, cap, nbytes);
+    }
+};
+
+constexpr int TS_JPEG_BITS = FNX_TS_QUALITY | FNX_TS_QUALITY_SCALE | FNX_TS_SCALE | FNX_TS_FALLBACK;
+constexpr int TS_PNG_BITS = FNX_TS_QUANTIZE | FNX_TS_SCALE_PNG | FNX_TS_FALLBACK_PNG;
+constexpr int TS_AUTO = -1;            // ts_run's `strategies`: hitTargetSize under Format: Auto -- the source's opacity picks the legs
+
+// hitTargetSize (targetsize.go:26-75) over the legs `strategies` names, behind the entries' argument checks.  cand[5]: strategy
+// 1, quantize, strategy 3, strategy 4 (FNX_TS_SCALE or FNX_TS_SCALE_PNG; never both in one call), the fallback (likewise).
+int ts_run(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, long long target_bytes, int strategies, const double *window,
+           const volatile int *cancel, fnx_size_candidate cand[5], int *winner, uint8_t *out, size_t cap, size_t *nbytes, uint8_t *img, int istride)
+{
+    std::memset(cand, 0, sizeof(fnx_size_candidate) * 5);
+    *winner = -1;
+    *nbytes = 0;
+    TsRun run{ctx, {}, w, h, target_bytes, window, cancel};
+    TsPng png{run};
+    FNX_TRY(stage_in(ctx, space, src, sstride, w, h, SLOT_IN_A, &run.s));
+    if (strategies == TS_AUTO) {
+        // canUseJPEG = isOpaque(original) (convert.go:67-74: the flat Pix slice; the source is tight here, so the staged image is it)
+        void *df = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_RESULT, 16, &df));
+        FNX_TRY(launch_scan_flags(ctx, run.s.p, static_cast<size_t>(h - 1) * run.s.stride + static_cast<size_t>(w) * 4, static_cast<uint32_t *>(df)));
+        uint32_t flags = 0;
+        FNX_TRY(fetch_bytes(ctx, df, &flags, sizeof(flags)));
+        strategies = FNX_TS_QUANTIZE | ((flags & 1u) ? FNX_TS_SCALE_PNG | FNX_TS_FALLBACK_PNG : TS_JPEG_BITS);
+    }
+    // the legs in the reference's order, ctx.Err() before each
+    if ((strategies & FNX_TS_QUALITY) && !run.cancelled()) FNX_TRY(run.quality(&cand[0]));
+    if ((strategies & FNX_TS_QUANTIZE) && !run.cancelled()) FNX_TRY(png.quantize(&cand[1]));
+    if ((strategies & FNX_TS_QUALITY_SCALE) && !run.cancelled()) FNX_TRY(run.quality_scale(&cand[2]));
+    auto none = [&] { return !cand[0].strategy && !cand[1].strategy && !cand[2].strategy && !cand[3].strategy; };
+    if ((strategies & FNX_TS_SCALE) && none() && !run.cancelled()) FNX_TRY(run.scale(&cand[3]));
+    if ((strategies & FNX_TS_SCALE_PNG) && none() && !run.cancelled()) FNX_TRY(png.scale(&cand[3]));
+    if ((strategies & FNX_TS_FALLBACK) && none()) FNX_TRY(run.fallback(&cand[4]));       // also after a cancellation
+    if ((strategies & FNX_TS_FALLBACK_PNG) && none()) FNX_TRY(png.fallback(&cand[4]));
+    int best = -1;
+    for (int i = 0; i < 5; i++)
+        if (cand[i].strategy && (best < 0 || better_fit(cand[i], cand[best], target_bytes))) best = i;
+    if (best < 0) return FNX_NOOP;
+    *winner = best;
+    const fnx_size_candidate &c = cand[best];
+    const hipMemcpyKind down = space == FNX_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (c.strategy & TS_PNG_BITS) {
+        if (img && png.image(c))
+            FNX_HIP(hipMemcpy2DAsync(img, istride, png.image(c), size_t(c.final_w) * 4, size_t(c.final_w) * 4, c.final_h, down, ctx->stream));
+        if (!out && cap == 0) *nbytes = static_cast<size_t>(c.nbytes);       // the size only: the leg's query was the file's
+        else FNX_TRY(png.file(c, out, cap, nbytes));
+        if (space == FNX_HOST) FNX_HIP(hipStreamSynchronize(ctx->stream));
+        return FNX_OK;
+    }
+    JpegPlanes pl;
+    if (best == 2 || best == 3) {
+        // the winner's image (SLOT_TS_SCALED) and its planes once more: a later query may have used SLOT_JPEG1
+        const uint8_t *scaled = static_cast<const uint8_t *>(ctx->slot[SLOT_TS_SCALED].p);
+        FNX_TRY(jpeg_ycc_planes(ctx, SLOT_JPEG1, scaled, c.final_w * 4, c.final_w, c.final_h, &pl));
+        if (img) FNX_HIP(hipMemcpy2DAsync(img, istride, scaled, size_t(c.final_w) * 4, size_t(c.final_w) * 4, c.final_h, down, ctx->stream));
+    } else {
+        FNX_TRY(run.orig_planes());
+        pl = run.orig;
+    }
+    FNX_TRY(jpeg_file_from_planes(ctx, pl, c.final_w, c.final_h, c.quality, out, cap, nbytes));
+    if (space == FNX_HOST) FNX_HIP(hipStreamSynchronize(ctx->stream));
+    return FNX_OK;
+}
+
+// cand5's entries at[0 .. n) as the n candidates of an entry that runs a subset of the legs, the winner's index likewise
+void ts_pick(const fnx_size_candidate cand5[5], int winner5, const int *at, int n, fnx_size_candidate *cand, int *winner)
+{
+    *winner = -1;
+    for (int i = 0; i < n; i++) {
+        cand[i] = cand5[at[i]];
+        if (at[i] == winner5) *winner = i;
+    }
+}
+
 }  // namespace
 
 int fnx_jpeg_target_size(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, long long target_bytes, int strategies,
@@ -770,42 +991,62 @@ int fnx_jpeg_target_size(fnx_ctx *ctx, int space, const uint8_t *src, int sstrid
     FNX_REQUIRE(window, "target_size: window is required");
     FNX_REQUIRE(jpeg_dims(w, h), "target_size: dimensions must be 1..65535 (JPEG dims are 16-bit)");
     FNX_REQUIRE(target_bytes > 0, "target_size: target_bytes must be > 0");
-    FNX_REQUIRE(strategies > 0 && (strategies & ~(FNX_TS_QUALITY | FNX_TS_QUALITY_SCALE | FNX_TS_SCALE | FNX_TS_FALLBACK)) == 0,
-                "target_size: strategies must be a non-empty subset of bits 1, 2, 4, 8");
+    FNX_REQUIRE(strategies > 0 && (strategies & ~TS_JPEG_BITS) == 0, "target_size: strategies must be a non-empty subset of bits 1, 2, 4, 8");
     FNX_REQUIRE(img == nullptr || istride >= 4 * w, "target_size: img needs a stride of at least 4 * w (the source's width)");
     FNX_TRY(check_img(src, sstride, w, h, "src"));
-    std::memset(cand, 0, sizeof(fnx_size_candidate) * 4);
-    *winner = -1;
-    *nbytes = 0;
-    TsRun run{ctx, {}, w, h, target_bytes, window, cancel};
-    FNX_TRY(stage_in(ctx, space, src, sstride, w, h, SLOT_IN_A, &run.s));
-    // hitTargetSize (targetsize.go:26-75): the JPEG legs in the reference's order, ctx.Err() before each
-    if ((strategies & FNX_TS_QUALITY) && !run.cancelled()) FNX_TRY(run.quality(&cand[0]));
-    if ((strategies & FNX_TS_QUALITY_SCALE) && !run.cancelled()) FNX_TRY(run.quality_scale(&cand[1]));
-    auto none = [&] { return !cand[0].strategy && !cand[1].strategy && !cand[2].strategy; };
-    if ((strategies & FNX_TS_SCALE) && none() && !run.cancelled()) FNX_TRY(run.scale(&cand[2]));
-    if ((strategies & FNX_TS_FALLBACK) && none()) FNX_TRY(run.fallback(&cand[3]));       // also after a cancellation
-    int best = -1;
-    for (int i = 0; i < 4; i++)
-        if (cand[i].strategy && (best < 0 || better_fit(cand[i], cand[best], target_bytes))) best = i;
-    if (best < 0) return FNX_NOOP;
-    *winner = best;
-    const fnx_size_candidate &c = cand[best];
-    JpegPlanes pl;
-    if (best == 1 || best == 2) {
-        // the winner's image (SLOT_TS_SCALED) and its planes once more: a later query may have used SLOT_JPEG1
-        const uint8_t *scaled = static_cast<const uint8_t *>(ctx->slot[SLOT_TS_SCALED].p);
-        FNX_TRY(jpeg_ycc_planes(ctx, SLOT_JPEG1, scaled, c.final_w * 4, c.final_w, c.final_h, &pl));
-        if (img)
-            FNX_HIP(hipMemcpy2DAsync(img, istride, scaled, size_t(c.final_w) * 4, size_t(c.final_w) * 4, c.final_h,
-                                     space == FNX_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
-    } else {
-        FNX_TRY(run.orig_planes());
-        pl = run.orig;
+    fnx_size_candidate c5[5];
+    int w5 = -1;
+    const int rc = ts_run(ctx, space, src, sstride, w, h, target_bytes, strategies, window, cancel, c5, &w5, out, cap, nbytes, img, istride);
+    static const int at[4] = {0, 2, 3, 4};
+    ts_pick(c5, w5, at, 4, cand, winner);
+    return rc;
+}
+
+int fnx_png_target_size(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, long long target_bytes, int strategies,
+                        const double *window, const volatile int *cancel, fnx_size_candidate cand[3], int *winner, uint8_t *out, size_t cap,
+                        size_t *nbytes, uint8_t *img, int istride)
+{
+    FNX_TRY(check_space(space));
+    FNX_REQUIRE(cand && winner && nbytes, "png_target_size: cand, winner and nbytes are required");
+    FNX_REQUIRE(window, "png_target_size: window is required");
+    FNX_REQUIRE(jpeg_dims(w, h), "png_target_size: dimensions must be 1..65535");
+    FNX_REQUIRE(target_bytes > 0, "png_target_size: target_bytes must be > 0");
+    FNX_REQUIRE(strategies > 0 && (strategies & ~TS_PNG_BITS) == 0, "png_target_size: strategies must be a non-empty subset of bits 16, 32, 64");
+    FNX_REQUIRE(out != nullptr || cap == 0, "png_target_size: out is null");
+    FNX_REQUIRE(img == nullptr || istride >= 4 * w, "png_target_size: img needs a stride of at least 4 * w (the source's width)");
+    FNX_TRY(check_img(src, sstride, w, h, "src"));
+    FNX_REQUIRE(!(strategies & FNX_TS_QUANTIZE) || sstride == 4 * w,
+                "png_target_size: quantize takes tight images only (sstride == 4*w): medianCut samples the flat Pix slice");
+    FNX_REQUIRE(space == FNX_HOST || (reinterpret_cast<uintptr_t>(src) & 3u) == 0, "a device image is 4-byte aligned");
+    FNX_ENTER(ctx);                                                  // every refusal above comes before the ctx is looked at
+    fnx_size_candidate c5[5];
+    int w5 = -1;
+    const int rc = ts_run(ctx, space, src, sstride, w, h, target_bytes, strategies, window, cancel, c5, &w5, out, cap, nbytes, img, istride);
+    static const int at[3] = {1, 3, 4};
+    ts_pick(c5, w5, at, 3, cand, winner);
+    return rc;
+}
+
+int fnx_hit_target_size(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, long long target_bytes, int format,
+                        const double *window, const volatile int *cancel, fnx_size_candidate cand[5], int *winner, uint8_t *out, size_t cap,
+                        size_t *nbytes, uint8_t *img, int istride)
+{
+    FNX_TRY(check_space(space));
+    FNX_REQUIRE(cand && winner && nbytes, "hit_target_size: cand, winner and nbytes are required");
+    FNX_REQUIRE(window, "hit_target_size: window is required");
+    FNX_REQUIRE(jpeg_dims(w, h), "hit_target_size: dimensions must be 1..65535");
+    FNX_REQUIRE(target_bytes > 0, "hit_target_size: target_bytes must be > 0");
+    FNX_REQUIRE(format == FNX_FORMAT_AUTO || format == FNX_FORMAT_JPEG || format == FNX_FORMAT_PNG, "hit_target_size: format is 0 (Auto), 1 (JPEG) or 2 (PNG)");
+    FNX_REQUIRE(img == nullptr || istride >= 4 * w, "hit_target_size: img needs a stride of at least 4 * w (the source's width)");
+    FNX_TRY(check_img(src, sstride, w, h, "src"));
+    if (format != FNX_FORMAT_JPEG) {
+        FNX_REQUIRE(out != nullptr || cap == 0, "hit_target_size: out is null");
+        FNX_REQUIRE(sstride == 4 * w, "hit_target_size: quantize takes tight images only (sstride == 4*w): medianCut samples the flat Pix slice");
+        FNX_REQUIRE(space == FNX_HOST || (reinterpret_cast<uintptr_t>(src) & 3u) == 0, "a device image is 4-byte aligned");
     }
-    FNX_TRY(jpeg_file_from_planes(ctx, pl, c.final_w, c.final_h, c.quality, out, cap, nbytes));
-    if (space == FNX_HOST) FNX_HIP(hipStreamSynchronize(ctx->stream));
-    return FNX_OK;
+    FNX_ENTER(ctx);                                                  // every refusal above comes before the ctx is looked at
+    const int strategies = format == FNX_FORMAT_JPEG ? TS_JPEG_BITS : (format == FNX_FORMAT_PNG ? TS_PNG_BITS : TS_AUTO);
+    return ts_run(ctx, space, src, sstride, w, h, target_bytes, strategies, window, cancel, cand, winner, out, cap, nbytes, img, istride);
 }
 
 // ---- image.Decode of a baseline JPEG on the device (third slice: jpeg_dec.hip) ----------------

@@ -325,20 +325,44 @@ int deflate_device(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, bool o
     return FNX_OK;
 }
 
-int png_encode_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors, int opaque, const uint8_t *palette,
-                      uint8_t *out, size_t cap, size_t *nbytes)
+// a file's row stage into SLOT_PNG_STREAM (*d_stream, *stream_bytes): room for RGBA rows when the call itself finds the opacity
+static int png_rows_to_stream(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors, int opaque,
+                              const uint8_t **d_stream, size_t *stream_bytes, int *color_type, int *bit_depth)
 {
-    // the row stage into device scratch: room for RGBA rows when the call itself finds the opacity
     const size_t row_max = kind == FNX_PNG_NRGBA ? static_cast<size_t>(w) * (opaque == 1 ? 3 : 4) : static_cast<size_t>(w);
     const size_t stream_cap = static_cast<size_t>(h) * (row_max + 1);
     void *dstream = nullptr;
     FNX_TRY(scratch(ctx, SLOT_PNG_STREAM, stream_cap + 16, &dstream));
+    *d_stream = static_cast<const uint8_t *>(dstream);
+    return png_filter_device(ctx, kind, src, sstride, w, h, ncolors, opaque, true, static_cast<uint8_t *>(dstream), stream_cap, stream_bytes,
+                             color_type, bit_depth);
+}
+
+int png_size_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors, int opaque, const uint8_t *palette,
+                    size_t *nbytes)
+{
+    const uint8_t *dstream = nullptr;
+    size_t stream_bytes = 0;
+    int color_type = 0, bit_depth = 0;
+    FNX_TRY(png_rows_to_stream(ctx, kind, src, sstride, w, h, ncolors, opaque, &dstream, &stream_bytes, &color_type, &bit_depth));
+    const unsigned long long *d_size = nullptr;
+    FNX_TRY(launch_deflate_size(ctx, dstream, stream_bytes, static_cast<int>(stream_bytes / h), &d_size));
+    unsigned long long zsize = 0;
+    FNX_TRY(fetch_bytes(ctx, d_size, &zsize, sizeof(zsize)));
+    const PngFrame frame{w, h, color_type, bit_depth, ncolors, palette};
+    *nbytes = frame.file_bytes(static_cast<size_t>(zsize));
+    return FNX_OK;
+}
+
+int png_encode_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors, int opaque, const uint8_t *palette,
+                      uint8_t *out, size_t cap, size_t *nbytes)
+{
+    const uint8_t *dstream = nullptr;
     size_t stream_bytes = 0, zsize = 0;
     int color_type = 0, bit_depth = 0;
-    FNX_TRY(png_filter_device(ctx, kind, src, sstride, w, h, ncolors, opaque, true, static_cast<uint8_t *>(dstream), stream_cap, &stream_bytes,
-                              &color_type, &bit_depth));
+    FNX_TRY(png_rows_to_stream(ctx, kind, src, sstride, w, h, ncolors, opaque, &dstream, &stream_bytes, &color_type, &bit_depth));
     uint8_t *dz = nullptr;
-    FNX_TRY(deflate_gathered(ctx, static_cast<const uint8_t *>(dstream), stream_bytes, static_cast<int>(stream_bytes / h), &dz, &zsize));
+    FNX_TRY(deflate_gathered(ctx, dstream, stream_bytes, static_cast<int>(stream_bytes / h), &dz, &zsize));
 
     const PngFrame frame{w, h, color_type, bit_depth, ncolors, palette};
     *nbytes = frame.file_bytes(zsize);
@@ -477,6 +501,17 @@ int fnx_png_encode(fnx_ctx *ctx, int space, int kind, const uint8_t *src, int ss
     const uint8_t *dsrc = nullptr;
     FNX_TRY(stage_rows_source(ctx, space, kind, src, sstride, w, h, &dsrc));
     return png_encode_device(ctx, kind, dsrc, sstride, w, h, ncolors, opaque, palette, out, cap, nbytes);
+}
+
+int fnx_png_encoded_size(fnx_ctx *ctx, int space, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors, int opaque,
+                         const uint8_t *palette, size_t *nbytes)
+{
+    FNX_TRY(check_rows_source(space, kind, src != nullptr && nbytes != nullptr, "src and nbytes", src, sstride, w, h, ncolors, palette != nullptr,
+                              opaque, nullptr, 0));
+    FNX_ENTER(ctx);
+    const uint8_t *dsrc = nullptr;
+    FNX_TRY(stage_rows_source(ctx, space, kind, src, sstride, w, h, &dsrc));
+    return png_size_device(ctx, kind, dsrc, sstride, w, h, ncolors, opaque, palette, nbytes);
 }
 
 int fnx_png_decode(fnx_ctx *ctx, const uint8_t *data, size_t n, int space, uint8_t *dst, int dstride, int *w, int *h)

@@ -420,6 +420,53 @@ int fnx_jpeg_target_size(fnx_ctx *ctx, int space, const uint8_t *src, int sstrid
                          int strategies, const double *window /* 64 */, const volatile int *cancel /* may be NULL */,
                          fnx_size_candidate cand[4], int *winner, uint8_t *out, size_t cap, size_t *nbytes, uint8_t *img,
                          int istride);
+/* hitTargetSize's PNG legs (targetsize.go:39-43, 51-90, 180-206, 285-347) in one call on a resident image, the sibling of
+ * fnx_jpeg_target_size: every "how many bytes?" is fnx_png_encoded_size's question (the deflate kernels' size-only forms, 8
+ * bytes back), a file is made once, for the winner.  `strategies`: a non-empty subset of */
+#define FNX_TS_QUANTIZE     16  /* strategy 2: quantizeStrategy                      targetsize.go:39-43, 180-206 */
+#define FNX_TS_SCALE_PNG    32  /* strategy 4 with format PNG: scaleSearch/testScaleFits/executeFinalScaleEncode
+                                   targetsize.go:51-62, 285-347; only when no strategy of this call produced a candidate */
+#define FNX_TS_FALLBACK_PNG  64 /* fallbackTargetSizeEncode's PNG branch: compressPNG(original), ssim 1.0; only when nothing else
+                                   targetsize.go:64-90 */
+/* (fnx_jpeg_target_size and fennec_CompressFileTargetSize refuse these bits, this entry refuses the four JPEG bits.)
+ * Quantize: medianCut ONCE at the levels 16, 32, 64, 128, 256 (the palettes are prefixes of one run; they stay on the device),
+ * then the levels from 256 down: applyPalette's index plane, the size of its paletted file (bit depth by the level's colour
+ * count as fnx_png_filter's table says, no tRNS), the first level at or under the target wins; only for it palettedToNRGBA and
+ * SSIMFast run.  A level whose colour count equals the level's before it (the run stopped early) takes that level's size.
+ * Scale: the reference's twelve bisection steps, per step boxDownsample and the size of the scaled NRGBA image's file (RGB rows
+ * when it is Opaque(); no tryPalettize, no toGray: testScaleFits hands png.Encode the image as it is), then lanczosResize at the
+ * best scale and its file's size -- which may be over the target, as in the reference.  Fallback: fnx_png_reduce(256) and the
+ * reduced image's file, ssim exactly 1.0.  quality is 0 in every candidate.
+ * WHAT "FITS" MEANS: every size is the size of THIS library's file under the ctx's deflate level, not the size Go's
+ * compress/flate would give (the same opt-in fennec_CompressFilePNG asks for).  A winner reported at or under the target IS a
+ * file at or under the target; which level or scale wins can differ from the reference's for targets between the two encoders'
+ * sizes.  FNX_DEFLATE_LEVEL_DENSE is recommended here: its sizes are the nearer to png.BestCompression's.
+ * cand[0] quantize, cand[1] scale, cand[2] fallback; steps: the size queries the leg ran (the final Lanczos file's and the
+ * fallback's one included; a level that took its neighbour's size ran none).  *winner, out / cap / *nbytes, cancel (looked at
+ * before each leg and each scale step; the fallback runs also after a cancellation), the return codes and the cap-too-small
+ * protocol (FNX_ERR_INVALID with *nbytes, cand, *winner and img filled) are fnx_jpeg_target_size's.  img (may be NULL; in
+ * `space`, stride istride >= 4 w): the quantize winner's w x h quantized image or the scale winner's final_w x final_h Lanczos
+ * image; untouched for the fallback (the image is the source).  FNX_ERR_INVALID before any device work also for a padded
+ * source (sstride != 4 w) with FNX_TS_QUANTIZE: medianCut samples the flat Pix slice (fnx_median_cut). */
+int fnx_png_target_size(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, long long target_bytes,
+                        int strategies /* subset of the three */, const double *window /* 64 */, const volatile int *cancel /* may be NULL */,
+                        fnx_size_candidate cand[3], int *winner, uint8_t *out, size_t cap, size_t *nbytes, uint8_t *img, int istride);
+/* All of hitTargetSize (targetsize.go:26-75) in one call, the source staged once, SSIMFast's prepared side of it shared by
+ * every leg.  format: Options.Format (types.go:35-42): */
+#define FNX_FORMAT_AUTO 0
+#define FNX_FORMAT_JPEG 1
+#define FNX_FORMAT_PNG  2
+/* canUseJPEG = format != PNG && isOpaque(src) (the flat scan of fennec_isOpaque).  cand[0]: strategy 1 and cand[2]: strategy 3
+ * (when canUseJPEG or format == JPEG); cand[1]: quantize (format != JPEG); cand[3]: strategy 4 when nothing before it produced
+ * a candidate, in the format the reference picks -- its `strategy` says which, FNX_TS_SCALE or FNX_TS_SCALE_PNG; cand[4]: the
+ * fallback when there is still none, FNX_TS_FALLBACK or FNX_TS_FALLBACK_PNG.  *winner: betterFit over the candidates in that
+ * order, a tie keeping the earlier one; the output's format is read off cand[*winner].strategy (a PNG leg's bit: a PNG file).
+ * With format == FNX_FORMAT_JPEG the call IS fnx_jpeg_target_size with all four bits: the same fields (cand[0], [2], [3], [4])
+ * and the same bytes.  The PNG legs' sizes are this library's (see fnx_png_target_size).  Everything else -- cancel, out / cap
+ * / *nbytes, img, the return codes -- as fnx_jpeg_target_size; a padded source is refused unless format == FNX_FORMAT_JPEG. */
+int fnx_hit_target_size(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, long long target_bytes, int format,
+                        const double *window /* 64 */, const volatile int *cancel /* may be NULL */, fnx_size_candidate cand[5], int *winner,
+                        uint8_t *out, size_t cap, size_t *nbytes, uint8_t *img, int istride);
 /* SURVEY 8(f)2, third slice -- image.Decode of a JPEG source (batch.go:88-101 via io.go:60-95) on the device:
  * dst = toNRGBARef(jpeg.Decode(data)), *w x *h.  `data` is HOST memory (the file); dst is in `space`.  dst == NULL:
  * only the dimensions (jpeg.DecodeConfig) -- and whether the device decoder takes the file at all (host work: ctx may be
@@ -793,6 +840,16 @@ int fnx_ctx_set_deflate_level(fnx_ctx *ctx, int level);
  * written.  Decodes to the source's pixels; differs from the reference's file in the deflate bytes only. */
 int fnx_png_encode(fnx_ctx *ctx, int space, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors /* paletted: 1..256 */,
                    int opaque /* 1, 0, or -1: decide as Opaque() does */, const uint8_t *palette, uint8_t *out, size_t cap, size_t *nbytes);
+/* The size fnx_png_encode's file would have under this ctx's deflate level, same arguments, nothing but 8 bytes crossing
+ * back: the row stage, then the chunk kernels' SIZE-ONLY forms -- the same parse and the same choice among dynamic, fixed
+ * and stored, stopped where the block's bit count is known: no codes, no bits, no output slots, no gather, no file -- and
+ * deflate_size_kernel, which adds the chunks' byte counts.  *nbytes == the *nbytes fnx_png_encode reports for the same
+ * arguments on the same ctx, for every image.  palette: REQUIRED for FNX_PNG_PALETTED, as fnx_png_encode requires it (its
+ * alphas decide the tRNS chunk's length; the colours are not read); ignored otherwise.  One host wait (a second one in front
+ * of it when opaque == -1).  fnx_ctx_last_kernel(ctx, FNX_PROF_MAIN) names deflate_chunk_size_kernel, at
+ * FNX_DEFLATE_LEVEL_DENSE deflate_dense_chunk_size_kernel. */
+int fnx_png_encoded_size(fnx_ctx *ctx, int space, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors /* paletted: 1..256 */,
+                         int opaque /* 1, 0, or -1 */, const uint8_t *palette, size_t *nbytes);
 
 /* ---- PNG sources: loadImage's image.Decode + toNRGBA for a .png (io.go:65-88 -> convert.go:12-64) --------------------- */
 /* The zlib stream src[0 .. n) (RFC 1950: CM 8, CINFO <= 7, FCHECK; a preset dictionary is refused) of stored, fixed and dynamic
@@ -1121,10 +1178,9 @@ int fennec_CompressBatchJPEGOpts(int device, int workers, int n, const uint8_t *
  * fennec_CompressFileJPEG stages them (opts->file; its auto_format and target_ssim are ignored), then ONE
  * fnx_jpeg_target_size on the resident image with the library's SSIM window: cand, *winner, out / cap / *nbytes and cancel are
  * that call's.  `strategies` with all four bits is hitTargetSize under Format: JPEG (targetsize.go:26-75 with wantJPEG).
- * Format: Auto runs quantizeStrategy between strategies 1 and 3, and its loop stays the caller's: such a caller passes
- * strategy subsets (FNX_TS_QUALITY, then its own quantizeStrategy -- fnx_quantize is one iteration of it up to the png.Encode
- * size test -- then the rest) and applies betterFit over all candidates
- * itself, as go/fennec_hip.go's hitTargetSize does over decoded images.
+ * Format: Auto and Format: PNG (quantizeStrategy between strategies 1 and 3, the PNG scale search, the PNG fallback, betterFit
+ * over everything) are fennec_CompressFileHitTargetSize below; go/fennec_hip.go's hitTargetSize still composes them itself
+ * over decoded images.
  * dims[0..1] = OriginalDimensions (after orientation); dims[2..3] = the winner's final_w x final_h (fennec.go:153 overwrites
  * FinalDimensions with the size result's) -- the staged image's size when there is no winner.
  * FNX_OK: a winner, its file in out.  FNX_NOOP: no candidate (possible only without FNX_TS_FALLBACK).  FNX_ERR_UNSUPPORTED
@@ -1142,6 +1198,14 @@ typedef struct fennec_TargetOptions {
 int fennec_CompressFileTargetSize(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_TargetOptions *opts,
                                   const volatile int *cancel /* may be NULL */, fnx_size_candidate cand[4], int *winner,
                                   uint8_t *out, size_t cap, size_t *nbytes, int dims[4]);
+/* The same from a file's bytes under any Options.Format: fennec_CompressFileTargetSize's staging exactly (decode a JPEG or PNG
+ * source, orientation, smartResize: `file`), then ONE fnx_hit_target_size on the resident image with the library's SSIM window.
+ * cand, *winner, out / cap / *nbytes, cancel: that call's; dims as fennec_CompressFileTargetSize's.  FNX_ERR_INVALID before any
+ * device work: a NULL among ctx, data, file, cand, winner, nbytes, dims (out may be NULL with cap == 0), target_bytes <= 0, a
+ * format outside 0..2.  The pool over files (fennec_CompressBatchTargetSize) stays on the JPEG legs. */
+int fennec_CompressFileHitTargetSize(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_FileOptions *file, long long target_bytes,
+                                     int format, const volatile int *cancel /* may be NULL */, fnx_size_candidate cand[5], int *winner,
+                                     uint8_t *out, size_t cap, size_t *nbytes, int dims[4]);
 /* The pool of fennec_CompressBatchJPEGOpts over files in target-size mode: per item fennec_CompressFileTargetSize under
  * item_opts[i] when that is not NULL, else under *default_opts (batch.go:101-105); `cancel` is the pool's (checked before each
  * item) and each item's (checked where hitTargetSize checks ctx.Err()).  Per result: quality and ssim the winner's,

@@ -78,9 +78,9 @@ inline unsigned long long __shfl_xor(unsigned long long v, int off, int width)
     static_cast<uint32_t>(((static_cast<uint64_t>(hi) << 32) | static_cast<uint64_t>(lo)) >> (8 * ((sel) & 3)))
 
 // ---- the host side of launch_deflate: a context that only hands out memory
-struct fnx_ctx { void *slot[3]; void *stream; int deflate_level; };
+struct fnx_ctx { void *slot[4]; void *stream; int deflate_level; };
 namespace fnx {
-enum Slot { SLOT_DEFLATE_TOK, SLOT_DEFLATE_SLOTS, SLOT_DEFLATE_OUT };
+enum Slot { SLOT_DEFLATE_TOK, SLOT_DEFLATE_SLOTS, SLOT_DEFLATE_OUT, SLOT_DEFLATE_SIZE };
 inline int scratch(fnx_ctx *ctx, Slot s, size_t bytes, void **out)
 {
     free(ctx->slot[s]);

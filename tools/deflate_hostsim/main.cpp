@@ -11,6 +11,9 @@
 // Switches, anywhere on the line, that leave the other arguments' meaning as it is: --dense runs the dense level's kernels
 // (FNX_DEFLATE_LEVEL_DENSE; TOKENS then holds the lazy walk's tokens); --table FILE (with --dense, single stream) writes the
 // dense parse's per-position table beside them, per chunk its length and that many words L << 16 | D - 1 (0: no match).
+// --size-only (single stream, with or without --dense): IN [row [src_offset]] alone; runs launch_deflate_size -- the chunk kernels'
+// size-only forms and deflate_size_kernel -- and prints a line "chunk C BYTES" per chunk and "total BYTES"; the program checks that
+// neither the slot area nor the output slot was asked for.
 // Built by the Makefile beside it from a COPY of fennec_amd/csrc/deflate.hip against the stand-in common.hpp / devutil.hpp of
 // this directory; meant for sanitizer builds (-fsanitize=address,undefined) and for reading a stream without a GPU.
 #include "deflate_hip.inc"
@@ -37,6 +40,31 @@ static bool read_file(const char *name, std::vector<uint8_t> *out)
 
 static int g_level = FNX_DEFLATE_LEVEL_FAST;
 static const char *g_table = nullptr;
+
+static int size_only(int argc, char **argv)
+{
+    if (argc < 2) return fail("usage: deflate_hostsim --size-only IN [row [src_offset]]");
+    const int row = argc > 2 ? atoi(argv[2]) : 0;
+    const size_t soff = argc > 3 ? static_cast<size_t>(atoi(argv[3])) : 0;
+    if (soff > 15) return fail("offsets are 0 .. 15");
+    std::vector<uint8_t> in;
+    if (!read_file(argv[1], &in) || in.empty()) return fail("cannot read IN, or it is empty");
+    const size_t n = in.size();
+    uint8_t *src = static_cast<uint8_t *>(aligned_alloc(16, (soff + n + 15) & ~size_t(15)));
+    if (!src) return fail("out of memory");
+    memcpy(src + soff, in.data(), n);
+    fnx_ctx ctx{};
+    ctx.deflate_level = g_level;
+    const unsigned long long *size = nullptr;
+    if (fnx::launch_deflate_size(&ctx, src + soff, n, row, &size) != FNX_OK) return fail("launch_deflate_size failed");
+    if (ctx.slot[fnx::SLOT_DEFLATE_SLOTS] || ctx.slot[fnx::SLOT_DEFLATE_OUT]) return fail("the size-only form asked for the slot area or the output");
+    const uint32_t *meta = reinterpret_cast<const uint32_t *>(static_cast<const uint8_t *>(ctx.slot[fnx::SLOT_DEFLATE_SIZE]) + 16);
+    for (size_t c = 0; c < fnx::deflate_chunks(n); c++) printf("chunk %zu %u\n", c, meta[4 * c]);
+    printf("total %llu\n", *size);
+    for (void *p : ctx.slot) free(p);
+    free(src);
+    return 0;
+}
 
 static int batch(int argc, char **argv)
 {
@@ -89,14 +117,18 @@ static int batch(int argc, char **argv)
 int main(int argc, char **argv)
 {
     int kept = 1;
+    bool sizes = false;
     for (int i = 1; i < argc; i++) {
         if (strcmp(argv[i], "--dense") == 0) g_level = FNX_DEFLATE_LEVEL_DENSE;
+        else if (strcmp(argv[i], "--size-only") == 0) sizes = true;
         else if (strcmp(argv[i], "--table") == 0 && i + 1 < argc) g_table = argv[++i];
         else argv[kept++] = argv[i];
     }
     argc = kept;
     const bool dense = g_level == FNX_DEFLATE_LEVEL_DENSE;
     if (g_table && !dense) return fail("--table goes with --dense");
+    if (sizes && (g_table || (argc > 1 && strcmp(argv[1], "--batch") == 0))) return fail("--size-only goes with a single stream and no --table");
+    if (sizes) return size_only(argc, argv);
     if (argc > 1 && strcmp(argv[1], "--batch") == 0) return batch(argc, argv);
     if (argc < 3) return fail("usage: deflate_hostsim IN OUT [row [src_offset [dst_offset [TOKENS]]]]");
     const int row = argc > 3 ? atoi(argv[3]) : 0;
