@@ -30,6 +30,9 @@
 // host); a scan that ends early or holds a code outside its table is FNX_ERR_INVALID.  Restated from ITU T.81 and
 // reader.go / scan.go / huffman.go's published behaviour, not from Go's source: bit-exact against the CPU restatement
 // the tests hold (which libjpeg-turbo's files and hand-built ones exercise: DESIGN.md 5.13), parity with Go unpinned.
+// Steps 5 and 6 are also held by an arithmetic-level reference (tests/jpeg_backend_ref.py: numpy int64 with Go's int32 wrap made
+// explicit) where that arithmetic leaves its usual range: DC sums beyond 16 bits, DC x q beyond 2^31, quantisers up to 255 with
+// AC sizes up to 15, IDCT operations that wrap, restart intervals across MCU rows for every sampling.
 // The span decoder itself -- geometry, arguments, state word, dec_span, the sync tables -- is jpeg_dec_span.inc, which
 // tools/jpeg_dec_hostsim includes as well.
 #include <cstdio>

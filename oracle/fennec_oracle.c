@@ -1517,24 +1517,29 @@ ORC_API void orc_jpeg_fdct(int32_t *b)
 }
 
 /* idct.go: Chen-Wang, w_k = 2048*sqrt(2)*cos(k*pi/16) */
-#define JI_W1 2841
-#define JI_W2 2676
-#define JI_W3 2408
-#define JI_W5 1609
-#define JI_W6 1108
-#define JI_W7 565
-#define JI_R2 181
+#define JI_W1 2841u
+#define JI_W2 2676u
+#define JI_W3 2408u
+#define JI_W5 1609u
+#define JI_W6 1108u
+#define JI_W7 565u
+#define JI_R2 181u
+
+/* Go's int32 wraps on + - * << where C's overflows undefined: the passes run in uint32_t, which wraps by definition, and go
+ * through int32_t only for the arithmetic >> (tests/jpeg_backend_ref.py holds them to that on coefficients that do wrap). */
+#define JI_SHR(x, n) ((uint32_t)((int32_t)(x) >> (n)))
 
 ORC_API void orc_jpeg_idct(int32_t *src)
 {
     for (int y = 0; y < 8; y++) {                                      /* horizontal 1-D IDCT */
         int32_t *s = src + 8 * y;
         if (s[1] == 0 && s[2] == 0 && s[3] == 0 && s[4] == 0 && s[5] == 0 && s[6] == 0 && s[7] == 0) {
-            const int32_t dc = s[0] << 3;
+            const int32_t dc = (int32_t)((uint32_t)s[0] << 3);
             for (int i = 0; i < 8; i++) s[i] = dc;
             continue;
         }
-        int32_t x0 = (s[0] << 11) + 128, x1 = s[4] << 11, x2 = s[6], x3 = s[2], x4 = s[1], x5 = s[7], x6 = s[5], x7 = s[3], x8;
+        uint32_t x0 = ((uint32_t)s[0] << 11) + 128, x1 = (uint32_t)s[4] << 11, x2 = (uint32_t)s[6], x3 = (uint32_t)s[2], x4 = (uint32_t)s[1],
+                 x5 = (uint32_t)s[7], x6 = (uint32_t)s[5], x7 = (uint32_t)s[3], x8;
         x8 = JI_W7 * (x4 + x5);
         x4 = x8 + (JI_W1 - JI_W7) * x4;
         x5 = x8 - (JI_W1 + JI_W7) * x5;
@@ -1554,26 +1559,27 @@ ORC_API void orc_jpeg_idct(int32_t *src)
         x8 -= x3;
         x3 = x0 + x2;
         x0 -= x2;
-        x2 = (JI_R2 * (x4 + x5) + 128) >> 8;
-        x4 = (JI_R2 * (x4 - x5) + 128) >> 8;
-        s[0] = (x7 + x1) >> 8; s[1] = (x3 + x2) >> 8; s[2] = (x0 + x4) >> 8; s[3] = (x8 + x6) >> 8;
-        s[4] = (x8 - x6) >> 8; s[5] = (x0 - x4) >> 8; s[6] = (x3 - x2) >> 8; s[7] = (x7 - x1) >> 8;
+        x2 = JI_SHR(JI_R2 * (x4 + x5) + 128, 8);
+        x4 = JI_SHR(JI_R2 * (x4 - x5) + 128, 8);
+        s[0] = (int32_t)JI_SHR(x7 + x1, 8); s[1] = (int32_t)JI_SHR(x3 + x2, 8); s[2] = (int32_t)JI_SHR(x0 + x4, 8);
+        s[3] = (int32_t)JI_SHR(x8 + x6, 8); s[4] = (int32_t)JI_SHR(x8 - x6, 8); s[5] = (int32_t)JI_SHR(x0 - x4, 8);
+        s[6] = (int32_t)JI_SHR(x3 - x2, 8); s[7] = (int32_t)JI_SHR(x7 - x1, 8);
     }
     for (int x = 0; x < 8; x++) {                                      /* vertical 1-D IDCT (no all-zero shortcut) */
         int32_t *s = src + x;
-        int32_t y0 = (s[8 * 0] << 8) + 8192, y1 = s[8 * 4] << 8, y2 = s[8 * 6], y3 = s[8 * 2], y4 = s[8 * 1], y5 = s[8 * 7],
-                y6 = s[8 * 5], y7 = s[8 * 3], y8;
+        uint32_t y0 = ((uint32_t)s[8 * 0] << 8) + 8192, y1 = (uint32_t)s[8 * 4] << 8, y2 = (uint32_t)s[8 * 6], y3 = (uint32_t)s[8 * 2],
+                 y4 = (uint32_t)s[8 * 1], y5 = (uint32_t)s[8 * 7], y6 = (uint32_t)s[8 * 5], y7 = (uint32_t)s[8 * 3], y8;
         y8 = JI_W7 * (y4 + y5) + 4;
-        y4 = (y8 + (JI_W1 - JI_W7) * y4) >> 3;
-        y5 = (y8 - (JI_W1 + JI_W7) * y5) >> 3;
+        y4 = JI_SHR(y8 + (JI_W1 - JI_W7) * y4, 3);
+        y5 = JI_SHR(y8 - (JI_W1 + JI_W7) * y5, 3);
         y8 = JI_W3 * (y6 + y7) + 4;
-        y6 = (y8 - (JI_W3 - JI_W5) * y6) >> 3;
-        y7 = (y8 - (JI_W3 + JI_W5) * y7) >> 3;
+        y6 = JI_SHR(y8 - (JI_W3 - JI_W5) * y6, 3);
+        y7 = JI_SHR(y8 - (JI_W3 + JI_W5) * y7, 3);
         y8 = y0 + y1;
         y0 -= y1;
         y1 = JI_W6 * (y3 + y2) + 4;
-        y2 = (y1 - (JI_W2 + JI_W6) * y2) >> 3;
-        y3 = (y1 + (JI_W2 - JI_W6) * y3) >> 3;
+        y2 = JI_SHR(y1 - (JI_W2 + JI_W6) * y2, 3);
+        y3 = JI_SHR(y1 + (JI_W2 - JI_W6) * y3, 3);
         y1 = y4 + y6;
         y4 -= y6;
         y6 = y5 + y7;
@@ -1582,10 +1588,11 @@ ORC_API void orc_jpeg_idct(int32_t *src)
         y8 -= y3;
         y3 = y0 + y2;
         y0 -= y2;
-        y2 = (JI_R2 * (y4 + y5) + 128) >> 8;
-        y4 = (JI_R2 * (y4 - y5) + 128) >> 8;
-        s[8 * 0] = (y7 + y1) >> 14; s[8 * 1] = (y3 + y2) >> 14; s[8 * 2] = (y0 + y4) >> 14; s[8 * 3] = (y8 + y6) >> 14;
-        s[8 * 4] = (y8 - y6) >> 14; s[8 * 5] = (y0 - y4) >> 14; s[8 * 6] = (y3 - y2) >> 14; s[8 * 7] = (y7 - y1) >> 14;
+        y2 = JI_SHR(JI_R2 * (y4 + y5) + 128, 8);
+        y4 = JI_SHR(JI_R2 * (y4 - y5) + 128, 8);
+        s[8 * 0] = (int32_t)JI_SHR(y7 + y1, 14); s[8 * 1] = (int32_t)JI_SHR(y3 + y2, 14); s[8 * 2] = (int32_t)JI_SHR(y0 + y4, 14);
+        s[8 * 3] = (int32_t)JI_SHR(y8 + y6, 14); s[8 * 4] = (int32_t)JI_SHR(y8 - y6, 14); s[8 * 5] = (int32_t)JI_SHR(y0 - y4, 14);
+        s[8 * 6] = (int32_t)JI_SHR(y3 - y2, 14); s[8 * 7] = (int32_t)JI_SHR(y7 - y1, 14);
     }
 }
 
@@ -2210,8 +2217,8 @@ static int orc_jpeg_decode_scans(const uint8_t *data, long n, int *wd, int *ht, 
                                 zig++;
                                 const int s = jr_symbol(&br, &dt[0][td[i]]);
                                 if (br.bad || s > 16) { rc = -10; goto out; }
-                                pred[c] += jr_receive_extend(&br, s);
-                                b[0] = pred[c] * ((int32_t)1 << al);
+                                pred[c] = (int32_t)((uint32_t)pred[c] + (uint32_t)jr_receive_extend(&br, s));
+                                b[0] = (int32_t)((uint32_t)pred[c] << al);      /* int32 here too; beyond 16 bits it is refused below (-13) */
                             }
                             if (zig <= ze && eob_run > 0) eob_run--;
                             else {
@@ -2345,7 +2352,9 @@ ORC_API int orc_jpeg_decode_cmyk(const uint8_t *data, long n, int *wd, int *ht, 
 
 /* Decodes `data` into MCU-padded planes (yp: ys x 8*vmax*my rows ...).  Returns 1, with *wd, *ht, *ratio
  * (image.YCbCrSubsampleRatio: 0 4:4:4, 1 4:2:2, 2 4:2:0, 3 4:4:0; -1: one component, image.Gray) set, or a negative
- * error.  Call with yp == NULL to learn the dims first. */
+ * error.  Call with yp == NULL to learn the dims first.  coef (optional): the quantised coefficients as int16, which every AC
+ * value fits; of a DC that a chain of differences has carried beyond 16 bits it holds the low 16 -- the PIXELS are made from the
+ * int32 prediction.  (The scan-by-scan decoder above, which SOF1, SOF2 and four-component files take, refuses such a file.) */
 ORC_API int orc_jpeg_decode_planes(const uint8_t *data, long n, int *wd, int *ht, int *ratio, uint8_t *yp, uint8_t *cbp, uint8_t *crp,
                                    int16_t *coef)
 {
@@ -2451,8 +2460,8 @@ ORC_API int orc_jpeg_decode_planes(const uint8_t *data, long n, int *wd, int *ht
                             int16_t zz[64];
                             for (int k = 0; k < 64; k++) { b[k] = 0; zz[k] = 0; }
                             const int s = jr_symbol(&br, &dt[0][td[c]]);
-                            pred[c] += jr_receive_extend(&br, s);
-                            zz[0] = (int16_t)pred[c];
+                            pred[c] = (int32_t)((uint32_t)pred[c] + (uint32_t)jr_receive_extend(&br, s));
+                            zz[0] = (int16_t)pred[c];                             /* coef: the DC's low 16 bits */
                             for (int zig = 1; zig < 64;) {
                                 const int rs = jr_symbol(&br, &dt[1][ta[c]]);
                                 const int rr = rs >> 4, ss = rs & 15;
@@ -2469,7 +2478,10 @@ ORC_API int orc_jpeg_decode_planes(const uint8_t *data, long n, int *wd, int *ht
                             if (br.bad) return -10;
                             if (coef) for (int k = 0; k < 64; k++) coef[64 * blk + k] = zz[k];
                             const uint8_t *qq = q[comp_q[c]];
-                            for (int zig = 0; zig < 64; zig++) b[jpeg_unzig[zig]] = (int32_t)zz[zig] * (int32_t)qq[jpeg_unzig[zig]];
+                            for (int zig = 1; zig < 64; zig++) b[jpeg_unzig[zig]] = (int32_t)zz[zig] * (int32_t)qq[jpeg_unzig[zig]];
+                            /* the DC is the int32 prediction itself -- a chain of differences may leave 16 bits, and its product
+                             * with the quantiser 32 (scan.go keeps dc[] and the block in int32; unsigned here: Go's wrap, defined) */
+                            b[0] = (int32_t)((uint32_t)pred[c] * (uint32_t)qq[0]);
                             orc_jpeg_idct(b);
                             for (int k = 0; k < 64; k++) b[k] = b[k] < -128 ? 0 : (b[k] > 127 ? 255 : b[k] + 128);
                             if (c == 0) {

@@ -497,7 +497,9 @@ def jpeg_encode(img: np.ndarray, quality: int, with_coefficients: bool = False):
 
 def jpeg_decode_planes(data: bytes, with_coefficients: bool = False):
     """A baseline one- or three-component file (4:4:4, 4:2:2, 4:2:0, 4:4:0, 4:1:1, 4:1:0) -> (w, h, ratio, Y, Cb, Cr) MCU-padded planes as
-    reader.go would hold them [, coefficients]; ratio -1 and Cb = Cr = None: one component (image.Gray)."""
+    reader.go would hold them [, coefficients]; ratio -1 and Cb = Cr = None: one component (image.Gray).  The coefficients are
+    int16, zig-zag order, the DC absolute: of a DC that a chain of differences has carried beyond 16 bits, its low 16 bits (the
+    planes are made from the int32 value, as image/jpeg makes them)."""
     buf = np.frombuffer(data, dtype=np.uint8)
     L = lib()
     L.orc_jpeg_decode_planes.restype = C.c_int

@@ -74,7 +74,8 @@ class Crafted:
     start; nslots, dc_of_slot, ac_of_slot: the MCU's layout and the Table of every slot."""
 
 
-def encode(coef, w, h, dc_tabs, ac_tabs, sampling=None, qtabs=None, restart=0, comp_tabs=None, tile=1, extra=None, cut=None, header_tabs=None):
+def encode(coef, w, h, dc_tabs, ac_tabs, sampling=None, qtabs=None, restart=0, comp_tabs=None, tile=1, extra=None, cut=None, header_tabs=None,
+           max_ac_size=10):
     """coef: (blocks, 64) quantised coefficients, zig-zag order, blocks in scan order, DC absolute.  dc_tabs / ac_tabs: one or two
     Tables (ids 0, 1).  sampling: None for one component, or the luminance factors (hy, vy) of a three-component file.
     qtabs: one or two lists of 64 (zig-zag order, as a DQT segment holds them); default: all ones.  restart: MCUs per interval.
@@ -84,7 +85,8 @@ def encode(coef, w, h, dc_tabs, ac_tabs, sampling=None, qtabs=None, restart=0, c
     sym then maps the first period, coef and string are the whole scan's.
     extra: {interval: bytes} put behind that interval's padding, in front of its marker (a DAMAGED file: data the image does
     not have); cut: {interval: n} instead removes the last n bytes in front of the marker.
-    header_tabs: (dc_tabs, ac_tabs) the DHT segments state where they are NOT the tables the scan was coded with (damaged too)."""
+    header_tabs: (dc_tabs, ac_tabs) the DHT segments state where they are NOT the tables the scan was coded with (damaged too).
+    max_ac_size: the largest AC size coded, up to 15 (baseline files of 8-bit images stay within 10; image/jpeg reads them all)."""
     coef = np.asarray(coef)
     assert coef.ndim == 2 and coef.shape[1] == 64
     ncomp = 1 if sampling is None else 3
@@ -143,7 +145,7 @@ def encode(coef, w, h, dc_tabs, ac_tabs, sampling=None, qtabs=None, restart=0, c
                 z += 16
                 run -= 16
             n, bits = _amp(int(zz[k]))
-            assert 1 <= n <= 10, "an AC value beyond size 10"
+            assert 1 <= n <= max_ac_size <= 15, f"an AC value beyond size {max_ac_size}"
             s = (run << 4) | n
             code, ln = ac[s]
             syms.append((pos, ln, n, z, slot, s, tab_of_slot[slot][1], b))
