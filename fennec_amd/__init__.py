@@ -46,6 +46,7 @@ FNX_PNG_DECODE_CHUNK = 32                                     # fnx_png_decode_b
 FNX_PNG_COMPRESS_CHUNK = 32                                   # fnx_png_compress_batch: images per set of launches, at most
 FNX_DEFLATE_CHUNK, FNX_DEFLATE_SUB = 32768, 128               # deflate.hip: bytes per chunk (= per workgroup, per block) and per lane
 FNX_DEFLATE_LEVEL_FAST, FNX_DEFLATE_LEVEL_DENSE = 0, 1         # fnx_ctx_set_deflate_level
+FNX_JPEG_HUFFMAN_STANDARD, FNX_JPEG_HUFFMAN_OPTIMIZED = 0, 1   # fnx_ctx_set_jpeg_huffman
 FNX_DEFLATE_DENSE_DEPTH = 32                                   # the dense level: the most chain candidates a position tries
 PROF_MAIN, PROF_SSIM, PROF_RESIZE, PROF_FX, PROF_JPEG = 1, 2, 4, 8, 16
 
@@ -172,6 +173,10 @@ def load_library() -> C.CDLL:
         _sig(L, "fnx_ctx_set_ssim_mode", i, [ctx, i])
         _sig(L, "fnx_ctx_set_png_adam7", i, [ctx, i])
         _sig(L, "fnx_ctx_set_deflate_level", i, [ctx, i])
+        _sig(L, "fnx_ctx_set_jpeg_huffman", i, [ctx, i])
+        _sig(L, "fnx_jpeg_symbol_histogram", i, [ctx, i] + img + [i, i, i, C.POINTER(C.c_uint32)])
+        _sig(L, "fnx_jpeg_huffman_tables", i, [ctx, C.POINTER(C.c_uint32), _u8p, _u8p, C.POINTER(C.c_int), C.POINTER(C.c_uint32),
+                                               C.POINTER(C.c_int)])
         _sig(L, "fnx_png_adam7_passes", i, [i, i, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)])
         _sig(L, "fnx_malloc", i, [ctx, C.c_size_t, C.POINTER(C.c_void_p)])
         _sig(L, "fnx_free", i, [ctx, C.c_void_p])
@@ -480,6 +485,19 @@ class Context:
                 raise FennecError(f"set_deflate_level: 'fast' or 'dense', not {level!r}")
             level = names[level]
         self._chk(self._lib.fnx_ctx_set_deflate_level(self._h, int(level)), "fnx_ctx_set_deflate_level")
+
+    def set_jpeg_huffman(self, mode) -> None:
+        """fnx_ctx_set_jpeg_huffman: "standard" (FNX_JPEG_HUFFMAN_STANDARD, the default: the typical tables of T.81 Annex K.3.3,
+        the bytes the library always wrote) or "optimized" (FNX_JPEG_HUFFMAN_OPTIMIZED: the four tables built from the file's
+        own symbols, Annex K.2 -- the same coefficients in fewer bytes) for every JPEG file and file size of this ctx:
+        jpeg_encode, jpeg_encoded_size, jpeg_encode_scaled, jpeg_size_search, jpeg_compress, jpeg_target_size, hit_target_size,
+        jpeg_recompress, the file entries, jpeg_compress_batch, jpeg_recompress_batch.  The integer constants are accepted too."""
+        if isinstance(mode, str):
+            names = {"standard": FNX_JPEG_HUFFMAN_STANDARD, "optimized": FNX_JPEG_HUFFMAN_OPTIMIZED}
+            if mode not in names:
+                raise FennecError(f"set_jpeg_huffman: 'standard' or 'optimized', not {mode!r}")
+            mode = names[mode]
+        self._chk(self._lib.fnx_ctx_set_jpeg_huffman(self._h, int(mode)), "fnx_ctx_set_jpeg_huffman")
 
     def set_form(self, name: str, value=None) -> None:
         """fnx_ctx_set_form: which of several kernels that compute the same bytes this ctx takes (tests, A/B timing);
@@ -853,6 +871,32 @@ class Context:
             if rc == FNX_OK:
                 return buf[:n.value].tobytes()
         self._chk(rc, "fnx_jpeg_encode")
+
+    def jpeg_symbol_histogram(self, img, quality: int):
+        """fnx_jpeg_symbol_histogram -> (4, 256) uint32: how often the scan of jpeg_encode(img, quality) codes every symbol with
+        the luminance DC, luminance AC, chrominance DC and chrominance AC table (jpeg_symhist_kernel's counts)."""
+        s = _Img(img)
+        hist = np.zeros((4, 256), dtype=np.uint32)
+        with self._ordered(img):
+            self._chk(self._lib.fnx_jpeg_symbol_histogram(self._h, s.space, s.ptr, s.stride, s.w, s.h, int(quality),
+                                                          hist.ctypes.data_as(C.POINTER(C.c_uint32))), "fnx_jpeg_symbol_histogram")
+        return hist
+
+    def jpeg_huffman_tables(self, hist):
+        """fnx_jpeg_huffman_tables: jpeg_hufftab_kernel on four histograms ((4, 256), none all zero) -> a list of four dicts
+        {bits: 16 counts, vals: the values in code order, lut: (256,) uint32 length << 24 | code, standard: bool}."""
+        h = np.ascontiguousarray(hist, dtype=np.uint32)
+        if h.shape != (4, 256):
+            raise FennecError("jpeg_huffman_tables: hist must be (4, 256)")
+        bits = np.zeros((4, 16), dtype=np.uint8)
+        vals = np.zeros((4, 256), dtype=np.uint8)
+        lut = np.zeros((4, 256), dtype=np.uint32)
+        nvals = (C.c_int * 4)()
+        std = (C.c_int * 4)()
+        self._chk(self._lib.fnx_jpeg_huffman_tables(self._h, h.ctypes.data_as(C.POINTER(C.c_uint32)), bits.ctypes.data_as(_u8p),
+                                                    vals.ctypes.data_as(_u8p), nvals, lut.ctypes.data_as(C.POINTER(C.c_uint32)), std),
+                  "fnx_jpeg_huffman_tables")
+        return [dict(bits=bits[t].tolist(), vals=vals[t, :nvals[t]].tolist(), lut=lut[t].copy(), standard=bool(std[t])) for t in range(4)]
 
     def jpeg_encoded_size(self, img, quality: int) -> int:
         """len(jpeg.Encode(img, quality)) without fetching the bytes (fnx_jpeg_encode's size query)."""

@@ -100,6 +100,7 @@ enum Slot {
     SLOT_JPEG3,
     SLOT_JPEG_ENC, SLOT_JPEG_ENC2, SLOT_JPEG_LUT, SLOT_JPEG_ECS,   // jpeg.hip's entropy coder
     SLOT_JPEG_FF,    // jpeg_ffcount_strips_kernel's 0xff total, zero between queries
+    SLOT_JPEG_HUFF, SLOT_JPEG_HUFF_STD,   // jpeg.hip's optimised Huffman tables: the images' symbol histograms and look-up words; the standard tables for a table that takes them
     SLOT_FILE0, SLOT_FILE1, SLOT_FILE_SAMPLES,                     // host_api.cpp: fennec_CompressFileJPEG's images between its stages
     SLOT_JPEG_DEC, SLOT_JPEG_DEC_PLANES, SLOT_JPEG_DEC_IMG,        // jpeg_dec.hip: the decoder's work arrays, its planes, toNRGBARef's image
     SLOT_AN_HASH0, SLOT_AN_HASH1,   // analyze.hip: the colour-set tables of this call and the next (the launch that uses one zeroes the other)
@@ -228,6 +229,7 @@ struct fnx_ctx {
     // name the route the library took instead of inferring it from environment switches
     const char *route[8] = {"", "", "", "", "", "", "", ""};
     int png_adam7 = 0;           // fnx_ctx_set_png_adam7: 1 -- the PNG entries decode Adam7-interlaced files instead of refusing them
+    int jpeg_huffman = 0;        // fnx_ctx_set_jpeg_huffman: FNX_JPEG_HUFFMAN_STANDARD / _OPTIMIZED -- the tables of every JPEG file (and size) this ctx makes
     int deflate_level = 0;       // fnx_ctx_set_deflate_level: FNX_DEFLATE_LEVEL_FAST / _DENSE -- which chunk kernels launch_deflate and launch_deflate_batch run
     int ssim_mode = 0;           // fnx_ctx_set_ssim_mode: FNX_SSIM_EXACT (fp64 moments) / FNX_SSIM_FAST (fp32 moments for full-resolution planes)
     // fnx_ctx_set_form: the kernel forms this ctx was told to take ("" = the product's own choice)
@@ -647,8 +649,16 @@ int launch_jpeg_ycc_planes(fnx_ctx *ctx, const uint8_t *dy, int dys, const uint8
 // the planes of boxDownsample(src, dw, dh) straight from the w x h source, the downsampled image never written
 int launch_jpeg_box_ycc(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, int dw, int dh, uint8_t *yp, uint8_t *cbp,
                         uint8_t *crp);
-void jpeg_header(int w, int h, int quality, std::vector<uint8_t> &out);
-int jpeg_entropy_code(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *const planes[3], unsigned long long *totals);
+// a Huffman table's record as jpeg_hufftab_kernel leaves it (jpeg_hufftab.inc): [0] the number of values, [1] 1 when the table
+// is the class's standard one (a code size above 32), then the DHT body's bytes in memory order: 16 counts, 256 values
+constexpr int JPEG_HUFF_REC_WORDS = 70;
+// rec: nullptr for the typical tables, else the file's four records (fnx_ctx_set_jpeg_huffman: FNX_JPEG_HUFFMAN_OPTIMIZED)
+void jpeg_header(int w, int h, int quality, std::vector<uint8_t> &out, const uint32_t *rec = nullptr);
+int jpeg_entropy_code(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *const planes[3], unsigned long long *totals,
+                      uint32_t *rec = nullptr);
+// the kernels of the optimised tables on their own (fnx_jpeg_symbol_histogram, fnx_jpeg_huffman_tables): host results
+int jpeg_symbol_hist_of(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *const planes[3], uint32_t *hist);
+int jpeg_huffman_tables_of(fnx_ctx *ctx, const uint32_t *hist, uint32_t *lut, uint32_t *rec);
 size_t jpeg_ecs_capacity(unsigned long long total_bits);
 int jpeg_entropy_pack(fnx_ctx *ctx, int w, int h, unsigned long long total_bits, uint8_t *ecs, unsigned long long *totals);
 // behind jpeg_entropy_code on the same stream: totals[1] = the 0xff bytes of the string, counted from the blocks' strips (no packed string)
@@ -672,7 +682,7 @@ int launch_box_downsample_ycc_batch(fnx_ctx *ctx, int njobs, const uint8_t *plan
                                     int ystride, int cstride, int srcW, int srcH, uint8_t *dst, size_t dst_bytes, int dstW, int dstH);
 size_t jpeg_entropy_batch_bytes(int w, int h);
 int jpeg_entropy_code_batch(fnx_ctx *ctx, int n, int w, int h, const uint8_t *planes, const int *d_quality, const uint32_t *d_qtab,
-                            unsigned long long *tot);
+                            unsigned long long *tot, uint32_t *rec = nullptr);
 int jpeg_entropy_pack_batch(fnx_ctx *ctx, int n, int w, int h, const unsigned long long *tbits, uint8_t **ecs, size_t *ecs_off,
                             unsigned long long *fftot);
 

@@ -594,15 +594,21 @@ struct CodeArgs {
     int seg;                  // blocks per image: the batched form's images lie back to back (one image: seg = nblk)
 };
 
+// PER_IMAGE: a.lut holds four tables for every image ([nblk / seg][4][256], jpeg_hufftab_kernel's), and a workgroup's blocks
+// may belong to two images: each lane reads its own image's tables where they are
+template <bool PER_IMAGE>
 __global__ __launch_bounds__(256) void jpeg_code_kernel(CodeArgs a)
 {
-    __shared__ uint32_t s_lut[4 * 256];
-    for (int i = threadIdx.x; i < 4 * 256; i += 256) s_lut[i] = a.lut[i];
-    __syncthreads();
+    __shared__ uint32_t s_lut[PER_IMAGE ? 1 : 4 * 256];
+    if (!PER_IMAGE) {
+        for (int i = threadIdx.x; i < 4 * 256; i += 256) s_lut[i] = a.lut[i];
+        __syncthreads();
+    }
     const int blk = blockIdx.x * 256 + threadIdx.x;
     if (blk >= a.nblk) return;
     const int j = blk % 6;
-    const uint32_t *dc_lut = s_lut + (j < 4 ? 0 : 512), *ac_lut = dc_lut + 256;
+    const uint32_t *luts = PER_IMAGE ? a.lut + static_cast<size_t>(blk / a.seg) * (4 * 256) : s_lut;
+    const uint32_t *dc_lut = luts + (j < 4 ? 0 : 512), *ac_lut = dc_lut + 256;
     // the component's previous block in scan order
     const int prev = j == 0 ? blk - 3 : (j < 4 ? blk - 1 : blk - 6);
     const int first = blk - blk % a.seg;                   // the image's first block (seg is a multiple of 6)
@@ -649,6 +655,105 @@ __global__ __launch_bounds__(256) void jpeg_code_kernel(CodeArgs a)
     }
     if (nacc > 0) a.strip[static_cast<size_t>(nw) * a.nblk + blk] = static_cast<uint32_t>(acc << (32 - nacc));   // left-aligned, zero tail
     a.nbits[blk] = static_cast<uint32_t>(32 * nw + nacc);
+}
+
+// ------------------------------------------------------------------------------------
+// Optimised Huffman tables (fnx_ctx_set_jpeg_huffman(ctx, FNX_JPEG_HUFFMAN_OPTIMIZED)): the four tables of
+// a file built from the symbols its own scan codes (T.81 Annex K.2), between the coefficient kernel and the code kernel,
+// without the host:
+//   jpeg_symhist_kernel   lane = block: the symbols jpeg_code_kernel will emit for it, counted into the workgroup's LDS
+//                         histogram [4][256] (luminance DC, luminance AC, chrominance DC, chrominance AC), the non-zero bins
+//                         added to the image's histogram (zeroed on the stream before)
+//   jpeg_hufftab_kernel   one wave per (image, table): jpeg_hufftab.inc -- the code look-up words jpeg_code_kernel reads, and
+//                         the table's record (counts and values of its DHT body, "standard table taken") for the host's header
+// ------------------------------------------------------------------------------------
+struct SymHistArgs {
+    const int16_t *coef;      // jpeg_coef_kernel's
+    uint32_t *hist;           // [images][4][256], zero
+    int nblk;                 // blocks of all images
+    int seg;                  // blocks per image (a multiple of 6)
+    int gx;                   // workgroups per image: image = blockIdx.x / gx
+};
+
+__global__ __launch_bounds__(256) void jpeg_symhist_kernel(SymHistArgs a)
+{
+    __shared__ uint32_t s_h[4 * 256];
+    for (int i = threadIdx.x; i < 4 * 256; i += 256) s_h[i] = 0;
+    __syncthreads();
+    const int img = blockIdx.x / a.gx;
+    const int i = (blockIdx.x - img * a.gx) * 256 + threadIdx.x;        // the block inside its image
+    if (i < a.seg) {
+        const int first = img * a.seg, blk = first + i;
+        const int j = i % 6;
+        uint32_t *dc_h = s_h + (j < 4 ? 0 : 512), *ac_h = dc_h + 256;
+        const int prev = j == 0 ? blk - 3 : (j < 4 ? blk - 1 : blk - 6);  // as jpeg_code_kernel
+        const int32_t dc = a.coef[blk];
+        const int32_t pd = prev >= first ? static_cast<int32_t>(a.coef[prev]) : 0;
+        const int32_t d = dc - pd;
+        atomicAdd(&dc_h[(32 - __clz(d < 0 ? -d : d)) & 255], 1u);
+        int run = 0;
+        for (int zig = 1; zig < 64; zig++) {
+            const int32_t ac = a.coef[static_cast<size_t>(zig) * a.nblk + blk];
+            if (ac == 0) {
+                run++;
+            } else {
+                if (run > 15) {
+                    atomicAdd(&ac_h[0xf0], static_cast<uint32_t>(run >> 4));
+                    run &= 15;
+                }
+                atomicAdd(&ac_h[((run << 4) | (32 - __clz(ac < 0 ? -ac : ac))) & 255], 1u);
+                run = 0;
+            }
+        }
+        if (run > 0) atomicAdd(&ac_h[0x00], 1u);
+    }
+    __syncthreads();
+    uint32_t *out = a.hist + static_cast<size_t>(img) * (4 * 256);
+    for (int k = threadIdx.x; k < 4 * 256; k += 256) {
+        const uint32_t v = s_h[k];
+        if (v) atomicAdd(&out[k], v);
+    }
+}
+
+// the wave's two smallest keys out of every lane's two (k1 <= k2): after the butterfly all 64 lanes hold them.  The lane sets
+// that meet in a step are disjoint, so no key is counted twice; ~0 ("none") loses every comparison
+__device__ __forceinline__ void ht_wave_min2(unsigned long long &k1, unsigned long long &k2)
+{
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned long long o1 = __shfl_xor(k1, off, 64), o2 = __shfl_xor(k2, off, 64);
+        const unsigned long long lo = k1 < o1 ? k1 : o1, hi = k1 < o1 ? o1 : k1;
+        const unsigned long long m2 = k2 < o2 ? k2 : o2;
+        k1 = lo;
+        k2 = hi < m2 ? hi : m2;
+    }
+}
+
+#define HT_FN __device__ __forceinline__
+#define HT_UNROLL _Pragma("unroll")
+#define HT_PHASE(call) { call; } __syncthreads();
+#define HT_MIN2 ht_wave_min2(ln.k1, ln.k2)
+#define HT_LANE0(field) ln.field
+#define HT_ATOMIC_ADD(p, v) atomicAdd(p, v)
+#define HT_ATOMIC_OR(p, v) atomicOr(p, v)
+#define HT_RUN_PARAMS , HtLane &ln, int lane
+#include "jpeg_hufftab.inc"
+
+struct HuffTabArgs {
+    const uint32_t *hist;     // [units][256]: unit = image * 4 + table
+    uint32_t *lut;            // [units][256]
+    uint32_t *rec;            // [units][HT_REC_WORDS] (host-mapped)
+    const uint32_t *std_lut;  // [4][256] huffman_luts()
+    const uint32_t *std_rec;  // [4][HT_REC_WORDS] huffman_std_recs()
+};
+
+__global__ __launch_bounds__(64) void jpeg_hufftab_kernel(HuffTabArgs a)
+{
+    __shared__ HtShared s;
+    HtLane ln;
+    const int u = blockIdx.x, t = u & 3;
+    ht_run(a.hist + static_cast<size_t>(u) * 256, a.lut + static_cast<size_t>(u) * 256, a.rec + static_cast<size_t>(u) * HT_REC_WORDS,
+           a.std_lut + t * 256, a.std_rec + t * HT_REC_WORDS, s, ln, static_cast<int>(threadIdx.x));
 }
 
 // ---- exclusive prefix sum of n uint32 into uint64: 2048 per workgroup, then the workgroups' totals ----
@@ -783,32 +888,7 @@ __global__ __launch_bounds__(256) void jpeg_stuff_kernel(StuffArgs a)
     }
 }
 
-// ITU T.81 Annex K.3.3, the order of writer.go's theHuffmanSpec: luminance DC, luminance AC, chrominance DC, chrominance AC
-static const uint8_t HCOUNT[4][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0},
-                                      {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125},
-                                      {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0},
-                                      {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119}};
-static const uint8_t HDC[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
-static const uint8_t HAC_LUM[162] = {
-    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
-    0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
-    0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
-    0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
-    0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
-    0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
-    0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
-    0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
-static const uint8_t HAC_CHR[162] = {
-    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
-    0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
-    0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
-    0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74,
-    0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
-    0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
-    0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
-    0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
-static const uint8_t *HVAL[4] = {HDC, HAC_LUM, HDC, HAC_CHR};
-static const int HNVAL[4] = {12, 162, 12, 162};
+#include "jpeg_huffman_std.inc"
 
 static void quant_tables(int quality, uint32_t (&q)[2][64], uint32_t (&magic)[2][64])
 {
@@ -824,8 +904,10 @@ static void quant_tables(int quality, uint32_t (&q)[2][64], uint32_t (&magic)[2]
         }
 }
 
-// the bytes jpeg.Encode writes before the entropy-coded segment
-void jpeg_header(int w, int h, int quality, std::vector<uint8_t> &o)
+// the bytes jpeg.Encode writes before the entropy-coded segment.  rec: nullptr -- the four typical tables; else the four
+// records jpeg_hufftab_kernel left (JPEG_HUFF_REC_WORDS each): still ONE DHT segment, the tables in the same order, each with
+// the counts and the values of its record, 2 + sum(17 + values) bytes
+void jpeg_header(int w, int h, int quality, std::vector<uint8_t> &o, const uint32_t *rec)
 {
     uint32_t q[2][64], magic[2][64];
     quant_tables(quality, q, magic);
@@ -843,12 +925,18 @@ void jpeg_header(int w, int h, int quality, std::vector<uint8_t> &o)
     o.push_back(3);
     const uint8_t comp[9] = {1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1};
     o.insert(o.end(), comp, comp + 9);
+    auto nvals = [&](int t) { return !rec ? HNVAL[t] : (rec[t * HT_REC_WORDS] > 256u ? 256 : static_cast<int>(rec[t * HT_REC_WORDS])); };
     int dht = 2;
-    for (int t = 0; t < 4; t++) dht += 1 + 16 + HNVAL[t];
+    for (int t = 0; t < 4; t++) dht += 1 + 16 + nvals(t);
     marker(0xc4, dht);
     const uint8_t tcth[4] = {0x00, 0x10, 0x01, 0x11};
     for (int t = 0; t < 4; t++) {
         o.push_back(tcth[t]);
+        if (rec) {
+            const uint8_t *body = reinterpret_cast<const uint8_t *>(rec + t * HT_REC_WORDS + 2);    // 16 counts, the values
+            o.insert(o.end(), body, body + 16 + nvals(t));
+            continue;
+        }
         o.insert(o.end(), HCOUNT[t], HCOUNT[t] + 16);
         o.insert(o.end(), HVAL[t], HVAL[t] + HNVAL[t]);
     }
@@ -876,7 +964,114 @@ static void huffman_luts(uint32_t *luts)        // [4][256]: length << 24 | code
 //   jpeg_entropy_code   coefficients, per-block codes, their prefix sum; totals[0] (device) = bits of the string
 //   jpeg_entropy_pack   (total_bits known on the host) the string packed, stuffed into `ecs`; totals[1] = 0xff bytes in it
 // planes: jpeg_ycc_kernel's output.
-int jpeg_entropy_code(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *const planes[3], unsigned long long *totals)
+static_assert(JPEG_HUFF_REC_WORDS == HT_REC_WORDS, "common.hpp's record size is jpeg_hufftab.inc's");
+
+// the four standard tables as jpeg_hufftab_kernel's records (what it hands out for a table that took the standard one)
+static void huffman_std_recs(uint32_t *recs)
+{
+    for (int t = 0; t < 4; t++) {
+        uint32_t *rec = recs + t * HT_REC_WORDS;
+        std::memset(rec, 0, sizeof(uint32_t) * HT_REC_WORDS);
+        rec[0] = static_cast<uint32_t>(HNVAL[t]);
+        uint8_t *body = reinterpret_cast<uint8_t *>(rec + 2);
+        std::memcpy(body, HCOUNT[t], 16);
+        std::memcpy(body + 16, HVAL[t], static_cast<size_t>(HNVAL[t]));
+    }
+}
+
+// the standard tables on the device, for the tables that take them: [0] huffman_luts(), [1] huffman_std_recs()
+static int upload_huffman_std(fnx_ctx *ctx, void **dp)
+{
+    uint32_t std_lut[4 * 256], std_rec[4 * HT_REC_WORDS];
+    huffman_luts(std_lut);
+    huffman_std_recs(std_rec);
+    const void *hosts[2] = {std_lut, std_rec};
+    const size_t sizes[2] = {sizeof(std_lut), sizeof(std_rec)};
+    return upload_tables(ctx, SLOT_JPEG_HUFF_STD, hosts, sizes, 2, dp);
+}
+
+// jpeg_symhist_kernel over the blocks of `units / 4` images in `coef` (seg blocks each), then jpeg_hufftab_kernel: the tables'
+// look-up words -> *d_lut ([units][256], device), their records -> rec (host-mapped, [units][JPEG_HUFF_REC_WORDS])
+static int launch_jpeg_hufftabs(fnx_ctx *ctx, const int16_t *coef, int nimg, int seg, uint32_t *rec, const uint32_t **d_lut)
+{
+    const size_t words = static_cast<size_t>(nimg) * 4 * 256;
+    void *hs = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_JPEG_HUFF, 2 * sizeof(uint32_t) * words, &hs));
+    uint32_t *hist = static_cast<uint32_t *>(hs), *lut = hist + words;
+    void *dp[2];
+    FNX_TRY(upload_huffman_std(ctx, dp));
+    FNX_HIP(hipMemsetAsync(hist, 0, sizeof(uint32_t) * words, ctx->stream));
+    SymHistArgs sa{coef, hist, nimg * seg, seg, (seg + 255) / 256};
+    hipLaunchKernelGGL(jpeg_symhist_kernel, dim3(sa.gx * nimg), dim3(256), 0, ctx->stream, sa);
+    HuffTabArgs ha{hist, lut, rec, static_cast<const uint32_t *>(dp[0]), static_cast<const uint32_t *>(dp[1])};
+    hipLaunchKernelGGL(jpeg_hufftab_kernel, dim3(4 * nimg), dim3(64), 0, ctx->stream, ha);
+    FNX_HIP(hipGetLastError());
+    *d_lut = lut;
+    return FNX_OK;
+}
+
+// fnx_jpeg_huffman_tables: jpeg_hufftab_kernel on the caller's four histograms (host) -> lut [4][256], rec [4][JPEG_HUFF_REC_WORDS] (host)
+int jpeg_huffman_tables_of(fnx_ctx *ctx, const uint32_t *hist, uint32_t *lut, uint32_t *rec)
+{
+    void *hs = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_JPEG_HUFF, 2 * sizeof(uint32_t) * 4 * 256, &hs));
+    uint32_t *d_hist = static_cast<uint32_t *>(hs), *d_lut = d_hist + 4 * 256;
+    void *dp[2];
+    FNX_TRY(upload_huffman_std(ctx, dp));
+    void *pin = nullptr;
+    FNX_TRY(pinned_alloc(ctx, sizeof(uint32_t) * 4 * (256 + HT_REC_WORDS), &pin));
+    uint32_t *p_hist = static_cast<uint32_t *>(pin), *p_rec = p_hist + 4 * 256;
+    std::memcpy(p_hist, hist, sizeof(uint32_t) * 4 * 256);
+    std::memset(p_rec, 0xff, sizeof(uint32_t) * 4 * HT_REC_WORDS);
+    FNX_HIP(hipMemcpyAsync(d_hist, p_hist, sizeof(uint32_t) * 4 * 256, hipMemcpyHostToDevice, ctx->stream));
+    HuffTabArgs ha{d_hist, d_lut, p_rec, static_cast<const uint32_t *>(dp[0]), static_cast<const uint32_t *>(dp[1])};
+    hipLaunchKernelGGL(jpeg_hufftab_kernel, dim3(4), dim3(64), 0, ctx->stream, ha);
+    FNX_HIP(hipGetLastError());
+    note_route(ctx, FNX_PROF_JPEG, "jpeg_hufftab_kernel");
+    FNX_TRY(fetch_bytes(ctx, d_lut, lut, sizeof(uint32_t) * 4 * 256));
+    std::memcpy(rec, p_rec, sizeof(uint32_t) * 4 * HT_REC_WORDS);
+    return FNX_OK;
+}
+
+static void coef_args(int w, int h, int quality, const uint8_t *const planes[3], int16_t *coef, CoefArgs *ca)
+{
+    int ys, yh, cs, chh;
+    jpeg_plane_dims(w, h, &ys, &yh, &cs, &chh);
+    quant_tables(quality, ca->q, ca->magic);
+    for (int pl = 0; pl < 3; pl++) {
+        ca->in[pl] = planes[pl];
+        ca->stride[pl] = pl ? cs : ys;
+        ca->nbx[pl] = (pl ? cs : ys) / 8;
+        ca->nblocks[pl] = ca->nbx[pl] * ((pl ? chh : yh) / 8);
+    }
+    ca->coef = coef; ca->mx = ys / 16; ca->nblk = (ys / 16) * (yh / 16) * 6;
+}
+
+// fnx_jpeg_symbol_histogram: what jpeg_symhist_kernel counts for the image of `planes` at `quality` -> hist [4][256] (host)
+int jpeg_symbol_hist_of(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *const planes[3], uint32_t *hist)
+{
+    int ys, yh, cs, chh;
+    jpeg_plane_dims(w, h, &ys, &yh, &cs, &chh);
+    const int nblk = (ys / 16) * (yh / 16) * 6;
+    void *sc = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_JPEG_ENC, sizeof(int16_t) * 64 * static_cast<size_t>(nblk) + 256, &sc));
+    void *hs = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_JPEG_HUFF, 2 * sizeof(uint32_t) * 4 * 256, &hs));
+    CoefArgs ca{};
+    coef_args(w, h, quality, planes, static_cast<int16_t *>(sc), &ca);
+    hipLaunchKernelGGL(jpeg_coef_kernel, dim3((ca.nblocks[0] + 255) / 256, 3), dim3(256), 0, ctx->stream, ca);
+    FNX_HIP(hipMemsetAsync(hs, 0, sizeof(uint32_t) * 4 * 256, ctx->stream));
+    SymHistArgs sa{ca.coef, static_cast<uint32_t *>(hs), nblk, nblk, (nblk + 255) / 256};
+    hipLaunchKernelGGL(jpeg_symhist_kernel, dim3(sa.gx), dim3(256), 0, ctx->stream, sa);
+    FNX_HIP(hipGetLastError());
+    note_route(ctx, FNX_PROF_JPEG, "jpeg_symhist_kernel");
+    return fetch_bytes(ctx, hs, hist, sizeof(uint32_t) * 4 * 256);
+}
+
+// rec: nullptr -- the typical tables (what the library always wrote); else host-mapped room for four records
+// (JPEG_HUFF_REC_WORDS each): the tables are built from this image's symbols (launch_jpeg_hufftabs) and the records are there
+// when totals[0] is
+int jpeg_entropy_code(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *const planes[3], unsigned long long *totals, uint32_t *rec)
 {
     int ys, yh, cs, chh;
     jpeg_plane_dims(w, h, &ys, &yh, &cs, &chh);
@@ -893,26 +1088,23 @@ int jpeg_entropy_code(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *co
     uint32_t *nbits = reinterpret_cast<uint32_t *>(p); p += b_nbits;
     unsigned long long *pos = reinterpret_cast<unsigned long long *>(p); p += b_pos;
     unsigned long long *wgt = reinterpret_cast<unsigned long long *>(p);
-    uint32_t hlut[4 * 256];
-    huffman_luts(hlut);
     void *dlut = nullptr;
-    FNX_TRY(upload_table(ctx, SLOT_JPEG_LUT, hlut, sizeof(hlut), &dlut));
+    if (!rec) {
+        uint32_t hlut[4 * 256];
+        huffman_luts(hlut);
+        FNX_TRY(upload_table(ctx, SLOT_JPEG_LUT, hlut, sizeof(hlut), &dlut));
+    }
 
     CoefArgs ca{};
-    quant_tables(quality, ca.q, ca.magic);
-    for (int pl = 0; pl < 3; pl++) {
-        ca.in[pl] = planes[pl];
-        ca.stride[pl] = pl ? cs : ys;
-        ca.nbx[pl] = (pl ? cs : ys) / 8;
-        ca.nblocks[pl] = ca.nbx[pl] * ((pl ? chh : yh) / 8);
-    }
-    ca.coef = coef; ca.mx = mx; ca.nblk = nblk;
+    coef_args(w, h, quality, planes, coef, &ca);
     FNX_TRY(prof_begin(ctx, FNX_PROF_JPEG));
     hipLaunchKernelGGL(jpeg_coef_kernel, dim3((ca.nblocks[0] + 255) / 256, 3), dim3(256), 0, ctx->stream, ca);
     FNX_HIP(hipGetLastError());
     FNX_TRY(prof_end(ctx));
-    CodeArgs co{coef, static_cast<const uint32_t *>(dlut), strip, nbits, nblk, nblk};
-    hipLaunchKernelGGL(jpeg_code_kernel, dim3((nblk + 255) / 256), dim3(256), 0, ctx->stream, co);
+    const uint32_t *lut = static_cast<const uint32_t *>(dlut);
+    if (rec) FNX_TRY(launch_jpeg_hufftabs(ctx, coef, 1, nblk, rec, &lut));
+    CodeArgs co{coef, lut, strip, nbits, nblk, nblk};
+    hipLaunchKernelGGL(jpeg_code_kernel<false>, dim3((nblk + 255) / 256), dim3(256), 0, ctx->stream, co);
     FNX_HIP(hipGetLastError());
     return launch_scan(ctx, nbits, pos, wgt, nblk, totals);
 }
@@ -1224,8 +1416,9 @@ size_t jpeg_entropy_batch_bytes(int w, int h)
 }
 
 // phase 1 of n images: coefficients at quality[i] (device [n]), codes, positions; tot[i] (host-mapped, n) = bits of image i
+// rec: nullptr, or host-mapped room for every image's four records ([n][4][JPEG_HUFF_REC_WORDS]): tables per image
 int jpeg_entropy_code_batch(fnx_ctx *ctx, int n, int w, int h, const uint8_t *planes, const int *d_quality, const uint32_t *d_qtab,
-                            unsigned long long *tot)
+                            unsigned long long *tot, uint32_t *rec)
 {
     int seg;
     size_t sz[5];
@@ -1244,10 +1437,12 @@ int jpeg_entropy_code_batch(fnx_ctx *ctx, int n, int w, int h, const uint8_t *pl
     uint32_t *nbits = reinterpret_cast<uint32_t *>(p); p += sz[2];
     unsigned long long *pos = reinterpret_cast<unsigned long long *>(p); p += sz[3];
     unsigned long long *wgt = reinterpret_cast<unsigned long long *>(p);
-    uint32_t hlut[4 * 256];
-    huffman_luts(hlut);
     void *dlut = nullptr;
-    FNX_TRY(upload_table(ctx, SLOT_JPEG_LUT, hlut, sizeof(hlut), &dlut));
+    if (!rec) {
+        uint32_t hlut[4 * 256];
+        huffman_luts(hlut);
+        FNX_TRY(upload_table(ctx, SLOT_JPEG_LUT, hlut, sizeof(hlut), &dlut));
+    }
 
     CoefBatchArgs cb{};
     int ys, yh, cs, chh;
@@ -1267,8 +1462,11 @@ int jpeg_entropy_code_batch(fnx_ctx *ctx, int n, int w, int h, const uint8_t *pl
     hipLaunchKernelGGL(jpeg_coef_batch_kernel, dim3(cb.gx * n, 3), dim3(256), 0, ctx->stream, cb);
     FNX_HIP(hipGetLastError());
     FNX_TRY(prof_end(ctx));
-    CodeArgs co{coef, static_cast<const uint32_t *>(dlut), strip, nbits, nblk, seg};
-    hipLaunchKernelGGL(jpeg_code_kernel, dim3((nblk + 255) / 256), dim3(256), 0, ctx->stream, co);
+    const uint32_t *lut = static_cast<const uint32_t *>(dlut);
+    if (rec) FNX_TRY(launch_jpeg_hufftabs(ctx, coef, n, seg, rec, &lut));
+    CodeArgs co{coef, lut, strip, nbits, nblk, seg};
+    if (rec) hipLaunchKernelGGL(jpeg_code_kernel<true>, dim3((nblk + 255) / 256), dim3(256), 0, ctx->stream, co);
+    else hipLaunchKernelGGL(jpeg_code_kernel<false>, dim3((nblk + 255) / 256), dim3(256), 0, ctx->stream, co);
     FNX_HIP(hipGetLastError());
     FNX_TRY(launch_scan(ctx, nbits, pos, wgt, nblk, nullptr));
     hipLaunchKernelGGL(seg_bits_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, pos, nbits, seg, n, tot);

@@ -165,20 +165,23 @@ bool jpeg_size_one_wait(const fnx_ctx *ctx)
 // the file of `orig`'s image at `quality` into host memory (see fnx_jpeg_encode)
 int jpeg_file_from_planes(fnx_ctx *ctx, const JpegPlanes &orig, int w, int h, int quality, uint8_t *out, size_t cap, size_t *nbytes)
 {
-    // two u64 the kernels write and the host reads: bits of the scan's string, 0xff bytes in it
+    // two u64 the kernels write and the host reads: bits of the scan's string, 0xff bytes in it; under
+    // FNX_JPEG_HUFFMAN_OPTIMIZED the four tables' records (their DHT bodies) come back behind them, in the same wait
+    const bool opt = ctx->jpeg_huffman == FNX_JPEG_HUFFMAN_OPTIMIZED;
     double *slot;
-    FNX_TRY(result_slot(ctx, 2, &slot));
+    FNX_TRY(result_slot(ctx, opt ? 2 + (4 * JPEG_HUFF_REC_WORDS + 1) / 2 : 2, &slot));
     unsigned long long *totals = reinterpret_cast<unsigned long long *>(slot);
     totals[0] = totals[1] = ~0ull;
+    uint32_t *rec = opt ? reinterpret_cast<uint32_t *>(totals + 2) : nullptr;
     const uint8_t *planes[3] = {orig.p[0], orig.p[1], orig.p[2]};
-    FNX_TRY(jpeg_entropy_code(ctx, w, h, quality, planes, totals));
+    FNX_TRY(jpeg_entropy_code(ctx, w, h, quality, planes, totals, rec));
     if (out == nullptr && cap == 0 && jpeg_size_one_wait(ctx)) {
         // a size query never needs the packed string: the stuffed bytes are counted from the blocks' strips behind the scan,
         // and both totals come back in ONE wait (jpeg.hip: jpeg_ffcount_strips_kernel)
         FNX_TRY(jpeg_entropy_ffcount(ctx, w, h, totals));
         FNX_HIP(hipStreamSynchronize(ctx->stream));
         std::vector<uint8_t> hdr;
-        jpeg_header(w, h, quality, hdr);
+        jpeg_header(w, h, quality, hdr, rec);
         *nbytes = jpeg_file_frame(hdr, jpeg_ecs_bytes(totals[0], totals[1]), nullptr, 0);
         return FNX_OK;
     }
@@ -190,7 +193,7 @@ int jpeg_file_from_planes(fnx_ctx *ctx, const JpegPlanes &orig, int w, int h, in
     FNX_HIP(hipStreamSynchronize(ctx->stream));
     const size_t ecs_bytes = jpeg_ecs_bytes(tbits, totals[1]);
     std::vector<uint8_t> hdr;
-    jpeg_header(w, h, quality, hdr);
+    jpeg_header(w, h, quality, hdr, rec);
     const size_t total = jpeg_file_frame(hdr, ecs_bytes, out, cap);
     *nbytes = total;
     if (out == nullptr && cap == 0) return FNX_OK;       // size query: targetsize.go's searches need len(encoded) only
@@ -276,6 +279,54 @@ int fnx_jpeg_encode(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, in
     FNX_TRY(stage_in(ctx, space, src, sstride, w, h, SLOT_IN_A, &s));
     FNX_TRY(jpeg_ycc_planes(ctx, SLOT_JPEG0, s.p, s.stride, w, h, &orig));
     return jpeg_file_from_planes(ctx, orig, w, h, quality, out, cap, nbytes);
+}
+
+int fnx_jpeg_symbol_histogram(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int quality, uint32_t hist[4][256])
+{
+    if (!ctx || !src || !hist) { set_error("fnx_jpeg_symbol_histogram: null argument"); return FNX_ERR_INVALID; }
+    FNX_ENTER(ctx);
+    FNX_TRY(check_space(space));
+    FNX_REQUIRE(jpeg_dims(w, h), "symbol histogram arguments (JPEG dims are 16-bit)");
+    FNX_TRY(check_img(src, sstride, w, h, "src"));
+    DevImg s;
+    JpegPlanes orig;
+    FNX_TRY(stage_in(ctx, space, src, sstride, w, h, SLOT_IN_A, &s));
+    FNX_TRY(jpeg_ycc_planes(ctx, SLOT_JPEG0, s.p, s.stride, w, h, &orig));
+    const uint8_t *planes[3] = {orig.p[0], orig.p[1], orig.p[2]};
+    return jpeg_symbol_hist_of(ctx, w, h, quality, planes, &hist[0][0]);
+}
+
+int fnx_jpeg_huffman_tables(fnx_ctx *ctx, const uint32_t hist[4][256], uint8_t bits[4][16], uint8_t vals[4][256], int nvals[4],
+                            uint32_t lut[4][256], int standard[4])
+{
+    // (the arguments first, the ctx last: what is wrong with a call does not depend on there being a device)
+    if (!hist || !bits || !vals || !nvals || !lut || !standard) {
+        set_error("fnx_jpeg_huffman_tables: null argument");
+        return FNX_ERR_INVALID;
+    }
+    for (int t = 0; t < 4; t++) {
+        bool any = false;
+        for (int i = 0; i < 256; i++) any = any || hist[t][i] != 0;
+        if (!any) {
+            set_error("fnx_jpeg_huffman_tables: invalid argument: table %d's histogram is all zero", t);
+            return FNX_ERR_INVALID;
+        }
+    }
+    if (!ctx) { set_error("fnx_jpeg_huffman_tables: null ctx"); return FNX_ERR_INVALID; }
+    FNX_ENTER(ctx);
+    uint32_t rec[4 * JPEG_HUFF_REC_WORDS];
+    FNX_TRY(jpeg_huffman_tables_of(ctx, &hist[0][0], &lut[0][0], rec));
+    for (int t = 0; t < 4; t++) {
+        const uint32_t *r = rec + t * JPEG_HUFF_REC_WORDS;
+        FNX_REQUIRE(r[0] >= 1 && r[0] <= 256 && r[1] <= 1, "jpeg_hufftab_kernel left no table");
+        const uint8_t *body = reinterpret_cast<const uint8_t *>(r + 2);
+        nvals[t] = static_cast<int>(r[0]);
+        standard[t] = static_cast<int>(r[1]);
+        std::memcpy(bits[t], body, 16);
+        std::memset(vals[t], 0, 256);
+        std::memcpy(vals[t], body + 16, r[0]);
+    }
+    return FNX_OK;
 }
 
 int fnx_jpeg_size_search(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, long long target_bytes, int skip_ssim,
@@ -410,6 +461,7 @@ int jpeg_compress_group(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sst
     std::vector<unsigned long long> tbits(chunk);
     std::vector<size_t> ecs_off(chunk), ecs_len(chunk), host_off(chunk);
     std::vector<std::vector<uint8_t>> hdr(101);
+    std::vector<uint32_t> recs;                          // FNX_JPEG_HUFFMAN_OPTIMIZED: the chunk's table records
     for (int c0 = 0; c0 < n; c0 += chunk) {
         const int m = n - c0 < chunk ? n - c0 : chunk;
         void *t = nullptr;
@@ -482,13 +534,18 @@ int jpeg_compress_group(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sst
         // compress.go:76-86: every item's file at its best quality (100 when nothing reached the target), entropy-coded together
         for (int i = 0; i < m; i++) qv[i] = st[i].best_q;
         FNX_TRY(upload_table(ctx, SLOT_JPEG_JOBS, qv.data(), sizeof(int) * m, &t));
+        // (FNX_JPEG_HUFFMAN_OPTIMIZED: every item's four table records behind the totals, in the same pinned read-back)
+        const bool opt = ctx->jpeg_huffman == FNX_JPEG_HUFFMAN_OPTIMIZED;
+        const size_t rec_words = opt ? static_cast<size_t>(4) * JPEG_HUFF_REC_WORDS * m : 0;
         void *pin = nullptr;
-        FNX_TRY(pinned_alloc(ctx, sizeof(unsigned long long) * 2 * m, &pin));
+        FNX_TRY(pinned_alloc(ctx, sizeof(unsigned long long) * 2 * m + sizeof(uint32_t) * rec_words, &pin));
         unsigned long long *tot = static_cast<unsigned long long *>(pin);
         for (int i = 0; i < 2 * m; i++) tot[i] = ~0ull;
-        FNX_TRY(jpeg_entropy_code_batch(ctx, m, w, h, orig, static_cast<const int *>(t), d_qtab, tot));
+        uint32_t *rec = opt ? reinterpret_cast<uint32_t *>(tot + 2 * m) : nullptr;
+        FNX_TRY(jpeg_entropy_code_batch(ctx, m, w, h, orig, static_cast<const int *>(t), d_qtab, tot, rec));
         FNX_HIP(hipStreamSynchronize(ctx->stream));
         for (int i = 0; i < m; i++) tbits[i] = tot[i];
+        if (opt) recs.assign(rec, rec + rec_words);          // (the ring may wrap under the segments' staging below)
         uint8_t *ecs = nullptr;
         FNX_TRY(jpeg_entropy_pack_batch(ctx, m, w, h, tbits.data(), &ecs, ecs_off.data(), tot + m));
         FNX_HIP(hipStreamSynchronize(ctx->stream));
@@ -518,7 +575,12 @@ int jpeg_compress_group(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sst
         FNX_HIP(hipStreamSynchronize(ctx->stream));
         for (int i = 0; i < m; i++) {
             const int k = c0 + i, q = st[i].best_q;
-            if (hdr[q].empty()) jpeg_header(w, h, q, hdr[q]);
+            if (opt) {                                       // the item's own tables: its own header
+                hdr[q].clear();
+                jpeg_header(w, h, q, hdr[q], recs.data() + static_cast<size_t>(i) * 4 * JPEG_HUFF_REC_WORDS);
+            } else if (hdr[q].empty()) {
+                jpeg_header(w, h, q, hdr[q]);
+            }
             const size_t eb = ecs_len[i], total = jpeg_file_frame(hdr[q], eb, outs[k], caps[k]);
             nbytes[k] = total;
             quality[k] = q;

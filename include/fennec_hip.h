@@ -366,20 +366,22 @@ int fnx_jpeg_roundtrip(fnx_ctx *ctx, int space, const uint8_t *src, int sstride,
  * FNX_ERR_INVALID with *nbytes set when cap is too small (call again); out == NULL with cap == 0 asks for the size
  * only (what targetsize.go's searches look at) and copies nothing.  Decoding the file gives exactly
  * fnx_jpeg_roundtrip's pixels (the entropy coder is lossless).  Restated from ITU T.81 and Go's file layout, not from
- * Go's source: byte parity with jpeg.Encode is unpinned; libjpeg-turbo decodes the files. */
+ * Go's source: byte parity with jpeg.Encode is unpinned; libjpeg-turbo decodes the files.
+ * The file's Huffman tables follow fnx_ctx_set_jpeg_huffman. */
 int fnx_jpeg_encode(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int quality, uint8_t *out, size_t cap,
                     size_t *nbytes);
 /* jpegQualitySearchOpt (targetsize.go:125-176): the HIGHEST quality whose file fits target_bytes -- the bisection over
  * [lo, hi] the reference picks from the bits per pixel, every candidate's size from the device's entropy coder
  * (nothing is copied for a candidate), then the winner's file into `out` and, unless skip_ssim, its SSIMFast against the
  * source (the reference's computeSSIMNRGBA of the decoded winner).  FNX_NOOP: no quality fits (bestBuf == nil).
- * FNX_ERR_INVALID with *nbytes set when cap is too small. */
+ * FNX_ERR_INVALID with *nbytes set when cap is too small. The file's Huffman tables follow fnx_ctx_set_jpeg_huffman. */
 int fnx_jpeg_size_search(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, long long target_bytes, int skip_ssim,
                          const double *window /* 64; may be NULL with skip_ssim */, uint8_t *out, size_t cap, size_t *nbytes,
                          int *quality, double *ssim, int *steps /* may be NULL */);
 /* compressJPEGOptimal (compress.go:21-87) for one image in one call: the quality search of fnx_jpeg_quality_search, then
  * the file at the quality it found (100 when nothing reached the target) as fnx_jpeg_encode writes it -- one upload of
- * the source, no host codec.  *ssim is the winning candidate's SSIMFast (1.0 when none won, as the reference reports). */
+ * the source, no host codec.  *ssim is the winning candidate's SSIMFast (1.0 when none won, as the reference reports).
+ * The file's Huffman tables follow fnx_ctx_set_jpeg_huffman. */
 int fnx_jpeg_compress(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, double target_ssim,
                       const double *window /* 64 */, uint8_t *out, size_t cap, size_t *nbytes, int *quality, double *ssim,
                       int *steps /* may be NULL */);
@@ -388,9 +390,48 @@ int fnx_jpeg_quality_search(fnx_ctx *ctx, int space, const uint8_t *src, int sst
 /* jpeg.Encode(boxDownsample(src, dw, dh), quality) (ssim.go:244, io.go:157): the scaled image is never materialised --
  * the box sums go straight into the encoder's YCbCr planes (jpeg.hip: jpeg_box_ycc_kernel).  src is w x h in `space`,
  * dw x dh anything from 1 x 1 up to 65535 (also above w x h, as boxDownsample allows).  out / cap / *nbytes as
- * fnx_jpeg_encode: out == NULL with cap == 0: the size only (testScaleFits / findBestScale*'s question). */
+ * fnx_jpeg_encode: out == NULL with cap == 0: the size only (testScaleFits / findBestScale*'s question).
+ * The file's Huffman tables follow fnx_ctx_set_jpeg_huffman. */
 int fnx_jpeg_encode_scaled(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int dw, int dh,
                            int quality, uint8_t *out, size_t cap, size_t *nbytes);
+/* The Huffman tables of the JPEG files a ctx writes.  FNX_JPEG_HUFFMAN_STANDARD (the default) is what the library always
+ * wrote: the four typical tables of ITU T.81 Annex K.3.3, byte for byte.  FNX_JPEG_HUFFMAN_OPTIMIZED builds the four tables
+ * (luminance DC, luminance AC, chrominance DC, chrominance AC; Y against Cb + Cr as before) from the symbols this file's own
+ * scan codes -- what jpegtran -optimize does.  No coefficient changes, so no pixel and no SSIM score does: the same image
+ * costs fewer bytes (types.go:146-153 and io.go:151-158 reserve their options for such an encoder).  The tables, exactly:
+ *  - symbols: per block the category of its DC difference (predictions per component in scan order) and its (run, size)
+ *    pairs, ZRL and EOB as the coder emits them; a symbol that does not occur gets no code and is not listed.
+ *  - code sizes: T.81 Annex K.2, figures K.1 to K.4, over slots 0..255 (the symbols) and slot 256, a reserved symbol of
+ *    frequency 1.  V1 is the slot of least non-zero frequency, V2 the slot of least non-zero frequency among the others; among
+ *    equal frequencies the LARGEST slot index wins, both times.  V2 is merged into V1's slot.  Figure K.3 runs from length 32
+ *    down to 17; the reserved symbol is then taken from the longest length in use.  HUFFVAL is ordered by (unlimited code
+ *    size, symbol value); codes are canonical (Annex C).  (libjpeg's order: Pillow's optimize=True tables are these.)
+ *  - a table whose unlimited code sizes exceed 32 is the standard table of its class, complete (a safety stop that real
+ *    images do not reach).
+ * The file keeps ONE DHT segment with the four tables in the same order; its length is 2 + sum(17 + symbols).
+ * Followed by every entry that makes a JPEG file, or asks for its size, with this ctx -- fnx_jpeg_encode, fnx_jpeg_encode_scaled,
+ * fnx_jpeg_size_search, fnx_jpeg_compress, fnx_jpeg_target_size, fnx_hit_target_size's JPEG legs, fnx_jpeg_recompress,
+ * fennec_CompressFileJPEG, fennec_CompressFileTargetSize, fennec_CompressFileHitTargetSize, both size-query routes (the packed
+ * string and form "jpeg_size" "1") -- and by fnx_jpeg_compress_batch and fnx_jpeg_recompress_batch, tables per image: a batch's
+ * files stay byte for byte the single call's on the same ctx.  No host wait is added anywhere: the tables are built on the
+ * device (csrc/jpeg.hip: jpeg_symhist_kernel, jpeg_hufftab_kernel; tools/jpeg_hufftab_hostsim runs the latter's text on the
+ * CPU) and their DHT bodies come back with the totals.  The fennec_CompressBatch* pools and the Go shim create their own
+ * contexts and keep the default.  The quality search's round trip never codes symbols and is untouched.  DESIGN.md 5.16.
+ * ctx == NULL or any other mode: FNX_ERR_INVALID, nothing changed. */
+#define FNX_JPEG_HUFFMAN_STANDARD  0
+#define FNX_JPEG_HUFFMAN_OPTIMIZED 1
+int fnx_ctx_set_jpeg_huffman(fnx_ctx *ctx, int mode);
+/* What jpeg_symhist_kernel counts for this image at this quality: hist[t][s] = how often the scan of fnx_jpeg_encode(src,
+ * quality) codes symbol s with table t (0 luminance DC, 1 luminance AC, 2 chrominance DC, 3 chrominance AC).  Independent of
+ * the ctx's Huffman mode.  NULL ctx, src or hist: FNX_ERR_INVALID. */
+int fnx_jpeg_symbol_histogram(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int quality,
+                              uint32_t hist[4][256]);
+/* jpeg_hufftab_kernel on the caller's four histograms (HOST; the tables are independent of each other): per table the DHT
+ * body -- bits[t][L - 1] codes of length L, the nvals[t] values vals[t][..] in code order (the rest zero) -- the code look-up
+ * words the coder reads, lut[t][s] = length << 24 | code (0: no code), and standard[t] = 1 when the table is the standard
+ * table of its class (see above).  A NULL pointer or a table whose histogram is all zero: FNX_ERR_INVALID. */
+int fnx_jpeg_huffman_tables(fnx_ctx *ctx, const uint32_t hist[4][256], uint8_t bits[4][16], uint8_t vals[4][256], int nvals[4],
+                            uint32_t lut[4][256], int standard[4]);
 /* hitTargetSize's JPEG strategies (targetsize.go:26-357) in one call, the source staged once and every scale step's
  * file size taken on the device (fnx_jpeg_encode_scaled's planes; 8 bytes come back per size query).  `strategies`: */
 #define FNX_TS_QUALITY 1       /* strategy 1: jpegQualitySearch(src)                        targetsize.go:33-37, 117-176 */
@@ -415,7 +456,8 @@ typedef struct fnx_size_candidate {
  * the source).  *cancel != 0 (may be NULL) is looked at where the reference checks ctx.Err(): before each strategy and
  * each scale step; the fallback runs also after a cancellation, as the reference's does.  FNX_OK: there is a winner;
  * FNX_NOOP: no candidate; FNX_ERR_INVALID: bad arguments, or cap too small -- then *nbytes, cand, *winner and img are
- * filled and fnx_jpeg_encode(img or src, cand[*winner].quality) gives the file without searching again. */
+ * filled and fnx_jpeg_encode(img or src, cand[*winner].quality) gives the file without searching again.
+ * The file's Huffman tables follow fnx_ctx_set_jpeg_huffman. */
 int fnx_jpeg_target_size(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, long long target_bytes,
                          int strategies, const double *window /* 64 */, const volatile int *cancel /* may be NULL */,
                          fnx_size_candidate cand[4], int *winner, uint8_t *out, size_t cap, size_t *nbytes, uint8_t *img,
@@ -463,7 +505,8 @@ int fnx_png_target_size(fnx_ctx *ctx, int space, const uint8_t *src, int sstride
  * order, a tie keeping the earlier one; the output's format is read off cand[*winner].strategy (a PNG leg's bit: a PNG file).
  * With format == FNX_FORMAT_JPEG the call IS fnx_jpeg_target_size with all four bits: the same fields (cand[0], [2], [3], [4])
  * and the same bytes.  The PNG legs' sizes are this library's (see fnx_png_target_size).  Everything else -- cancel, out / cap
- * / *nbytes, img, the return codes -- as fnx_jpeg_target_size; a padded source is refused unless format == FNX_FORMAT_JPEG. */
+ * / *nbytes, img, the return codes -- as fnx_jpeg_target_size; a padded source is refused unless format == FNX_FORMAT_JPEG.
+ * The file's Huffman tables follow fnx_ctx_set_jpeg_huffman. */
 int fnx_hit_target_size(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, long long target_bytes, int format,
                         const double *window /* 64 */, const volatile int *cancel /* may be NULL */, fnx_size_candidate cand[5], int *winner,
                         uint8_t *out, size_t cap, size_t *nbytes, uint8_t *img, int istride);
@@ -497,7 +540,7 @@ int fnx_jpeg_progressive_coefficients(const uint8_t *data, size_t n, int16_t *co
 /* CompressBatch's per-item body for a JPEG source in one call (batch.go:88-122 -> compress.go:21-87): decode `data`
  * on the device, run compressJPEGOptimal's quality search there and write the winner's file into `out` -- the file
  * bytes go up, the new file's bytes come down, no host codec.  Arguments as fnx_jpeg_compress; *w, *h: the image's
- * dimensions.  FNX_ERR_UNSUPPORTED as fnx_jpeg_decode. */
+ * dimensions.  FNX_ERR_UNSUPPORTED as fnx_jpeg_decode. The file's Huffman tables follow fnx_ctx_set_jpeg_huffman. */
 int fnx_jpeg_recompress(fnx_ctx *ctx, const uint8_t *data, size_t n, double target_ssim, const double *window /* 64 */, uint8_t *out,
                         size_t cap, size_t *nbytes, int *quality, double *ssim, int *steps /* may be NULL */, int *w, int *h);
 
@@ -555,7 +598,8 @@ int fnx_msssim_batch_enqueue(fnx_ctx *ctx, int n, const uint8_t *const *as, int 
  * those fnx_jpeg_compress returns for the same image and target, byte for byte and bit for bit.  status[i]: FNX_OK, or
  * FNX_ERR_INVALID when caps[i] is too small -- nbytes[i] and quality[i] are then set, and fnx_jpeg_encode at quality[i]
  * gives the file without searching again.  Returns FNX_OK when the batch ran (per-item outcomes in status), an error
- * for bad arguments before anything is launched.  Blocking; like the other blocking forms, it needs an empty result FIFO. */
+ * for bad arguments before anything is launched.  Blocking; like the other blocking forms, it needs an empty result FIFO.
+ * Every item's Huffman tables follow fnx_ctx_set_jpeg_huffman (tables per image). */
 int fnx_jpeg_compress_batch(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstride, int w, int h,
                             const double *target_ssim /* n */, const double *window /* 64 */,
                             uint8_t *const *outs, const size_t *caps, size_t *nbytes /* n */, int *quality /* n */,
@@ -578,7 +622,8 @@ int fnx_jpeg_decode_batch(fnx_ctx *ctx, int n, const uint8_t *const *files, cons
  * fnx_jpeg_decode_batch into images that stay on the device, then fnx_jpeg_compress_batch's search and files once per
  * geometry among them.  Per item, (file bytes, quality, ssim, steps, w, h) are fnx_jpeg_recompress's for the same file and
  * target.  status[i]: FNX_OK; the decoder's answer for a file it refused (nbytes[i] = 0); FNX_ERR_INVALID when caps[i] is too
- * small, with nbytes[i] and quality[i] set as in fnx_jpeg_compress_batch.  Return value as fnx_jpeg_decode_batch. */
+ * small, with nbytes[i] and quality[i] set as in fnx_jpeg_compress_batch.  Return value as fnx_jpeg_decode_batch.
+ * Every item's Huffman tables follow fnx_ctx_set_jpeg_huffman (tables per image). */
 int fnx_jpeg_recompress_batch(fnx_ctx *ctx, int n, const uint8_t *const *files, const size_t *sizes,
                               const double *target_ssim /* n */, const double *window /* 64 */, uint8_t *const *outs,
                               const size_t *caps, size_t *nbytes /* n */, int *quality /* n */, double *ssim /* n */,
@@ -1123,6 +1168,7 @@ typedef struct fennec_FileOptions {
     int32_t auto_format; /* != 0: Format Auto */
     double target_ssim;  /* Options.Quality.targetSSIM() or Options.TargetSSIM */
 } fennec_FileOptions;
+/* (The file's Huffman tables follow fnx_ctx_set_jpeg_huffman.) */
 int fennec_CompressFileJPEG(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_FileOptions *opts, uint8_t *out, size_t cap,
                             size_t *nbytes, int *quality, double *ssim, int *steps /* may be NULL */, int dims[4]);
 /* CompressFile's PNG branch for a JPEG source, up to the encoder (fennec.go:107-141 -> compressPNG, compress.go:90-153 with
@@ -1195,6 +1241,7 @@ typedef struct fennec_TargetOptions {
     int32_t strategies;      /* FNX_TS_* mask; all four bits = Format: JPEG */
     int32_t reserved;        /* 0 */
 } fennec_TargetOptions;      /* 40 bytes */
+/* (The file's Huffman tables follow fnx_ctx_set_jpeg_huffman.) */
 int fennec_CompressFileTargetSize(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_TargetOptions *opts,
                                   const volatile int *cancel /* may be NULL */, fnx_size_candidate cand[4], int *winner,
                                   uint8_t *out, size_t cap, size_t *nbytes, int dims[4]);
@@ -1202,7 +1249,8 @@ int fennec_CompressFileTargetSize(fnx_ctx *ctx, const uint8_t *data, size_t n, c
  * source, orientation, smartResize: `file`), then ONE fnx_hit_target_size on the resident image with the library's SSIM window.
  * cand, *winner, out / cap / *nbytes, cancel: that call's; dims as fennec_CompressFileTargetSize's.  FNX_ERR_INVALID before any
  * device work: a NULL among ctx, data, file, cand, winner, nbytes, dims (out may be NULL with cap == 0), target_bytes <= 0, a
- * format outside 0..2.  The pool over files (fennec_CompressBatchTargetSize) stays on the JPEG legs. */
+ * format outside 0..2.  The pool over files (fennec_CompressBatchTargetSize) stays on the JPEG legs.
+ * The file's Huffman tables follow fnx_ctx_set_jpeg_huffman. */
 int fennec_CompressFileHitTargetSize(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_FileOptions *file, long long target_bytes,
                                      int format, const volatile int *cancel /* may be NULL */, fnx_size_candidate cand[5], int *winner,
                                      uint8_t *out, size_t cap, size_t *nbytes, int dims[4]);
