@@ -749,6 +749,11 @@ static int launch_fx(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h
     const int stream_on = stream_env ? atoi(stream_env) : 1;
     const bool streams = march && stream_on && w < 65536 && h < 65536 && static_cast<long long>(h) * sstride < (1ll << 31);
     if (nz > 1 && (!streams || sstride != w * 4)) return FNX_NOOP;       // (a SubImage's flat-copy pass is per image)
+    // the route as fnx_ctx_last_kernel(ctx, FNX_PROF_FX) answers it: the form that computes the interior, and the flat pass of a SubImage
+    const bool flat = sstride != w * 4;
+    note_route(ctx, FNX_PROF_FX, streams ? (flat ? "fx_stream_kernel + fx_flat_kernel" : "fx_stream_kernel")
+                                 : march ? (flat ? "fx_march_kernel + fx_flat_kernel" : "fx_march_kernel")
+                                         : (flat ? "fx_ref_kernel + fx_flat_kernel" : "fx_ref_kernel"));
     FNX_TRY(prof_begin(ctx, FNX_PROF_FX));
     if (streams) {
         // one wave per (strip, segment); segments sized so that the launch is one round of resident waves
@@ -776,7 +781,7 @@ static int launch_fx(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h
         dim3 grid((w + FXR_TW - 1) / FXR_TW, (h + FXR_TH - 1) / FXR_TH);
         hipLaunchKernelGGL((fx_ref_kernel<MODE>), grid, dim3(256), 0, ctx->stream, a);
     }
-    if (sstride != w * 4) {                                      // a SubImage: the reference's flat copies (see fx_flat_kernel)
+    if (flat) {                                                  // a SubImage: the reference's flat copies (see fx_flat_kernel)
         dim3 grid((w + 63) / 64, (h + 3) / 4);
         hipLaunchKernelGGL((fx_flat_kernel<MODE>), grid, dim3(256), 0, ctx->stream, a);
     }

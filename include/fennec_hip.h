@@ -147,9 +147,12 @@ int fnx_ctx_sync(fnx_ctx *ctx);
 int fnx_ctx_profile(fnx_ctx *ctx, int enable);
 int fnx_ctx_kernel_ms(fnx_ctx *ctx, float *ms);
 /* The kernel the ctx's LAST call of one class (one FNX_PROF_* bit: MAIN = GaussianBlur, SSIM = the windowed kernel,
- * RESIZE = lanczosResize) really launched, as a static string ("" before the first such call, NULL for a bad
- * argument): which of the routes the dispatch took (matrix pipe, direct, generic; fused, two-pass ...).  Reporting
- * only: bench.py names its roofline kernel with it.  No reference counterpart. */
+ * RESIZE = lanczosResize, FX = gaussianBlur3x3 / Sharpen / AdaptiveSharpen) really launched, as a static string ("" before
+ * the first such call, NULL for a bad argument): which of the routes the dispatch took (matrix pipe, direct, generic;
+ * fused, two-pass ...).  FX answers "fx_stream_kernel", "fx_march_kernel" (the tile kernel) or "fx_ref_kernel" (fp64, the
+ * reference's operation order: amounts outside the guard's bound, Sharpen amounts with a near-tie product), with
+ * " + fx_flat_kernel" behind it for a SubImage (stride != 4 w).  Reporting only: bench.py names its roofline kernel with
+ * it.  No reference counterpart. */
 const char *fnx_ctx_last_kernel(fnx_ctx *ctx, int prof_class);
 /* Arithmetic of the windowed statistics of FULL-RESOLUTION SSIM (ssim.go:24-43, 110-148: planes of 4 M windows and more --
  * fnx_ssim, fnx_ssim_enqueue, fennec_SSIM on large images; SSIMFast / MSSSIM planes are <= 512 px and always exact):

@@ -378,9 +378,13 @@ def sharpen(img, strength):
     h, w = img.shape[:2]
     if w < 3 or h < 3:
         return img
+    return sharpen_amount(img, 1.0 + strength * 1.5)
+
+
+def sharpen_amount(img, amount):
+    """effects.go:28-42 for the unsharp amount itself (the reference passes 1 + 1.5 strength only): w, h >= 3"""
     blur = blur3x3(img)[..., :3].astype(np.float64)
     orig = img[..., :3].astype(np.float64)
-    amount = 1.0 + strength * 1.5
     out = np.empty_like(img)
     out[..., :3] = clampF(orig + amount * (orig - blur))
     out[..., 3] = img[..., 3]
@@ -407,9 +411,14 @@ def adaptive_sharpen(img, strength):
     h, w = img.shape[:2]
     if w < 3 or h < 3:
         return img
+    return adaptive_sharpen_amount(img, 1.0 + strength * 2.0)
+
+
+def adaptive_sharpen_amount(img, amount):
+    """effects.go:66-88 for the amount itself (the reference passes 1 + 2 strength only): w, h >= 3"""
+    h, w = img.shape[:2]
     blur = blur3x3(img)[1:h - 1, 1:w - 1, :3].astype(np.float64)
     orig = img[1:h - 1, 1:w - 1, :3].astype(np.float64)
-    amount = 1.0 + strength * 2.0
     local = amount * edge_strength(img)
     out = flat_pix_image(img)                          # effects.go:68
     out[1:h - 1, 1:w - 1, :3] = clampF(orig + local[..., None] * (orig - blur))

@@ -86,6 +86,15 @@ def test_set_form_needs_a_ctx_and_a_known_name(lib):
     assert lib.fnx_ctx_set_form(None, b"fx_ref", b"1") == fennec_amd.FNX_ERR_INVALID
 
 
+def test_last_kernel_needs_a_ctx_and_the_library_names_the_fx_routes(lib):
+    """fnx_ctx_last_kernel(ctx, FNX_PROF_FX): NULL without a ctx; the six routes of effects.hip's dispatch are static strings of the library"""
+    assert lib.fnx_ctx_last_kernel(None, fennec_amd.PROF_FX) is None
+    blob = open(fennec_amd.LIB_PATH, "rb").read()
+    for kernel in ("fx_stream_kernel", "fx_march_kernel", "fx_ref_kernel"):
+        for tail in ("", " + fx_flat_kernel"):
+            assert (kernel + tail).encode() + b"\0" in blob, kernel + tail
+
+
 def test_table_generators_match_oracle(lib, orc):
     assert np.array_equal(fennec_amd.gaussianKernel(), orc.gaussian_kernel())
     for s in (0.3, 1.0, 2.0, 2.5, 20.0):
