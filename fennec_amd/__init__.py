@@ -48,6 +48,8 @@ FNX_DEFLATE_CHUNK, FNX_DEFLATE_SUB = 32768, 128               # deflate.hip: byt
 FNX_DEFLATE_LEVEL_FAST, FNX_DEFLATE_LEVEL_DENSE = 0, 1         # fnx_ctx_set_deflate_level
 FNX_JPEG_HUFFMAN_STANDARD, FNX_JPEG_HUFFMAN_OPTIMIZED = 0, 1   # fnx_ctx_set_jpeg_huffman
 FNX_DEFLATE_DENSE_DEPTH = 32                                   # the dense level: the most chain candidates a position tries
+FNX_CRC_RUN, FNX_CRC_PIECE = 64, 16384                         # crc32.hip: bytes per lane and per workgroup
+FNX_PNG_CRC_HOST, FNX_PNG_CRC_DEVICE = 0, 1                    # fnx_ctx_set_png_crc
 PROF_MAIN, PROF_SSIM, PROF_RESIZE, PROF_FX, PROF_JPEG = 1, 2, 4, 8, 16
 
 _u8p = C.c_void_p
@@ -174,6 +176,8 @@ def load_library() -> C.CDLL:
         _sig(L, "fnx_ctx_set_png_adam7", i, [ctx, i])
         _sig(L, "fnx_ctx_set_deflate_level", i, [ctx, i])
         _sig(L, "fnx_ctx_set_jpeg_huffman", i, [ctx, i])
+        _sig(L, "fnx_ctx_set_png_crc", i, [ctx, i])
+        _sig(L, "fnx_crc32", i, [ctx, i, _u8p, C.c_size_t, C.c_uint32, C.POINTER(C.c_uint32)])
         _sig(L, "fnx_jpeg_symbol_histogram", i, [ctx, i] + img + [i, i, i, C.POINTER(C.c_uint32)])
         _sig(L, "fnx_jpeg_huffman_tables", i, [ctx, C.POINTER(C.c_uint32), _u8p, _u8p, C.POINTER(C.c_int), C.POINTER(C.c_uint32),
                                                C.POINTER(C.c_int)])
@@ -498,6 +502,19 @@ class Context:
                 raise FennecError(f"set_jpeg_huffman: 'standard' or 'optimized', not {mode!r}")
             mode = names[mode]
         self._chk(self._lib.fnx_ctx_set_jpeg_huffman(self._h, int(mode)), "fnx_ctx_set_jpeg_huffman")
+
+    def set_png_crc(self, mode) -> None:
+        """fnx_ctx_set_png_crc: "host" (FNX_PNG_CRC_HOST, the default: the host walks the IDAT chunk once its bytes have come
+        down) or "device" (FNX_PNG_CRC_DEVICE: crc32.hip's kernels read the gathered stream on the device and the CRC word
+        comes down with the sizes) for every PNG file this ctx makes from a device deflate: png_encode,
+        compress_png(device_deflate=True), compress_file_png, hit_target_size, png_compress_batch, png_recompress_batch.  The
+        files are the same bytes.  The integer constants are accepted too."""
+        if isinstance(mode, str):
+            names = {"host": FNX_PNG_CRC_HOST, "device": FNX_PNG_CRC_DEVICE}
+            if mode not in names:
+                raise FennecError(f"set_png_crc: 'host' or 'device', not {mode!r}")
+            mode = names[mode]
+        self._chk(self._lib.fnx_ctx_set_png_crc(self._h, int(mode)), "fnx_ctx_set_png_crc")
 
     def set_form(self, name: str, value=None) -> None:
         """fnx_ctx_set_form: which of several kernels that compute the same bytes this ctx takes (tests, A/B timing);
@@ -1829,6 +1846,24 @@ class Context:
         view = out[:size.value]
         return view.tobytes() if fresh and not on_device else view
 
+    def crc32(self, data, crc: int = 0) -> int:
+        """zlib.crc32(data, crc) on the device (fnx_crc32; crc32.hip): data is bytes or a flat uint8 numpy array (uploaded
+        first) or a flat uint8 device tensor (read where it lies, at any alignment); crc the CRC of what came before."""
+        if _is_torch(data):
+            import torch
+            if not data.is_cuda or data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+                raise FennecError("a device buffer must be a flat contiguous uint8 CUDA/HIP tensor")
+            space, ptr, n, keep = FNX_DEVICE, data.data_ptr(), int(data.shape[0]), data
+        else:
+            keep = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data
+            if not isinstance(keep, np.ndarray) or keep.dtype != np.uint8 or keep.ndim != 1 or not keep.flags.c_contiguous:
+                raise FennecError("a host buffer must be bytes or a flat contiguous uint8 numpy array")
+            space, ptr, n = FNX_HOST, keep.ctypes.data, int(keep.shape[0])
+        out = C.c_uint32(0)
+        with self._ordered(keep if space == FNX_DEVICE else None):
+            self._chk(self._lib.fnx_crc32(self._h, space, ptr if n else None, n, int(crc) & 0xffffffff, C.byref(out)), "fnx_crc32")
+        return int(out.value)
+
     def png_encode(self, src, kind: int | None = None, ncolors: int = 0, opaque: int = -1, palette=None) -> bytes:
         """The complete PNG file of `src` (fnx_png_encode): png_filter's row stage and the deflate on the device, the chunks
         (signature, IHDR, PLTE and tRNS for paletted kinds, one IDAT, IEND: png_file's layout) and their CRCs on the host.
@@ -2287,6 +2322,7 @@ def deflate(buf, row=0): return default_context(_dev_of(buf)).deflate(buf, row)
 def png_encode(src, kind=None, ncolors=0, opaque=-1, palette=None): return default_context(_dev_of(src)).png_encode(src, kind, ncolors, opaque, palette)
 def png_encoded_size(src, kind=None, ncolors=0, opaque=-1, palette=None): return default_context(_dev_of(src)).png_encoded_size(src, kind, ncolors, opaque, palette)
 def deflate_bound(n): return int(load_library().fnx_deflate_bound(int(n)))
+def crc32(data, crc=0): return default_context(_dev_of(data)).crc32(data, crc)
 def png_file_bound(w, h): return int(load_library().fnx_png_file_bound(int(w), int(h)))
 
 

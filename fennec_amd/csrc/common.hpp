@@ -117,6 +117,7 @@ enum Slot {
     // unit and image tables of its four stages; fnx_png_recompress_batch: the decoded images of a span
     SLOT_PNG_CB_WORK, SLOT_PNG_CB_PLANES, SLOT_PNG_CB_STREAMS, SLOT_PNG_CB_TAB0, SLOT_PNG_CB_TAB1, SLOT_PNG_CB_TAB2, SLOT_PNG_CB_TAB3, SLOT_PNG_CB_IMG,
     SLOT_MEDIAN_CUT, SLOT_MEDIAN_CUT_TAB,   // median_cut.hip: both sample buffers and the palettes; palette.hip: apply_palette's tables made on the device from them
+    SLOT_CRC, SLOT_CRC_TAB,   // crc32.hip: the pieces' words (and fnx_crc32's result word); the batch's unit and stream tables
     SLOT_DONE,       // workgroup counters of the kernels that finish their own reduction (ssim.hip), zero between launches
     SLOT_COUNT
 };
@@ -231,6 +232,7 @@ struct fnx_ctx {
     int png_adam7 = 0;           // fnx_ctx_set_png_adam7: 1 -- the PNG entries decode Adam7-interlaced files instead of refusing them
     int jpeg_huffman = 0;        // fnx_ctx_set_jpeg_huffman: FNX_JPEG_HUFFMAN_STANDARD / _OPTIMIZED -- the tables of every JPEG file (and size) this ctx makes
     int deflate_level = 0;       // fnx_ctx_set_deflate_level: FNX_DEFLATE_LEVEL_FAST / _DENSE -- which chunk kernels launch_deflate and launch_deflate_batch run
+    int png_crc = 0;             // fnx_ctx_set_png_crc: FNX_PNG_CRC_HOST / _DEVICE -- where the IDAT CRC of this ctx's device-deflated PNG files comes from
     int ssim_mode = 0;           // fnx_ctx_set_ssim_mode: FNX_SSIM_EXACT (fp64 moments) / FNX_SSIM_FAST (fp32 moments for full-resolution planes)
     // fnx_ctx_set_form: the kernel forms this ctx was told to take ("" = the product's own choice)
     char form[fnx::FORM_COUNT][8] = {};
@@ -543,6 +545,7 @@ int png_filter_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, i
 // deflate.hip: the zlib stream of n >= 1 device bytes into d_out (device, cap bytes; a larger stream writes nothing);
 // *d_size: the device word that holds the stream's size once both kernels have run.  row: a match-distance hint, 0 for none.
 // (deflate_chunks, deflate_bound: deflate_batch.hpp)
+// (the 8 bytes behind *d_size are spare: png_encode_device's CRC word, fetched with the size)
 int launch_deflate(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, uint8_t *d_out, size_t cap, const unsigned long long **d_size);
 // the size launch_deflate's stream would have under the ctx's level, and nothing else: the chunk kernels' size-only forms (the
 // parse and the choice of form; no codes, no bits, no slots) and deflate_size_kernel.  *d_size: the device word with the size
@@ -580,6 +583,10 @@ struct PngFrame {
 uint8_t *png_frame_head(const PngFrame &f, uint8_t *out);
 // the IDAT chunk whose zsize body bytes are in place, and IEND
 void png_frame_tail(uint8_t *idat, size_t zsize);
+// the same with the IDAT chunk's CRC given (the finished one, as the device's fold kernel writes it): no byte of the body is read
+void png_frame_tail(uint8_t *idat, size_t zsize, uint32_t idat_crc);
+// the CRC register after the four bytes "IDAT" from all ones: what the device's CRC of a chunk's body starts from
+uint32_t png_idat_seed();
 // ---- fnx_png_compress_batch: a chunk of images through one set of launches (png_compress_plan.hpp has the host plan) ----
 struct PngCbSrc {                        // an image of the chunk: DEVICE, NRGBA, 4-byte aligned, the flat Pix readable
     const uint8_t *src;
@@ -604,8 +611,18 @@ int png_cb_al4(const uint8_t *src, int sstride);
 int launch_png_rows_batch(fnx_ctx *ctx, const PngCbUnit *d_units, const int nunits[PNG_CB_FORMS], const PngCbRows *d_rows);
 // deflate.hip: deflate_chunk_batch_kernel, deflate_gather_batch_kernel over DEVICE tables of nunits units and m streams;
 // out_bytes: the sum of the streams' bounds.  *d_out: the zlib streams back to back at their true sizes, *d_sizes: the m sizes
+// (*d_sizes + m, as words: room for the streams' CRCs -- launch_crc32_batch -- so that they come down with the sizes)
 int launch_deflate_batch(fnx_ctx *ctx, const DeflateBatchUnit *d_units, const DeflateBatchImage *d_images, uint32_t nunits, uint32_t m,
                          size_t out_bytes, const uint8_t **d_out, const unsigned long long **d_sizes);
+// crc32.hip: crc32_pieces_kernel, crc32_fold_kernel over the device bytes at d_src -> the finished CRC-32 in the device word
+// *d_crc.  n_max: the bytes the grid covers; d_n: nullptr (the length is n_max) or the DEVICE word that holds the length once
+// the kernels in front have run (held to n_max).  seed: the register the bytes start from (0xffffffff: a CRC of its own).
+// Nothing is waited for.
+int launch_crc32(fnx_ctx *ctx, const uint8_t *d_src, size_t n_max, const unsigned long long *d_n, uint32_t seed, uint32_t *d_crc);
+// the batched twins over launch_deflate_batch's *d_out and *d_sizes: bounds[i] = deflate_bound of stream i (HOST, m of them),
+// d_crcs: m device words
+int launch_crc32_batch(fnx_ctx *ctx, const uint8_t *d_out, const unsigned long long *d_sizes, const size_t *bounds, uint32_t m, uint32_t seed,
+                       uint32_t *d_crcs);
 // jpeg_api.cpp: fnx_jpeg_decode_batch's body (the files' images into DEVICE dsts; per item fnx_jpeg_decode's answer)
 int jpeg_decode_batch_device(fnx_ctx *ctx, int n, const uint8_t *const *files, const size_t *sizes, uint8_t *const *dsts, const int *dstrides,
                              int *ws, int *hs, int *status);

@@ -438,7 +438,7 @@ int launch_deflate(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, uint8_
     const bool dense = ctx->deflate_level == FNX_DEFLATE_LEVEL_DENSE;
     void *dt = nullptr, *ds = nullptr;
     FNX_TRY(scratch(ctx, SLOT_DEFLATE_TOK, nchunks * (dense ? DF_DENSE_WORDS : DF_C) * sizeof(uint32_t) + 16, &dt));
-    // the result word, the chunks' (bytes, a, b, len), the chunks' slots
+    // the result word (16 bytes: the size, and room for the PNG route's CRC word), the chunks' (bytes, a, b, len), the chunks' slots
     const size_t meta_bytes = (16 * nchunks + 16 + 15) & ~size_t(15);
     FNX_TRY(scratch(ctx, SLOT_DEFLATE_SLOTS, meta_bytes + nchunks * DF_SLOT + 16, &ds));
     uint8_t *p = static_cast<uint8_t *>(ds);
@@ -501,8 +501,8 @@ int launch_deflate_batch(fnx_ctx *ctx, const DeflateBatchUnit *d_units, const De
     const bool dense = ctx->deflate_level == FNX_DEFLATE_LEVEL_DENSE;
     void *dt = nullptr, *ds = nullptr, *dz = nullptr;
     FNX_TRY(scratch(ctx, SLOT_DEFLATE_TOK, static_cast<size_t>(nunits) * (dense ? DF_DENSE_WORDS : DF_C) * sizeof(uint32_t) + 16, &dt));
-    // the streams' sizes, the units' (bytes, a, b, len), the units' slots
-    const size_t sizes_bytes = (8 * static_cast<size_t>(m) + 15) & ~size_t(15);
+    // the streams' sizes (and a word each behind them for crc32.hip's CRCs), the units' (bytes, a, b, len), the units' slots
+    const size_t sizes_bytes = (12 * static_cast<size_t>(m) + 15) & ~size_t(15);
     const size_t meta_bytes = 16 * static_cast<size_t>(nunits);
     FNX_TRY(scratch(ctx, SLOT_DEFLATE_SLOTS, sizes_bytes + meta_bytes + static_cast<size_t>(nunits) * DF_SLOT + 16, &ds));
     FNX_TRY(scratch(ctx, SLOT_DEFLATE_OUT, out_bytes + 16, &dz));

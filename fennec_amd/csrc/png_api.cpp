@@ -1,7 +1,8 @@
 // The PNG entry points.  Towards a file: fnx_png_reduce (png_reduce.hip: compressPNG's pixel stages), fnx_png_filter
 // (png_filter.hip's row stage), fnx_deflate_bound and fnx_deflate (deflate.hip's two kernels behind the argument checks and the
 // staging of the three spaces), fnx_png_encode (the row stage, then the deflate, on the device; the file's chunks and their
-// CRCs on the host: png_frame.cpp).  From a file: fnx_png_decode -- png_parse.cpp's host side (chunk walk, inflate, the filter
+// CRCs on the host: png_frame.cpp -- the IDAT chunk's from crc32.hip's kernels on a ctx at FNX_PNG_CRC_DEVICE), fnx_crc32
+// (those kernels on any bytes).  From a file: fnx_png_decode -- png_parse.cpp's host side (chunk walk, inflate, the filter
 // bytes), then png_decode.hip's two kernels (an Adam7 file on a ctx that accepts it: a descriptor per pass, the batched
 // unfilter kernel once, png_expand_adam7_kernel) -- and fnx_png_decode_batch, which does the host side of a chunk of files
 // on several threads and sends the chunk through one set of launches.  Both ways: fnx_png_compress_batch /
@@ -288,25 +289,34 @@ int png_filter_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, i
 }
 
 // ---- the deflate, and the file around it ---------------------------------------------------------------------------
-// the zlib stream of n device bytes into d_out (device, cap bytes), its size waited for
-static int deflate_into(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, uint8_t *d_out, size_t cap, size_t *size)
+// the zlib stream of n device bytes into d_out (device, cap bytes), its size waited for.  idat_crc (a PNG route on a ctx at
+// FNX_PNG_CRC_DEVICE; else nullptr): the CRC-32 of "IDAT" and the stream, from the CRC kernels behind the gather -- their grid
+// covers cap bytes, the length is the gather's size word, and the CRC word lies behind that word and comes down with it
+static int deflate_into(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, uint8_t *d_out, size_t cap, size_t *size, uint32_t *idat_crc = nullptr)
 {
     const unsigned long long *d_size = nullptr;
     FNX_TRY(launch_deflate(ctx, d_src, n, row, d_out, cap, &d_size));
-    unsigned long long got = 0;
-    FNX_TRY(fetch_bytes(ctx, d_size, &got, sizeof(got)));
-    *size = static_cast<size_t>(got);
+    if (idat_crc) {
+        uint32_t *d_crc = reinterpret_cast<uint32_t *>(const_cast<unsigned long long *>(d_size) + 1);
+        FNX_TRY(launch_crc32(ctx, d_out, cap, d_size, png_idat_seed(), d_crc));
+        note_route(ctx, FNX_PROF_MAIN, ctx->deflate_level == FNX_DEFLATE_LEVEL_DENSE ? "deflate_dense_chunk_kernel, crc32_pieces_kernel"
+                                                                                     : "deflate_chunk_kernel, crc32_pieces_kernel");
+    }
+    unsigned long long got[2] = {0, 0};
+    FNX_TRY(fetch_bytes(ctx, d_size, got, idat_crc ? sizeof got : sizeof got[0]));
+    *size = static_cast<size_t>(got[0]);
+    if (idat_crc) *idat_crc = static_cast<uint32_t>(got[1]);
     return FNX_OK;
 }
 
 // the same, gathered on the device in SLOT_DEFLATE_OUT (*d_out), from where it is copied once its size is known
-static int deflate_gathered(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, uint8_t **d_out, size_t *size)
+static int deflate_gathered(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, uint8_t **d_out, size_t *size, uint32_t *idat_crc = nullptr)
 {
     void *t = nullptr;
     const size_t cap = deflate_bound(n);
     FNX_TRY(scratch(ctx, SLOT_DEFLATE_OUT, cap + 16, &t));
     *d_out = static_cast<uint8_t *>(t);
-    return deflate_into(ctx, d_src, n, row, *d_out, cap, size);
+    return deflate_into(ctx, d_src, n, row, *d_out, cap, size, idat_crc);
 }
 
 int deflate_device(fnx_ctx *ctx, const uint8_t *d_src, size_t n, int row, bool out_on_device, uint8_t *out, size_t cap, size_t *nbytes)
@@ -362,7 +372,9 @@ int png_encode_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, i
     int color_type = 0, bit_depth = 0;
     FNX_TRY(png_rows_to_stream(ctx, kind, src, sstride, w, h, ncolors, opaque, &dstream, &stream_bytes, &color_type, &bit_depth));
     uint8_t *dz = nullptr;
-    FNX_TRY(deflate_gathered(ctx, dstream, stream_bytes, static_cast<int>(stream_bytes / h), &dz, &zsize));
+    const bool device_crc = ctx->png_crc == FNX_PNG_CRC_DEVICE;
+    uint32_t idat_crc = 0;
+    FNX_TRY(deflate_gathered(ctx, dstream, stream_bytes, static_cast<int>(stream_bytes / h), &dz, &zsize, device_crc ? &idat_crc : nullptr));
 
     const PngFrame frame{w, h, color_type, bit_depth, ncolors, palette};
     *nbytes = frame.file_bytes(zsize);
@@ -377,7 +389,8 @@ int png_encode_device(fnx_ctx *ctx, int kind, const uint8_t *src, int sstride, i
     uint8_t *at = png_frame_head(frame, out);
     FNX_HIP(hipMemcpyAsync(at + 8, dz, zsize, hipMemcpyDeviceToHost, ctx->stream));
     FNX_HIP(hipStreamSynchronize(ctx->stream));
-    png_frame_tail(at, zsize);
+    if (device_crc) png_frame_tail(at, zsize, idat_crc);
+    else png_frame_tail(at, zsize);
     return FNX_OK;
 }
 
@@ -490,6 +503,31 @@ int fnx_deflate(fnx_ctx *ctx, int space, const uint8_t *src, size_t n, int row, 
         dsrc = static_cast<const uint8_t *>(d);
     }
     return deflate_device(ctx, dsrc, n, row, space == FNX_DEVICE, out, cap, nbytes);
+}
+
+int fnx_crc32(fnx_ctx *ctx, int space, const uint8_t *src, size_t n, uint32_t crc, uint32_t *out)
+{
+    FNX_REQUIRE(ctx != nullptr, "ctx is null");
+    FNX_REQUIRE(space == FNX_HOST || space == FNX_DEVICE, "space: FNX_HOST or FNX_DEVICE");
+    FNX_REQUIRE(out != nullptr, "out is null");
+    FNX_REQUIRE(src != nullptr || n == 0, "src is null");
+    if (n == 0) {
+        *out = crc;
+        return FNX_OK;
+    }
+    FNX_ENTER(ctx);
+    const uint8_t *dsrc = src;
+    if (space == FNX_HOST) {
+        void *d = nullptr;
+        FNX_TRY(scratch(ctx, SLOT_IN_A, n + 16, &d));
+        FNX_HIP(hipMemcpyAsync(d, src, n, hipMemcpyHostToDevice, ctx->stream));
+        dsrc = static_cast<const uint8_t *>(d);
+    }
+    void *dres = nullptr;
+    FNX_TRY(scratch(ctx, SLOT_RESULT, 16, &dres));
+    note_route(ctx, FNX_PROF_MAIN, "crc32_pieces_kernel");
+    FNX_TRY(launch_crc32(ctx, dsrc, n, nullptr, ~crc, static_cast<uint32_t *>(dres)));
+    return fetch_bytes(ctx, dres, out, sizeof *out);
 }
 
 int fnx_png_encode(fnx_ctx *ctx, int space, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors, int opaque,
@@ -672,6 +710,12 @@ constexpr const char *PNG_CB_ROUTE =
 constexpr const char *PNG_CB_ROUTE_DENSE =                            // on a ctx at FNX_DEFLATE_LEVEL_DENSE
     "png_colors_batch_kernel, png_finish_batch_kernel, png_flags_batch_kernel, png_plane_batch_kernel, png_filter_batch_kernel, "
     "png_pack_batch_kernel, deflate_dense_chunk_batch_kernel, deflate_gather_batch_kernel";
+constexpr const char *PNG_CB_ROUTE_CRC =                              // on a ctx at FNX_PNG_CRC_DEVICE
+    "png_colors_batch_kernel, png_finish_batch_kernel, png_flags_batch_kernel, png_plane_batch_kernel, png_filter_batch_kernel, "
+    "png_pack_batch_kernel, deflate_chunk_batch_kernel, deflate_gather_batch_kernel, crc32_pieces_batch_kernel, crc32_fold_batch_kernel";
+constexpr const char *PNG_CB_ROUTE_DENSE_CRC =                        // at both
+    "png_colors_batch_kernel, png_finish_batch_kernel, png_flags_batch_kernel, png_plane_batch_kernel, png_filter_batch_kernel, "
+    "png_pack_batch_kernel, deflate_dense_chunk_batch_kernel, deflate_gather_batch_kernel, crc32_pieces_batch_kernel, crc32_fold_batch_kernel";
 
 // `bytes` device bytes into pinned host memory, waited for: one of a chunk's three host waits
 int png_cb_fetch(fnx_ctx *ctx, const void *d, size_t bytes, const uint8_t **host)
@@ -685,13 +729,15 @@ int png_cb_fetch(fnx_ctx *ctx, const void *d, size_t bytes, const uint8_t **host
 }
 
 // One chunk: m images that passed their argument checks (at[j]: image j's place in the caller's arrays) through one set of
-// launches and three host waits -- the classification words, the streams' sizes, the streams' bytes.  (The three fetches and
+// launches and three host waits -- the classification words, the streams' sizes (on a ctx at FNX_PNG_CRC_DEVICE: and their IDAT
+// CRCs, from the CRC kernels behind the gather), the streams' bytes.  (The three fetches and
 // the table uploads take their pinned bytes from the ctx's ring: where the ring grows or wraps, pinned_alloc waits for the
 // stream once more -- by then the stream is idle or nearly so, but it is a wait.)
 int png_compress_chunk(fnx_ctx *ctx, int m, const PngCbSrc *imgs, const int *at, int base, uint8_t *const *outs, const size_t *caps, size_t *nbytes,
                        int *kinds, int *status, FirstRefusal *first)
 {
-    note_route(ctx, FNX_PROF_MAIN, ctx->deflate_level == FNX_DEFLATE_LEVEL_DENSE ? PNG_CB_ROUTE_DENSE : PNG_CB_ROUTE);
+    const bool dense = ctx->deflate_level == FNX_DEFLATE_LEVEL_DENSE, device_crc = ctx->png_crc == FNX_PNG_CRC_DEVICE;
+    note_route(ctx, FNX_PROF_MAIN, device_crc ? (dense ? PNG_CB_ROUTE_DENSE_CRC : PNG_CB_ROUTE_CRC) : (dense ? PNG_CB_ROUTE_DENSE : PNG_CB_ROUTE));
     const void *d_results = nullptr;
     FNX_TRY(launch_png_classify_batch(ctx, m, imgs, &d_results));
     const size_t rb = png_result_bytes();
@@ -769,9 +815,17 @@ int png_compress_chunk(fnx_ctx *ctx, int m, const PngCbSrc *imgs, const int *at,
         FNX_TRY(launch_deflate_batch(ctx, static_cast<const DeflateBatchUnit *>(dp[0]), static_cast<const DeflateBatchImage *>(dp[1]),
                                      static_cast<uint32_t>(du.size()), static_cast<uint32_t>(m), plan.out_bytes, &d_out, &d_sizes));
     }
-    FNX_TRY(png_cb_fetch(ctx, d_sizes, sizeof(unsigned long long) * m, &pin));  // wait 2
+    if (device_crc) {                                                        // the CRC words lie behind the sizes
+        std::vector<size_t> bounds(m);
+        for (int j = 0; j < m; j++) bounds[j] = deflate_bound(plan.images[j].stream_bytes);
+        FNX_TRY(launch_crc32_batch(ctx, d_out, d_sizes, bounds.data(), static_cast<uint32_t>(m), png_idat_seed(),
+                                   reinterpret_cast<uint32_t *>(const_cast<unsigned long long *>(d_sizes) + m)));
+    }
+    FNX_TRY(png_cb_fetch(ctx, d_sizes, (sizeof(unsigned long long) + (device_crc ? sizeof(uint32_t) : 0)) * m, &pin));  // wait 2
     std::vector<unsigned long long> zsizes(m);
     std::memcpy(zsizes.data(), pin, sizeof(unsigned long long) * m);
+    std::vector<uint32_t> idat_crcs(device_crc ? m : 0);
+    if (device_crc) std::memcpy(idat_crcs.data(), pin + sizeof(unsigned long long) * m, sizeof(uint32_t) * m);
     size_t total = 0;
     for (int j = 0; j < m; j++) {
         if (zsizes[j] > deflate_bound(plan.images[j].stream_bytes)) {
@@ -782,7 +836,7 @@ int png_compress_chunk(fnx_ctx *ctx, int m, const PngCbSrc *imgs, const int *at,
     }
     FNX_TRY(png_cb_fetch(ctx, d_out, total, &pin));                           // wait 3: the streams' own bytes, back to back
 
-    // the files: the chunks around each stream and their CRCs, on this thread
+    // the files: the chunks around each stream and their CRCs (the IDAT chunk's as fnx_ctx_set_png_crc says), on this thread
     size_t off = 0;
     for (int j = 0; j < m; j++) {
         const int i = at[j];
@@ -802,7 +856,8 @@ int png_compress_chunk(fnx_ctx *ctx, int m, const PngCbSrc *imgs, const int *at,
         } else {
             uint8_t *idat = png_frame_head(frame, outs[i]);
             std::memcpy(idat + 8, pin + off, zsize);
-            png_frame_tail(idat, zsize);
+            if (device_crc) png_frame_tail(idat, zsize, idat_crcs[j]);
+            else png_frame_tail(idat, zsize);
             status[i] = FNX_OK;
         }
         off += zsize;

@@ -1,6 +1,7 @@
 // The file around a zlib stream: signature, IHDR, PLTE + tRNS for colour type 3, one IDAT, IEND, and the chunks' CRCs -- what
-// fnx_png_encode and the compress batch write on the host.  Plain C++: no HIP call, no ctx (tools/png_frame_host.cpp runs it
-// under the sanitizers).
+// fnx_png_encode and the compress batch write on the host (on a ctx at FNX_PNG_CRC_DEVICE the IDAT chunk's CRC is handed in:
+// crc32.hip).  Plain C++: no HIP call, no ctx (tools/png_frame_host.cpp and tools/png_frame_crc_host.cpp run it under the
+// sanitizers).
 #include "common.hpp"
 
 namespace fnx {
@@ -45,13 +46,21 @@ void put_be32(uint8_t *p, uint32_t v)
     p[0] = static_cast<uint8_t>(v >> 24); p[1] = static_cast<uint8_t>(v >> 16); p[2] = static_cast<uint8_t>(v >> 8); p[3] = static_cast<uint8_t>(v);
 }
 
-// a chunk whose `len` body bytes already sit at at + 8: length and tag in front, CRC behind; returns the chunk's end
-uint8_t *close_chunk(uint8_t *at, const char *tag, size_t len)
+// a chunk whose `len` body bytes already sit at at + 8 and whose CRC is given: length and tag in front, CRC behind (the body
+// is not read); returns the chunk's end
+uint8_t *close_chunk(uint8_t *at, const char *tag, size_t len, uint32_t crc)
 {
     put_be32(at, static_cast<uint32_t>(len));
     std::memcpy(at + 4, tag, 4);
-    put_be32(at + 8 + len, ~crc32_update(0xffffffffu, at + 4, 4 + len));
+    put_be32(at + 8 + len, crc);
     return at + 12 + len;
+}
+
+// the same with the CRC computed here, over the tag and the body
+uint8_t *close_chunk(uint8_t *at, const char *tag, size_t len)
+{
+    std::memcpy(at + 4, tag, 4);
+    return close_chunk(at, tag, len, ~crc32_update(0xffffffffu, at + 4, 4 + len));
 }
 
 }  // namespace
@@ -79,6 +88,16 @@ uint8_t *png_frame_head(const PngFrame &f, uint8_t *out)
 void png_frame_tail(uint8_t *idat, size_t zsize)
 {
     close_chunk(close_chunk(idat, "IDAT", zsize), "IEND", 0);
+}
+
+void png_frame_tail(uint8_t *idat, size_t zsize, uint32_t idat_crc)
+{
+    close_chunk(close_chunk(idat, "IDAT", zsize, idat_crc), "IEND", 0);
+}
+
+uint32_t png_idat_seed()
+{
+    return crc32_update(0xffffffffu, reinterpret_cast<const uint8_t *>("IDAT"), 4);
 }
 
 }  // namespace fnx

@@ -549,6 +549,13 @@ int fnx_ctx_set_deflate_level(fnx_ctx *ctx, int level)
     return FNX_OK;
 }
 
+int fnx_ctx_set_png_crc(fnx_ctx *ctx, int mode)
+{
+    if (!ctx || (mode != FNX_PNG_CRC_HOST && mode != FNX_PNG_CRC_DEVICE)) { fnx::set_error("fnx_ctx_set_png_crc: bad argument"); return FNX_ERR_INVALID; }
+    ctx->png_crc = mode;
+    return FNX_OK;
+}
+
 int fnx_ctx_set_jpeg_huffman(fnx_ctx *ctx, int mode)
 {
     if (!ctx || (mode != FNX_JPEG_HUFFMAN_STANDARD && mode != FNX_JPEG_HUFFMAN_OPTIMIZED)) { fnx::set_error("fnx_ctx_set_jpeg_huffman: bad argument"); return FNX_ERR_INVALID; }

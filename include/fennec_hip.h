@@ -884,7 +884,9 @@ int fnx_ctx_set_deflate_level(fnx_ctx *ctx, int level);
  * where src lives; out is ALWAYS host memory.  The file: signature, IHDR, for colour type 3 PLTE (3 bytes per entry) and
  * tRNS (the alphas up to and including the last entry whose alpha != 255; omitted when there is none), one IDAT holding the
  * zlib stream, IEND -- the chunk layout of the Python binding's png_file.  The chunk CRCs are computed on the host over
- * bytes that are there anyway.  *nbytes: the file's size; cap < *nbytes: FNX_ERR_INVALID with *nbytes set, nothing
+ * bytes that are there anyway -- on a ctx at FNX_PNG_CRC_DEVICE (fnx_ctx_set_png_crc) the IDAT chunk's alone comes from the
+ * device, and fnx_ctx_last_kernel(ctx, FNX_PROF_MAIN) then names "deflate_chunk_kernel, crc32_pieces_kernel" (the dense
+ * level: its chunk kernel).  *nbytes: the file's size; cap < *nbytes: FNX_ERR_INVALID with *nbytes set, nothing
  * written.  Decodes to the source's pixels; differs from the reference's file in the deflate bytes only. */
 int fnx_png_encode(fnx_ctx *ctx, int space, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors /* paletted: 1..256 */,
                    int opaque /* 1, 0, or -1: decide as Opaque() does */, const uint8_t *palette, uint8_t *out, size_t cap, size_t *nbytes);
@@ -898,6 +900,37 @@ int fnx_png_encode(fnx_ctx *ctx, int space, int kind, const uint8_t *src, int ss
  * FNX_DEFLATE_LEVEL_DENSE deflate_dense_chunk_size_kernel. */
 int fnx_png_encoded_size(fnx_ctx *ctx, int space, int kind, const uint8_t *src, int sstride, int w, int h, int ncolors /* paletted: 1..256 */,
                          int opaque /* 1, 0, or -1 */, const uint8_t *palette, size_t *nbytes);
+
+/* ---- CRC-32 on the device (csrc/crc32.hip) ---------------------------------------------------------------------------- */
+/* PNG's and zlib's CRC-32 (reflected polynomial 0xedb88320, register from all ones, inverted at the end).  The bytes are cut
+ * into pieces of FNX_CRC_PIECE bytes, one workgroup each, a lane a contiguous run of FNX_CRC_RUN bytes (slice-by-4 from tables
+ * in shared memory); the lanes' remainders are folded inside the workgroup, and a second kernel folds the pieces' words and
+ * the seed into the answer -- a CRC is as combinable as deflate's Adler-32: with R(M) the register after M from 0,
+ * R(A B) = R(A) x^(8 |B|) xor R(B) mod the polynomial.  No workgroup waits for another; the result is a function of the bytes.
+ * DESIGN.md section 5.17. */
+#define FNX_CRC_RUN   64      /* bytes per lane */
+#define FNX_CRC_PIECE 16384   /* bytes per workgroup = 256 runs */
+/* *out = zlib.crc32(src[0 .. n), crc): crc is the finished CRC of what came before, 0 for none.  space: FNX_HOST (src is
+ * uploaded first) or FNX_DEVICE (resident bytes, any alignment).  n == 0: *out = crc, nothing launched.  Bad arguments are
+ * refused before anything is launched.  One host wait.  Kernels: crc32_pieces_kernel (the one fnx_ctx_last_kernel(ctx,
+ * FNX_PROF_MAIN) names), crc32_fold_kernel. */
+int fnx_crc32(fnx_ctx *ctx, int space, const uint8_t *src, size_t n, uint32_t crc, uint32_t *out);
+/* Where the IDAT chunk's CRC of the PNG files ONE ctx makes from a device deflate comes from.  FNX_PNG_CRC_HOST (default): the
+ * host walks the chunk's bytes once they have come down, as before the setting existed.  FNX_PNG_CRC_DEVICE: the CRC kernels
+ * above read the gathered zlib stream where deflate_gather_kernel / deflate_gather_batch_kernel left it (grid sized by
+ * fnx_deflate_bound, the stream's length read on the device from the gather's size word, the batch's streams found by the
+ * gather's size words; seed: the register after "IDAT"), and the CRC word comes down with a copy the route makes anyway -- the
+ * size fetch of the single route, the sizes of the batch's second wait: no further host wait.  The files are byte for byte the
+ * host mode's, at either deflate level.  Followed by every entry that makes a PNG file from a device deflate with this ctx:
+ * fnx_png_encode, fennec_CompressFilePNG, fnx_hit_target_size's winner file, fennec_CompressFileHitTargetSize,
+ * fnx_png_compress_batch, fnx_png_recompress_batch; their kernel list in fnx_ctx_last_kernel(ctx, FNX_PROF_MAIN) then also
+ * names crc32_pieces_kernel (the batch: crc32_pieces_batch_kernel).  The small chunks (IHDR, PLTE, tRNS, IEND) keep the host's
+ * CRC.  Routes whose deflate runs on the host ignore the setting: fennec_CompressFilePNGStream, the Python binding's
+ * compress_png without device_deflate, the fennec_CompressBatch* pools, the Go shim.  ctx == NULL or any other mode:
+ * FNX_ERR_INVALID, nothing changed. */
+#define FNX_PNG_CRC_HOST   0
+#define FNX_PNG_CRC_DEVICE 1
+int fnx_ctx_set_png_crc(fnx_ctx *ctx, int mode);
 
 /* ---- PNG sources: loadImage's image.Decode + toNRGBA for a .png (io.go:65-88 -> convert.go:12-64) --------------------- */
 /* The zlib stream src[0 .. n) (RFC 1950: CM 8, CINFO <= 7, FCHECK; a preset dictionary is refused) of stored, fixed and dynamic
