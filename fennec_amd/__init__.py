@@ -172,6 +172,7 @@ def load_library() -> C.CDLL:
         _sig(L, "fnx_ctx_kernel_ms", i, [ctx, C.POINTER(C.c_float)])
         _sig(L, "fnx_ctx_last_kernel", C.c_char_p, [ctx, i])
         _sig(L, "fnx_ctx_set_form", i, [ctx, C.c_char_p, C.c_char_p])
+        _sig(L, "fnx_ctx_resize_mfma_report", i, [ctx, C.POINTER(C.c_uint), C.POINTER(C.c_uint)])
         _sig(L, "fnx_ctx_set_ssim_mode", i, [ctx, i])
         _sig(L, "fnx_ctx_set_png_adam7", i, [ctx, i])
         _sig(L, "fnx_ctx_set_deflate_level", i, [ctx, i])
@@ -194,6 +195,7 @@ def load_library() -> C.CDLL:
         _sig(L, "fnx_resize_h", i, [ctx, i] + img + [i, i, _i32p, _i32p, _f64p] + img + [i])
         _sig(L, "fnx_resize_v", i, [ctx, i] + img + [i, i, _i32p, _i32p, _f64p] + img + [i])
         _sig(L, "fnx_lanczos_resize", i, [ctx, i] + img + [i, i, _i32p, _i32p, _f64p, _i32p, _i32p, _f64p] + img + [i, i])
+        _sig(L, "fnx_resize_fixed_point", i, [_i32p, _i32p, _f64p, i, i, C.POINTER(i), C.POINTER(i), _i32p, _i32p, _i32p])
         _sig(L, "fnx_box_downsample", i, [ctx, i] + img + [i, i] + img + [i, i])
         tabs = [_i32p, _i32p, _f64p, _i32p, _i32p, _f64p]   # offH, idxH, wH, offV, idxV, wV
         _sig(L, "fnx_lanczos_box_downsample", i, [ctx, i] + img + [i, i] + tabs + [i, i] + img + [i, i])
@@ -467,6 +469,14 @@ class Context:
         if s is None:
             raise FennecError("fnx_ctx_last_kernel: bad class")
         return s.decode()
+
+    def resize_mfma_report(self):
+        """fnx_ctx_resize_mfma_report, after sync(): (gave_up, workgroups) of this ctx's most recent resize call that launched
+        resize_mfma_kernel -- how many of its workgroups handed their region back to resize_fused_sparse_kernel, and how many
+        it launched; workgroups == 0: no such call on record.  Reporting only."""
+        g, n = C.c_uint(0), C.c_uint(0)
+        self._chk(self._lib.fnx_ctx_resize_mfma_report(self._h, C.byref(g), C.byref(n)), "fnx_ctx_resize_mfma_report")
+        return int(g.value), int(n.value)
 
     def set_ssim_mode(self, fast: bool) -> None:
         """fnx_ctx_set_ssim_mode: fp32 moments (<= 1e-6) instead of fp64 (<= 1e-9) for full-resolution SSIM planes"""
@@ -2426,6 +2436,26 @@ def blur_fixed_point(kernel):
     if rc != 0:
         raise RuntimeError("fnx_blur_fixed_point failed")
     return np.array(list(wq), dtype=np.int64), float(err.value)
+
+
+def resize_fixed_point(table, src_n):
+    """fnx_resize_fixed_point: (S, G, first, count, wq) of one CSR tap table (off, idx, wt) over src_n source px as the
+    matrix-pipe resize kernel quantises it -- first / count: int32 per output, wq: int64 of shape (nout, 16), zeros behind the
+    taps -- or None when the table is not that kernel's.  Host arithmetic only."""
+    off, idx, wt = table
+    off, po = _i32(off); idx, pi = _i32(idx); wt, pw = _f64(wt)
+    nout = len(off) - 1
+    S, G = C.c_int(0), C.c_int(0)
+    first = np.zeros(max(nout, 1), dtype=np.int32)
+    count = np.zeros(max(nout, 1), dtype=np.int32)
+    wq = np.zeros((max(nout, 1), 16), dtype=np.int32)
+    rc = load_library().fnx_resize_fixed_point(po, pi, pw, nout, int(src_n), C.byref(S), C.byref(G), first.ctypes.data_as(_i32p),
+                                               count.ctypes.data_as(_i32p), wq.ctypes.data_as(_i32p))
+    if rc == FNX_NOOP:
+        return None
+    if rc != 0:
+        raise FennecError("fnx_resize_fixed_point: " + (load_library().fnx_last_error() or b"").decode())
+    return int(S.value), int(G.value), first, count, wq.astype(np.int64)
 
 
 def blurKernel(sigma):

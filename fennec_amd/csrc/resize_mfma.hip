@@ -456,18 +456,27 @@ void resize_mfma_free(RzMfTable *t)
     *t = RzMfTable();
 }
 
-// The matrix form of one tap table; false (nothing allocated): outside what the kernel covers.
+// The fixed point of one tap table: S, the guard G and per output the first source index, the tap count and the integer
+// weights Wq (sum Wq = 2^S).  false: outside what the kernel covers.  Stated once: resize_mfma_build lays its matrices out
+// from this, fnx_resize_fixed_point hands it to callers and tests as it is.
 // `inv`: 1 / a per output as the guard form computed it (resize.hip: build_guard, a = sum of 255 w in tap order).
-bool resize_mfma_build(const fnx_ctx *ctx, const TapTable &t, int srcN, bool vertical, const double *inv, RzMfTable *out)
+struct RmQuant {
+    int S = 22;
+    long long gq = 0;
+    std::vector<int> first, cnt;
+    std::vector<std::vector<long long>> wq;
+};
+
+static bool rm_quantise(const TapTable &t, int srcN, const double *inv, RmQuant *q)
 {
-    *out = RzMfTable();
-    const int mode = resize_mfma_mode(ctx);
     const int nout = t.nout;
-    if (mode == 0 || nout < 16 || srcN < 16) return false;
-    if (mode == 1 && 4 * srcN < 5 * nout) return false;              // (the header's last paragraph)
+    if (nout < 16 || srcN < 16) return false;
     // fixed-point weights per output
-    std::vector<std::vector<long long>> wq(nout);
-    std::vector<int> first(nout), cnt(nout);
+    std::vector<std::vector<long long>> &wq = q->wq;
+    std::vector<int> &first = q->first, &cnt = q->cnt;
+    wq.assign(nout, std::vector<long long>());
+    first.assign(nout, 0);
+    cnt.assign(nout, 0);
     long double emax = 0, wmax = 0;
     std::vector<std::vector<long double>> Wr(nout);
     for (int d = 0; d < nout; d++) {
@@ -522,6 +531,25 @@ bool resize_mfma_build(const fnx_ctx *ctx, const TapTable &t, int srcN, bool ver
     // G: the fixed-point bound, the reference's own fp64 chain (< 1e-11 = 4e-5 units) and two units for this arithmetic
     const long long gq = static_cast<long long>(ceill(emax)) + 2;
     if (gq > (1 << 14)) return false;
+    q->S = S;
+    q->gq = gq;
+    return true;
+}
+
+// The matrix form of one tap table; false (nothing allocated): outside what the kernel covers.
+bool resize_mfma_build(const fnx_ctx *ctx, const TapTable &t, int srcN, bool vertical, const double *inv, RzMfTable *out)
+{
+    *out = RzMfTable();
+    const int mode = resize_mfma_mode(ctx);
+    const int nout = t.nout;
+    if (mode == 0) return false;
+    if (mode == 1 && 4 * srcN < 5 * nout) return false;              // (the header's last paragraph)
+    RmQuant q;
+    if (!rm_quantise(t, srcN, inv, &q)) return false;
+    const std::vector<std::vector<long long>> &wq = q.wq;
+    const std::vector<int> &first = q.first, &cnt = q.cnt;
+    const int S = q.S;
+    const long long gq = q.gq;
     out->S = S;
     out->seed = static_cast<int>((192u << S) + (1u << (S - 1)) + static_cast<uint32_t>(gq));     // 128 (the bytes' offset) + 64 (the sums')
     out->thr = static_cast<int>(2 * gq);
@@ -706,3 +734,43 @@ int resize_mfma_launch(fnx_ctx *ctx, const RzMfTable &h, const RzMfTable &v,
 }
 
 }  // namespace fnx
+
+extern "C" int fnx_resize_fixed_point(const int32_t *offset, const int32_t *index, const double *weight, int nout, int srcN,
+                                      int *S, int *G, int32_t *first, int32_t *count, int32_t *wq)
+{
+    if (!offset || !index || !weight || !S || !G || !first || !count || !wq || nout < 1 || srcN < 1) {
+        fnx::set_error("invalid argument: fnx_resize_fixed_point");
+        return FNX_ERR_INVALID;
+    }
+    for (int d = 0; d < nout; d++) {
+        if (offset[d] < 0 || offset[d + 1] < offset[d]) {
+            fnx::set_error("fnx_resize_fixed_point: tap table offsets");
+            return FNX_ERR_INVALID;
+        }
+    }
+    for (int i = offset[0]; i < offset[nout]; i++) {
+        if (index[i] < 0 || index[i] >= srcN) {
+            fnx::set_error("fnx_resize_fixed_point: tap index outside the source");
+            return FNX_ERR_INVALID;
+        }
+    }
+    fnx::TapTable t;
+    t.off = offset; t.idx = index; t.wt = weight; t.nout = nout;
+    // 1 / a as build_guard (resize.hip) computes it: a = the sum of 255 w in tap order
+    std::vector<double> inv(nout);
+    for (int d = 0; d < nout; d++) {
+        double a = 0;
+        for (int k = offset[d]; k < offset[d + 1]; k++) a += 255.0 * weight[k];
+        inv[d] = 1.0 / a;
+    }
+    fnx::RmQuant q;
+    if (!fnx::rm_quantise(t, srcN, inv.data(), &q)) return FNX_NOOP;
+    *S = q.S;
+    *G = static_cast<int>(q.gq);
+    for (int d = 0; d < nout; d++) {
+        first[d] = q.first[d];
+        count[d] = q.cnt[d];
+        for (int k = 0; k < fnx::RM_MAXTAPS; k++) wq[fnx::RM_MAXTAPS * d + k] = k < q.cnt[d] ? static_cast<int32_t>(q.wq[d][k]) : 0;
+    }
+    return FNX_OK;
+}

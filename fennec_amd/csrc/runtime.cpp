@@ -584,6 +584,23 @@ const char *fnx_ctx_last_kernel(fnx_ctx *ctx, int prof_class)
     return ctx->route[i];
 }
 
+int fnx_ctx_resize_mfma_report(fnx_ctx *ctx, unsigned *gave_up, unsigned *workgroups)
+{
+    if (!ctx || !gave_up || !workgroups) { fnx::set_error("fnx_ctx_resize_mfma_report: null argument"); return FNX_ERR_INVALID; }
+    *gave_up = *workgroups = 0;
+    if (!ctx->rz_report || ctx->rz_last_gen == 0) return FNX_OK;     // no launch of resize_mfma_kernel on record
+    // the word resize_fused_sparse_kernel leaves behind the matrix kernel (gen << 32 | workgroups that gave up); only read here:
+    // resize_fused's cool-down reads the same word at the next call
+    const unsigned long long repv = *reinterpret_cast<volatile unsigned long long *>(ctx->rz_report);
+    if (static_cast<uint32_t>(repv >> 32) != ctx->rz_last_gen) {
+        fnx::set_error("fnx_ctx_resize_mfma_report: the last resize has not finished (fnx_ctx_sync first)");
+        return FNX_ERR_INVALID;
+    }
+    *gave_up = static_cast<unsigned>(repv & 0xffffffffull);
+    *workgroups = static_cast<unsigned>(ctx->rz_last_cells);
+    return FNX_OK;
+}
+
 int fnx_ctx_kernel_ms(fnx_ctx *ctx, float *ms)
 {
     FNX_TRY(bind_quiet(ctx));

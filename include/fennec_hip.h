@@ -261,6 +261,31 @@ int fnx_lanczos_resize(fnx_ctx *ctx, int space, const uint8_t *src, int sstride,
                        int srcH, const int32_t *offH, const int32_t *idxH, const double *wH,
                        const int32_t *offV, const int32_t *idxV, const double *wV,
                        uint8_t *dst, int dstride, int dstW, int dstH);
+/* The fixed-point form the matrix-pipe resize kernel (csrc/resize_mfma.hip: resize_mfma_kernel) gives ONE tap table of
+ * nout outputs over srcN source px, for callers and tests that want to reason about it -- the very arithmetic the plan
+ * builder runs (one function serves both), as under fnx_ctx_set_form(ctx, "resize_mfma", "2"):
+ *   *S            the weights' binary point, 22 or 23 (23 where every |W_k| 2^23 <= 8355000; W_k = fl(255 w_k) * inv, inv =
+ *                 1.0 / a, a = the sum of fl(255 w_k) in tap order)
+ *   *G            the rounding guard in units of 2^-S: ceil(255 max(P, N)) + 2, P / N the largest sums of the positive /
+ *                 negative differences Wq_k - W_k 2^S of one output
+ *   first[d], count[d], wq[16 d .. 16 d + count[d])   output d's first source index, taps (<= 16) and integer weights, whose
+ *                 sum is 2^S exactly (zeros behind the taps)
+ * With u = sum_k Wq_k (R_k - 128) + (192 << S) + 2^(S-1) + G, an exact uint32, the kernel writes clamp((u >> S) - 64, 0, 255)
+ * unless u mod 2^S < 2 G: such a sample is recomputed in fp64 in the reference's own order (resize.go:95-112).
+ * Host arithmetic only: no ctx, no device.  FNX_NOOP: the table is not the kernel's (nout or srcN below 16, an output with
+ * more than 16 taps or a gap in its indices, a outside [254.5, 255.5), negative lobes beyond 63 / 255, a weight three signed
+ * base-256 digits do not reach) -- nothing is written.  FNX_ERR_INVALID: a NULL pointer, decreasing offsets, an index
+ * outside the source.  What a plan adds for the H or V direction (window widths of a 16-output group) is not covered here.
+ * No reference counterpart. */
+int fnx_resize_fixed_point(const int32_t *offset, const int32_t *index, const double *weight, int nout, int srcN,
+                           int *S, int *G, int32_t *first /* nout */, int32_t *count /* nout */, int32_t *wq /* 16*nout */);
+/* What became of the workgroups of the ctx's most recent resize call that launched resize_mfma_kernel (a batch counts as
+ * one call), to be asked after fnx_ctx_sync: *workgroups = how many it launched, *gave_up = how many of them handed their
+ * region back to resize_fused_sparse_kernel (translucent pixels, a set dense with flagged samples).  *workgroups == 0: no
+ * such call is on record (none yet, or a later resize call has taken the count for its cool-down decision).  Reporting
+ * only, as fnx_ctx_last_kernel: reading it changes nothing, the cool-down reads the same word at the next call.  NULL ctx or
+ * outputs, or a call still running: FNX_ERR_INVALID.  No reference counterpart. */
+int fnx_ctx_resize_mfma_report(fnx_ctx *ctx, unsigned *gave_up, unsigned *workgroups);
 /* lanczosResize of n same-geometry DEVICE images (srcs / dsts: host arrays of device pointers) with one tap-table pair: the
  * bytes of n fnx_lanczos_resize calls, enqueued as ONE set of launches where the one-launch kernels apply (a 4K resize
  * alone is ~700 workgroups on 768-1024 resident slots: one under-filled round; a batch fills the machine and pays the

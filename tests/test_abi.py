@@ -95,6 +95,32 @@ def test_last_kernel_needs_a_ctx_and_the_library_names_the_fx_routes(lib):
             assert (kernel + tail).encode() + b"\0" in blob, kernel + tail
 
 
+def test_resize_reports_refuse_null_arguments(lib):
+    """fnx_ctx_resize_mfma_report and fnx_resize_fixed_point (reporting only, the latter host arithmetic without a ctx): both
+    are exported, a NULL ctx or NULL outputs are FNX_ERR_INVALID, and a table outside the kernel's domain is FNX_NOOP"""
+    C = ctypes
+    names = fennec_amd.exported_symbols()
+    assert "fnx_ctx_resize_mfma_report" in names and "fnx_resize_fixed_point" in names
+    g, n = C.c_uint(7), C.c_uint(7)
+    assert lib.fnx_ctx_resize_mfma_report(None, C.byref(g), C.byref(n)) == fennec_amd.FNX_ERR_INVALID and lib.fnx_last_error()
+    assert (g.value, n.value) == (7, 7)
+    off, idx, wt = fennec_amd.precomputeWeights(32, 64)
+    i32p, f64p = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    po, pi, pw = off.ctypes.data_as(i32p), idx.ctypes.data_as(i32p), wt.ctypes.data_as(f64p)
+    S, G = C.c_int(0), C.c_int(0)
+    first, count, wq = np.zeros(32, np.int32), np.zeros(32, np.int32), np.zeros(32 * 16, np.int32)
+    pf, pc, pq = (a.ctypes.data_as(i32p) for a in (first, count, wq))
+    assert lib.fnx_resize_fixed_point(po, pi, pw, 32, 64, C.byref(S), C.byref(G), pf, pc, pq) == fennec_amd.FNX_OK
+    assert S.value == 23 and G.value > 2 and int(wq[:16].sum()) == 1 << 23 and count[0] >= 1
+    for args in ((None, pi, pw, 32, 64, C.byref(S), C.byref(G), pf, pc, pq), (po, None, pw, 32, 64, C.byref(S), C.byref(G), pf, pc, pq),
+                 (po, pi, None, 32, 64, C.byref(S), C.byref(G), pf, pc, pq), (po, pi, pw, 32, 64, None, C.byref(G), pf, pc, pq),
+                 (po, pi, pw, 32, 64, C.byref(S), None, pf, pc, pq), (po, pi, pw, 32, 64, C.byref(S), C.byref(G), None, pc, pq),
+                 (po, pi, pw, 32, 64, C.byref(S), C.byref(G), pf, None, pq), (po, pi, pw, 32, 64, C.byref(S), C.byref(G), pf, pc, None),
+                 (po, pi, pw, 0, 64, C.byref(S), C.byref(G), pf, pc, pq), (po, pi, pw, 32, 63, C.byref(S), C.byref(G), pf, pc, pq)):
+        assert lib.fnx_resize_fixed_point(*args) == fennec_amd.FNX_ERR_INVALID, args[3:5]
+    assert lib.fnx_resize_fixed_point(po, pi, pw, 15, 64, C.byref(S), C.byref(G), pf, pc, pq) == fennec_amd.FNX_NOOP
+
+
 def test_table_generators_match_oracle(lib, orc):
     assert np.array_equal(fennec_amd.gaussianKernel(), orc.gaussian_kernel())
     for s in (0.3, 1.0, 2.0, 2.5, 20.0):
