@@ -31,7 +31,7 @@ struct PassArgs2 {
     const uint8_t *const *srcs;
     int sstride, w, h;
     int upr;                 // 4-px units per row (tight images: ONE row of w*h px)
-    uint32_t upr_magic;      // ceil(2^32 / upr)
+    uint32_t upr_magic;      // ceil(2^32 / upr) for upr > 1 (an_row_of)
     int rows, row_px;        // iteration space: rows x row_px pixels
     int vec;                 // 16-byte loads allowed
     long long units;
@@ -49,6 +49,13 @@ __device__ __forceinline__ int an_pixel(uint32_t p, double &bright, uint32_t &fl
     const uint32_t r = p & 0xffu, g = (p >> 8) & 0xffu, b = (p >> 16) & 0xffu;
     flags |= ((p >> 24) < 255u ? 1u : 0u) | ((r != g || g != b) ? 2u : 0u);
     return static_cast<int>(lum + 0.5);                        // analyze.go:64
+}
+
+// row of unit u in a strided image: u / upr by the host's magic (u < 2^32 / upr is checked there).  One unit per row (w <= 4)
+// has no magic -- ceil(2^32 / 1) does not fit the word, it arrives as 0 and every unit landed in row 0: the row is u itself.
+__device__ __forceinline__ int an_row_of(long long u, int upr, uint32_t upr_magic)
+{
+    return upr == 1 ? static_cast<int>(u) : static_cast<int>(__umulhi(static_cast<uint32_t>(u), upr_magic));
 }
 
 // two histogram increments; equal bins (flat image areas) become ONE atomic of 2
@@ -81,7 +88,7 @@ __global__ __launch_bounds__(256) void analyze_pass_kernel(PassArgs2 a)
         int y = 0;
         long long c = u;
         if (a.rows > 1) {
-            y = __umulhi(static_cast<uint32_t>(u), a.upr_magic);   // u < 2^32 / upr is checked by the host
+            y = an_row_of(u, a.upr, a.upr_magic);
             c = u - static_cast<long long>(y) * a.upr;
         }
         const long long x = 4 * c;
@@ -340,6 +347,7 @@ int launch_analyze(fnx_ctx *ctx, int n, const uint8_t *src, const uint8_t *const
         return FNX_ERR_INVALID;
     }
     pa.row_px = static_cast<int>(row_px);
+    note_route(ctx, FNX_PROF_MAIN, "analyze_pass_kernel");
     FNX_TRY(prof_begin(ctx));
     hipLaunchKernelGGL(analyze_pass_kernel, dim3(G, n), dim3(256), 0, ctx->stream, pa);
     FNX_HIP(hipGetLastError());
@@ -456,7 +464,7 @@ __global__ __launch_bounds__(AN1_T) void analyze_one_kernel(An1Args a)
             int y = 0;
             long long c = u;
             if (a.p.rows > 1) {
-                y = __umulhi(static_cast<uint32_t>(u), a.p.upr_magic);
+                y = an_row_of(u, a.p.upr, a.p.upr_magic);
                 c = u - static_cast<long long>(y) * a.p.upr;
             }
             const long long x = 4 * c;

@@ -1490,11 +1490,12 @@ void fnx_prepared_free(fnx_ctx *ctx, fnx_prepared *p)
 
 // ---- Analyze (analyze.go:26-124) and the flat scans (convert.go:66-84) --------------------
 // One launch per call (analyze.hip: analyze_one_kernel): the results land in pinned host memory, each image's ready word
-// after them; this thread watches the words (FNX_ANALYZE_STAGED=1: the staged launches of rounds 1-4, A/B and tests).
-static bool analyze_staged()
+// after them; this thread watches the words.  Form "analyze_staged" = "1": the staged launches (launch_analyze) for every
+// call -- what a batch of more than 4096 images takes -- for A/B and tests.
+static bool analyze_staged(const fnx_ctx *ctx)
 {
-    static const bool v = [] { const char *e = dev_env("FNX_ANALYZE_STAGED"); return e && e[0] == '1'; }();
-    return v;
+    const char *e = form_value(ctx, FORM_ANALYZE_STAGED);
+    return e && e[0] == '1';
 }
 
 static int analyze_direct(fnx_ctx *ctx, int n, const uint8_t *src, const uint8_t *const *srcs, int sstride, int w, int h, bool al,
@@ -1543,7 +1544,7 @@ int fnx_analyze(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w,
     DevImg s;
     FNX_TRY(stage_in(ctx, space, src, sstride, w, h, SLOT_IN_A, &s));
     const bool al = (reinterpret_cast<uintptr_t>(s.p) & 15u) == 0;
-    if (!analyze_staged()) {
+    if (!analyze_staged(ctx)) {
         FNX_TRY(analyze_direct(ctx, 1, s.p, nullptr, s.stride, w, h, al, out));
     } else {
         void *dres = nullptr;
@@ -1566,7 +1567,7 @@ int fnx_analyze_batch(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sstri
     const bool al = all_aligned16(n, srcs, 0);
     void *dp = nullptr;
     FNX_TRY(upload_table(ctx, SLOT_PTRS, srcs, sizeof(void *) * size_t(n), &dp));
-    if (!analyze_staged() && n <= 4096) {
+    if (!analyze_staged(ctx) && n <= 4096) {
         FNX_TRY(analyze_direct(ctx, n, nullptr, static_cast<const uint8_t *const *>(dp), sstride, w, h, al, out));
     } else {
         void *dres = nullptr;

@@ -40,6 +40,7 @@ enum Form {
     FORM_MSSSIM_FOLD,        // "msssim_fold":     "0" = a finish launch instead of the fold in the window kernel
     FORM_MSSSIM_BOXFLY,      // "msssim_boxfly":   "1" = levels 1..4's boxes taken on the fly
     FORM_PALETTE_GRID,       // "palette_grid":    "0" every image walks the whole palette / "1" every image takes the grid
+    FORM_ANALYZE_STAGED,     // "analyze_staged":  "1" = analyze.hip's staged launches (what batches of more than 4096 images take) instead of the one-launch form
     FORM_RESIZE_BOX,         // "resize_box":      "1" = resize_box_kernel where its domain allows (default: the resize kernels, then the box kernel)
     FORM_JPEG_SIZE,          // "jpeg_size":       "1" = a size-only JPEG query counts the stuffed bytes from the strips, one wait (default: packed and stuffed as a file is)
     FORM_COUNT

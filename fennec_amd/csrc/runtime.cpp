@@ -99,7 +99,8 @@ OpRange::~OpRange()
 }
 
 static const char *const FORM_NAMES[FORM_COUNT] = {"fx_stream", "fx_pairs", "fx_ref", "resize_mfma", "resize_fp64", "resize_fused",
-                                                   "msssim_levelwise", "msssim_nofuse0", "msssim_fold", "msssim_boxfly", "palette_grid", "resize_box", "jpeg_size"};
+                                                   "msssim_levelwise", "msssim_nofuse0", "msssim_fold", "msssim_boxfly", "palette_grid", "analyze_staged", "resize_box",
+                                                   "jpeg_size"};
 
 const char *form_value(const fnx_ctx *ctx, Form f)
 {

@@ -184,6 +184,9 @@ int fnx_ctx_set_png_adam7(fnx_ctx *ctx, int accept);
  *   "resize_fused" "0"     the two-pass resize kernels
  *   "msssim_levelwise" "1", "msssim_nofuse0" "1", "msssim_fold" "0", "msssim_boxfly" "1"   MSSSIM's launch structure
  *   "palette_grid" "0|1"   applyPalette: whole-palette walk for every image / the candidate grid for every image
+ *   "analyze_staged" "1"   fnx_analyze, fnx_analyze_batch: the staged launches (analyze_pass_kernel and the kernels after it) for
+ *                          every call ("0" and the default: one launch, analyze_one_kernel, and the staged launches for a batch
+ *                          of more than 4096 images).  fnx_ctx_last_kernel(ctx, FNX_PROF_MAIN) names the route's first kernel
  *   "resize_box" "1"       fnx_lanczos_box_downsample, fnx_ssim_fast_resized, target-size mode: resize_box_kernel where its
  *                          domain allows ("0" and the default: lanczosResize into scratch, then the box kernel)
  *   "jpeg_size" "1"        a size-only JPEG query (out == NULL with cap == 0 in fnx_jpeg_encode / _encode_scaled, every query of

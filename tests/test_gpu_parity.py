@@ -27,7 +27,7 @@ def _module_ctx():
 
 
 FORM_NAMES = ("fx_stream", "fx_pairs", "fx_ref", "resize_mfma", "resize_fp64", "resize_fused", "msssim_levelwise",
-              "msssim_nofuse0", "msssim_fold", "msssim_boxfly", "palette_grid")
+              "msssim_nofuse0", "msssim_fold", "msssim_boxfly", "palette_grid", "analyze_staged")
 
 
 @pytest.fixture()
@@ -1379,31 +1379,7 @@ def test_device_views_at_4_byte_alignment(ctx, orc):
 
 
 # ------------------------------------------------------------------ Analyze (analyze.go), SURVEY 8(f).3
-def _serial_sum_tol(n):
-    """brightSum is ONE serial fp64 chain over all n pixels in the reference (analyze.go:63): its
-    own rounding error is bounded by (n-1)*2^-53 relative (1.1e-12 observed at 4K, against the
-    exact sum); the device's fixed-tree sum is closer to exact, so the bar is the chain's bound."""
-    return max(1e-12, n * 2.0 ** -53)
-
-
-
-def _check_analysis(raw, st, want):
-    """raw = fnx_analyze's accumulators, st = ImageStats dict, want = oracle."""
-    assert np.array_equal(raw["histogram"].astype(np.float64), want["histogram"])      # exact
-    for k in ("has_alpha", "is_grayscale", "unique_colors", "sample_count", "edge_count", "edge_total"):
-        assert raw[k] == want[k], k
-    rel = _serial_sum_tol(want["width"] * want["height"])
-    assert abs(raw["bright_sum"] - want["bright_sum"]) <= rel * abs(want["bright_sum"])
-    # (lum - mean)^2 terms inherit the mean's last-bit difference: absolute floor for flat images
-    assert abs(raw["variance_sum"] - want["variance_sum"]) <= 1e-9 * abs(want["variance_sum"]) + 1e-6
-    assert (st["Width"], st["Height"]) == (want["width"], want["height"])
-    assert (st["HasAlpha"], st["IsGrayscale"], st["UniqueColors"]) == (want["has_alpha"], want["is_grayscale"], want["unique_colors"])
-    assert abs(st["Entropy"] - want["entropy"]) <= 1e-12
-    assert st["EdgeDensity"] == want["edge_density"]
-    assert abs(st["MeanBrightness"] - want["mean_brightness"]) <= rel * max(1.0, want["mean_brightness"])
-    assert abs(st["Contrast"] - want["contrast"]) <= 1e-9
-    assert (st["RecommendedFormat"], st["RecommendedQuality"]) == (want["recommended_format"], want["recommended_quality"])
-    assert st["EstimatedCompression"] == want["estimated_compression"]
+from analyze_cases import _check_analysis, _serial_sum_tol      # (the bars live beside the crafted cases: tests/analyze_cases.py)
 
 
 ANALYZE_IMAGES = dict(IMAGES)
