@@ -47,6 +47,7 @@ FNX_PNG_COMPRESS_CHUNK = 32                                   # fnx_png_compress
 FNX_DEFLATE_CHUNK, FNX_DEFLATE_SUB = 32768, 128               # deflate.hip: bytes per chunk (= per workgroup, per block) and per lane
 FNX_DEFLATE_LEVEL_FAST, FNX_DEFLATE_LEVEL_DENSE = 0, 1         # fnx_ctx_set_deflate_level
 FNX_JPEG_HUFFMAN_STANDARD, FNX_JPEG_HUFFMAN_OPTIMIZED = 0, 1   # fnx_ctx_set_jpeg_huffman
+FNX_JPEG_SUBSAMPLING_420, FNX_JPEG_SUBSAMPLING_444 = 0, 1      # fnx_ctx_set_jpeg_subsampling
 FNX_DEFLATE_DENSE_DEPTH = 32                                   # the dense level: the most chain candidates a position tries
 FNX_CRC_RUN, FNX_CRC_PIECE = 64, 16384                         # crc32.hip: bytes per lane and per workgroup
 FNX_PNG_CRC_HOST, FNX_PNG_CRC_DEVICE = 0, 1                    # fnx_ctx_set_png_crc
@@ -177,6 +178,7 @@ def load_library() -> C.CDLL:
         _sig(L, "fnx_ctx_set_png_adam7", i, [ctx, i])
         _sig(L, "fnx_ctx_set_deflate_level", i, [ctx, i])
         _sig(L, "fnx_ctx_set_jpeg_huffman", i, [ctx, i])
+        _sig(L, "fnx_ctx_set_jpeg_subsampling", i, [ctx, i])
         _sig(L, "fnx_ctx_set_png_crc", i, [ctx, i])
         _sig(L, "fnx_crc32", i, [ctx, i, _u8p, C.c_size_t, C.c_uint32, C.POINTER(C.c_uint32)])
         _sig(L, "fnx_jpeg_symbol_histogram", i, [ctx, i] + img + [i, i, i, C.POINTER(C.c_uint32)])
@@ -512,6 +514,19 @@ class Context:
                 raise FennecError(f"set_jpeg_huffman: 'standard' or 'optimized', not {mode!r}")
             mode = names[mode]
         self._chk(self._lib.fnx_ctx_set_jpeg_huffman(self._h, int(mode)), "fnx_ctx_set_jpeg_huffman")
+
+    def set_jpeg_subsampling(self, mode) -> None:
+        """fnx_ctx_set_jpeg_subsampling: "420" (FNX_JPEG_SUBSAMPLING_420, the default: the bytes the library always wrote) or
+        "444" (FNX_JPEG_SUBSAMPLING_444: chroma at full resolution, every component at sampling 1 x 1) for the single-image
+        entries of this ctx: jpeg_roundtrip, jpeg_quality_search, jpeg_encode, jpeg_encoded_size, jpeg_compress,
+        jpeg_size_search, jpeg_symbol_histogram.  Every other JPEG-writing entry refuses a ctx set to "444" (FennecError,
+        FNX_ERR_UNSUPPORTED).  The integer constants are accepted too."""
+        if isinstance(mode, str):
+            names = {"420": FNX_JPEG_SUBSAMPLING_420, "444": FNX_JPEG_SUBSAMPLING_444}
+            if mode not in names:
+                raise FennecError(f"set_jpeg_subsampling: '420' or '444', not {mode!r}")
+            mode = names[mode]
+        self._chk(self._lib.fnx_ctx_set_jpeg_subsampling(self._h, int(mode)), "fnx_ctx_set_jpeg_subsampling")
 
     def set_png_crc(self, mode) -> None:
         """fnx_ctx_set_png_crc: "host" (FNX_PNG_CRC_HOST, the default: the host walks the IDAT chunk once its bytes have come

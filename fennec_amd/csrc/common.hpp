@@ -232,6 +232,7 @@ struct fnx_ctx {
     const char *route[8] = {"", "", "", "", "", "", "", ""};
     int png_adam7 = 0;           // fnx_ctx_set_png_adam7: 1 -- the PNG entries decode Adam7-interlaced files instead of refusing them
     int jpeg_huffman = 0;        // fnx_ctx_set_jpeg_huffman: FNX_JPEG_HUFFMAN_STANDARD / _OPTIMIZED -- the tables of every JPEG file (and size) this ctx makes
+    int jpeg_subsampling = 0;    // fnx_ctx_set_jpeg_subsampling: FNX_JPEG_SUBSAMPLING_420 / _444 -- the single-image JPEG entries follow it, the others refuse 4:4:4
     int deflate_level = 0;       // fnx_ctx_set_deflate_level: FNX_DEFLATE_LEVEL_FAST / _DENSE -- which chunk kernels launch_deflate and launch_deflate_batch run
     int png_crc = 0;             // fnx_ctx_set_png_crc: FNX_PNG_CRC_HOST / _DEVICE -- where the IDAT CRC of this ctx's device-deflated PNG files comes from
     int ssim_mode = 0;           // fnx_ctx_set_ssim_mode: FNX_SSIM_EXACT (fp64 moments) / FNX_SSIM_FAST (fp32 moments for full-resolution planes)
@@ -658,10 +659,11 @@ int launch_ycbcr_to_nrgba(fnx_ctx *ctx, const uint8_t *y, int ystride, const uin
                           int cstride, int ratio, int w, int h, uint8_t *dst, int dstride);
 int launch_orient(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, int orient,
                   uint8_t *dst, int dstride);
-// jpeg.hip: plane geometry of the 4:2:0 round trip (Y: ys x yh, Cb / Cr: cs x ch), the quality-independent colour
-// conversion + chroma averaging, and fdct / quantise / dequantise / idct of every block at `quality` (in -> out)
-void jpeg_plane_dims(int w, int h, int *ys, int *yh, int *cs, int *ch);
-int launch_jpeg_ycc(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, uint8_t *yp, uint8_t *cbp, uint8_t *crp);
+// jpeg.hip: plane geometry of the round trip (Y: ys x yh, Cb / Cr: cs x ch), the quality-independent colour
+// conversion + chroma averaging, and fdct / quantise / dequantise / idct of every block at `quality` (in -> out).
+// mode: FNX_JPEG_SUBSAMPLING_420 / _444 (jpeg_layout.hpp); the single-image forms take it, the batched forms are 4:2:0
+void jpeg_plane_dims(int w, int h, int *ys, int *yh, int *cs, int *ch, int mode = 0);
+int launch_jpeg_ycc(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, uint8_t *yp, uint8_t *cbp, uint8_t *crp, int mode = 0);
 int launch_jpeg_ycc_planes(fnx_ctx *ctx, const uint8_t *dy, int dys, const uint8_t *dcb, const uint8_t *dcr, int dcs, int ratio, int w, int h,
                            uint8_t *yp, uint8_t *cbp, uint8_t *crp);
 // the planes of boxDownsample(src, dw, dh) straight from the w x h source, the downsampled image never written
@@ -671,17 +673,21 @@ int launch_jpeg_box_ycc(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, in
 // is the class's standard one (a code size above 32), then the DHT body's bytes in memory order: 16 counts, 256 values
 constexpr int JPEG_HUFF_REC_WORDS = 70;
 // rec: nullptr for the typical tables, else the file's four records (fnx_ctx_set_jpeg_huffman: FNX_JPEG_HUFFMAN_OPTIMIZED)
-void jpeg_header(int w, int h, int quality, std::vector<uint8_t> &out, const uint32_t *rec = nullptr);
+void jpeg_header(int w, int h, int quality, std::vector<uint8_t> &out, const uint32_t *rec = nullptr, int mode = 0);
 int jpeg_entropy_code(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *const planes[3], unsigned long long *totals,
-                      uint32_t *rec = nullptr);
+                      uint32_t *rec = nullptr, int mode = 0);
 // the kernels of the optimised tables on their own (fnx_jpeg_symbol_histogram, fnx_jpeg_huffman_tables): host results
-int jpeg_symbol_hist_of(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *const planes[3], uint32_t *hist);
+int jpeg_symbol_hist_of(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *const planes[3], uint32_t *hist, int mode = 0);
 int jpeg_huffman_tables_of(fnx_ctx *ctx, const uint32_t *hist, uint32_t *lut, uint32_t *rec);
 size_t jpeg_ecs_capacity(unsigned long long total_bits);
-int jpeg_entropy_pack(fnx_ctx *ctx, int w, int h, unsigned long long total_bits, uint8_t *ecs, unsigned long long *totals);
+int jpeg_entropy_pack(fnx_ctx *ctx, int w, int h, unsigned long long total_bits, uint8_t *ecs, unsigned long long *totals, int mode = 0);
 // behind jpeg_entropy_code on the same stream: totals[1] = the 0xff bytes of the string, counted from the blocks' strips (no packed string)
-int jpeg_entropy_ffcount(fnx_ctx *ctx, int w, int h, unsigned long long *totals);
-int launch_jpeg_blocks(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *const in[3], uint8_t *const out[3]);
+int jpeg_entropy_ffcount(fnx_ctx *ctx, int w, int h, unsigned long long *totals, int mode = 0);
+int launch_jpeg_blocks(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *const in[3], uint8_t *const out[3], int mode = 0);
+// jpeg_api.cpp: the JPEG-writing entries that have no 4:4:4 form refuse a ctx set to FNX_JPEG_SUBSAMPLING_444 with this, first thing:
+// FNX_ERR_UNSUPPORTED and a message that names `entry` and "4:4:4"; nothing launched, uploaded or written.  A NULL ctx passes
+// (the entry's own checks answer for it)
+int jpeg_refuse_444(const fnx_ctx *ctx, const char *entry);
 // ---- batched forms (fnx_jpeg_compress_batch): n images of one geometry, the image index in grid x ----
 constexpr int JPEG_QTAB_WORDS = 101 * 2 * 2 * 64;   // [quality 0..100][luma, chroma][step, magic][64]: the per-ctx quality table
 void jpeg_qtab(uint32_t *tab);

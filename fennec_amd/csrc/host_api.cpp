@@ -467,6 +467,7 @@ static int file_stages(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec
 int fennec_CompressFileJPEG(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_FileOptions *o, uint8_t *out, size_t cap,
                             size_t *nbytes, int *quality, double *ssim, int *steps, int dims[4])
 {
+    FNX_TRY(jpeg_refuse_444(ctx, "fennec_CompressFileJPEG"));
     if (!ctx || !data || !o || !nbytes || !quality || !ssim || !dims) {
         set_error("invalid argument: CompressFileJPEG");
         return FNX_ERR_INVALID;
@@ -810,6 +811,7 @@ static void target_size_dims(const fnx_size_candidate *cand, int winner, int dim
 int fennec_CompressFileTargetSize(fnx_ctx *ctx, const uint8_t *data, size_t n, const fennec_TargetOptions *o, const volatile int *cancel,
                                   fnx_size_candidate cand[4], int *winner, uint8_t *out, size_t cap, size_t *nbytes, int dims[4])
 {
+    FNX_TRY(jpeg_refuse_444(ctx, "fennec_CompressFileTargetSize"));
     if (!data || !o || !cand || !winner || !nbytes || !dims || (!out && cap)) {
         set_error("invalid argument: CompressFileTargetSize: NULL argument");
         return FNX_ERR_INVALID;
@@ -833,6 +835,7 @@ int fennec_CompressFileHitTargetSize(fnx_ctx *ctx, const uint8_t *data, size_t n
                                      const volatile int *cancel, fnx_size_candidate cand[5], int *winner, uint8_t *out, size_t cap, size_t *nbytes,
                                      int dims[4])
 {
+    FNX_TRY(jpeg_refuse_444(ctx, "fennec_CompressFileHitTargetSize"));
     if (!data || !file || !cand || !winner || !nbytes || !dims || (!out && cap)) {
         set_error("invalid argument: CompressFileHitTargetSize: NULL argument");
         return FNX_ERR_INVALID;

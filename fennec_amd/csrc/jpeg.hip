@@ -16,6 +16,7 @@
 #include "common.hpp"
 #include "devutil.hpp"
 #include "jpeg_idct.hpp"
+#include "jpeg_layout.hpp"
 
 namespace fnx {
 
@@ -94,6 +95,39 @@ __device__ __forceinline__ void jpeg_ycc_body(const YccArgs &a, int bx, int by)
 __global__ __launch_bounds__(256) void jpeg_ycc_kernel(YccArgs a)
 {
     jpeg_ycc_body(a, blockIdx.x, blockIdx.y);
+}
+
+// 4:4:4 (fnx_ctx_set_jpeg_subsampling, jpeg_layout.hpp): three planes of one size, ps x ph (multiples of 8), no scale().  A lane's
+// 4 x 2 patch gives 8 samples to each plane: two 32-bit stores per plane (ps and the lane's column are multiples of 4, the
+// plane bases jpeg_planes': 4-byte aligned)
+struct Ycc444Args {
+    const uint8_t *src;
+    int sstride, w, h;
+    uint8_t *yp, *cbp, *crp;
+    int ps, ph;
+};
+
+__global__ __launch_bounds__(256) void jpeg_ycc444_kernel(Ycc444Args a)
+{
+    const int px = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;
+    const int py = (blockIdx.y * 4 + (threadIdx.x >> 6)) * 2;
+    if (px >= a.ps || py >= a.ph) return;
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        const uint8_t *row = a.src + static_cast<size_t>(min(py + j, a.h - 1)) * a.sstride;     // toYCbCr clamps to the last row / column
+        uint32_t y4 = 0, cb4 = 0, cr4 = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t ycc = rgb_to_ycc(ld_px(row, min(px + i, a.w - 1)));
+            y4 |= (ycc & 0xffu) << (8 * i);
+            cb4 |= ((ycc >> 8) & 0xffu) << (8 * i);
+            cr4 |= ((ycc >> 16) & 0xffu) << (8 * i);
+        }
+        const size_t o = static_cast<size_t>(py + j) * a.ps + px;
+        *reinterpret_cast<uint32_t *>(a.yp + o) = y4;
+        *reinterpret_cast<uint32_t *>(a.cbp + o) = cb4;
+        *reinterpret_cast<uint32_t *>(a.crp + o) = cr4;
+    }
 }
 
 // fnx_jpeg_compress_batch: the unquantised planes of n sources of one geometry.  Image = blockIdx.x / gx (images in x: the
@@ -395,15 +429,25 @@ static const uint8_t K2[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 9
                                47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
                                99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
 
-void jpeg_plane_dims(int w, int h, int *ys, int *yh, int *cs, int *chh)
+void jpeg_plane_dims(int w, int h, int *ys, int *yh, int *cs, int *chh, int mode)
 {
-    const int mx = (w + 15) / 16, my = (h + 15) / 16;
-    *ys = 16 * mx; *yh = 16 * my; *cs = 8 * mx; *chh = 8 * my;
+    int mx, my;
+    jpeg_layout_dims(mode, w, h, ys, yh, cs, chh, &mx, &my);
 }
 
 // src (device NRGBA) -> the unquantised planes (quality-independent: once per source)
-int launch_jpeg_ycc(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, uint8_t *yp, uint8_t *cbp, uint8_t *crp)
+int launch_jpeg_ycc(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, int h, uint8_t *yp, uint8_t *cbp, uint8_t *crp, int mode)
 {
+    if (mode == JPEG_444) {
+        Ycc444Args b{};
+        int cs, chh;
+        jpeg_plane_dims(w, h, &b.ps, &b.ph, &cs, &chh, mode);
+        b.src = src; b.sstride = sstride; b.w = w; b.h = h; b.yp = yp; b.cbp = cbp; b.crp = crp;
+        hipLaunchKernelGGL(jpeg_ycc444_kernel, dim3((b.ps / 4 + 63) / 64, (b.ph / 2 + 3) / 4), dim3(256), 0, ctx->stream, b);
+        FNX_HIP(hipGetLastError());
+        note_route(ctx, FNX_PROF_JPEG, "jpeg_ycc444_kernel");
+        return FNX_OK;
+    }
     YccArgs a{};
     int yh, chh;
     jpeg_plane_dims(w, h, &a.ys, &yh, &a.cs, &chh);
@@ -459,11 +503,11 @@ int launch_jpeg_box_ycc(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, in
 }
 
 // the planes at `quality`: fdct, quantise, dequantise, idct of every block (in -> out; in == out is allowed)
-int launch_jpeg_blocks(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *const in[3], uint8_t *const out[3])
+int launch_jpeg_blocks(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *const in[3], uint8_t *const out[3], int mode)
 {
     BlockArgs a{};
     int ys, yh, cs, chh;
-    jpeg_plane_dims(w, h, &ys, &yh, &cs, &chh);
+    jpeg_plane_dims(w, h, &ys, &yh, &cs, &chh, mode);
     if (quality < 1) quality = 1;
     if (quality > 100) quality = 100;
     const int scale = quality < 50 ? 5000 / quality : 200 - quality * 2;
@@ -521,8 +565,9 @@ struct CoefArgs {
 };
 
 // lane = block (plane-major, so that loads coalesce); stores go to the block's place in SCAN order:
-// MCU-major, Y0 Y1 Y2 Y3 Cb Cr inside an MCU (writer.go writeSOS).  in: the image's planes; base: its first block in the
-// coefficient array (0 for one image)
+// MCU-major, Y0 Y1 Y2 Y3 Cb Cr (4:4:4: Y Cb Cr) inside an MCU (writer.go writeSOS; jpeg_layout.hpp).  in: the image's planes;
+// base: its first block in the coefficient array (0 for one image)
+template <int MODE>
 __device__ __forceinline__ void jpeg_coef_body(const CoefArgs &a, const uint8_t *const in[3], int plane, int i, const uint32_t *q_tab,
                                                const uint32_t *magic_tab, int base)
 {
@@ -540,7 +585,7 @@ __device__ __forceinline__ void jpeg_coef_body(const CoefArgs &a, const uint8_t 
     for (int r = 0; r < 8; r++) fdct8<1>(b[8 * r], b[8 * r + 1], b[8 * r + 2], b[8 * r + 3], b[8 * r + 4], b[8 * r + 5], b[8 * r + 6], b[8 * r + 7]);
 #pragma unroll
     for (int c = 0; c < 8; c++) fdct8<2>(b[c], b[8 + c], b[16 + c], b[24 + c], b[32 + c], b[40 + c], b[48 + c], b[56 + c]);
-    const int sb = base + (plane == 0 ? ((by >> 1) * a.mx + (bx >> 1)) * 6 + (by & 1) * 2 + (bx & 1) : (by * a.mx + bx) * 6 + 3 + plane);
+    const int sb = base + jpeg_scan_index(MODE, a.mx, plane, bx, by);
 #pragma unroll
     for (int k = 0; k < 64; k++) {
         const int32_t q = static_cast<int32_t>(q_tab[k]);
@@ -550,13 +595,14 @@ __device__ __forceinline__ void jpeg_coef_body(const CoefArgs &a, const uint8_t 
     }
 }
 
+template <int MODE>
 __global__ __launch_bounds__(256) void jpeg_coef_kernel(CoefArgs a)
 {
     const int plane = blockIdx.y;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.nblocks[plane]) return;
     const int t = plane ? 1 : 0;
-    jpeg_coef_body(a, a.in, plane, i, a.q[t], a.magic[t], 0);
+    jpeg_coef_body<MODE>(a, a.in, plane, i, a.q[t], a.magic[t], 0);
 }
 
 // the winners of fnx_jpeg_compress_batch: image = blockIdx.x / gx, its planes at planes + image * plane_bytes, its blocks at
@@ -580,7 +626,7 @@ __global__ __launch_bounds__(256) void jpeg_coef_batch_kernel(CoefBatchArgs b)
     const uint8_t *base = b.planes + static_cast<size_t>(img) * b.plane_bytes;
     const uint8_t *const in[3] = {base + b.off[0], base + b.off[1], base + b.off[2]};
     const uint32_t *qt = b.qtab + (static_cast<size_t>(b.quality[img]) * 2 + t) * 128;
-    jpeg_coef_body(b.one, in, plane, i, qt, qt + 64, img * b.seg);
+    jpeg_coef_body<JPEG_420>(b.one, in, plane, i, qt, qt + 64, img * b.seg);
 }
 
 constexpr int JPEG_STRIP = 52;            // words per block's staging strip: 20 + 63 * 26 bits at most
@@ -591,12 +637,12 @@ struct CodeArgs {
     uint32_t *strip;          // [JPEG_STRIP][nblk]
     uint32_t *nbits;          // [nblk]
     int nblk;
-    int seg;                  // blocks per image: the batched form's images lie back to back (one image: seg = nblk)
+    int seg;                  // blocks per image, whole MCUs: the batched form's images lie back to back (one image: seg = nblk)
 };
 
 // PER_IMAGE: a.lut holds four tables for every image ([nblk / seg][4][256], jpeg_hufftab_kernel's), and a workgroup's blocks
 // may belong to two images: each lane reads its own image's tables where they are
-template <bool PER_IMAGE>
+template <bool PER_IMAGE, int MODE>
 __global__ __launch_bounds__(256) void jpeg_code_kernel(CodeArgs a)
 {
     __shared__ uint32_t s_lut[PER_IMAGE ? 1 : 4 * 256];
@@ -606,12 +652,12 @@ __global__ __launch_bounds__(256) void jpeg_code_kernel(CodeArgs a)
     }
     const int blk = blockIdx.x * 256 + threadIdx.x;
     if (blk >= a.nblk) return;
-    const int j = blk % 6;
+    const int j = blk % jpeg_mcu_blocks(MODE);             // the block's place in its MCU (seg is a multiple of the MCU's blocks)
     const uint32_t *luts = PER_IMAGE ? a.lut + static_cast<size_t>(blk / a.seg) * (4 * 256) : s_lut;
-    const uint32_t *dc_lut = luts + (j < 4 ? 0 : 512), *ac_lut = dc_lut + 256;
+    const uint32_t *dc_lut = luts + (jpeg_slot_class(MODE, j) ? 512 : 0), *ac_lut = dc_lut + 256;
     // the component's previous block in scan order
-    const int prev = j == 0 ? blk - 3 : (j < 4 ? blk - 1 : blk - 6);
-    const int first = blk - blk % a.seg;                   // the image's first block (seg is a multiple of 6)
+    const int prev = blk - jpeg_slot_prev(MODE, j);
+    const int first = blk - blk % a.seg;                   // the image's first block
     const int32_t dc = a.coef[blk];
     const int32_t pd = prev >= first ? static_cast<int32_t>(a.coef[prev]) : 0;
     unsigned long long acc = 0;      // MSB-first bit accumulator: the low `nacc` bits are pending
@@ -671,10 +717,11 @@ struct SymHistArgs {
     const int16_t *coef;      // jpeg_coef_kernel's
     uint32_t *hist;           // [images][4][256], zero
     int nblk;                 // blocks of all images
-    int seg;                  // blocks per image (a multiple of 6)
+    int seg;                  // blocks per image (whole MCUs)
     int gx;                   // workgroups per image: image = blockIdx.x / gx
 };
 
+template <int MODE>
 __global__ __launch_bounds__(256) void jpeg_symhist_kernel(SymHistArgs a)
 {
     __shared__ uint32_t s_h[4 * 256];
@@ -684,9 +731,9 @@ __global__ __launch_bounds__(256) void jpeg_symhist_kernel(SymHistArgs a)
     const int i = (blockIdx.x - img * a.gx) * 256 + threadIdx.x;        // the block inside its image
     if (i < a.seg) {
         const int first = img * a.seg, blk = first + i;
-        const int j = i % 6;
-        uint32_t *dc_h = s_h + (j < 4 ? 0 : 512), *ac_h = dc_h + 256;
-        const int prev = j == 0 ? blk - 3 : (j < 4 ? blk - 1 : blk - 6);  // as jpeg_code_kernel
+        const int j = i % jpeg_mcu_blocks(MODE);
+        uint32_t *dc_h = s_h + (jpeg_slot_class(MODE, j) ? 512 : 0), *ac_h = dc_h + 256;
+        const int prev = blk - jpeg_slot_prev(MODE, j);                   // as jpeg_code_kernel
         const int32_t dc = a.coef[blk];
         const int32_t pd = prev >= first ? static_cast<int32_t>(a.coef[prev]) : 0;
         const int32_t d = dc - pd;
@@ -907,7 +954,7 @@ static void quant_tables(int quality, uint32_t (&q)[2][64], uint32_t (&magic)[2]
 // the bytes jpeg.Encode writes before the entropy-coded segment.  rec: nullptr -- the four typical tables; else the four
 // records jpeg_hufftab_kernel left (JPEG_HUFF_REC_WORDS each): still ONE DHT segment, the tables in the same order, each with
 // the counts and the values of its record, 2 + sum(17 + values) bytes
-void jpeg_header(int w, int h, int quality, std::vector<uint8_t> &o, const uint32_t *rec)
+void jpeg_header(int w, int h, int quality, std::vector<uint8_t> &o, const uint32_t *rec, int mode)
 {
     uint32_t q[2][64], magic[2][64];
     quant_tables(quality, q, magic);
@@ -923,7 +970,7 @@ void jpeg_header(int w, int h, int quality, std::vector<uint8_t> &o, const uint3
     o.push_back(uint8_t(h >> 8)); o.push_back(uint8_t(h & 0xff));
     o.push_back(uint8_t(w >> 8)); o.push_back(uint8_t(w & 0xff));
     o.push_back(3);
-    const uint8_t comp[9] = {1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1};
+    const uint8_t comp[9] = {1, static_cast<uint8_t>(jpeg_y_sampling(mode)), 0, 2, 0x11, 1, 3, 0x11, 1};
     o.insert(o.end(), comp, comp + 9);
     auto nvals = [&](int t) { return !rec ? HNVAL[t] : (rec[t * HT_REC_WORDS] > 256u ? 256 : static_cast<int>(rec[t * HT_REC_WORDS])); };
     int dht = 2;
@@ -992,7 +1039,7 @@ static int upload_huffman_std(fnx_ctx *ctx, void **dp)
 
 // jpeg_symhist_kernel over the blocks of `units / 4` images in `coef` (seg blocks each), then jpeg_hufftab_kernel: the tables'
 // look-up words -> *d_lut ([units][256], device), their records -> rec (host-mapped, [units][JPEG_HUFF_REC_WORDS])
-static int launch_jpeg_hufftabs(fnx_ctx *ctx, const int16_t *coef, int nimg, int seg, uint32_t *rec, const uint32_t **d_lut)
+static int launch_jpeg_hufftabs(fnx_ctx *ctx, const int16_t *coef, int nimg, int seg, uint32_t *rec, const uint32_t **d_lut, int mode = JPEG_420)
 {
     const size_t words = static_cast<size_t>(nimg) * 4 * 256;
     void *hs = nullptr;
@@ -1002,7 +1049,8 @@ static int launch_jpeg_hufftabs(fnx_ctx *ctx, const int16_t *coef, int nimg, int
     FNX_TRY(upload_huffman_std(ctx, dp));
     FNX_HIP(hipMemsetAsync(hist, 0, sizeof(uint32_t) * words, ctx->stream));
     SymHistArgs sa{coef, hist, nimg * seg, seg, (seg + 255) / 256};
-    hipLaunchKernelGGL(jpeg_symhist_kernel, dim3(sa.gx * nimg), dim3(256), 0, ctx->stream, sa);
+    if (mode == JPEG_444) hipLaunchKernelGGL(jpeg_symhist_kernel<JPEG_444>, dim3(sa.gx * nimg), dim3(256), 0, ctx->stream, sa);
+    else hipLaunchKernelGGL(jpeg_symhist_kernel<JPEG_420>, dim3(sa.gx * nimg), dim3(256), 0, ctx->stream, sa);
     HuffTabArgs ha{hist, lut, rec, static_cast<const uint32_t *>(dp[0]), static_cast<const uint32_t *>(dp[1])};
     hipLaunchKernelGGL(jpeg_hufftab_kernel, dim3(4 * nimg), dim3(64), 0, ctx->stream, ha);
     FNX_HIP(hipGetLastError());
@@ -1033,10 +1081,10 @@ int jpeg_huffman_tables_of(fnx_ctx *ctx, const uint32_t *hist, uint32_t *lut, ui
     return FNX_OK;
 }
 
-static void coef_args(int w, int h, int quality, const uint8_t *const planes[3], int16_t *coef, CoefArgs *ca)
+static void coef_args(int mode, int w, int h, int quality, const uint8_t *const planes[3], int16_t *coef, CoefArgs *ca)
 {
-    int ys, yh, cs, chh;
-    jpeg_plane_dims(w, h, &ys, &yh, &cs, &chh);
+    int ys, yh, cs, chh, mx, my;
+    jpeg_layout_dims(mode, w, h, &ys, &yh, &cs, &chh, &mx, &my);
     quant_tables(quality, ca->q, ca->magic);
     for (int pl = 0; pl < 3; pl++) {
         ca->in[pl] = planes[pl];
@@ -1044,25 +1092,39 @@ static void coef_args(int w, int h, int quality, const uint8_t *const planes[3],
         ca->nbx[pl] = (pl ? cs : ys) / 8;
         ca->nblocks[pl] = ca->nbx[pl] * ((pl ? chh : yh) / 8);
     }
-    ca->coef = coef; ca->mx = ys / 16; ca->nblk = (ys / 16) * (yh / 16) * 6;
+    ca->coef = coef; ca->mx = mx; ca->nblk = jpeg_scan_blocks(mode, mx, my);
+}
+
+// blocks in the scan of a w x h image
+static int scan_blocks(int mode, int w, int h)
+{
+    int ys, yh, cs, chh, mx, my;
+    jpeg_layout_dims(mode, w, h, &ys, &yh, &cs, &chh, &mx, &my);
+    return jpeg_scan_blocks(mode, mx, my);
+}
+
+static void launch_jpeg_coef(fnx_ctx *ctx, int mode, const CoefArgs &ca)
+{
+    const dim3 grid((ca.nblocks[0] + 255) / 256, 3);
+    if (mode == JPEG_444) hipLaunchKernelGGL(jpeg_coef_kernel<JPEG_444>, grid, dim3(256), 0, ctx->stream, ca);
+    else hipLaunchKernelGGL(jpeg_coef_kernel<JPEG_420>, grid, dim3(256), 0, ctx->stream, ca);
 }
 
 // fnx_jpeg_symbol_histogram: what jpeg_symhist_kernel counts for the image of `planes` at `quality` -> hist [4][256] (host)
-int jpeg_symbol_hist_of(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *const planes[3], uint32_t *hist)
+int jpeg_symbol_hist_of(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *const planes[3], uint32_t *hist, int mode)
 {
-    int ys, yh, cs, chh;
-    jpeg_plane_dims(w, h, &ys, &yh, &cs, &chh);
-    const int nblk = (ys / 16) * (yh / 16) * 6;
+    const int nblk = scan_blocks(mode, w, h);
     void *sc = nullptr;
     FNX_TRY(scratch(ctx, SLOT_JPEG_ENC, sizeof(int16_t) * 64 * static_cast<size_t>(nblk) + 256, &sc));
     void *hs = nullptr;
     FNX_TRY(scratch(ctx, SLOT_JPEG_HUFF, 2 * sizeof(uint32_t) * 4 * 256, &hs));
     CoefArgs ca{};
-    coef_args(w, h, quality, planes, static_cast<int16_t *>(sc), &ca);
-    hipLaunchKernelGGL(jpeg_coef_kernel, dim3((ca.nblocks[0] + 255) / 256, 3), dim3(256), 0, ctx->stream, ca);
+    coef_args(mode, w, h, quality, planes, static_cast<int16_t *>(sc), &ca);
+    launch_jpeg_coef(ctx, mode, ca);
     FNX_HIP(hipMemsetAsync(hs, 0, sizeof(uint32_t) * 4 * 256, ctx->stream));
     SymHistArgs sa{ca.coef, static_cast<uint32_t *>(hs), nblk, nblk, (nblk + 255) / 256};
-    hipLaunchKernelGGL(jpeg_symhist_kernel, dim3(sa.gx), dim3(256), 0, ctx->stream, sa);
+    if (mode == JPEG_444) hipLaunchKernelGGL(jpeg_symhist_kernel<JPEG_444>, dim3(sa.gx), dim3(256), 0, ctx->stream, sa);
+    else hipLaunchKernelGGL(jpeg_symhist_kernel<JPEG_420>, dim3(sa.gx), dim3(256), 0, ctx->stream, sa);
     FNX_HIP(hipGetLastError());
     note_route(ctx, FNX_PROF_JPEG, "jpeg_symhist_kernel");
     return fetch_bytes(ctx, hs, hist, sizeof(uint32_t) * 4 * 256);
@@ -1071,11 +1133,10 @@ int jpeg_symbol_hist_of(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *
 // rec: nullptr -- the typical tables (what the library always wrote); else host-mapped room for four records
 // (JPEG_HUFF_REC_WORDS each): the tables are built from this image's symbols (launch_jpeg_hufftabs) and the records are there
 // when totals[0] is
-int jpeg_entropy_code(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *const planes[3], unsigned long long *totals, uint32_t *rec)
+int jpeg_entropy_code(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *const planes[3], unsigned long long *totals, uint32_t *rec,
+                      int mode)
 {
-    int ys, yh, cs, chh;
-    jpeg_plane_dims(w, h, &ys, &yh, &cs, &chh);
-    const int mx = ys / 16, my = yh / 16, nblk = mx * my * 6;
+    const int nblk = scan_blocks(mode, w, h);
     const size_t strip_words = static_cast<size_t>(nblk) * JPEG_STRIP;
     auto al = [](size_t n) { return (n + 255) & ~size_t(255); };
     const size_t b_coef = al(sizeof(int16_t) * 64 * nblk), b_strip = al(4 * strip_words), b_nbits = al(4 * size_t(nblk)),
@@ -1096,15 +1157,16 @@ int jpeg_entropy_code(fnx_ctx *ctx, int w, int h, int quality, const uint8_t *co
     }
 
     CoefArgs ca{};
-    coef_args(w, h, quality, planes, coef, &ca);
+    coef_args(mode, w, h, quality, planes, coef, &ca);
     FNX_TRY(prof_begin(ctx, FNX_PROF_JPEG));
-    hipLaunchKernelGGL(jpeg_coef_kernel, dim3((ca.nblocks[0] + 255) / 256, 3), dim3(256), 0, ctx->stream, ca);
+    launch_jpeg_coef(ctx, mode, ca);
     FNX_HIP(hipGetLastError());
     FNX_TRY(prof_end(ctx));
     const uint32_t *lut = static_cast<const uint32_t *>(dlut);
-    if (rec) FNX_TRY(launch_jpeg_hufftabs(ctx, coef, 1, nblk, rec, &lut));
+    if (rec) FNX_TRY(launch_jpeg_hufftabs(ctx, coef, 1, nblk, rec, &lut, mode));
     CodeArgs co{coef, lut, strip, nbits, nblk, nblk};
-    hipLaunchKernelGGL(jpeg_code_kernel<false>, dim3((nblk + 255) / 256), dim3(256), 0, ctx->stream, co);
+    if (mode == JPEG_444) hipLaunchKernelGGL((jpeg_code_kernel<false, JPEG_444>), dim3((nblk + 255) / 256), dim3(256), 0, ctx->stream, co);
+    else hipLaunchKernelGGL((jpeg_code_kernel<false, JPEG_420>), dim3((nblk + 255) / 256), dim3(256), 0, ctx->stream, co);
     FNX_HIP(hipGetLastError());
     return launch_scan(ctx, nbits, pos, wgt, nblk, totals);
 }
@@ -1114,11 +1176,9 @@ size_t jpeg_ecs_capacity(unsigned long long total_bits)
     return static_cast<size_t>((total_bits + 7) / 8) * 2 + 64;        // every byte could be 0xff
 }
 
-int jpeg_entropy_pack(fnx_ctx *ctx, int w, int h, unsigned long long total_bits, uint8_t *ecs, unsigned long long *totals)
+int jpeg_entropy_pack(fnx_ctx *ctx, int w, int h, unsigned long long total_bits, uint8_t *ecs, unsigned long long *totals, int mode)
 {
-    int ys, yh, cs, chh;
-    jpeg_plane_dims(w, h, &ys, &yh, &cs, &chh);
-    const int nblk = (ys / 16) * (yh / 16) * 6;
+    const int nblk = scan_blocks(mode, w, h);
     const size_t strip_words = static_cast<size_t>(nblk) * JPEG_STRIP;
     auto al = [](size_t n) { return (n + 255) & ~size_t(255); };
     // phase-1 layout again (same slot, same sizes: nothing moves)
@@ -1192,11 +1252,9 @@ __global__ __launch_bounds__(64) void jpeg_ffcount_finish_kernel(unsigned long l
     if (threadIdx.x == 0) out[0] = atomicExch(total, 0ull);
 }
 
-int jpeg_entropy_ffcount(fnx_ctx *ctx, int w, int h, unsigned long long *totals)
+int jpeg_entropy_ffcount(fnx_ctx *ctx, int w, int h, unsigned long long *totals, int mode)
 {
-    int ys, yh, cs, chh;
-    jpeg_plane_dims(w, h, &ys, &yh, &cs, &chh);
-    const int nblk = (ys / 16) * (yh / 16) * 6;
+    const int nblk = scan_blocks(mode, w, h);
     auto al = [](size_t n) { return (n + 255) & ~size_t(255); };
     // jpeg_entropy_code's layout (same slot, same sizes: nothing moves)
     const size_t b_coef = al(sizeof(int16_t) * 64 * nblk), b_strip = al(4 * static_cast<size_t>(nblk) * JPEG_STRIP), b_nbits = al(4 * size_t(nblk));
@@ -1394,9 +1452,7 @@ __global__ __launch_bounds__(256) void jpeg_stuff_batch_kernel(StuffBatchArgs b)
 
 static void entropy_batch_layout(int n, int w, int h, int *seg, size_t *sizes)
 {
-    int ys, yh, cs, chh;
-    jpeg_plane_dims(w, h, &ys, &yh, &cs, &chh);
-    *seg = (ys / 16) * (yh / 16) * 6;
+    *seg = scan_blocks(JPEG_420, w, h);
     const size_t nblk = static_cast<size_t>(n) * *seg;
     auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
     sizes[0] = al(sizeof(int16_t) * 64 * nblk);
@@ -1452,7 +1508,7 @@ int jpeg_entropy_code_batch(fnx_ctx *ctx, int n, int w, int h, const uint8_t *pl
         cb.one.nbx[pl] = (pl ? cs : ys) / 8;
         cb.one.nblocks[pl] = cb.one.nbx[pl] * ((pl ? chh : yh) / 8);
     }
-    cb.one.coef = coef; cb.one.mx = ys / 16; cb.one.nblk = nblk;
+    cb.one.coef = coef; cb.one.mx = ys / jpeg_mcu_px(JPEG_420); cb.one.nblk = nblk;
     cb.planes = planes;
     cb.plane_bytes = jpeg_batch_plane_bytes(w, h, &cb.off[1], &cb.off[2]);
     cb.off[0] = 0;
@@ -1465,8 +1521,8 @@ int jpeg_entropy_code_batch(fnx_ctx *ctx, int n, int w, int h, const uint8_t *pl
     const uint32_t *lut = static_cast<const uint32_t *>(dlut);
     if (rec) FNX_TRY(launch_jpeg_hufftabs(ctx, coef, n, seg, rec, &lut));
     CodeArgs co{coef, lut, strip, nbits, nblk, seg};
-    if (rec) hipLaunchKernelGGL(jpeg_code_kernel<true>, dim3((nblk + 255) / 256), dim3(256), 0, ctx->stream, co);
-    else hipLaunchKernelGGL(jpeg_code_kernel<false>, dim3((nblk + 255) / 256), dim3(256), 0, ctx->stream, co);
+    if (rec) hipLaunchKernelGGL((jpeg_code_kernel<true, JPEG_420>), dim3((nblk + 255) / 256), dim3(256), 0, ctx->stream, co);
+    else hipLaunchKernelGGL((jpeg_code_kernel<false, JPEG_420>), dim3((nblk + 255) / 256), dim3(256), 0, ctx->stream, co);
     FNX_HIP(hipGetLastError());
     FNX_TRY(launch_scan(ctx, nbits, pos, wgt, nblk, nullptr));
     hipLaunchKernelGGL(seg_bits_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, pos, nbits, seg, n, tot);

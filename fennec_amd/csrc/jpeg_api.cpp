@@ -1,8 +1,21 @@
 // fnx_jpeg_* entry points: the JPEG encoder's host flow (compress.go, targetsize.go) around jpeg.hip's kernels, and the
 // decoder's around jpeg_dec.hip and jpeg_prog.cpp.
 #include "common.hpp"
+#include "jpeg_layout.hpp"
 
 using namespace fnx;
+
+namespace fnx {
+
+int jpeg_refuse_444(const fnx_ctx *ctx, const char *entry)
+{
+    if (!ctx || ctx->jpeg_subsampling != FNX_JPEG_SUBSAMPLING_444) return FNX_OK;
+    set_error("%s: not supported on a ctx set to 4:4:4 chroma (fnx_ctx_set_jpeg_subsampling): only fnx_jpeg_roundtrip, fnx_jpeg_quality_search, "
+              "fnx_jpeg_encode, fnx_jpeg_compress, fnx_jpeg_size_search and fnx_jpeg_symbol_histogram follow the mode", entry);
+    return FNX_ERR_UNSUPPORTED;
+}
+
+}  // namespace fnx
 
 // ---- the JPEG quantisation round trip (compress.go:45-74; SURVEY 8(f)2, first slice: jpeg.hip) -------------
 namespace {
@@ -13,11 +26,14 @@ bool jpeg_dims(int w, int h) { return w >= 1 && w <= 65535 && h >= 1 && h <= 655
 struct JpegPlanes {
     uint8_t *p[3];
     int ys, yh, cs, ch;
+    int mode;                   // FNX_JPEG_SUBSAMPLING_*: the layout these planes have, and with them every file made of them
 };
 
+// planes in the ctx's subsampling mode (the entries without a 4:4:4 form have refused such a ctx: theirs are 4:2:0)
 int jpeg_planes(fnx_ctx *ctx, Slot slot, int w, int h, JpegPlanes *jp)
 {
-    jpeg_plane_dims(w, h, &jp->ys, &jp->yh, &jp->cs, &jp->ch);
+    jp->mode = ctx->jpeg_subsampling;
+    jpeg_plane_dims(w, h, &jp->ys, &jp->yh, &jp->cs, &jp->ch, jp->mode);
     const size_t yb = static_cast<size_t>(jp->ys) * jp->yh, cb = static_cast<size_t>(jp->cs) * jp->ch;
     void *t = nullptr;
     FNX_TRY(scratch(ctx, slot, yb + 2 * cb + 16, &t));
@@ -31,7 +47,7 @@ int jpeg_planes(fnx_ctx *ctx, Slot slot, int w, int h, JpegPlanes *jp)
 int jpeg_ycc_planes(fnx_ctx *ctx, Slot slot, const uint8_t *img, int stride, int w, int h, JpegPlanes *pl)
 {
     FNX_TRY(jpeg_planes(ctx, slot, w, h, pl));
-    return launch_jpeg_ycc(ctx, img, stride, w, h, pl->p[0], pl->p[1], pl->p[2]);
+    return launch_jpeg_ycc(ctx, img, stride, w, h, pl->p[0], pl->p[1], pl->p[2], pl->mode);
 }
 
 // planes at `quality` from the unquantised planes in SLOT_JPEG0, then the NRGBA image toNRGBARef makes of them
@@ -40,8 +56,8 @@ int jpeg_decode_at(fnx_ctx *ctx, const JpegPlanes &orig, int w, int h, int quali
     JpegPlanes work;
     FNX_TRY(jpeg_planes(ctx, SLOT_JPEG1, w, h, &work));
     const uint8_t *in[3] = {orig.p[0], orig.p[1], orig.p[2]};
-    FNX_TRY(launch_jpeg_blocks(ctx, w, h, quality, in, work.p));
-    return launch_ycbcr_to_nrgba(ctx, work.p[0], work.ys, work.p[1], work.p[2], work.cs, 2, w, h, dst, dstride);
+    FNX_TRY(launch_jpeg_blocks(ctx, w, h, quality, in, work.p, work.mode));
+    return launch_ycbcr_to_nrgba(ctx, work.p[0], work.ys, work.p[1], work.p[2], work.cs, jpeg_ycbcr_ratio(work.mode), w, h, dst, dstride);
 }
 
 // the source side of every SSIMFast of a call (ssim.go:52-58), prepared once: its dims and its plane's buffer in SLOT_JPEG3
@@ -104,14 +120,15 @@ int jpeg_search_device(fnx_ctx *ctx, const fnx_prepared &ref, const JpegPlanes &
         JpegPlanes work;
         FNX_TRY(jpeg_planes(ctx, SLOT_JPEG1, w, h, &work));
         const uint8_t *in[3] = {orig.p[0], orig.p[1], orig.p[2]};
-        FNX_TRY(launch_jpeg_blocks(ctx, w, h, mid, in, work.p));
-        bool fused = false;
-        if (ds) FNX_TRY(launch_box_downsample_ycc(ctx, work.p[0], work.ys, work.p[1], work.p[2], work.cs, 2, w, h, static_cast<uint8_t *>(cand),
+        FNX_TRY(launch_jpeg_blocks(ctx, w, h, mid, in, work.p, work.mode));
+        const int ratio = jpeg_ycbcr_ratio(work.mode);
+        bool fused = false;                                       // (a 4:4:4 candidate: "not fused" where the box sums have no form for it)
+        if (ds) FNX_TRY(launch_box_downsample_ycc(ctx, work.p[0], work.ys, work.p[1], work.p[2], work.cs, ratio, w, h, static_cast<uint8_t *>(cand),
                                                   ref.pw * 4, ref.pw, ref.ph, &fused));
         if (fused) {
             FNX_TRY(against_device(ctx, &ref, static_cast<const uint8_t *>(cand), ref.pw * 4, window, &v, true));
         } else {
-            FNX_TRY(launch_ycbcr_to_nrgba(ctx, work.p[0], work.ys, work.p[1], work.p[2], work.cs, 2, w, h, static_cast<uint8_t *>(dec), w * 4));
+            FNX_TRY(launch_ycbcr_to_nrgba(ctx, work.p[0], work.ys, work.p[1], work.p[2], work.cs, ratio, w, h, static_cast<uint8_t *>(dec), w * 4));
             FNX_TRY(against_device(ctx, &ref, static_cast<const uint8_t *>(dec), w * 4, window, &v));
         }
         qs.record(mid, v);
@@ -174,14 +191,14 @@ int jpeg_file_from_planes(fnx_ctx *ctx, const JpegPlanes &orig, int w, int h, in
     totals[0] = totals[1] = ~0ull;
     uint32_t *rec = opt ? reinterpret_cast<uint32_t *>(totals + 2) : nullptr;
     const uint8_t *planes[3] = {orig.p[0], orig.p[1], orig.p[2]};
-    FNX_TRY(jpeg_entropy_code(ctx, w, h, quality, planes, totals, rec));
+    FNX_TRY(jpeg_entropy_code(ctx, w, h, quality, planes, totals, rec, orig.mode));
     if (out == nullptr && cap == 0 && jpeg_size_one_wait(ctx)) {
         // a size query never needs the packed string: the stuffed bytes are counted from the blocks' strips behind the scan,
         // and both totals come back in ONE wait (jpeg.hip: jpeg_ffcount_strips_kernel)
-        FNX_TRY(jpeg_entropy_ffcount(ctx, w, h, totals));
+        FNX_TRY(jpeg_entropy_ffcount(ctx, w, h, totals, orig.mode));
         FNX_HIP(hipStreamSynchronize(ctx->stream));
         std::vector<uint8_t> hdr;
-        jpeg_header(w, h, quality, hdr, rec);
+        jpeg_header(w, h, quality, hdr, rec, orig.mode);
         *nbytes = jpeg_file_frame(hdr, jpeg_ecs_bytes(totals[0], totals[1]), nullptr, 0);
         return FNX_OK;
     }
@@ -189,11 +206,11 @@ int jpeg_file_from_planes(fnx_ctx *ctx, const JpegPlanes &orig, int w, int h, in
     const unsigned long long tbits = totals[0];
     void *ecs = nullptr;
     FNX_TRY(scratch(ctx, SLOT_JPEG_ECS, jpeg_ecs_capacity(tbits), &ecs));
-    FNX_TRY(jpeg_entropy_pack(ctx, w, h, tbits, static_cast<uint8_t *>(ecs), totals));
+    FNX_TRY(jpeg_entropy_pack(ctx, w, h, tbits, static_cast<uint8_t *>(ecs), totals, orig.mode));
     FNX_HIP(hipStreamSynchronize(ctx->stream));
     const size_t ecs_bytes = jpeg_ecs_bytes(tbits, totals[1]);
     std::vector<uint8_t> hdr;
-    jpeg_header(w, h, quality, hdr, rec);
+    jpeg_header(w, h, quality, hdr, rec, orig.mode);
     const size_t total = jpeg_file_frame(hdr, ecs_bytes, out, cap);
     *nbytes = total;
     if (out == nullptr && cap == 0) return FNX_OK;       // size query: targetsize.go's searches need len(encoded) only
@@ -293,7 +310,7 @@ int fnx_jpeg_symbol_histogram(fnx_ctx *ctx, int space, const uint8_t *src, int s
     FNX_TRY(stage_in(ctx, space, src, sstride, w, h, SLOT_IN_A, &s));
     FNX_TRY(jpeg_ycc_planes(ctx, SLOT_JPEG0, s.p, s.stride, w, h, &orig));
     const uint8_t *planes[3] = {orig.p[0], orig.p[1], orig.p[2]};
-    return jpeg_symbol_hist_of(ctx, w, h, quality, planes, &hist[0][0]);
+    return jpeg_symbol_hist_of(ctx, w, h, quality, planes, &hist[0][0], orig.mode);
 }
 
 int fnx_jpeg_huffman_tables(fnx_ctx *ctx, const uint32_t hist[4][256], uint8_t bits[4][16], uint8_t vals[4][256], int nvals[4],
@@ -410,6 +427,7 @@ int fnx_jpeg_compress_batch(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int
                             const double *window, uint8_t *const *outs, const size_t *caps, size_t *nbytes, int *quality, double *ssim,
                             int *steps, int *status)
 {
+    FNX_TRY(jpeg_refuse_444(ctx, "fnx_jpeg_compress_batch"));
     FNX_ENTER(ctx);
     FNX_REQUIRE(n >= 1 && n <= FNX_BATCH_MAX, "compress batch: n must be 1..FNX_BATCH_MAX (65535)");
     FNX_REQUIRE(srcs && target_ssim && outs && caps && nbytes && quality && ssim && status, "compress batch: NULL array");
@@ -602,6 +620,7 @@ int jpeg_compress_group(fnx_ctx *ctx, int n, const uint8_t *const *srcs, int sst
 int fnx_jpeg_encode_scaled(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int dw, int dh, int quality,
                            uint8_t *out, size_t cap, size_t *nbytes)
 {
+    FNX_TRY(jpeg_refuse_444(ctx, "fnx_jpeg_encode_scaled"));
     FNX_ENTER(ctx);
     FNX_TRY(check_space(space));
     FNX_REQUIRE(nbytes != nullptr && w > 0 && h > 0 && jpeg_dims(dw, dh), "encode_scaled arguments (JPEG dims are 16-bit)");
@@ -1047,6 +1066,7 @@ int fnx_jpeg_target_size(fnx_ctx *ctx, int space, const uint8_t *src, int sstrid
                          const double *window, const volatile int *cancel, fnx_size_candidate cand[4], int *winner, uint8_t *out,
                          size_t cap, size_t *nbytes, uint8_t *img, int istride)
 {
+    FNX_TRY(jpeg_refuse_444(ctx, "fnx_jpeg_target_size"));
     FNX_ENTER(ctx);
     FNX_TRY(check_space(space));
     FNX_REQUIRE(cand && winner && nbytes, "target_size: cand, winner and nbytes are required");
@@ -1093,6 +1113,7 @@ int fnx_hit_target_size(fnx_ctx *ctx, int space, const uint8_t *src, int sstride
                         const double *window, const volatile int *cancel, fnx_size_candidate cand[5], int *winner, uint8_t *out, size_t cap,
                         size_t *nbytes, uint8_t *img, int istride)
 {
+    FNX_TRY(jpeg_refuse_444(ctx, "fnx_hit_target_size"));         // up front, whatever the format and the image would pick
     FNX_TRY(check_space(space));
     FNX_REQUIRE(cand && winner && nbytes, "hit_target_size: cand, winner and nbytes are required");
     FNX_REQUIRE(window, "hit_target_size: window is required");
@@ -1261,6 +1282,7 @@ int fnx_jpeg_progressive_coefficients(const uint8_t *data, size_t n, int16_t *co
 int fnx_jpeg_recompress(fnx_ctx *ctx, const uint8_t *data, size_t n, double target_ssim, const double *window, uint8_t *out, size_t cap,
                         size_t *nbytes, int *quality, double *ssim, int *steps, int *w, int *h)
 {
+    FNX_TRY(jpeg_refuse_444(ctx, "fnx_jpeg_recompress"));
     FNX_ENTER(ctx);
     FNX_REQUIRE(data && window && nbytes && quality && ssim && w && h, "recompress arguments");
     *nbytes = 0;
@@ -1306,6 +1328,7 @@ int fnx_jpeg_recompress_batch(fnx_ctx *ctx, int n, const uint8_t *const *files, 
                               const double *window, uint8_t *const *outs, const size_t *caps, size_t *nbytes, int *quality, double *ssim,
                               int *steps, int *ws, int *hs, int *status)
 {
+    FNX_TRY(jpeg_refuse_444(ctx, "fnx_jpeg_recompress_batch"));
     FNX_ENTER(ctx);
     FNX_REQUIRE(n >= 1 && n <= FNX_BATCH_MAX, "recompress batch: n must be 1..FNX_BATCH_MAX (65535)");
     FNX_REQUIRE(files && sizes && target_ssim && outs && caps && nbytes && quality && ssim && ws && hs && status, "recompress batch: NULL array");

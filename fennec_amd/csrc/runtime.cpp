@@ -564,6 +564,13 @@ int fnx_ctx_set_jpeg_huffman(fnx_ctx *ctx, int mode)
     return FNX_OK;
 }
 
+int fnx_ctx_set_jpeg_subsampling(fnx_ctx *ctx, int mode)
+{
+    if (!ctx || (mode != FNX_JPEG_SUBSAMPLING_420 && mode != FNX_JPEG_SUBSAMPLING_444)) { fnx::set_error("fnx_ctx_set_jpeg_subsampling: bad argument"); return FNX_ERR_INVALID; }
+    ctx->jpeg_subsampling = mode;
+    return FNX_OK;
+}
+
 int fnx_ctx_set_ssim_mode(fnx_ctx *ctx, int mode)
 {
     if (!ctx || (mode != FNX_SSIM_EXACT && mode != FNX_SSIM_FAST)) { fnx::set_error("fnx_ctx_set_ssim_mode: bad argument"); return FNX_ERR_INVALID; }

@@ -385,7 +385,7 @@ void fnx_prepared_free(fnx_ctx *ctx, fnx_prepared *p);
  * jpeg.Encode(src, Options{Quality: quality}))) as far as the PIXELS go (compress.go:50-58 via io.go:157-169): baseline
  * 4:2:0, Go's colour equations, integer FDCT / IDCT and quantiser scaling, no entropy coding (it is lossless).  The
  * arithmetic restates Go's standard library, which is not part of the reference tree: parity with Go is unpinned twice
- * over; against the oracle's restatement it is bit-exact. */
+ * over; against the oracle's restatement it is bit-exact.  4:4:4 on a ctx set so: fnx_ctx_set_jpeg_subsampling. */
 int fnx_jpeg_roundtrip(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int quality,
                        uint8_t *dst, int dstride);
 /* compressJPEGOptimal's binary search (compress.go:21-74) with every candidate quality round-tripped and scored on the
@@ -398,21 +398,22 @@ int fnx_jpeg_roundtrip(fnx_ctx *ctx, int space, const uint8_t *src, int sstride,
  * only (what targetsize.go's searches look at) and copies nothing.  Decoding the file gives exactly
  * fnx_jpeg_roundtrip's pixels (the entropy coder is lossless).  Restated from ITU T.81 and Go's file layout, not from
  * Go's source: byte parity with jpeg.Encode is unpinned; libjpeg-turbo decodes the files.
- * The file's Huffman tables follow fnx_ctx_set_jpeg_huffman. */
+ * The file's Huffman tables follow fnx_ctx_set_jpeg_huffman, its chroma subsampling fnx_ctx_set_jpeg_subsampling. */
 int fnx_jpeg_encode(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int quality, uint8_t *out, size_t cap,
                     size_t *nbytes);
 /* jpegQualitySearchOpt (targetsize.go:125-176): the HIGHEST quality whose file fits target_bytes -- the bisection over
  * [lo, hi] the reference picks from the bits per pixel, every candidate's size from the device's entropy coder
  * (nothing is copied for a candidate), then the winner's file into `out` and, unless skip_ssim, its SSIMFast against the
  * source (the reference's computeSSIMNRGBA of the decoded winner).  FNX_NOOP: no quality fits (bestBuf == nil).
- * FNX_ERR_INVALID with *nbytes set when cap is too small. The file's Huffman tables follow fnx_ctx_set_jpeg_huffman. */
+ * FNX_ERR_INVALID with *nbytes set when cap is too small. The file's Huffman tables follow fnx_ctx_set_jpeg_huffman, its chroma
+ * subsampling fnx_ctx_set_jpeg_subsampling. */
 int fnx_jpeg_size_search(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, long long target_bytes, int skip_ssim,
                          const double *window /* 64; may be NULL with skip_ssim */, uint8_t *out, size_t cap, size_t *nbytes,
                          int *quality, double *ssim, int *steps /* may be NULL */);
 /* compressJPEGOptimal (compress.go:21-87) for one image in one call: the quality search of fnx_jpeg_quality_search, then
  * the file at the quality it found (100 when nothing reached the target) as fnx_jpeg_encode writes it -- one upload of
  * the source, no host codec.  *ssim is the winning candidate's SSIMFast (1.0 when none won, as the reference reports).
- * The file's Huffman tables follow fnx_ctx_set_jpeg_huffman. */
+ * The file's Huffman tables follow fnx_ctx_set_jpeg_huffman; the search and the file follow fnx_ctx_set_jpeg_subsampling. */
 int fnx_jpeg_compress(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, double target_ssim,
                       const double *window /* 64 */, uint8_t *out, size_t cap, size_t *nbytes, int *quality, double *ssim,
                       int *steps /* may be NULL */);
@@ -454,7 +455,8 @@ int fnx_jpeg_encode_scaled(fnx_ctx *ctx, int space, const uint8_t *src, int sstr
 int fnx_ctx_set_jpeg_huffman(fnx_ctx *ctx, int mode);
 /* What jpeg_symhist_kernel counts for this image at this quality: hist[t][s] = how often the scan of fnx_jpeg_encode(src,
  * quality) codes symbol s with table t (0 luminance DC, 1 luminance AC, 2 chrominance DC, 3 chrominance AC).  Independent of
- * the ctx's Huffman mode.  NULL ctx, src or hist: FNX_ERR_INVALID. */
+ * the ctx's Huffman mode; the scan is the ctx's subsampling mode's (fnx_ctx_set_jpeg_subsampling).  NULL ctx, src or hist:
+ * FNX_ERR_INVALID. */
 int fnx_jpeg_symbol_histogram(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h, int quality,
                               uint32_t hist[4][256]);
 /* jpeg_hufftab_kernel on the caller's four histograms (HOST; the tables are independent of each other): per table the DHT
@@ -463,6 +465,32 @@ int fnx_jpeg_symbol_histogram(fnx_ctx *ctx, int space, const uint8_t *src, int s
  * table of its class (see above).  A NULL pointer or a table whose histogram is all zero: FNX_ERR_INVALID. */
 int fnx_jpeg_huffman_tables(fnx_ctx *ctx, const uint32_t hist[4][256], uint8_t bits[4][16], uint8_t vals[4][256], int nvals[4],
                             uint32_t lut[4][256], int standard[4]);
+/* The chroma subsampling of the JPEG files a ctx writes from ONE resident image.  FNX_JPEG_SUBSAMPLING_420 (the default) is
+ * what the library always wrote.  FNX_JPEG_SUBSAMPLING_444 keeps the chroma at full resolution: the option the reference
+ * reserves for "a custom encoder" (Options.Subsample, types.go:146-153; encodeJPEG drops it, io.go:151-158).  The file,
+ * exactly -- writer.go's with every component at sampling 1 x 1:
+ *  - padding: mx = (w + 7) / 8, my = (h + 7) / 8 MCUs of 8 x 8 px.
+ *  - scan order: blocks in raster order; the MCU is three blocks, Y Cb Cr.
+ *  - pixels of a block: block (bx, by) takes pixels min(8 bx + i, w - 1), min(8 by + j, h - 1) (toYCbCr's clamp).
+ *  - colour: a pixel goes through color.RGBToYCbCr of its (for alpha < 255: premultiplied) RGB, as at 4:2:0; no averaging.
+ *  - DCT and quantiser: unchanged (fdct, div(b, 8 q); table 0 for Y, table 1 for Cb and Cr).
+ *  - DC prediction: per component, from the component's previous block, three scan positions back; 0 at the first MCU.
+ *  - Huffman classes: luminance for Y, chrominance for Cb and Cr, as at 4:2:0.
+ *  - header: byte for byte the 4:2:0 header of the same w, h, quality and Huffman mode, except the Y component's sampling byte
+ *    in SOF0: 0x11 instead of 0x22.
+ *  - decoding: the file decodes to an image.YCbCr of ratio 4:4:4; toNRGBARef of it is what fnx_jpeg_roundtrip returns.
+ * FOLLOWED by fnx_jpeg_roundtrip, fnx_jpeg_quality_search, fnx_jpeg_encode, fnx_jpeg_compress, fnx_jpeg_size_search and
+ * fnx_jpeg_symbol_histogram (compressJPEGOptimal and jpegQualitySearch on a resident image), in both Huffman modes and on both
+ * size-query routes; no host wait is added.  REFUSED on a ctx set to 4:4:4, with FNX_ERR_UNSUPPORTED before anything is
+ * launched, uploaded or written and a message naming the entry and "4:4:4": fnx_jpeg_encode_scaled, fnx_jpeg_target_size,
+ * fnx_hit_target_size (whatever its format), fnx_jpeg_recompress, fnx_jpeg_compress_batch, fnx_jpeg_recompress_batch,
+ * fennec_CompressFileJPEG, fennec_CompressFileTargetSize, fennec_CompressFileHitTargetSize.  The decoders, the PNG entries and
+ * everything else ignore the mode; the fennec_CompressBatch* pools and the Go shim create their own contexts and keep 4:2:0.
+ * csrc/jpeg_layout.hpp states the two layouts once for host and device code; csrc/jpeg.hip: jpeg_ycc444_kernel.  DESIGN.md 5.18.
+ * ctx == NULL or any other mode: FNX_ERR_INVALID, nothing changed. */
+#define FNX_JPEG_SUBSAMPLING_420 0   /* default: what the library always wrote */
+#define FNX_JPEG_SUBSAMPLING_444 1
+int fnx_ctx_set_jpeg_subsampling(fnx_ctx *ctx, int mode);
 /* hitTargetSize's JPEG strategies (targetsize.go:26-357) in one call, the source staged once and every scale step's
  * file size taken on the device (fnx_jpeg_encode_scaled's planes; 8 bytes come back per size query).  `strategies`: */
 #define FNX_TS_QUALITY 1       /* strategy 1: jpegQualitySearch(src)                        targetsize.go:33-37, 117-176 */
