@@ -279,6 +279,7 @@ int launch_apply_palette(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, i
             tab[256 + 2 * i] = (255u - r) | ((255u - g) << 8) | ((255u - b) << 16);
             tab[256 + 2 * i + 1] = (r * r + g * g + b * b) * 256u + static_cast<uint32_t>(i);
         }
+        note_route(ctx, FNX_PROF_MAIN, "apply_palette_grid_kernel");
         void *d = nullptr, *grid = nullptr;
         FNX_TRY(upload_table(ctx, SLOT_TABLE0, tab.data(), sizeof(uint32_t) * tab.size(), &d));
         FNX_TRY(scratch(ctx, SLOT_TMP1, static_cast<size_t>(PG_CELLS) * PG_REC, &grid));
@@ -295,6 +296,7 @@ int launch_apply_palette(fnx_ctx *ctx, const uint8_t *src, int sstride, int w, i
         FNX_HIP(hipGetLastError());
         return FNX_OK;
     }
+    note_route(ctx, FNX_PROF_MAIN, "apply_palette_kernel");
     const int npad = (n + 7) & ~7;
     std::vector<uint32_t> tab(3 * static_cast<size_t>(npad), 0u);
     for (int i = 0; i < npad; i++) {
@@ -345,6 +347,7 @@ int launch_apply_palette_device(fnx_ctx *ctx, const uint8_t *src, int sstride, i
     if (w <= 0 || h <= 0) return FNX_OK;
     const int mode = palette_grid_mode(ctx);
     const bool grid = mode == 1 || (mode != 0 && static_cast<long>(w) * h >= 262144L);      // as launch_apply_palette chooses
+    note_route(ctx, FNX_PROF_MAIN, grid ? "apply_palette_grid_kernel" : "apply_palette_kernel");
     void *d = nullptr;
     FNX_TRY(scratch(ctx, SLOT_MEDIAN_CUT_TAB, sizeof(uint32_t) * 768, &d));
     PalTabArgs ta{d_palette, d_ncolors, static_cast<uint32_t *>(d), grid ? 1 : 0};

@@ -768,7 +768,10 @@ int fnx_ssim_fast_against_ycbcr(fnx_ctx *ctx, const fnx_prepared *ref, int space
  * 505-517); `indices` = image.Paletted.Pix (w x h bytes, stride istride), `quantized` =
  * palettedToNRGBA of it (NRGBA, alpha 255).  Either output may be NULL.  palette: ncolors x 4
  * HOST bytes r,g,b,a with a == 255 (what medianCut emits: fnx_median_cut below, or the
- * caller's own).  Integer arithmetic: bit-exact. */
+ * caller's own).  Integer arithmetic: bit-exact.  The route the call took -- "apply_palette_grid_kernel"
+ * (images of 256 k pixels and more, or the form palette_grid = "1") or "apply_palette_kernel" -- is
+ * fnx_ctx_last_kernel(ctx, FNX_PROF_MAIN) after the call; fnx_quantize's applyPalette step notes its route the
+ * same way (it is the call's last note of that class when ssim == NULL). */
 int fnx_apply_palette(fnx_ctx *ctx, int space, const uint8_t *src, int sstride, int w, int h,
                       const uint8_t *palette, int ncolors, uint8_t *indices, int istride,
                       uint8_t *quantized, int qstride);
